@@ -12,9 +12,12 @@ Inputs (observations, candidates) are resident in HBM before the timed region st
 refits redundantly (bitwise-identical factor, zero communication) and sweeps its contiguous candidate
 slice, so the job is STRONG scaling: total work fixed at M candidates.
 
-Launch:  python bench.py [--gpus 1 --steps K --warmup W --workload ns|b|c|d|e]
+Launch:  python bench.py [--gpus 1 --steps K --warmup W --workload ns|b|c|d|e] [--full] [--dump-outputs DIR]
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and reports them (with the stage times
+and the roofline of those steps).  --full adds everything else the line used to carry, each leg outside the timed region:
+the warm step, the L-BFGS-B refinement, the CPU baseline with its parity record (and the 'ns2' selection record), the
+plug-in-level step.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float64).
 """
 import argparse
 import json
@@ -306,6 +309,14 @@ def parity_record(w, ref_vals, dev_vals):
     return out
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the last timed step handed its caller, one DIR/<name>.npy each, in float64 (indices
+    below 2^53 are exact there), so that two builds can be compared output for output on identical inputs."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), np.asarray(a, dtype=np.float64))
+
+
 def ensemble_hypers(w, n):
     """n hyper-parameter vectors around the workload's own (what an MCMC chain over (sn2, rho, ell, bias) holds): member 0 is
     the workload's point estimate.  Shared by bench.py --ensemble and tests/test_gpu_ensemble_grid.py."""
@@ -383,6 +394,8 @@ def ensemble_bench(args):
         dist.destroy_process_group()
         if rank != 0:
             return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'top_val': best[0], 'top_idx': best[1]})
     sec = elapsed / args.steps
     tot = {kk: sum(t[kk] for t in tms) for kk in ('gram', 'cholesky', 'trtri', 'alpha', 'cross_gram', 'sweep_trmm', 'acq_topk',
                                                   'sweep_trmm_launches', 'sweep_trmm_flop')}
@@ -406,7 +419,7 @@ def ensemble_bench(args):
                         'flop_per_launch': tot['sweep_trmm_flop'] / max(tot['sweep_trmm_launches'], 1),
                         'work': 'members x N^2 flop per candidate (algorithmic)', 'sclk_mhz': sclk,
                         'frac_at_measured_clock': ach / (FP64_MFMA_PEAK_TFLOPS * sclk / 2400.0) if sclk else None}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # the oracle's ensemble on a bounded sample: ALL n member fits in full + the members' EI / UCB on nc candidates
         from oracle import gp_ref
         nc = min(args.cpu_candidates or max(4096, (1 << 17) // n), Ml)
@@ -651,12 +664,17 @@ def main_sharded(args):
             name, val = kv.split('=')
             r._engine().set_option(name, int(val))
 
+    ei_target = {}                             # the EI target of the latest step (--dump-outputs)
+
     def step():
         def refit(r):
             r._fitted = False
             return r._engine()
         msh._run([lambda r=r: refit(r) for r in gp.replicas])
-        param = float(np.max(gp.posterior_mean_at_data())) if w['acq'] == 'ei' else ucb_beta(N)
+        if w['acq'] == 'ei':
+            param = ei_target['target'] = float(np.max(gp.posterior_mean_at_data()))
+        else:
+            param = ucb_beta(N)
         return gp.acq_topk(w['acq'], param, grid, k)
 
     def sync():
@@ -672,6 +690,8 @@ def main_sharded(args):
         best = step()
     sync()
     sec = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(top_val=best[0], top_idx=best[1], **ei_target))
     tms = [r._engine().timers(reset=True) for r in gp.replicas]
     stages = ('gram', 'cholesky', 'trtri', 'alpha', 'cross_gram', 'sweep_trmm', 'acq_topk')
     per = {kk: {'min': min(t[kk] for t in tms) / args.steps, 'mean': float(np.mean([t[kk] for t in tms])) / args.steps,
@@ -691,7 +711,7 @@ def main_sharded(args):
            'roofline': {'kernel': SWEEP_KERNEL, 'bound': 'mfma', 'achieved': ach, 'peak': FP64_MFMA_PEAK_TFLOPS,
                         'unit': 'TFLOP/s', 'frac': ach / FP64_MFMA_PEAK_TFLOPS, 'traffic': None,
                         'launches': int(tm['sweep_trmm_launches']), 'of': 'replica 0'}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         span = M // P
         nc = min(args.cpu_candidates or (M if N <= 2048 else (1 << 17)), span)
         out['cpu_baseline'], _ = cpu_baseline(w, nc, span, [])
@@ -709,9 +729,9 @@ def main():
     ap.add_argument('--chunk', type=int, default=0)
     ap.add_argument('--tile-order', type=int, default=-1)
     ap.add_argument('--draws', type=int, default=0, help='Thompson draws (default: 64 for workload d, 8 for e)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-refine', action='store_true', help='skip the separately reported L-BFGS refinement')
-    ap.add_argument('--cpu-candidates', type=int, default=0, help='candidates in the CPU sample (0 = auto)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and its parity records')
+    ap.add_argument('--no-refine', action='store_true', help='with --full: skip the separately reported L-BFGS refinement')
+    ap.add_argument('--cpu-candidates', type=int, default=0, help='candidates in the CPU sample of --full (0 = auto)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='process-group backend; gloo only for dry runs of the N>1 path')
     ap.add_argument('--share-device', type=int, default=-1,
@@ -722,7 +742,7 @@ def main():
                     help='observations appended per warm step (q of a batch-BO add_data(X, Y)); their cache '
                          'corrections share one pass over the candidates')
     ap.add_argument('--warm-steps', type=int, default=8,
-                    help='also time this many WARM iterations (append one observation + re-score the cached '
+                    help='with --full: also time this many WARM iterations (append one observation + re-score the cached '
                          'sweep sums); reported separately as warm_step, never as value; 0 = skip')
     ap.add_argument('--exchange', default='auto', choices=['auto', 'torch', 'gpx'],
                     help="transport of the top-k exchange: gpx = libgpx's own RCCL binding (gpx_topk_allgather: the pairs go "
@@ -731,11 +751,11 @@ def main():
                          "to torch -- loudly, on stderr and in collective.exchange -- only if the RCCL binding cannot be "
                          "brought up on every rank (or the ranks share one device: dry runs)")
     ap.add_argument('--plugin-steps', type=int, default=12,
-                    help='also time this many iterations of pybo_amd.solve_bayesopt THROUGH THE PLUGIN API at the '
+                    help='with --full: also time this many iterations of pybo_amd.solve_bayesopt THROUGH THE PLUGIN API at the '
                          'workload size (cold + warm; reported separately as plugin_step); 0 = skip')
     ap.add_argument('--ensemble', type=int, default=0,
                     help='n > 0: time the step with the reference\'s DEFAULT model instead -- an ensemble of n GPs (pybo/bayesopt.py:115: '
-                         'MCMC(gp, n=10)): n fits + ONE gpx_ensemble_sweep over the grid; own roofline (n x N^2 x M flop) and cpu_baseline')
+                         'MCMC(gp, n=10)): n fits + ONE gpx_ensemble_sweep over the grid; own roofline (n x N^2 x M flop) and (--full) cpu_baseline')
     ap.add_argument('--cpu-baseline-worker', default='', help=argparse.SUPPRESS)
     ap.add_argument('--cpu-span', type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument('--cpu-draws', default='', help=argparse.SUPPRESS)
@@ -745,7 +765,16 @@ def main():
                          "sharded: ONE process drives --gpus devices through pybo_amd.models.ShardedGP + "
                          "ShardedDeviceGrid -- the drop-in under solve_bayesopt(), no process group")
     ap.add_argument('--init-timeout', type=int, default=180, help='seconds to wait for the process group / RCCL to come up')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs beside the headline (warm step, refinement, CPU baseline + parity records, '
+                         'plug-in-level step); without it the run times the steps and reports them, nothing else')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step returned as DIR/<name>.npy in float64: top_val and top_idx (the '
+                         'top-k values and global indices; one pair per draw for Thompson), and target (the EI target) '
+                         'for EI workloads in the spmd and sharded modes; the ensemble step\'s target is fixed, not computed')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.cpu_baseline_worker:                      # child of cpu_baseline_unpinned: no GPU, no process group
         import pickle
@@ -866,6 +895,7 @@ def main():
         mine = [s for s in range(S) if s % world == rank]      # draws are the sharded unit here
 
     split = {'local': [], 'exchange': []}      # per step, this rank: seconds before / inside the exchange
+    ei_target = {}                             # the EI target of the latest step (--dump-outputs)
 
     def step():
         t_a = time.perf_counter()
@@ -905,7 +935,7 @@ def main():
         else:
             if w['acq'] == 'ei':
                 _, mx = eng.mean_at_obs()
-                param = mx
+                param = ei_target['target'] = mx
             elif w['acq'] == 'ucb':
                 param = ucb_beta(N)
             tv, ti = eng.sweep_dev(w['acq'], param, dXc.data_ptr(), Ml, k)
@@ -951,6 +981,9 @@ def main():
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
     tm = eng.timers(reset=True)
+    if rank == 0 and args.dump_outputs:
+        # the merged (value, global index) pairs of the last timed step: top-k over the grid, or one per Thompson draw
+        dump_outputs(args.dump_outputs, dict(top_val=best[0], top_idx=best[1], **ei_target))
     # every rank's own view of the timed region (N > 1: gathered so that ONE line tells where the time went on WHICH rank)
     mine_rec = {'rank': rank, 'device': local, 'local_ms': 1e3 * float(np.mean(split['local'])),
                 'exchange_ms': 1e3 * float(np.mean(split['exchange'])),
@@ -969,7 +1002,7 @@ def main():
     # (gpx_append), corrects the cached per-candidate sums of the last sweep for it (N*M covariance evaluations
     # instead of the N^2*M product) and re-scores the grid (gpx_sweep_update).  N grows by one per step.
     warm = None
-    if args.warm_steps > 0 and w['acq'] != 'thompson':
+    if args.full and args.warm_steps > 0 and w['acq'] != 'thompson':
         eng.set_option('sweep_cache', 1)
         step()                                          # one cold step fills the cache (untimed)
         eng.set_option('sweep_cache', 0)
@@ -1024,7 +1057,7 @@ def main():
     # grid sweep (pybo/solvers/lbfgs.py:56-68) -- the reference's behaviour (only the best seed's refinement is
     # returned, so only that one is computed) and the all-seeds variant in lock-step.
     refine = None
-    if rank == 0 and w['acq'] in ('ei', 'ucb') and not args.no_refine:
+    if args.full and rank == 0 and w['acq'] in ('ei', 'ucb') and not args.no_refine:
         import scipy.optimize
         from scipy.special import erfc
         from pybo_amd.solvers.lbfgs import _refine_lockstep
@@ -1223,7 +1256,7 @@ def main():
             out['warm_step'] = warm
         if 'roofline' not in out and 'cholesky' in fit:      # no sweep GEMM in this workload (Thompson)
             out['roofline'] = dict(fit['cholesky'], traffic=None)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # sample: the WHOLE sweep for N <= 2048 (config B: ~1 min of host time), otherwise SURVEY 8(d)'s 2^17
             # candidates (~100 s at N = 8192 on 128 BLAS threads) in TWO disjoint runs timed separately (linearity of the
             # extrapolation), labelled `extrapolated`.  With N > 1 ranks rank 0 times it (on its own shard) after the
@@ -1266,7 +1299,7 @@ def main():
                 # line therefore carries -- untimed -- the selection record of the variant 'ns2' (optimum off the centre): the
                 # device's top-k over the whole grid against the oracle's order.  The headline and its timing stay 'ns'.
                 out['parity']['nontrivial'] = nontrivial_selection_record(eng, dev, M, k, args.cpu_candidates)
-        if args.plugin_steps > 0 and world == 1 and w['acq'] in ('ei', 'ucb'):
+        if args.full and args.plugin_steps > 0 and world == 1 and w['acq'] in ('ei', 'ucb'):
             out['plugin_step'] = plugin_step(w, args.plugin_steps, k)
         print(json.dumps(out))
 

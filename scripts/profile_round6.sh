@@ -19,8 +19,8 @@ CPU=""; [ "$QUICK" = "quick" ] && CPU="--cpu-candidates 8192"
 # PMC: L2 -> fabric traffic of the sweep kernel (separate passes, --kernel-trace only): N = 8192 and config B's geometry
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 420 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -o p -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --warm-steps 0 --plugin-steps 0 --no-refine --candidates 131072 < /dev/null > $O/pmc_$c.log 2>&1
-  timeout 420 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmcb_$c -o p -- python $R/bench.py --workload b --steps 1 --warmup 0 --no-cpu-baseline --warm-steps 0 --plugin-steps 0 --no-refine --candidates 131072 < /dev/null > $O/pmcb_$c.log 2>&1
+  timeout 420 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -o p -- python $R/bench.py --steps 1 --warmup 0 --candidates 131072 < /dev/null > $O/pmc_$c.log 2>&1
+  timeout 420 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmcb_$c -o p -- python $R/bench.py --workload b --steps 1 --warmup 0 --candidates 131072 < /dev/null > $O/pmcb_$c.log 2>&1
 done
 f1=$(find $O/pmc_FETCH_SIZE -name "*counter_collection.csv" | head -1); f2=$(find $O/pmc_WRITE_SIZE -name "*counter_collection.csv" | head -1)
 if [ -n "$f1" ] && [ -n "$f2" ]; then python $R/scripts/pmc_traffic.py $f1 $f2 8192 65536 > $O/pmc_traffic.json; grep "k_sweep_trmm\|k_cross_gram" $f1 > $O/pmc_fetch_size.csv; grep "k_sweep_trmm\|k_cross_gram" $f2 > $O/pmc_write_size.csv; fi
@@ -29,25 +29,25 @@ if [ -n "$f1" ] && [ -n "$f2" ]; then python $R/scripts/pmc_traffic.py $f1 $f2 2
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmcb_FETCH_SIZE $O/pmcb_WRITE_SIZE
 mkdir -p $R/profiles; for f in pmc_traffic.json pmc_traffic_b.json; do [ -s $O/$f ] && cp $O/$f $R/profiles/r06_$f; done      # roofline.traffic of the bench lines below reads these
 cd $R
-timeout 1200 python bench.py --steps 5 --warmup 1 $CPU < /dev/null > $O/bench_ns.json 2> $O/bench_ns.err
-timeout 900 python bench.py --workload b --steps 5 --warmup 1 $CPU < /dev/null > $O/bench_b.json 2> $O/bench_b.err
-timeout 900 python bench.py --workload c --steps 3 --warmup 1 $CPU < /dev/null > $O/bench_c.json 2> $O/bench_c.err
+timeout 1200 python bench.py --full --steps 5 --warmup 1 $CPU < /dev/null > $O/bench_ns.json 2> $O/bench_ns.err
+timeout 900 python bench.py --full --workload b --steps 5 --warmup 1 $CPU < /dev/null > $O/bench_b.json 2> $O/bench_b.err
+timeout 900 python bench.py --full --workload c --steps 3 --warmup 1 $CPU < /dev/null > $O/bench_c.json 2> $O/bench_c.err
 for wl in d e; do
-  timeout 600 python bench.py --workload $wl --steps 3 --warmup 1 $CPU < /dev/null > $O/bench_$wl.json 2> $O/bench_$wl.err
+  timeout 600 python bench.py --full --workload $wl --steps 3 --warmup 1 $CPU < /dev/null > $O/bench_$wl.json 2> $O/bench_$wl.err
 done
-timeout 1200 python bench.py --ensemble 10 --steps 2 --warmup 1 < /dev/null > $O/bench_ns_ens10.json 2> $O/bench_ns_ens10.err
+timeout 1200 python bench.py --full --ensemble 10 --steps 2 --warmup 1 < /dev/null > $O/bench_ns_ens10.json 2> $O/bench_ns_ens10.err
 # the per-rank share of an 8-GPU run on one GPU (2^17 candidates): what the replicated fit costs there
-timeout 600 python bench.py --candidates 131072 --steps 5 --warmup 1 --no-cpu-baseline --plugin-steps 0 --no-refine --warm-steps 0 < /dev/null > $O/bench_ns_share8.json 2> $O/bench_ns_share8.err
+timeout 600 python bench.py --candidates 131072 --steps 5 --warmup 1 < /dev/null > $O/bench_ns_share8.json 2> $O/bench_ns_share8.err
 mkdir -p $R/profiles; for wl in ns b c d e; do [ -s $O/bench_$wl.json ] && cp $O/bench_$wl.json $R/profiles/r06_bench_$wl.json; done      # (what the N > 1 lines' scaling_model reads)
 # N > 1 code paths, dry runs on the one GPU (gloo transport, every rank on device 0; the RCCL launch must fail fast and loudly)
-timeout 600 python bench.py --gpus 2 --backend gloo --share-device 0 --steps 3 --warmup 1 --no-refine --plugin-steps 0 --cpu-candidates 8192 < /dev/null > $O/bench_ns_2ranks_gloo_shared_gpu.json 2> $O/bench_ns_2ranks.err
-timeout 600 python bench.py --gpus 2 --backend gloo --share-device 0 --workload d --steps 2 --warmup 1 --cpu-candidates 8192 < /dev/null > $O/bench_d_2ranks_gloo_shared_gpu.json 2> $O/bench_d_2ranks.err
+timeout 600 python bench.py --full --gpus 2 --backend gloo --share-device 0 --steps 3 --warmup 1 --no-refine --plugin-steps 0 --cpu-candidates 8192 < /dev/null > $O/bench_ns_2ranks_gloo_shared_gpu.json 2> $O/bench_ns_2ranks.err
+timeout 600 python bench.py --full --gpus 2 --backend gloo --share-device 0 --workload d --steps 2 --warmup 1 --cpu-candidates 8192 < /dev/null > $O/bench_d_2ranks_gloo_shared_gpu.json 2> $O/bench_d_2ranks.err
 ( timeout 300 python bench.py --gpus 2 --steps 1 --no-cpu-baseline < /dev/null; echo "exit code: $?" ) > $O/bench_gpus2_rccl_on_one_gpu.log 2>&1
 # kernel traces
-TOPN=24 timeout 420 bash scripts/trace.sh ns --steps 2 --warmup 1 --warm-steps 2 --plugin-steps 0 < /dev/null > $O/trace_ns.txt 2>&1
-TOPN=24 timeout 420 bash scripts/trace.sh b --workload b --steps 2 --warmup 1 --warm-steps 0 --plugin-steps 0 < /dev/null > $O/trace_b.txt 2>&1
-TOPN=24 timeout 420 bash scripts/trace.sh d --workload d --steps 2 --warmup 1 < /dev/null > $O/trace_d.txt 2>&1
-TOPN=24 timeout 420 bash scripts/trace.sh e --workload e --steps 2 --warmup 1 < /dev/null > $O/trace_e.txt 2>&1
+TOPN=24 timeout 420 bash scripts/trace.sh ns --full --steps 2 --warmup 1 --warm-steps 2 --plugin-steps 0 < /dev/null > $O/trace_ns.txt 2>&1
+TOPN=24 timeout 420 bash scripts/trace.sh b --full --workload b --steps 2 --warmup 1 --warm-steps 0 --plugin-steps 0 < /dev/null > $O/trace_b.txt 2>&1
+TOPN=24 timeout 420 bash scripts/trace.sh d --full --workload d --steps 2 --warmup 1 < /dev/null > $O/trace_d.txt 2>&1
+TOPN=24 timeout 420 bash scripts/trace.sh e --full --workload e --steps 2 --warmup 1 < /dev/null > $O/trace_e.txt 2>&1
 # PMC: MFMA busy of the sweep kernel: round 5's schedule (tile_order 27) and round 6's (19)
 cd /tmp && export TMPDIR=/tmp
 mkdir -p $O/pmc_sq

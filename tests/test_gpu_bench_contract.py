@@ -1,18 +1,21 @@
 """The bench.py contract the driver relies on, end to end on the device at a reduced candidate count: ONE JSON line
 with the metric / value / roofline / cpu_baseline fields (single rank), and the N > 1 launch path through
-torch.distributed.run (two gloo ranks sharing the one GPU of the box: same selected candidate as the single rank)."""
+torch.distributed.run (two gloo ranks sharing the one GPU of the box: same selected candidate as the single rank).
+A plain run (no --full) times the steps and nothing else; --dump-outputs writes what its last timed step returned."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ['--workload', 'b', '--candidates', '131072', '--steps', '2', '--warmup', '1', '--warm-steps', '2']
+# --full: the legs beside the headline (warm step, refinement, CPU baseline + parity, plug-in step) that these tests check
+COMMON = ['--workload', 'b', '--candidates', '131072', '--steps', '2', '--warmup', '1', '--warm-steps', '2', '--full']
 
 
 def _free_port():
@@ -80,3 +83,26 @@ def test_single_rank_line_reports_parity_and_the_plugin_level_step():
     assert p['max_rel_mu'] < 1e-6 and p['max_rel_s2'] < 1e-6 and p['max_rel_acq'] < 1e-6
     s = o['plugin_step']
     assert s['iterations'] == 3 and s['cold_ms'] > 0 and len(s['warm_ms_each']) == 2 and s['warm_ms'] > 0
+
+
+def test_plain_run_times_only_the_steps_and_dumps_their_outputs(tmp_path):
+    """Without --full the line carries the headline and the figures of the timed steps, none of the legs beside them.
+    --steps sets the number of timed steps: the sweep launches the run counts in its timed region scale with it.
+    --dump-outputs holds the last timed step's top-k and EI target, the same whatever the number of steps."""
+    plain = ['--workload', 'b', '--candidates', '131072', '--warmup', '1']
+    one = _line([sys.executable, 'bench.py'] + plain + ['--steps', '1', '--dump-outputs', str(tmp_path / 'one')])
+    o = _line([sys.executable, 'bench.py'] + plain + ['--steps', '3', '--dump-outputs', str(tmp_path / 'three')])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'roofline', 'selected'):
+        assert key in o, key
+    assert o['steps'] == 3 and abs(o['value'] * o['ms_per_step'] / 1e3 - 1.0) < 1e-9 and o['dtype'] == 'f64'
+    for key in ('warm_step', 'refine', 'cpu_baseline', 'parity', 'plugin_step'):
+        assert key not in o, key
+    assert one['roofline']['launches'] >= 1 and o['roofline']['launches'] == 3 * one['roofline']['launches']
+    names = ('top_val', 'top_idx', 'target')
+    got = {f: np.load(str(tmp_path / 'three' / (f + '.npy'))) for f in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got['top_val'].shape == got['top_idx'].shape == (10,)
+    assert int(got['top_idx'][0]) == o['selected']['index'] and float(got['top_val'][0]) == o['selected']['value']
+    assert np.all(np.diff(got['top_val']) <= 0)
+    for f in names:
+        assert np.array_equal(np.load(str(tmp_path / 'one' / (f + '.npy'))), got[f]), f
