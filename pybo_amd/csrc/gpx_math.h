@@ -45,7 +45,12 @@ __device__ __forceinline__ double exp_nonpos(double x) {
 // sqrt of a squared distance: x >= 0 (a sum of squares) or NaN.  v_rsq_f64 seed (5e-8) + one coupled Goldschmidt step +
 // two residual corrections -- the library's own iteration without its range scaling (4 instructions shorter): arguments
 // below 1e-280 (distances below 1e-140 length scales) give 0, which is what their covariance rounds to anyway.
-__device__ __forceinline__ double sqrt_r2(double x) {
+// x >= 1e300, +inf included (an overflowed scaled distance: very small length scales), gives `top` instead: every
+// covariance is 0 there, and `top` is chosen by the caller so that it stays 0 and not NaN (rsq(inf) = 0 would make g
+// NaN): Matern-1/2 passes x itself (exp(-x) = 0, also for +inf), Matern-5/2 and -3/2 pass 512, whose exponentials
+// exp(-sqrt(5) 512) and exp(-sqrt(3) 512) underflow to 0 as well while their polynomial factors stay finite (an
+// overflowed polynomial times 0 is NaN).  512 is an inline constant of the select (no register, no instruction).
+__device__ __forceinline__ double sqrt_r2(double x, double top) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y, h = 0.5 * y;
     const double r = fma(-h, g, 0.5);
@@ -55,26 +60,33 @@ __device__ __forceinline__ double sqrt_r2(double x) {
     g = fma(e, h, g);
     e = fma(-g, g, x);
     g = fma(e, h, g);
-    // 0 -> 0, NaN -> NaN; +inf (an overflowed scaled distance: very small length scales) -> +inf like the library's sqrt
-    // -- rsq(inf) = 0 makes g = inf * 0 = NaN, which would put NaN instead of 0 into every Matern covariance
-    return (x > 1.0e-280) ? ((x < 1.0e300) ? g : x) : x * 0.0;
+    return (x > 1.0e-280) ? ((x < 1.0e300) ? g : top) : x * 0.0;    // 0 -> 0, NaN -> NaN
 }
 
-// covariance as a function of the squared scaled distance r2 = sum_k ((x_k - z_k)/ell_k)^2
+// the polynomial factors of the Matern covariances in s = sqrt(2 nu) r.  Matern-5/2's 1 + s + 5/3 r^2 is written in s alone
+// (s^2 / 3 = 5/3 r^2), which stays finite for every s sqrt_r2 leads to -- (5/3) r2 overflows from r2 = 1.08e308 on; two
+// FMAs, as many as 1 + s + (5/3) r2 took
+__device__ __forceinline__ double m52_poly(double s) { return fma(s, fma(s, 1.0 / 3.0, 1.0), 1.0); }
+__device__ __forceinline__ double m32_poly(double s) { return 1.0 + s; }
+
+// covariance as a function of the squared scaled distance r2 = sum_k ((x_k - z_k)/ell_k)^2.  kern_and_grad
+// (kernels_grad.hip) evaluates its k by the same expressions in the same order: every path returns the same bits
+// for the same r2 (tests/test_gpu_devmath.py).  Accuracy there, against a 50-digit reference at the r2 consumed:
+// SE <= 1 ulp (normal results), Matern <= (3 + 2 s) eps relative; 0 wherever the exponential underflows, +inf included.
 __device__ __forceinline__ double kern_eval(int kid, double r2, double rho) {
     switch (kid) {
         case GPX_KERN_SE_ARD:
             return rho * exp_nonpos(-0.5 * r2);
         case GPX_KERN_MATERN52: {
-            const double s = 2.23606797749978969641 * sqrt_r2(r2);
-            return rho * (1.0 + s + (5.0 / 3.0) * r2) * exp_nonpos(-s);
+            const double s = 2.23606797749978969641 * sqrt_r2(r2, 512.0);
+            return rho * m52_poly(s) * exp_nonpos(-s);
         }
         case GPX_KERN_MATERN32: {
-            const double s = 1.73205080756887729353 * sqrt_r2(r2);
-            return rho * (1.0 + s) * exp_nonpos(-s);
+            const double s = 1.73205080756887729353 * sqrt_r2(r2, 512.0);
+            return rho * m32_poly(s) * exp_nonpos(-s);
         }
         default:
-            return rho * exp_nonpos(-sqrt_r2(r2));
+            return rho * exp_nonpos(-sqrt_r2(r2, r2));
     }
 }
 

@@ -20,8 +20,8 @@ namespace gpx {
 //   The candidate tile stays in LDS (k-major) for the workgroup's life; feature tiles stream through.
 //   Epilogue per accumulator element: theta_f * cos(z + b_f), summed over the tile's 128 columns into a
 //   per-row register, reduced across lanes / the two column-waves once at the end.
-// cos: 3-term Cody-Waite reduction by pi + one even polynomial on [-pi/2, pi/2] (see cos_cw).  |z| = |w.x + b| stays
-// far below the 2^20 pi validity range of the reduction.
+// cos: 2-term Cody-Waite reduction by pi + one even polynomial on [-pi/2, pi/2] (see cos_cw).  Its absolute error grows
+// with n = round(z / pi) by the dropped third term of pi: <= 3e-16 + |n| 4.05e-21 (tests/test_gpu_devmath.py).
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double cos_cw(double z) {
     // Round 3: reduction by pi (not pi/2) and ONE even polynomial on [-pi/2, pi/2]: cos z = (-1)^n cos r, r = z - n pi.
@@ -33,10 +33,12 @@ __device__ __forceinline__ double cos_cw(double z) {
     //     sits in t's low mantissa bits, so the parity of n is bit 0 of t's low word -- no v_rndne, no v_cvt_i32_f64;
     //   * the sign (-1)^n is that bit shifted into the sign position and XORed into the result's high word (two 32-bit
     //     operations, off the double-precision pipe) instead of a compare and two selects;
-    //   * two-term Cody-Waite: n pi_hi is exact (pi_hi has 33 significant bits, |n| < 2^20), the dropped third term is
-    //     n * 4e-21 -- below 1e-19 for any argument a feature can see;
+    //   * two-term Cody-Waite: z - n pi_hi is exact in the FMA (a multiple of 2^-52 below 2 in magnitude), r - n pi_lo rounds
+    //     once; the dropped third term |pi - pi_hi - pi_lo| = 4.04e-21 enters as |n| 4.04e-21 -- 4.2e-15 at |z| = 2^20 pi,
+    //     and |z| is not kept small: W carries 1/ell and, for Matern-1/2, Cauchy tails (|z| ~ 1e5-1e6 is routine there);
     //   * the Taylor series through r^20 / 20! (the next term is 1.8e-17 at |r| = pi/2).
-    // Absolute error <= 3e-16 (Horner over terms that sum to cosh(pi/2) = 2.5 in magnitude), as before; the features enter
+    // Absolute error <= 3e-16 + |n| 4.05e-21 (Horner over terms that sum to cosh(pi/2) = 2.5 in magnitude, plus the
+    // reduction), measured against a 50-digit reference up to |z| = 1e9 (tests/test_gpu_devmath.py); the features enter
     // sums of ~100 terms of size theta ~ 0.1, compared with the oracle at 1e-9 relative.
     const double t = fma(z, 3.18309886183790671538e-01, 6755399441055744.0);
     const double n = t - 6755399441055744.0;
