@@ -118,15 +118,112 @@ static void harvest(gpx_handle* h) {
     h->pending.clear();
 }
 
-// ---- lifetime ---------------------------------------------------------------------------------
-extern "C" int gpx_version(void) { return 600; }   // round * 100: 300 added gpx_predict_mean, gpx_var_at_obs, gpx_capacity, gpx_append_begin; 400 gpx_chol_trace, gpx_chol_tasks, GPX_OPTIONS; 500: timers slot 16; 510: timers slots 17, 18, options trtri_ahead*, chol_tg_fuse; 600: gpx_diagnostics, gpx_chol_tasks -> gpx_chol_tasks2 (pybo_amd/csrc/gpx_diag.h), the diagnostic options only in a -DGPX_DIAGNOSTICS build, tile_order default by size (7 below 32 block rows, 19 from there on)
-extern "C" int gpx_diagnostics(void) {
-#ifdef GPX_DIAGNOSTICS
-    return 1;
-#else
-    return 0;
-#endif
+// ---- options ----------------------------------------------------------------------------------
+// One row per option of gpx_set_option: the name; SHIP, or DIAG for the knobs of gpx_diag.h, which a library whose
+// gpx_diagnostics() is 0 refuses by name before looking at the value (a consumer of include/gpx.h cannot reach a switch
+// that leaves parts of a factorisation out); the accepted range [lo, hi] and the message that refuses a value outside it;
+// how an accepted value is stored; and where the range is not all accepted, the test `ok` (refused: `bad_ok`, else `bad`).
+enum { SHIP = 0, DIAG = 1 };
+struct Option {
+    const char* name;
+    int diag;
+    int64_t lo, hi;
+    const char* bad;
+    void (*set)(gpx_handle* h, int64_t v);
+    bool (*ok)(int64_t v) = nullptr;
+    const char* bad_ok = nullptr;
+};
+template <int gpx_handle::*F>
+static void store(gpx_handle* h, int64_t v) { h->*F = (int)v; }
+static bool mult128(int64_t v) { return v % 128 == 0; }
+static const int64_t BIG = INT64_MAX;
+static const char* const TG = "chol_tg*: out of range";
+static const char* const TRTRI = "trtri_ahead*: out of range";
+static const char* const XBG = "x_bg*: out of range";
+static const Option kOptions[] = {
+    {"chunk", SHIP, 128, BIG, "chunk must be a positive multiple of 128", [](gpx_handle* h, int64_t v) { h->chunk = v; }, mult128},
+    {"super_m", SHIP, 1, 16, "super_m must be 1, 2, 4, 8 or 16", store<&gpx_handle::super_m>, [](int64_t v) { return (v & (v - 1)) == 0; }},
+    {"tile_order", SHIP, -1, 31, "tile_order: -1 (by size) or bits 0-1 tile map (0..3), bits 2-4 k-loop schedule (1 .. 7)",
+     store<&gpx_handle::tile_order>, [](int64_t v) { return v == -1 || v >= 4; }},
+    {"sweep_cache", SHIP, -1, 1, "sweep_cache must be 1, 0 or -1",                                  // -1 also drops a live cache
+     [](gpx_handle* h, int64_t v) { h->cache_on = (v == 1); if (v < 0) { h->cache_valid = false; h->npend = 0; } }},
+    {"chol_w", SHIP, 0, 8, "chol_w must be 0 (by size) or in [2, 8]", store<&gpx_handle::chol_w>, [](int64_t v) { return v != 1; }},
+    {"chol_tg", SHIP, -1, 1000000000, TG, store<&gpx_handle::chol_tg>, [](int64_t v) { return v == 0 || v == 1; }, "chol_tg must be 0 or 1"},
+    {"chol_tg_chunks", DIAG, -1, 1000000000, TG, store<&gpx_handle::tg_chunks>},
+    {"chol_tg_grid", DIAG, -1, 1000000000, TG, store<&gpx_handle::tg_grid>},
+    {"chol_tg_trace", DIAG, -1, 1000000000, TG, store<&gpx_handle::tg_trace>},
+    {"chol_tg_isolate", DIAG, -1, 1000000000, TG, store<&gpx_handle::tg_isolate>},
+    {"chol_tg_nap", DIAG, -1, 1000000000, TG, [](gpx_handle* h, int64_t v) { h->tg_nap = (int)std::max<int64_t>(0, std::min<int64_t>(127, v)); }},
+    {"chol_tg_tmo_ms", SHIP, -1, 1000000000, TG, store<&gpx_handle::tg_tmo_ms>},
+    {"chol_tg_min", SHIP, -1, 1000000000, TG, [](gpx_handle* h, int64_t v) { h->tg_min = (int)std::max<int64_t>(1, v); }},
+    {"chol_tg_max", SHIP, -1, 1000000000, TG, [](gpx_handle* h, int64_t v) { h->tg_max = (int)std::max<int64_t>(1, v); }},
+    {"chol_tg_db", SHIP, -1, 1000000000, TG, [](gpx_handle* h, int64_t v) { h->tg_db = (v < 0) ? -1 : (v != 0 ? 1 : 0); }},
+    {"chol_tg_db_max", SHIP, -1, 1000000000, TG, [](gpx_handle* h, int64_t v) { h->tg_db_max = (int)std::max<int64_t>(0, v); }},
+    {"chol_tg_fuse", SHIP, -1, 1000000000, TG, [](gpx_handle* h, int64_t v) { h->tg_fuse = (v != 0) ? 1 : 0; }},
+    {"trtri_ahead", SHIP, 0, 1000000, TRTRI, [](gpx_handle* h, int64_t v) { h->trtri_ahead = (v != 0) ? 1 : 0; }},
+    {"trtri_ahead_min", SHIP, 0, 1000000, TRTRI, [](gpx_handle* h, int64_t v) { h->trtri_ahead_min = (int)std::max<int64_t>(4, v); }},
+    {"chol_fuse", SHIP, 0, 1, "chol_fuse must be 0 or 1", store<&gpx_handle::chol_fuse>},
+    {"chol_graph", SHIP, 0, 1, "chol_graph must be 0 or 1", store<&gpx_handle::chol_graph>},
+    {"chol_merge", SHIP, 0, 100000, "chol_merge: 0 (off) or a minimum number of block rows", store<&gpx_handle::chol_merge>},
+    {"chol_rl", SHIP, 0, 1, "chol_rl must be 0 or 1", store<&gpx_handle::chol_rl>},
+    {"x_skip", DIAG, 0, 7, "x_skip: bits 0..2", store<&gpx_handle::x_skip>},      // see launch_cholesky
+    {"x_bg", DIAG, 0, 10000000, XBG, store<&gpx_handle::x_bg>},
+    {"x_bg_lds", DIAG, 0, 10000000, XBG, store<&gpx_handle::x_bg_lds>},
+    {"x_bg_iters", DIAG, 0, 10000000, XBG, store<&gpx_handle::x_bg_iters>},
+    // A/B of the Thompson sweep kernels: process-wide, not per handle
+    {"x_rff", DIAG, 0, 1, "x_rff must be 0 (by size) or 1 (the round-3 kernel)", [](gpx_handle*, int64_t v) { gpx::g_rff_variant = (int)v; }},
+    {"grad_form", SHIP, 0, 2, "grad_form must be 0 (auto), 1 (two passes) or 2 (one pass)", store<&gpx_handle::grad_form>},
+    {"grad_rb_cs", DIAG, 0, 65536, "grad_rb_cs must be a multiple of 128 (0 = default)", store<&gpx_handle::grad_rb_cs>, mult128},
+    {"grad_kernel", SHIP, -1, 1, "grad_kernel must be -1 (auto), 0 or 1", store<&gpx_handle::grad_kernel>},
+    {"trtri_left", SHIP, 0, 1, "trtri_left must be 0 or 1", store<&gpx_handle::trtri_left>},
+    {"refine_inverse", SHIP, 0, 1, "refine_inverse must be 0 or 1", [](gpx_handle* h, int64_t v) { h->refine_inverse = (v != 0); }},
+    {"eager_inverse", SHIP, 0, 1, "eager_inverse must be 0 or 1", [](gpx_handle* h, int64_t v) { h->eager_inverse = (v != 0); }},
+};
+
+extern "C" int gpx_set_option(gpx_handle* h, const char* name, int64_t value) {
+    return guarded(h, [&]() -> int {
+        if (!h || !name) return GPX_EARG;
+        for (const Option& o : kOptions) {
+            if (strcmp(name, o.name)) continue;
+            if (o.diag && !gpx_diagnostics())
+                return fail(h, GPX_EARG, "diagnostic option: only in a library built with -DGPX_DIAGNOSTICS (libgpx_diag.so)");
+            if (value < o.lo || value > o.hi) return fail(h, GPX_EARG, o.bad);
+            if (o.ok && !o.ok(value)) return fail(h, GPX_EARG, o.bad_ok ? o.bad_ok : o.bad);
+            o.set(h, value);
+            return GPX_OK;
+        }
+        return fail(h, GPX_EARG, "unknown option");
+    });
 }
+
+// GPX_OPTIONS="name=value,name=value": options every new handle starts with (A/B runs THROUGH the plug-in layer, whose
+// handles the caller never sees).  Empty entries are skipped; returns the first entry that is malformed or that
+// gpx_set_option refuses, "" when all were applied.
+static std::string apply_env_options(gpx_handle* h) {
+    const char* env = getenv("GPX_OPTIONS");
+    const std::string all(env ? env : "");
+    for (size_t pos = 0; pos < all.size();) {
+        size_t end = all.find(',', pos);
+        if (end == std::string::npos) end = all.size();
+        const std::string kv = all.substr(pos, end - pos);
+        pos = end + 1;
+        if (kv.empty()) continue;
+        const size_t eq = kv.find('=');
+        char* tail = nullptr;
+        const long long v = (eq == std::string::npos) ? 0 : strtoll(kv.c_str() + eq + 1, &tail, 10);
+        if (eq == std::string::npos || eq == 0 || !tail || *tail != 0 || tail == kv.c_str() + eq + 1 ||
+            gpx_set_option(h, kv.substr(0, eq).c_str(), (int64_t)v) != GPX_OK)
+            return kv;
+    }
+    return "";
+}
+
+// ---- lifetime ---------------------------------------------------------------------------------
+// gpx_version() = round * 100.  300: gpx_predict_mean, gpx_var_at_obs, gpx_capacity, gpx_append_begin.  400: gpx_chol_trace,
+// gpx_chol_tasks, GPX_OPTIONS.  500: timers slot 16.  510: timers slots 17, 18, options trtri_ahead*, chol_tg_fuse.
+// 600: gpx_diagnostics, gpx_chol_tasks -> gpx_chol_tasks2 (gpx_diag.h), the diagnostic options only in the diagnostics
+// build, tile_order default by size (7 below 32 block rows, 19 from there on).
+extern "C" int gpx_version(void) { return 600; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -194,28 +291,13 @@ static int create_impl(int device, void* stream, gpx_handle** out) {
     (void)hipMemsetAsync(h->dclk, 0, 32, h->stream);
     (void)hipStreamSynchronize(h->stream);
     *out = h;
-    // GPX_OPTIONS="name=value,name=value": options every new handle starts with (A/B runs THROUGH the plug-in layer, whose
-    // handles the caller never sees); an unknown name or a bad value fails the creation loudly
-    if (const char* env = getenv("GPX_OPTIONS")) {
-        std::string all(env);
-        size_t pos = 0;
-        while (pos < all.size()) {
-            size_t end = all.find(',', pos);
-            if (end == std::string::npos) end = all.size();
-            const std::string kv = all.substr(pos, end - pos);
-            pos = end + 1;
-            if (kv.empty()) continue;
-            const size_t eq = kv.find('=');
-            char* tail = nullptr;
-            const long long v = (eq == std::string::npos) ? 0 : strtoll(kv.c_str() + eq + 1, &tail, 10);
-            if (eq == std::string::npos || eq == 0 || !tail || *tail != 0 || tail == kv.c_str() + eq + 1 ||
-                gpx_set_option(h, kv.substr(0, eq).c_str(), (int64_t)v) != GPX_OK) {
-                g_create_err = "gpx_create: GPX_OPTIONS: bad entry '" + kv + "'";
-                *out = nullptr;
-                gpx_destroy(h);
-                return GPX_EARG;
-            }
-        }
+    // an unknown name or a bad value in GPX_OPTIONS fails the creation loudly
+    const std::string bad = apply_env_options(h);
+    if (!bad.empty()) {
+        g_create_err = "gpx_create: GPX_OPTIONS: bad entry '" + bad + "'";
+        *out = nullptr;
+        gpx_destroy(h);
+        return GPX_EARG;
     }
     return GPX_OK;
 }
@@ -273,139 +355,6 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     return GPX_OK;
 }
 
-extern "C" int gpx_set_option(gpx_handle* h, const char* name, int64_t value) {
-    return guarded(h, [&]() -> int {
-        if (!h || !name) return GPX_EARG;
-        if (!strcmp(name, "chunk")) {
-            if (value < 128 || value % 128) return fail(h, GPX_EARG, "chunk must be a positive multiple of 128");
-            h->chunk = value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "super_m")) {
-            if (value != 1 && value != 2 && value != 4 && value != 8 && value != 16)
-                return fail(h, GPX_EARG, "super_m must be 1, 2, 4, 8 or 16");
-            h->super_m = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "tile_order")) {
-            if (value != -1 && (value < 4 || value > 31))
-                return fail(h, GPX_EARG, "tile_order: -1 (by size) or bits 0-1 tile map (0..3), bits 2-4 k-loop schedule (1 .. 7)");
-            h->tile_order = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "sweep_cache")) {
-            if (value < -1 || value > 1) return fail(h, GPX_EARG, "sweep_cache must be 1, 0 or -1");
-            h->cache_on = (value == 1);
-            if (value < 0) { h->cache_valid = false; h->npend = 0; }
-            return GPX_OK;
-        }
-        if (!strcmp(name, "chol_w")) {
-            if (value != 0 && (value < 2 || value > 8)) return fail(h, GPX_EARG, "chol_w must be 0 (by size) or in [2, 8]");
-            h->chol_w = (int)value;
-            return GPX_OK;
-        }
-#ifndef GPX_DIAGNOSTICS
-        // the shipping library knows the diagnostic knobs by name only: a consumer of include/gpx.h cannot reach a switch that
-        // leaves parts of a factorisation out (pybo_amd/csrc/gpx_diag.h; libgpx_diag.so accepts them)
-        for (const char* dn : {"chol_tg_chunks", "chol_tg_nap", "chol_tg_grid", "chol_tg_isolate", "chol_tg_trace", "grad_rb_cs", "x_rff",
-                               "x_skip", "x_bg", "x_bg_lds", "x_bg_iters"})
-            if (!strcmp(name, dn)) return fail(h, GPX_EARG, "diagnostic option: only in a library built with -DGPX_DIAGNOSTICS (libgpx_diag.so)");
-#endif
-        if (!strcmp(name, "chol_tg") || !strcmp(name, "chol_tg_chunks") ||
-            !strcmp(name, "chol_tg_grid") || !strcmp(name, "chol_tg_trace") || !strcmp(name, "chol_tg_tmo_ms") ||
-            !strcmp(name, "chol_tg_min") || !strcmp(name, "chol_tg_max") || !strcmp(name, "chol_tg_isolate") ||
-            !strcmp(name, "chol_tg_nap") || !strcmp(name, "chol_tg_db") || !strcmp(name, "chol_tg_db_max") ||
-            !strcmp(name, "chol_tg_fuse")) {
-            if (value < -1 || value > 1000000000) return fail(h, GPX_EARG, "chol_tg*: out of range");
-            const char* sub = name + 7;
-            if (*sub == 0) { if (value != 0 && value != 1) return fail(h, GPX_EARG, "chol_tg must be 0 or 1"); h->chol_tg = (int)value; }
-            else if (!strcmp(sub, "_db")) h->tg_db = (value < 0) ? -1 : (value != 0 ? 1 : 0);
-            else if (!strcmp(sub, "_db_max")) h->tg_db_max = (int)std::max<int64_t>(0, value);
-            else if (!strcmp(sub, "_nap")) h->tg_nap = (int)std::max<int64_t>(0, std::min<int64_t>(127, value));
-            else if (!strcmp(sub, "_chunks")) h->tg_chunks = (int)value;
-            else if (!strcmp(sub, "_grid")) h->tg_grid = (int)value;
-            else if (!strcmp(sub, "_trace")) h->tg_trace = (int)value;
-            else if (!strcmp(sub, "_tmo_ms")) h->tg_tmo_ms = (int)value;
-            else if (!strcmp(sub, "_isolate")) h->tg_isolate = (int)value;
-            else if (!strcmp(sub, "_fuse")) h->tg_fuse = (value != 0) ? 1 : 0;
-            else if (!strcmp(sub, "_max")) h->tg_max = (int)std::max<int64_t>(1, value);
-            else h->tg_min = (int)std::max<int64_t>(1, value);
-            return GPX_OK;
-        }
-        if (!strcmp(name, "trtri_ahead") || !strcmp(name, "trtri_ahead_min")) {
-            if (value < 0 || value > 1000000) return fail(h, GPX_EARG, "trtri_ahead*: out of range");
-            if (name[11] == 0) h->trtri_ahead = (value != 0) ? 1 : 0;
-            else h->trtri_ahead_min = (int)std::max<int64_t>(4, value);
-            return GPX_OK;
-        }
-        if (!strcmp(name, "chol_fuse")) {
-            if (value != 0 && value != 1) return fail(h, GPX_EARG, "chol_fuse must be 0 or 1");
-            h->chol_fuse = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "chol_graph")) {
-            if (value != 0 && value != 1) return fail(h, GPX_EARG, "chol_graph must be 0 or 1");
-            h->chol_graph = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "chol_merge")) {
-            if (value < 0 || value > 100000) return fail(h, GPX_EARG, "chol_merge: 0 (off) or a minimum number of block rows");
-            h->chol_merge = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "chol_rl")) {
-            if (value != 0 && value != 1) return fail(h, GPX_EARG, "chol_rl must be 0 or 1");
-            h->chol_rl = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "x_skip")) {       // diagnostic only: see launch_cholesky
-            if (value < 0 || value > 7) return fail(h, GPX_EARG, "x_skip: bits 0..2");
-            h->x_skip = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "x_bg") || !strcmp(name, "x_bg_lds") || !strcmp(name, "x_bg_iters")) {   // diagnostic only
-            if (value < 0 || value > 10000000) return fail(h, GPX_EARG, "x_bg*: out of range");
-            (name[4] == 0 ? h->x_bg : (name[5] == 'l' ? h->x_bg_lds : h->x_bg_iters)) = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "x_rff")) {       // diagnostic: A/B of the Thompson sweep kernels (process-wide)
-            if (value < 0 || value > 1) return fail(h, GPX_EARG, "x_rff must be 0 (by size) or 1 (the round-3 kernel)");
-            gpx::g_rff_variant = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "grad_form")) {
-            if (value < 0 || value > 2) return fail(h, GPX_EARG, "grad_form must be 0 (auto), 1 (two passes) or 2 (one pass)");
-            h->grad_form = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "grad_rb_cs")) {
-            if (value < 0 || value % 128 || value > 65536) return fail(h, GPX_EARG, "grad_rb_cs must be a multiple of 128 (0 = default)");
-            h->grad_rb_cs = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "grad_kernel")) {
-            if (value < -1 || value > 1) return fail(h, GPX_EARG, "grad_kernel must be -1 (auto), 0 or 1");
-            h->grad_kernel = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "trtri_left")) {
-            if (value != 0 && value != 1) return fail(h, GPX_EARG, "trtri_left must be 0 or 1");
-            h->trtri_left = (int)value;
-            return GPX_OK;
-        }
-        if (!strcmp(name, "refine_inverse")) {
-            if (value != 0 && value != 1) return fail(h, GPX_EARG, "refine_inverse must be 0 or 1");
-            h->refine_inverse = (value != 0);
-            return GPX_OK;
-        }
-        if (!strcmp(name, "eager_inverse")) {
-            if (value != 0 && value != 1) return fail(h, GPX_EARG, "eager_inverse must be 0 or 1");
-            h->eager_inverse = (value != 0);
-            return GPX_OK;
-        }
-        return fail(h, GPX_EARG, "unknown option");
-    });
-}
 
 extern "C" int gpx_sync(gpx_handle* h) {
     return guarded(h, [&]() -> int {
@@ -953,17 +902,59 @@ static int topk_core(gpx_handle* h, const double* d_vals, int64_t M, int64_t k, 
     return GPX_OK;
 }
 
+// The acquisition arguments of every sweep (`what` prefixes the message): the id and its parameter, then k and the top-k
+// outputs (two calls: ensemble_sweep checks its candidates between them).
+static int check_acq(gpx_handle* h, const char* what, int acq_id, const double* params, int nparams) {
+    if (acq_id < GPX_ACQ_EI || acq_id > GPX_ACQ_MEAN) return fail(h, GPX_EARG, (std::string(what) + ": unknown acquisition id").c_str());
+    if (acq_id != GPX_ACQ_MEAN && (nparams < 1 || !params))
+        return fail(h, GPX_EARG, (std::string(what) + ": missing acquisition parameter").c_str());
+    return GPX_OK;
+}
+
+static int check_topk(gpx_handle* h, const char* what, int64_t k, const double* top_val, const int64_t* top_idx) {
+    if (k < 0 || k > TOPK_MAX) return fail(h, GPX_EARG, (std::string(what) + ": k must be in [0, 4096]").c_str());
+    if (k > 0 && (!top_val || !top_idx)) return fail(h, GPX_EARG, (std::string(what) + ": NULL top-k output").c_str());
+    return GPX_OK;
+}
+
+// The host form of a sweep: stage [Xc (M,d), when given][acq M][mu M][s2 M] in h->dXc, run `core` on the device buffers
+// (mu / s2 only where the caller wants them), copy the requested outputs back and synchronise.  `sync_upload`: the core
+// reads the candidates from other streams.
+template <typename Core>
+static int staged_sweep(gpx_handle* h, const double* Xc, int64_t M, bool sync_upload, double* acq_all, double* mu, double* s2,
+                        Core&& core) {
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t nx = Xc ? M * h->d : 0;
+    int rc;
+    if ((rc = ensure(h, h->dXc, h->cap_xc, nx + 3 * M))) return rc;
+    double* dX = h->dXc;
+    double* dacq = dX + nx;
+    double* dmu = dacq + M;
+    double* ds2 = dmu + M;
+    if (Xc) {
+        Span sp(h, T_COPY);
+        HIPCHK(h, hipMemcpyAsync(dX, Xc, (size_t)nx * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    if (sync_upload) HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = core(dX, dacq, mu ? dmu : nullptr, s2 ? ds2 : nullptr))) return rc;
+    {
+        Span sp(h, T_COPY);
+        if (acq_all) HIPCHK(h, hipMemcpyAsync(acq_all, dacq, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
+        if (mu) HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
+        if (s2) HIPCHK(h, hipMemcpyAsync(s2, ds2, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return GPX_OK;
+}
+
 static int sweep_core(gpx_handle* h, int acq_id, const double* params, int nparams, const double* dXc,
                       int64_t M, int64_t k, double* top_val, int64_t* top_idx, double* d_acq,
                       double* d_mu, double* d_s2) {
     if (!h->fitted) return fail(h, GPX_ESTATE, "sweep: model is not fitted");
     if (!dXc || M < 1) return fail(h, GPX_EARG, "sweep: need M >= 1 candidates");
-    if (acq_id < GPX_ACQ_EI || acq_id > GPX_ACQ_MEAN) return fail(h, GPX_EARG, "sweep: unknown acquisition id");
-    if (acq_id != GPX_ACQ_MEAN && (nparams < 1 || !params)) return fail(h, GPX_EARG, "sweep: missing acquisition parameter");
-    if (k < 0 || k > TOPK_MAX) return fail(h, GPX_EARG, "sweep: k must be in [0, 4096]");
-    if (k > 0 && (!top_val || !top_idx)) return fail(h, GPX_EARG, "sweep: NULL top-k output");
-    HIPCHK(h, hipSetDevice(h->device));
     int rc;
+    if ((rc = check_acq(h, "sweep", acq_id, params, nparams)) || (rc = check_topk(h, "sweep", k, top_val, top_idx))) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
     if ((rc = ensure_inverse(h))) return rc;
     hipStream_t s = h->stream;
     const int64_t Np = h->Np;
@@ -1044,30 +1035,9 @@ extern "C" int gpx_sweep(gpx_handle* h, int acq_id, const double* params, int np
         if (!h) return GPX_EARG;
         if (!h->fitted) return fail(h, GPX_ESTATE, "sweep: model is not fitted");
         if (!Xc || M < 1) return fail(h, GPX_EARG, "sweep: need M >= 1 candidates");
-        HIPCHK(h, hipSetDevice(h->device));
-        int rc;
-        const int64_t d = h->d;
-        // staging: [Xc (M*d)] [acq M] [mu M] [s2 M]
-        if ((rc = ensure(h, h->dXc, h->cap_xc, M * d + 3 * M))) return rc;
-        double* dX = h->dXc;
-        double* dacq = dX + M * d;
-        double* dmu = dacq + M;
-        double* ds2 = dmu + M;
-        {
-            Span sp(h, T_COPY);
-            HIPCHK(h, hipMemcpyAsync(dX, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, h->stream));
-        }
-        rc = sweep_core(h, acq_id, params, nparams, dX, M, k, top_val, top_idx, dacq, mu ? dmu : nullptr,
-                        s2 ? ds2 : nullptr);
-        if (rc) return rc;
-        {
-            Span sp(h, T_COPY);
-            if (acq_all) HIPCHK(h, hipMemcpyAsync(acq_all, dacq, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-            if (mu) HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-            if (s2) HIPCHK(h, hipMemcpyAsync(s2, ds2, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return GPX_OK;
+        return staged_sweep(h, Xc, M, false, acq_all, mu, s2, [&](double* dX, double* dacq, double* dmu, double* ds2) {
+            return sweep_core(h, acq_id, params, nparams, dX, M, k, top_val, top_idx, dacq, dmu, ds2);
+        });
     });
 }
 
@@ -1079,13 +1049,11 @@ static int sweep_update_core(gpx_handle* h, int acq_id, const double* params, in
     if (!h->cache_valid)
         return fail(h, GPX_ESTATE, "sweep_update: no valid sweep cache (set option sweep_cache = 1 and run a full "
                                    "sweep; a refit invalidates it)");
-    if (acq_id < GPX_ACQ_EI || acq_id > GPX_ACQ_MEAN) return fail(h, GPX_EARG, "sweep_update: unknown acquisition id");
-    if (acq_id != GPX_ACQ_MEAN && (nparams < 1 || !params)) return fail(h, GPX_EARG, "sweep_update: missing acquisition parameter");
-    if (k < 0 || k > TOPK_MAX) return fail(h, GPX_EARG, "sweep_update: k must be in [0, 4096]");
-    if (k > 0 && (!top_val || !top_idx)) return fail(h, GPX_EARG, "sweep_update: NULL top-k output");
+    int rc;
+    if ((rc = check_acq(h, "sweep_update", acq_id, params, nparams)) || (rc = check_topk(h, "sweep_update", k, top_val, top_idx)))
+        return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const int64_t M = h->cache_M;
-    int rc;
     if ((rc = flush_pending(h))) return rc;
     if (!d_acq) {
         if ((rc = ensure(h, h->dout, h->cap_out, M))) return rc;
@@ -1117,24 +1085,9 @@ extern "C" int gpx_sweep_update(gpx_handle* h, int acq_id, const double* params,
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
         if (!h->cache_valid) return fail(h, GPX_ESTATE, "sweep_update: no valid sweep cache");
-        HIPCHK(h, hipSetDevice(h->device));
-        const int64_t M = h->cache_M;
-        int rc;
-        if ((rc = ensure(h, h->dXc, h->cap_xc, 3 * M))) return rc;       // staging [acq M][mu M][s2 M]
-        double* dacq = h->dXc;
-        double* dmu = dacq + M;
-        double* ds2 = dmu + M;
-        rc = sweep_update_core(h, acq_id, params, nparams, k, top_val, top_idx, dacq, mu ? dmu : nullptr,
-                               s2 ? ds2 : nullptr);
-        if (rc) return rc;
-        {
-            Span sp(h, T_COPY);
-            if (acq_all) HIPCHK(h, hipMemcpyAsync(acq_all, dacq, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-            if (mu) HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-            if (s2) HIPCHK(h, hipMemcpyAsync(s2, ds2, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return GPX_OK;
+        return staged_sweep(h, nullptr, h->cache_M, false, acq_all, mu, s2, [&](double*, double* dacq, double* dmu, double* ds2) {
+            return sweep_update_core(h, acq_id, params, nparams, k, top_val, top_idx, dacq, dmu, ds2);
+        });
     });
 }
 
@@ -1277,6 +1230,13 @@ extern "C" int gpx_rff_grad(gpx_handle* h, const double* W, const double* b, con
     });
 }
 
+// the wide-feature paths (n >= 128) one draw at a time: W (n,d) and b (n,) of draw q to the device
+static int upload_draw(gpx_handle* h, const double* W, const double* b, int64_t q, int64_t n, double* dW, double* db) {
+    HIPCHK(h, hipMemcpyAsync(dW, W + q * n * h->d, (size_t)n * h->d * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(db, b + q * n, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    return GPX_OK;
+}
+
 // feature Grams of S draws (n < 128 features each) on the device: dA (S,n,n), dv (S,n) inside h->drff, followed by
 // `extra` spare doubles (*dextra) for the caller
 static int rff_gram_batch_dev(gpx_handle* h, const double* W, const double* b, int64_t S, int64_t n, int64_t extra,
@@ -1336,8 +1296,7 @@ extern "C" int gpx_rff_gram_batch(gpx_handle* h, const double* W, const double* 
             double* dv = dA + n * n;
             double* dFt = dv + n;
             for (int64_t q = 0; q < S; ++q) {
-                HIPCHK(h, hipMemcpyAsync(dW, W + q * n * d, (size_t)n * d * 8, hipMemcpyHostToDevice, s));
-                HIPCHK(h, hipMemcpyAsync(db, b + q * n, (size_t)n * 8, hipMemcpyHostToDevice, s));
+                if ((rc = upload_draw(h, W, b, q, n, dW, db))) return rc;
                 {
                     Span sp(h, T_RFF);
                     launch_rff_gram(s, h->dXraw, dFt, N, (int)d, dW, db, (int)n, h->dy, h->bias, dA, dv);
@@ -1390,8 +1349,7 @@ extern "C" int gpx_rff_posterior(gpx_handle* h, const double* W, const double* b
             double* dFt = dR + np * np;
             int* pflag = h->dflag + 8;
             for (int64_t q = 0; q < S; ++q) {
-                HIPCHK(h, hipMemcpyAsync(dW, W + q * n * d, (size_t)n * d * 8, hipMemcpyHostToDevice, s));
-                HIPCHK(h, hipMemcpyAsync(db, b + q * n, (size_t)n * 8, hipMemcpyHostToDevice, s));
+                if ((rc = upload_draw(h, W, b, q, n, dW, db))) return rc;
                 HIPCHK(h, hipMemcpyAsync(dz, z + q * n, (size_t)n * 8, hipMemcpyHostToDevice, s));
                 int flag = 0;
                 {
@@ -1441,11 +1399,10 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
                          const double* dXc, int64_t M, int64_t k, double* top_val, int64_t* top_idx,
                          double* d_out, double* d_mu, double* d_s2) {
     gpx_handle* L = mem[0];
-    if (acq_id < GPX_ACQ_EI || acq_id > GPX_ACQ_MEAN) return fail(L, GPX_EARG, "ensemble_sweep: unknown acquisition id");
-    if (acq_id != GPX_ACQ_MEAN && (nparams < 1 || !params)) return fail(L, GPX_EARG, "ensemble_sweep: missing acquisition parameter");
+    int rc;
+    if ((rc = check_acq(L, "ensemble_sweep", acq_id, params, nparams))) return rc;
     if (!dXc || M < 1) return fail(L, GPX_EARG, "ensemble_sweep: need M >= 1 candidates");
-    if (k < 0 || k > TOPK_MAX) return fail(L, GPX_EARG, "ensemble_sweep: k must be in [0, 4096]");
-    if (k > 0 && (!top_val || !top_idx)) return fail(L, GPX_EARG, "ensemble_sweep: NULL top-k output");
+    if ((rc = check_topk(L, "ensemble_sweep", k, top_val, top_idx))) return rc;
     for (int m = 0; m < n; ++m) {
         if (!mem[m]->fitted) return fail(L, GPX_ESTATE, "ensemble_sweep: a member model is not fitted");
         if (mem[m]->device != L->device || mem[m]->d != L->d)
@@ -1454,7 +1411,6 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
     HIPCHK(L, hipSetDevice(L->device));
     // mixture moments for UCB / mean (mu = mean mu_m, s2 = mean(s2_m + mu_m^2) - mu^2), plain mean for EI / PI
     const int mode = (acq_id == GPX_ACQ_UCB || acq_id == GPX_ACQ_MEAN) ? 1 : 0;
-    int rc;
     if ((rc = ensure(L, L->dens, L->cap_ens, 5 * M))) return rc;
     double* acc0 = L->dens;
     double* acc1 = acc0 + M;
@@ -1526,30 +1482,10 @@ extern "C" int gpx_ensemble_sweep(gpx_handle* const* members, int n_members, int
         if (!Xc || M < 1) return fail(h, GPX_EARG, "ensemble_sweep: need M >= 1 candidates");
         if ((mu || s2) && acq_id != GPX_ACQ_UCB && acq_id != GPX_ACQ_MEAN)
             return fail(h, GPX_EARG, "ensemble_sweep: mixture moments are only formed for UCB / mean");
-        HIPCHK(h, hipSetDevice(h->device));
-        int rc;
-        const int64_t d = h->d;
-        if ((rc = ensure(h, h->dXc, h->cap_xc, M * d + 3 * M))) return rc;
-        double* dX = h->dXc;
-        double* dacq = dX + M * d;
-        double* dmu = dacq + M;
-        double* ds2 = dmu + M;
-        {
-            Span sp(h, T_COPY);
-            HIPCHK(h, hipMemcpyAsync(dX, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, h->stream));
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));     // the members read dX from their own streams
-        rc = ensemble_core(members, n_members, acq_id, params, nparams, dX, M, k, top_val, top_idx, dacq,
-                           mu ? dmu : nullptr, s2 ? ds2 : nullptr);
-        if (rc) return rc;
-        {
-            Span sp(h, T_COPY);
-            if (acq_all) HIPCHK(h, hipMemcpyAsync(acq_all, dacq, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-            if (mu) HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-            if (s2) HIPCHK(h, hipMemcpyAsync(s2, ds2, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return GPX_OK;
+        // (true: the members read the candidates from their own streams)
+        return staged_sweep(h, Xc, M, true, acq_all, mu, s2, [&](double* dX, double* dacq, double* dmu, double* ds2) {
+            return ensemble_core(members, n_members, acq_id, params, nparams, dX, M, k, top_val, top_idx, dacq, dmu, ds2);
+        });
     });
 }
 

@@ -1,10 +1,11 @@
 /*
  * gpx_diag.h -- diagnostic entry points and options of libgpx (NOT part of the shipping C-ABI, include/gpx.h).
  *
- * The entry points below are exported by every build (they only read).  The OPTIONS below are accepted by gpx_set_option
- * only in a library built with -DGPX_DIAGNOSTICS (build.sh builds it next to the shipping one: pybo_amd/csrc/libgpx_diag.so;
- * Python: GPX_DIAGNOSTICS=1 in the environment selects it, tests/conftest.py does); the shipping libgpx.so answers them
- * with GPX_EARG -- a consumer of include/gpx.h cannot switch parts of a factorisation off by a typo.
+ * The entry points below are exported by every build (they only read).  The OPTIONS below (the DIAG rows of gpx_set_option's
+ * table in api.hip) are accepted only by a library whose diag_flag.cpp was compiled with -DGPX_DIAGNOSTICS (build.sh builds
+ * it next to the shipping one: pybo_amd/csrc/libgpx_diag.so; Python: GPX_DIAGNOSTICS=1 in the environment selects it,
+ * tests/conftest.py does); the shipping libgpx.so answers them with GPX_EARG -- a consumer of include/gpx.h cannot switch
+ * parts of a factorisation off by a typo.
  *
  *   "chol_tg_chunks"  k-chunk sizes of the task-graph factorisation counted back from the pivot as decimal digits (9 = 16 blocks)
  *                     [0 = by size: 112489 = 1, 1, 2, 4, 8, 16, 16, ..; up to 36 blocks 11112489]

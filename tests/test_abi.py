@@ -35,7 +35,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_shipping_and_diagnostics_builds_export_the_same_abi():
-    """build.sh links two libraries from the same objects (api.hip compiled without / with -DGPX_DIAGNOSTICS): both export every
+    """build.sh links two libraries from the same objects but diag_flag.cpp (compiled without / with -DGPX_DIAGNOSTICS): both export every
     symbol of include/gpx.h and csrc/gpx_diag.h; gpx_diagnostics() tells them apart; the header stays within its size budget."""
     from pybo_amd import _lib
     libdir = os.path.join(ROOT, 'pybo_amd', 'csrc')
@@ -53,6 +53,34 @@ def test_shipping_and_diagnostics_builds_export_the_same_abi():
         assert '"%s"' % name not in public, name
 
 
+# what test_shipping_library_refuses_the_diagnostic_options offers the shipping library (every one must be refused)
+DIAG_PROBES = (('x_skip', 1), ('x_bg', 4), ('x_bg_lds', 8), ('x_bg_iters', 10), ('chol_tg_chunks', 1248), ('chol_tg_nap', 8),
+               ('chol_tg_grid', 64), ('chol_tg_isolate', 0), ('chol_tg_trace', 1), ('grad_rb_cs', 128), ('x_rff', 1))
+
+
+def _option_table():
+    """{name: diagnostic-only} from the rows of gpx_set_option's table in api.hip."""
+    src = open(os.path.join(ROOT, 'pybo_amd', 'csrc', 'api.hip')).read()
+    rows = re.findall(r'^\s*\{"([a-z0-9_]+)", (SHIP|DIAG),', src, flags=re.M)
+    return {name: flag == 'DIAG' for name, flag in rows}
+
+
+def test_option_table_agrees_with_the_headers():
+    """The option table in api.hip is the one list of options: every shipping row is documented in include/gpx.h, the
+    diagnostic rows are exactly the options gpx_diag.h documents, the shipping library's refusal test asks for diagnostic
+    rows only, and no preprocessor test of GPX_DIAGNOSTICS is left in api.hip (diag_flag.cpp is the only difference)."""
+    table = _option_table()
+    assert len(table) >= 30
+    public = open(os.path.join(ROOT, 'include', 'gpx.h')).read()
+    for name, diag in table.items():
+        assert diag or '"%s"' % name in public, name
+    quoted = set(re.findall(r'"([a-z][a-z0-9_]*)"', open(os.path.join(ROOT, 'pybo_amd', 'csrc', 'gpx_diag.h')).read()))
+    assert {name for name, diag in table.items() if diag} == quoted
+    assert {name for name, _ in DIAG_PROBES} <= {name for name, diag in table.items() if diag}
+    src = open(os.path.join(ROOT, 'pybo_amd', 'csrc', 'api.hip')).read()
+    assert not re.search(r'^\s*#\s*if.*GPX_DIAGNOSTICS', src, flags=re.M)
+
+
 @pytest.mark.gpu
 def test_shipping_library_refuses_the_diagnostic_options():
     """A handle of the SHIPPING library answers every diagnostic knob with GPX_EARG (and keeps working); the diagnostics build
@@ -66,8 +94,7 @@ def test_shipping_library_refuses_the_diagnostic_options():
     ship.gpx_destroy.argtypes = [C.c_void_p]
     h = C.c_void_p()
     assert ship.gpx_create(0, None, C.byref(h)) == 0
-    for name, val in (('x_skip', 1), ('x_bg', 4), ('x_bg_lds', 8), ('x_bg_iters', 10), ('chol_tg_chunks', 1248), ('chol_tg_nap', 8),
-                      ('chol_tg_grid', 64), ('chol_tg_isolate', 0), ('chol_tg_trace', 1), ('grad_rb_cs', 128), ('x_rff', 1)):
+    for name, val in DIAG_PROBES:
         assert ship.gpx_set_option(h, name.encode(), val) == _lib.GPX_EARG, name
         assert b'GPX_DIAGNOSTICS' in ship.gpx_last_error(h)
     for name, val in (('chunk', 256), ('tile_order', 27), ('chol_tg', 0), ('chol_tg_min', 3), ('eager_inverse', 1)):
