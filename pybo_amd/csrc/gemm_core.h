@@ -49,6 +49,20 @@ __device__ __forceinline__ void acc_zero(d4 (&acc)[4][4]) {
         for (int j = 0; j < 4; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
 }
 
+// The sustained shader clock of a launch (the power-bound sweeps: k_sweep_trmm*, k_rff_mfma5): every workgroup stamps both
+// clocks at entry and adds its lifetime in s_memtime ticks (shader clocks) to clk[0] and in wall_clock64 ticks (100 MHz) to
+// clk[1] at exit -- the bench line's roofline.frac_at_measured_clock (two atomics per workgroup of ~1.8 ms; clk may be null).
+struct LaunchClock {
+    const unsigned long long c0, r0;
+    __device__ __forceinline__ LaunchClock() : c0(__builtin_readcyclecounter()), r0(wall_clock64()) {}
+    __device__ __forceinline__ void add(unsigned long long* clk) const {
+        if (clk && threadIdx.x == 0) {
+            atomicAdd(clk, (unsigned long long)__builtin_readcyclecounter() - c0);
+            atomicAdd(clk + 1, (unsigned long long)wall_clock64() - r0);
+        }
+    }
+};
+
 // A, B already point at (k = 0, m = tile origin) / (k = 0, n = tile origin); k_lo, k_hi are multiples of BK;
 // all 256 threads of the workgroup must call this.
 //

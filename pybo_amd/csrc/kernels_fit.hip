@@ -590,111 +590,84 @@ void launch_cholesky(gpx_handle* h) {
 // `hb` merges block ranges [r1, r1+hb) and [r1+hb, r1+hb+size2):
 //      T_21 = - T_22 (L_21 T_11),   L_21(m,k) = R[r1+k][r2+m]
 // as two GEMM launches over all groups.  Every operand is k-major: L_21 via R, T_11 via T (row-major
-// lower), T_22 via U = T^T.  GEMM2 stores T_21 and, transposed, U_12, keeping both views current.
+// lower), T_22 via U = T^T.  The second product stores T_21 and, transposed, U_12, keeping both views current.
+//
+// A tile of either product is 128x128 (4 waves, operands by LDS-DMA) or, for the levels that do not fill the chip with
+// those, 64x64 (8 waves, gemm_tile_64_g): there the makespan was ONE workgroup walking the longest K (hb = 16 at
+// N = 8192: 512 tiles, K up to 2048, 480 us for 18 GFLOP = 38 TFLOP/s against 67 at the last level).  Four times the
+// workgroups, a quarter of the MFMA work each, and the triangular structure of T11 / T22 is followed at 64-row granularity.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(GEMM_THREADS, 2) void k_trtri_gemm1(const double* __restrict__ R,
-                                                                 const double* __restrict__ T,
-                                                                 double* __restrict__ W, int64_t Np,
-                                                                 int nP, int hb, int g0) {
-    // K-extent of a tile is (hb - bn) blocks: bn is the SLOW grid index so tiles are dispatched heaviest
-    // first (LPT) -- with bn fastest, some CU slots drew two K = hb*128 tiles and set the makespan
-    const int g = blockIdx.z + g0, bm = blockIdx.x, bn = blockIdx.y;
-    const int r1 = g * 2 * hb, r2 = r1 + hb;
-    if (r2 >= nP) return;
-    const int size2 = min(hb, nP - r2);
-    if (bm >= size2) return;
-    __shared__ __attribute__((aligned(16))) double smem[GEMM_LDS_F64];
-    const int64_t r1e = (int64_t)r1 * NB, r2e = (int64_t)r2 * NB;
-    const int64_t m0 = r2e + (int64_t)bm * NB, n0 = r1e + (int64_t)bn * NB;
-    d4 acc[4][4];
-    acc_zero(acc);
-    gemm_tile_128_l<32, 1, 2>(acc, R + r1e * Np + m0, Np, T + r1e * Np + n0, Np, bn * NB, hb * NB, smem);      // operands by LDS-DMA (round 6)
+struct Tile128 {
+    static constexpr int EDGE = NB, THREADS = GEMM_THREADS, WGS = 2, LDS_F64 = GEMM_LDS_F64;
+    typedef d4 Acc[4][4];
+    static __device__ __forceinline__ void zero(Acc& acc) { acc_zero(acc); }
+    // TAIL: the last k-block of the left factor is triangular: its all-zero quarter-rows are skipped (interleaved row blocks)
+    template <bool TAIL>
+    static __device__ __forceinline__ void loop(Acc& acc, const double* A, const double* B, int64_t Np, int k_lo, int k_hi, double* smem) {
+        gemm_tile_128_l<32, 1, 2, TAIL, TAIL>(acc, A, Np, B, Np, k_lo, k_hi, smem);
+    }
+    // f(row, column, value) for every accumulator element of this thread; ILV: the rows a TAIL loop leaves (acc_row_ilv)
+    template <bool ILV, class F>
+    static __device__ __forceinline__ void for_each(const Acc& acc, F f) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+            for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) W[(m0 + acc_row(i, r)) * Np + n0 + acc_col(j)] = acc[i][j][r];
-}
+                for (int r = 0; r < 4; ++r) f(ILV ? acc_row_ilv(i, r) : acc_row(i, r), acc_col(j), acc[i][j][r]);
+    }
+};
 
-__global__ __launch_bounds__(GEMM_THREADS, 2) void k_trtri_gemm2(const double* __restrict__ W,
-                                                                 double* __restrict__ T,
-                                                                 double* __restrict__ U, int64_t Np,
-                                                                 int nP, int hb, int g0) {
-    // K-extent is (bm + 1) blocks: heaviest (largest bm) first
-    const int g = blockIdx.z + g0, bm = hb - 1 - (int)blockIdx.y, bn = blockIdx.x;
-    const int r1 = g * 2 * hb, r2 = r1 + hb;
-    if (r2 >= nP) return;
-    const int size2 = min(hb, nP - r2);
-    if (bm >= size2) return;
-    __shared__ __attribute__((aligned(16))) double smem[GEMM_LDS_F64];
-    const int64_t r1e = (int64_t)r1 * NB, r2e = (int64_t)r2 * NB;
-    const int64_t m0 = r2e + (int64_t)bm * NB, n0 = r1e + (int64_t)bn * NB;
-    d4 acc[4][4];
-    acc_zero(acc);
-    // A(m,k) = T_22(m,k) = U[r2e+k][m0+m], k <= m  ->  k-blocks [0, bm]
-    gemm_tile_128_l<32, 1, 2, true, true>(acc, U + r2e * Np + m0, Np, W + r2e * Np + n0, Np, 0, (bm + 1) * NB, smem);      // the last k-block of T_22 is triangular: its all-zero quarter-rows are skipped (interleaved row blocks: acc_row_ilv)
+struct Tile64 {
+    static constexpr int EDGE = T64, THREADS = GEMM64_THREADS, WGS = 1, LDS_F64 = GEMM64_LDS_F64;
+    typedef d4 Acc[2];
+    static __device__ __forceinline__ void zero(Acc& acc) { acc[0] = acc[1] = (d4){0.0, 0.0, 0.0, 0.0}; }
+    template <bool TAIL>
+    static __device__ __forceinline__ void loop(Acc& acc, const double* A, const double* B, int64_t Np, int k_lo, int k_hi, double* smem) {
+        gemm_tile_64_g<false>(acc, A, Np, B, Np, k_lo, k_hi, smem);
+    }
+    template <bool ILV, class F>
+    static __device__ __forceinline__ void for_each(const Acc& acc, F f) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t gm = m0 + acc_row_ilv(i, r), gn = n0 + acc_col(j);
-                const double v = -acc[i][j][r];
-                T[gm * Np + gn] = v;
-                U[gn * Np + gm] = v;
-            }
-}
+            for (int r = 0; r < 4; ++r) f(acc_row64(i, r), acc_col64(), acc[i][r]);
+    }
+};
 
-// The same two products on 64x64 tiles (8 waves, gemm_tile_64_g) for the levels that do not fill the chip with
-// 128x128 tiles: there the makespan was ONE workgroup walking the longest K (hb = 16 at N = 8192: 512 tiles,
-// K up to 2048, 480 us for 18 GFLOP = 38 TFLOP/s against 67 at the last level).  Four times the workgroups, a
-// quarter of the MFMA work each, and the triangular structure of T11 / T22 is followed at 64-row granularity.
-__global__ __launch_bounds__(GEMM64_THREADS) void k_trtri_gemm1_64(const double* __restrict__ R,
-                                                                  const double* __restrict__ T,
-                                                                  double* __restrict__ W, int64_t Np, int nP,
-                                                                  int hb, int g0) {
-    const int g = blockIdx.z + g0, bm = blockIdx.x, bn = blockIdx.y;        // 64-row / 64-column tile indices
-    const int r1 = g * 2 * hb, r2 = r1 + hb;
-    if (r2 >= nP) return;
-    const int size2 = min(hb, nP - r2);
-    if (bm >= 2 * size2) return;
-    __shared__ __attribute__((aligned(16))) double smem[GEMM64_LDS_F64];
-    const int64_t r1e = (int64_t)r1 * NB, r2e = (int64_t)r2 * NB;
-    const int64_t m0 = r2e + (int64_t)bm * T64, n0 = r1e + (int64_t)bn * T64;
-    d4 acc[2] = {(d4){0.0, 0.0, 0.0, 0.0}, (d4){0.0, 0.0, 0.0, 0.0}};
-    gemm_tile_64_g<false>(acc, R + r1e * Np + m0, Np, T + r1e * Np + n0, Np, bn * T64, hb * NB, smem);   // T11[k][n] = 0 for k < n
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) W[(m0 + acc_row64(i, r)) * Np + n0 + acc_col64()] = acc[i][r];
-}
+// The two products of a level, C(m, n) = sum_k A(m, k) B(k, n) on the tile (bm, bn) of group g's (size2 x hb)-block T_21:
+//   HEAD  k over [bn, hb) blocks: B is the lower triangular T_11, zero for k < n.  K-extent of a tile is (hb - bn) blocks: bn is
+//         the SLOW grid index so tiles are dispatched heaviest first (LPT) -- with bn fastest, some CU slots drew two K = hb*128
+//         tiles and set the makespan.                                          A, B at block row r1
+//   TAIL  k over [0, bm]: A is the lower triangular T_22 (= U k-major), zero for k > m; bm counted DOWN from the top along the
+//         slow grid index (heaviest first).                                    A, B at block row r2
+// and the three ways they end: TO_W  out = C;  TO_WT  outT = C^T;  TO_TU  out = -C and outT = -C^T (T_21 and U_12).
+enum { HEAD, TAIL };
+enum { TO_W, TO_WT, TO_TU };
 
-__global__ __launch_bounds__(GEMM64_THREADS) void k_trtri_gemm2_64(const double* __restrict__ W,
-                                                                  double* __restrict__ T,
-                                                                  double* __restrict__ U, int64_t Np, int nP,
-                                                                  int hb, int g0) {
-    const int g = blockIdx.z + g0, bm = 2 * hb - 1 - (int)blockIdx.y, bn = blockIdx.x;   // heaviest (largest bm) first
+template <class Tile, int PROD, int STORE>
+__global__ __launch_bounds__(Tile::THREADS, Tile::WGS) void k_trtri_gemm(const double* __restrict__ A, const double* __restrict__ B,
+                                                                       double* __restrict__ out, double* __restrict__ outT,
+                                                                       int64_t Np, int nP, int hb, int g0) {
+    constexpr int E = Tile::EDGE, PER = NB / E;      // tile edge, tiles per 128-block
+    const int g = blockIdx.z + g0;
+    const int bm = (PROD == HEAD) ? (int)blockIdx.x : PER * hb - 1 - (int)blockIdx.y, bn = (PROD == HEAD) ? blockIdx.y : blockIdx.x;
     const int r1 = g * 2 * hb, r2 = r1 + hb;
     if (r2 >= nP) return;
     const int size2 = min(hb, nP - r2);
-    if (bm >= 2 * size2) return;
-    __shared__ __attribute__((aligned(16))) double smem[GEMM64_LDS_F64];
+    if (bm >= PER * size2) return;
+    __shared__ __attribute__((aligned(16))) double smem[Tile::LDS_F64];
     const int64_t r1e = (int64_t)r1 * NB, r2e = (int64_t)r2 * NB;
-    const int64_t m0 = r2e + (int64_t)bm * T64, n0 = r1e + (int64_t)bn * T64;
-    d4 acc[2] = {(d4){0.0, 0.0, 0.0, 0.0}, (d4){0.0, 0.0, 0.0, 0.0}};
-    // A(m,k) = T_22(m,k) = U[r2e+k][m0+m], zero for k > m  ->  k in [0, (bm + 1) * 64)
-    gemm_tile_64_g<false>(acc, U + r2e * Np + m0, Np, W + r2e * Np + n0, Np, 0, (bm + 1) * T64, smem);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int64_t gm = m0 + acc_row64(i, r), gn = n0 + acc_col64();
-            const double v = -acc[i][r];
-            T[gm * Np + gn] = v;
-            U[gn * Np + gm] = v;
-        }
+    const int64_t m0 = r2e + (int64_t)bm * E, n0 = r1e + (int64_t)bn * E;
+    typename Tile::Acc acc;
+    Tile::zero(acc);
+    if (PROD == HEAD) Tile::template loop<false>(acc, A + r1e * Np + m0, B + r1e * Np + n0, Np, bn * E, hb * NB, smem);
+    else Tile::template loop<true>(acc, A + r2e * Np + m0, B + r2e * Np + n0, Np, 0, (bm + 1) * E, smem);
+    Tile::template for_each<PROD == TAIL>(acc, [&](int row, int col, double v) {
+        const int64_t gm = m0 + row, gn = n0 + col;
+        if (STORE != TO_WT) out[gm * Np + gn] = (STORE == TO_TU) ? -v : v;
+        if (STORE != TO_W) outT[gn * Np + gm] = (STORE == TO_TU) ? -v : v;
+    });
 }
 
 // ---- the same recursion RE-ASSOCIATED (round 4, option trtri_left):  T_21 = - (T_22 L_21) T_11 -------------------------
@@ -707,123 +680,43 @@ __global__ __launch_bounds__(GEMM64_THREADS) void k_trtri_gemm2_64(const double*
 // 1.2-1.9x smaller with this order, the variance's is not; it costs one transposition pass (L_21 as a RIGHT factor needs
 // L row-major: the strictly upper 128-blocks of R go to the strictly LOWER blocks of the workspace S; W' = T_22 L_21 is
 // stored TRANSPOSED into S's upper blocks, where the second product reads it as its k-major left factor).  Off by default.
-__global__ __launch_bounds__(1024) void k_transpose_offdiag(const double* __restrict__ R, int64_t Np, double* __restrict__ Lrm) {
-    // 32 x 32 tiles of the strictly upper 128-blocks of R -> the mirrored position
-    const int by = blockIdx.y, bx = blockIdx.x;
-    if ((bx >> 2) <= (by >> 2)) return;
+//
+// At = A^T through 32 x 32 LDS tiles; OFFDIAG: only the tiles of the strictly upper 128-blocks (-> the mirrored position)
+template <bool OFFDIAG>
+__global__ __launch_bounds__(1024) void k_transpose(const double* __restrict__ A, int64_t Np, double* __restrict__ At) {
+    if (OFFDIAG && ((int)blockIdx.x >> 2) <= ((int)blockIdx.y >> 2)) return;
     __shared__ double tile[32][33];
-    const int64_t r0 = (int64_t)by * 32, c0 = (int64_t)bx * 32;
-    tile[threadIdx.y][threadIdx.x] = R[(r0 + threadIdx.y) * Np + c0 + threadIdx.x];
+    const int64_t r0 = (int64_t)blockIdx.y * 32, c0 = (int64_t)blockIdx.x * 32;
+    tile[threadIdx.y][threadIdx.x] = A[(r0 + threadIdx.y) * Np + c0 + threadIdx.x];
     __syncthreads();
-    Lrm[(c0 + threadIdx.y) * Np + r0 + threadIdx.x] = tile[threadIdx.x][threadIdx.y];
+    At[(c0 + threadIdx.y) * Np + r0 + threadIdx.x] = tile[threadIdx.x][threadIdx.y];
 }
 
-__global__ __launch_bounds__(GEMM_THREADS, 2) void k_trtri_gemm1r(const double* __restrict__ U, double* __restrict__ S,
-                                                                  int64_t Np, int nP, int hb) {
-    // W'(m, n) = sum_k T_22(m, k) L_21(k, n), k <= m: heaviest (largest bm) first
-    const int g = blockIdx.z, bm = hb - 1 - (int)blockIdx.y, bn = blockIdx.x;
-    const int r1 = g * 2 * hb, r2 = r1 + hb;
-    if (r2 >= nP) return;
-    const int size2 = min(hb, nP - r2);
-    if (bm >= size2) return;
-    __shared__ __attribute__((aligned(16))) double smem[GEMM_LDS_F64];
-    const int64_t r1e = (int64_t)r1 * NB, r2e = (int64_t)r2 * NB;
-    const int64_t m0 = r2e + (int64_t)bm * NB, n0 = r1e + (int64_t)bn * NB;
-    d4 acc[4][4];
-    acc_zero(acc);
-    gemm_tile_128_l<32, 1, 2, true, true>(acc, U + r2e * Np + m0, Np, S + r2e * Np + n0, Np, 0, (bm + 1) * NB, smem);      // the last k-block of T_22 is triangular: its all-zero quarter-rows are skipped (interleaved row blocks: acc_row_ilv)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) S[(n0 + acc_col(j)) * Np + m0 + acc_row_ilv(i, r)] = acc[i][j][r];     // W'^T, upper position
-}
-
-__global__ __launch_bounds__(GEMM_THREADS, 2) void k_trtri_gemm2r(const double* __restrict__ S, double* __restrict__ T,
-                                                                  double* __restrict__ U, int64_t Np, int nP, int hb) {
-    // T_21(m, n) = - sum_k W'(m, k) T_11(k, n), k >= n: bn is the SLOW grid index (heaviest first)
-    const int g = blockIdx.z, bm = blockIdx.x, bn = blockIdx.y;
-    const int r1 = g * 2 * hb, r2 = r1 + hb;
-    if (r2 >= nP) return;
-    const int size2 = min(hb, nP - r2);
-    if (bm >= size2) return;
-    __shared__ __attribute__((aligned(16))) double smem[GEMM_LDS_F64];
-    const int64_t r1e = (int64_t)r1 * NB, r2e = (int64_t)r2 * NB;
-    const int64_t m0 = r2e + (int64_t)bm * NB, n0 = r1e + (int64_t)bn * NB;
-    d4 acc[4][4];
-    acc_zero(acc);
-    gemm_tile_128_l<32, 1, 2>(acc, S + r1e * Np + m0, Np, T + r1e * Np + n0, Np, bn * NB, hb * NB, smem);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t gm = m0 + acc_row(i, r), gn = n0 + acc_col(j);
-                const double v = -acc[i][j][r];
-                T[gm * Np + gn] = v;
-                U[gn * Np + gm] = v;
-            }
-}
-
-__global__ __launch_bounds__(GEMM64_THREADS) void k_trtri_gemm1r_64(const double* __restrict__ U, double* __restrict__ S,
-                                                                   int64_t Np, int nP, int hb) {
-    const int g = blockIdx.z, bm = 2 * hb - 1 - (int)blockIdx.y, bn = blockIdx.x;   // heaviest (largest bm) first
-    const int r1 = g * 2 * hb, r2 = r1 + hb;
-    if (r2 >= nP) return;
-    const int size2 = min(hb, nP - r2);
-    if (bm >= 2 * size2) return;
-    __shared__ __attribute__((aligned(16))) double smem[GEMM64_LDS_F64];
-    const int64_t r1e = (int64_t)r1 * NB, r2e = (int64_t)r2 * NB;
-    const int64_t m0 = r2e + (int64_t)bm * T64, n0 = r1e + (int64_t)bn * T64;
-    d4 acc[2] = {(d4){0.0, 0.0, 0.0, 0.0}, (d4){0.0, 0.0, 0.0, 0.0}};
-    gemm_tile_64_g<false>(acc, U + r2e * Np + m0, Np, S + r2e * Np + n0, Np, 0, (bm + 1) * T64, smem);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) S[(n0 + acc_col64()) * Np + m0 + acc_row64(i, r)] = acc[i][r];
-}
-
-__global__ __launch_bounds__(GEMM64_THREADS) void k_trtri_gemm2r_64(const double* __restrict__ S, double* __restrict__ T,
-                                                                   double* __restrict__ U, int64_t Np, int nP, int hb) {
-    const int g = blockIdx.z, bm = blockIdx.x, bn = blockIdx.y;
-    const int r1 = g * 2 * hb, r2 = r1 + hb;
-    if (r2 >= nP) return;
-    const int size2 = min(hb, nP - r2);
-    if (bm >= 2 * size2) return;
-    __shared__ __attribute__((aligned(16))) double smem[GEMM64_LDS_F64];
-    const int64_t r1e = (int64_t)r1 * NB, r2e = (int64_t)r2 * NB;
-    const int64_t m0 = r2e + (int64_t)bm * T64, n0 = r1e + (int64_t)bn * T64;
-    d4 acc[2] = {(d4){0.0, 0.0, 0.0, 0.0}, (d4){0.0, 0.0, 0.0, 0.0}};
-    gemm_tile_64_g<false>(acc, S + r1e * Np + m0, Np, T + r1e * Np + n0, Np, bn * T64, hb * NB, smem);   // T11[k][n] = 0 for k < n
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int64_t gm = m0 + acc_row64(i, r), gn = n0 + acc_col64();
-            const double v = -acc[i][r];
-            T[gm * Np + gn] = v;
-            U[gn * Np + gm] = v;
-        }
-}
-
-// level hb over the groups [g0, g0 + ng): `which` = 1 the first product (W = L_21 T_11), 2 the second (T_21 = -T_22 W), 3 both.
+// level hb over the groups [g0, g0 + ng): `which` = 1 the first product, 2 the second, 3 both:
+//   default   W = L_21 T_11 (HEAD, into the workspace S), then T_21 = -T_22 W (TAIL)
+//   left      W'^T = (T_22 L_21)^T (TAIL, into S's upper blocks), then T_21 = -W' T_11 (HEAD)
 // The tile size follows the WHOLE level (ngroups_all), so that a level computed in two parts runs the same kernels.
-static void trtri_level(gpx_handle* h, hipStream_t s, int hb, int g0, int ng, int which) {
+static void trtri_level(gpx_handle* h, hipStream_t s, int hb, int g0, int ng, int which, bool left = false) {
     const int64_t Np = h->Np;
     const int nP = (int)(Np / NB);
     if (ng <= 0) return;
     const int ngroups_all = (nP + 2 * hb - 1) / (2 * hb);
-    if ((int64_t)hb * hb * ngroups_all >= 1024) {         // enough 128x128 tiles to fill the chip twice over
-        dim3 grid((unsigned)hb, (unsigned)hb, (unsigned)ng);
-        if (which & 1) hipLaunchKernelGGL(k_trtri_gemm1, grid, dim3(GEMM_THREADS), 0, s, h->dR, h->dT, h->dS, Np, nP, hb, g0);
-        if (which & 2) hipLaunchKernelGGL(k_trtri_gemm2, grid, dim3(GEMM_THREADS), 0, s, h->dS, h->dT, h->dU, Np, nP, hb, g0);
-    } else {
-        dim3 grid((unsigned)(2 * hb), (unsigned)(2 * hb), (unsigned)ng);
-        if (which & 1) hipLaunchKernelGGL(k_trtri_gemm1_64, grid, dim3(GEMM64_THREADS), 0, s, h->dR, h->dT, h->dS, Np, nP, hb, g0);
-        if (which & 2) hipLaunchKernelGGL(k_trtri_gemm2_64, grid, dim3(GEMM64_THREADS), 0, s, h->dS, h->dT, h->dU, Np, nP, hb, g0);
-    }
+    auto level = [&](auto tile) {
+        typedef decltype(tile) Tile;
+        const unsigned e = (unsigned)(hb * (NB / Tile::EDGE));
+        const dim3 grid(e, e, (unsigned)ng), blk(Tile::THREADS);
+        double* const none = nullptr;
+        if (which & 1) {
+            if (!left) hipLaunchKernelGGL((k_trtri_gemm<Tile, HEAD, TO_W>), grid, blk, 0, s, h->dR, h->dT, h->dS, none, Np, nP, hb, g0);
+            else hipLaunchKernelGGL((k_trtri_gemm<Tile, TAIL, TO_WT>), grid, blk, 0, s, h->dU, h->dS, none, h->dS, Np, nP, hb, g0);
+        }
+        if (which & 2) {
+            if (!left) hipLaunchKernelGGL((k_trtri_gemm<Tile, TAIL, TO_TU>), grid, blk, 0, s, h->dU, h->dS, h->dT, h->dU, Np, nP, hb, g0);
+            else hipLaunchKernelGGL((k_trtri_gemm<Tile, HEAD, TO_TU>), grid, blk, 0, s, h->dS, h->dT, h->dT, h->dU, Np, nP, hb, g0);
+        }
+    };
+    if ((int64_t)hb * hb * ngroups_all >= 1024) level(Tile128());         // enough 128x128 tiles to fill the chip twice over
+    else level(Tile64());
 }
 
 // the top level's split point: the largest power of two below nP (block rows [0, top) | [top, nP))
@@ -870,22 +763,9 @@ void launch_trtri(gpx_handle* h) {
     }
     const bool left = h->trtri_left != 0;          // re-associated recursion (option, off by default)
     if (left && nP > 1)
-        hipLaunchKernelGGL(k_transpose_offdiag, dim3((unsigned)(Np / 32), (unsigned)(Np / 32)), dim3(32, 32), 0, s, h->dR, Np, h->dS);
-    for (int hb = 1; hb < nP; hb *= 2) {
-        const int ngroups = (nP + 2 * hb - 1) / (2 * hb);
-        if (!left) { trtri_level(h, s, hb, 0, ngroups, 3); continue; }
-        if ((int64_t)hb * hb * ngroups >= 1024) {
-            dim3 grid((unsigned)hb, (unsigned)hb, (unsigned)ngroups);
-            hipLaunchKernelGGL(k_trtri_gemm1r, grid, dim3(GEMM_THREADS), 0, s, h->dU, h->dS, Np, nP, hb);
-            hipLaunchKernelGGL(k_trtri_gemm2r, grid, dim3(GEMM_THREADS), 0, s, h->dS, h->dT, h->dU, Np, nP, hb);
-        } else {
-            dim3 grid((unsigned)(2 * hb), (unsigned)(2 * hb), (unsigned)ngroups);
-            hipLaunchKernelGGL(k_trtri_gemm1r_64, grid, dim3(GEMM64_THREADS), 0, s, h->dU, h->dS, Np, nP, hb);
-            hipLaunchKernelGGL(k_trtri_gemm2r_64, grid, dim3(GEMM64_THREADS), 0, s, h->dS, h->dT, h->dU, Np, nP, hb);
-        }
-    }
+        hipLaunchKernelGGL(k_transpose<true>, dim3((unsigned)(Np / 32), (unsigned)(Np / 32)), dim3(32, 32), 0, s, h->dR, Np, h->dS);
+    for (int hb = 1; hb < nP; hb *= 2) trtri_level(h, s, hb, 0, (nP + 2 * hb - 1) / (2 * hb), 3, left);
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // OPTION "refine_inverse": one Newton step on the triangular inverse, in the form that serves the sweep.
@@ -899,20 +779,12 @@ void launch_trtri(gpx_handle* h) {
 // squares the left residual down to the rounding error of E itself (~eps |T| |L|, what a row-wise substitution leaves).
 // Both products are lower x lower triangular GEMMs on the tile engine; L as a k-major B operand needs a transposed
 // copy of R (every operand here is k-major: R row-major serves L only as an A operand).  2 N^3 / 3 more flop.
-//   k_transpose_full   Lrm = R^T                                  (Np x Np, 32 x 32 tiles through LDS)
+//   k_transpose<false>   Lrm = R^T                                (Np x Np, 32 x 32 tiles through LDS)
 //   k_tri_lower_prod<1>  Et(J-cols, I-rows) = (delta - sum_K T(I,K) L(K,J))^T        A = U (= T^T, k-major T), B = Lrm
 //   k_tri_lower_prod<2>  T1(I,J) = T(I,J) + sum_K E(I,K) T(K,J), U(J,I) = T1(I,J)^T   A = Et (k-major E), B = T
 // K runs over blocks J..I (both factors lower triangular).  T1 goes to the workspace (T is still being read), U is
 // rewritten in place (not an input of the second product); the caller swaps the T buffer with the workspace.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_transpose_full(const double* __restrict__ A, int64_t Np, double* __restrict__ At) {
-    __shared__ double tile[32][33];
-    const int64_t r0 = (int64_t)blockIdx.y * 32, c0 = (int64_t)blockIdx.x * 32;
-    tile[threadIdx.y][threadIdx.x] = A[(r0 + threadIdx.y) * Np + c0 + threadIdx.x];
-    __syncthreads();
-    At[(c0 + threadIdx.y) * Np + r0 + threadIdx.x] = tile[threadIdx.x][threadIdx.y];
-}
-
 template <int MODE>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void k_tri_lower_prod(const double* __restrict__ Ak,
                                                                     const double* __restrict__ Bk,
@@ -960,7 +832,7 @@ void launch_refine_inverse(gpx_handle* h, double* tmp) {
     const int nP = (int)(Np / NB);
     hipStream_t s = h->stream;
     const unsigned ntiles = (unsigned)(nP * (nP + 1) / 2);
-    hipLaunchKernelGGL(k_transpose_full, dim3((unsigned)(Np / 32), (unsigned)(Np / 32)), dim3(32, 32), 0, s, h->dR, Np, h->dS);
+    hipLaunchKernelGGL(k_transpose<false>, dim3((unsigned)(Np / 32), (unsigned)(Np / 32)), dim3(32, 32), 0, s, h->dR, Np, h->dS);
     hipLaunchKernelGGL(k_tri_lower_prod<1>, dim3(ntiles), dim3(GEMM_THREADS), 0, s, h->dU, h->dS, (const double*)nullptr,
                        (double*)nullptr, tmp, Np, nP);
     hipLaunchKernelGGL(k_tri_lower_prod<2>, dim3(ntiles), dim3(GEMM_THREADS), 0, s, tmp, h->dT, h->dT, h->dS, h->dU, Np, nP);

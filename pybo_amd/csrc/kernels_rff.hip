@@ -227,10 +227,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_rff_mfma5(const double* __r
                                                                double bias, const double* __restrict__ Xc, int64_t M,
                                                                double* __restrict__ vals, unsigned long long* clk) {
     extern __shared__ __attribute__((aligned(16))) double lds[];   // At[dp][LDT] | Bt[1 or 2][dp + 2][LDT] (rows dp, dp + 1: b, theta)
-    // the shader clock this launch sustains (it is power-bound: ~2.1 GHz against the 2.4 GHz of the peak): workgroup lifetimes
-    // in s_memtime and in 100 MHz ticks, as in k_sweep_trmm
-    const unsigned long long clk_c0 = __builtin_readcyclecounter();
-    const unsigned long long clk_r0 = wall_clock64();
+    const LaunchClock lc;      // the shader clock this launch sustains (it is power-bound: ~2.1 GHz against the 2.4 GHz of the peak)
     double* At = lds;
     double* Bt0 = lds + dp * LDT;
     const int bstride = (dp + 2) * LDT;
@@ -366,10 +363,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_rff_mfma5(const double* __r
             }
         __syncthreads();   // the next tile's image is complete
     }
-    if (clk && t == 0) {
-        atomicAdd(clk, (unsigned long long)__builtin_readcyclecounter() - clk_c0);
-        atomicAdd(clk + 1, (unsigned long long)wall_clock64() - clk_r0);
-    }
+    lc.add(clk);
 }
 
 // device staging layout for the MFMA path: [Wt S*nfb*dp*128][bt S*nfb*128][tt S*nfb*128]

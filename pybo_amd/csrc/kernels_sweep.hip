@@ -253,6 +253,35 @@ __device__ __forceinline__ void sweep_epilogue(const d4 (&acc)[4][4], const doub
     }
 }
 
+// The frame of every schedule of the dominant kernel: the workgroup's tile (or tile pair) from the map, per tile the operand
+// pointers, the K-extent and the up/down rule, the k-loop `loop(acc, At, Bt, kend, rev)` of the schedule, the epilogue.
+// (interleaved row blocks in every schedule: the column sums then add a tile's rows in the same order everywhere)
+template <int RES, class Loop>
+__device__ __forceinline__ void sweep_tiles(int b, const double* __restrict__ U, int64_t Np, const double* __restrict__ Ks, int NT,
+                                            const double* __restrict__ avec, double* __restrict__ Qp, double* __restrict__ Pp,
+                                            int64_t ldp, int order, int sm, unsigned long long* clk, double* smem, Loop loop) {
+    const LaunchClock lc;
+    const int nP = (int)(Np / TB);
+    int mt, nt, mt2;
+    if (!sweep_tile_of<RES>(b, order, sm, NT, nP, mt, nt, mt2)) return;
+#pragma unroll 1
+    for (int ph = 0; ph < 2; ++ph) {
+        if (ph == 1) {
+            if (mt2 < 0) break;
+            mt = mt2;
+            __syncthreads();               // the epilogue's LDS reads are done before the next tile stages
+        }
+        const int64_t m0 = (int64_t)mt * TB, n0 = (int64_t)nt * TB;
+        d4 acc[4][4];
+        acc_zero(acc);
+        loop(acc, U + m0, Ks + (int64_t)nt * Np * TB, (mt + 1) * TB, sweep_tile_rev(mt, nP));
+        // the k-loop ended on a barrier, LDS is free
+        sweep_epilogue<true>(acc, avec, m0, Qp + (int64_t)mt * ldp + n0, Pp + (int64_t)mt * ldp + n0, smem);
+    }
+    lc.add(clk);
+}
+
+// The register-staged schedules of rounds 1 (VAR 2), 2 (5) and 5 (6).
 template <int VAR>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm(const double* __restrict__ U, int64_t Np,
                                                                 const double* __restrict__ Ks,
@@ -262,44 +291,18 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm(const double* __
                                                                 double* __restrict__ Pp, int64_t ldp,
                                                                 int order, int sm, unsigned long long* clk) {
     __shared__ __attribute__((aligned(16))) double smem[GEMM_LDS_F64];
-    // the sustained shader clock of this launch: every workgroup adds its lifetime in s_memtime ticks (shader clocks) and in
-    // s_memrealtime ticks (100 MHz) to two counters -- the bench line's roofline.frac_at_measured_clock (two atomics per
-    // workgroup of ~1.8 ms)
-    const unsigned long long clk_c0 = __builtin_readcyclecounter();
-    const unsigned long long clk_r0 = wall_clock64();
-    const int nP = (int)(Np / TB);
-    int mt, nt, mt2;
-    if (!sweep_tile_of<64>(blockIdx.x, order, sm, NT, nP, mt, nt, mt2)) return;
-#pragma unroll 1
-  for (int ph = 0; ph < 2; ++ph) {
-    if (ph == 1) {
-        if (mt2 < 0) break;
-        mt = mt2;
-        __syncthreads();               // the epilogue's LDS reads are done before the next tile stages
-    }
-    const int64_t m0 = (int64_t)mt * TB, n0 = (int64_t)nt * TB;
-    d4 acc[4][4];
-    acc_zero(acc);
-    // (interleaved row blocks in every schedule: the column sums then add a tile's rows in the same order everywhere)
-    const double* At = U + m0;
-    const double* Bt = Ks + (int64_t)nt * Np * TB;
-    const int kend = (mt + 1) * TB;
-    if (!sweep_tile_rev(mt, nP)) {
-        if (VAR == 2) gemm_tile_128_b<true, true>(acc, At, Np, Bt, TB, 0, kend, smem);
-        else if (VAR == 5) gemm_tile_128_g<1, false, true>(acc, At, Np, Bt, TB, 0, kend, smem);
-        else gemm_tile_128_s<1, false, true>(acc, At, Np, Bt, TB, 0, kend, smem);
-    } else {
-        if (VAR == 2) gemm_rev32(0, kend, [&](int k0, int k1) { gemm_tile_128_b<true, true>(acc, At, Np, Bt, TB, k0, k1, smem); });
-        else if (VAR == 5) gemm_tile_128_g<1, false, true, true>(acc, At, Np, Bt, TB, 0, kend, smem);
-        else gemm_tile_128_s<1, false, true, true>(acc, At, Np, Bt, TB, 0, kend, smem);
-    }
-    // the k-loop ended on a barrier, LDS is free
-    sweep_epilogue<true>(acc, avec, m0, Qp + (int64_t)mt * ldp + n0, Pp + (int64_t)mt * ldp + n0, smem);
-  }
-    if (clk && threadIdx.x == 0) {
-        atomicAdd(clk, (unsigned long long)__builtin_readcyclecounter() - clk_c0);
-        atomicAdd(clk + 1, (unsigned long long)wall_clock64() - clk_r0);
-    }
+    sweep_tiles<64>(blockIdx.x, U, Np, Ks, NT, avec, Qp, Pp, ldp, order, sm, clk, smem,
+                    [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev) {
+        if (!rev) {
+            if (VAR == 2) gemm_tile_128_b<true, true>(acc, At, Np, Bt, TB, 0, kend, smem);
+            else if (VAR == 5) gemm_tile_128_g<1, false, true>(acc, At, Np, Bt, TB, 0, kend, smem);
+            else gemm_tile_128_s<1, false, true>(acc, At, Np, Bt, TB, 0, kend, smem);
+        } else {
+            if (VAR == 2) gemm_rev32(0, kend, [&](int k0, int k1) { gemm_tile_128_b<true, true>(acc, At, Np, Bt, TB, k0, k1, smem); });
+            else if (VAR == 5) gemm_tile_128_g<1, false, true, true>(acc, At, Np, Bt, TB, 0, kend, smem);
+            else gemm_tile_128_s<1, false, true, true>(acc, At, Np, Bt, TB, 0, kend, smem);
+        }
+    });
 }
 
 // The same tiles through the register-free k-loop (gemm_tile_128_l): WGS workgroups per compute unit.
@@ -313,34 +316,12 @@ __global__ __launch_bounds__(GEMM_THREADS, WGS) void k_sweep_trmm_l(const double
                                                                     int64_t ldp, int order, int sm,
                                                                     unsigned long long* clk, int b0) {
     __shared__ __attribute__((aligned(16))) double smem[gemm_l_lds_f64<BKL>()];
-    const unsigned long long clk_c0 = __builtin_readcyclecounter();
-    const unsigned long long clk_r0 = wall_clock64();
-    const int nP = (int)(Np / TB);
-    int mt, nt, mt2;
-    if (!sweep_tile_of<32 * WGS>((int)blockIdx.x + b0, order, sm, NT, nP, mt, nt, mt2)) return;
-#pragma unroll 1
-    for (int ph = 0; ph < 2; ++ph) {
-        if (ph == 1) {
-            if (mt2 < 0) break;
-            mt = mt2;
-            __syncthreads();               // the epilogue's LDS reads are done before the next tile's rows land
-        }
-        const int64_t m0 = (int64_t)mt * TB, n0 = (int64_t)nt * TB;
-        d4 acc[4][4];
-        acc_zero(acc);
-        const double* At = U + m0;
-        const double* Bt = Ks + (int64_t)nt * Np * TB;
-        const int kend = (mt + 1) * TB;
-        const bool rev = DOWN && sweep_tile_rev(mt, nP);
-        if (!rev) gemm_tile_128_l<BKL, PRIO, NSET, true, TRI, false, AUX>(acc, At, Np, Bt, TB, 0, kend, smem);
+    sweep_tiles<32 * WGS>((int)blockIdx.x + b0, U, Np, Ks, NT, avec, Qp, Pp, ldp, order, sm, clk, smem,
+                          [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev) {
+        if (!(DOWN && rev)) gemm_tile_128_l<BKL, PRIO, NSET, true, TRI, false, AUX>(acc, At, Np, Bt, TB, 0, kend, smem);
         else if constexpr (BKL == 32) gemm_tile_128_l<32, PRIO, NSET, true, TRI, false, AUX, true>(acc, At, Np, Bt, TB, 0, kend, smem);
         else gemm_rev32(0, kend, [&](int k0, int k1) { gemm_tile_128_l<BKL, PRIO, NSET, true, false, false, AUX>(acc, At, Np, Bt, TB, k0, k1, smem); });
-        sweep_epilogue<true>(acc, avec, m0, Qp + (int64_t)mt * ldp + n0, Pp + (int64_t)mt * ldp + n0, smem);
-    }
-    if (clk && threadIdx.x == 0) {
-        atomicAdd(clk, (unsigned long long)__builtin_readcyclecounter() - clk_c0);
-        atomicAdd(clk + 1, (unsigned long long)wall_clock64() - clk_r0);
-    }
+    });
 }
 
 // The same tiles on the barrier-free loop (gemm_tile_128_w: every wave fetches its own operand halves, one 16-row image per
@@ -351,32 +332,11 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm_w(const double* 
                                                                   double* __restrict__ Pp, int64_t ldp, int order, int sm,
                                                                   unsigned long long* clk) {
     __shared__ __attribute__((aligned(16))) double smem[4 * GEMM_W_IMG_F64];
-    const unsigned long long clk_c0 = __builtin_readcyclecounter();
-    const unsigned long long clk_r0 = wall_clock64();
-    const int nP = (int)(Np / TB);
-    int mt, nt, mt2;
-    if (!sweep_tile_of<64>(blockIdx.x, order, sm, NT, nP, mt, nt, mt2)) return;
-#pragma unroll 1
-    for (int ph = 0; ph < 2; ++ph) {
-        if (ph == 1) {
-            if (mt2 < 0) break;
-            mt = mt2;
-            __syncthreads();
-        }
-        const int64_t m0 = (int64_t)mt * TB, n0 = (int64_t)nt * TB;
-        d4 acc[4][4];
-        acc_zero(acc);
-        const double* At = U + m0;
-        const double* Bt = Ks + (int64_t)nt * Np * TB;
-        const int kend = (mt + 1) * TB;
-        if (!sweep_tile_rev(mt, nP)) gemm_tile_128_w<1, 1, false, true, 0, true>(acc, At, Np, Bt, TB, 0, kend, smem);
+    sweep_tiles<64>(blockIdx.x, U, Np, Ks, NT, avec, Qp, Pp, ldp, order, sm, clk, smem,
+                    [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev) {
+        if (!rev) gemm_tile_128_w<1, 1, false, true, 0, true>(acc, At, Np, Bt, TB, 0, kend, smem);
         else gemm_rev32(0, kend, [&](int k0, int k1) { gemm_tile_128_w<1, 1, false, true, 0, false>(acc, At, Np, Bt, TB, k0, k1, smem); });
-        sweep_epilogue<true>(acc, avec, m0, Qp + (int64_t)mt * ldp + n0, Pp + (int64_t)mt * ldp + n0, smem);
-    }
-    if (clk && threadIdx.x == 0) {
-        atomicAdd(clk, (unsigned long long)__builtin_readcyclecounter() - clk_c0);
-        atomicAdd(clk + 1, (unsigned long long)wall_clock64() - clk_r0);
-    }
+    });
 }
 
 void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, const double* Ks, int64_t ldk,
