@@ -76,6 +76,7 @@ int gpx_version(void);
  *                    register-staged loops of rounds 5 / 2 / 1: independently scheduled witnesses) [-1 = by size: 7 below 32 block rows, else 19]
  *   "super_m"        rows of the XCD super-tile of 64 workgroups: 1, 2, 4, 8, 16 [8 -> 8 x 8]
  *   "sweep_cache"    1: full sweeps keep candidates and reduced sums for gpx_sweep_update; 0: leave a live cache alone; -1: drop it [0]
+ *   "prune"          EI sweeps returning ONLY their top-k skip candidates whose bound cannot reach it: -1 by size and gate, 0 never, 1 where legal [-1]
  *   "eager_inverse"  1: form the triangular inverse inside gpx_fit instead of on first use [0]
  *   "trtri_ahead"    1: when the inverse is certain or likely to follow a fit, its part that needs only the factor's leading block
  *                    rows runs on a side stream behind the factorisation's tail, from "trtri_ahead_min" (8) blocks on [1]
@@ -287,7 +288,7 @@ int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, 
  * [14] its algorithmic fp64 lane operations, S n (d + 20) M per launch [15] fits whose task-graph factorisation gave up and re-ran on
  * the stream schedule [16] the shader clock in MHz the sweep_trmm launches sustained (their workgroups' s_memtime over s_memrealtime
  * ticks) [17] the same for the Thompson sweep kernel [18] inversions whose leading part ran behind the factorisation ("trtri_ahead":
- * for those [2] holds only what was left after the factor was done).  Synchronises the stream.  Returns the slots written (<= n). */
+ * for those [2] holds only what was left after the factor was done) [19] bound pass of selection-only sweeps.  Synchronises; returns slots written. */
 int gpx_timers(gpx_handle *h, double *out, int n, int reset);
 /* 1 when the library was built with -DGPX_DIAGNOSTICS (the diagnostic options above are accepted), else 0 */
 int gpx_diagnostics(void);

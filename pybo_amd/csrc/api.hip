@@ -147,6 +147,7 @@ static const Option kOptions[] = {
      store<&gpx_handle::tile_order>, [](int64_t v) { return v == -1 || v >= 4; }},
     {"sweep_cache", SHIP, -1, 1, "sweep_cache must be 1, 0 or -1",                                  // -1 also drops a live cache
      [](gpx_handle* h, int64_t v) { h->cache_on = (v == 1); if (v < 0) { h->cache_valid = false; h->npend = 0; } }},
+    {"prune", SHIP, -1, 1, "prune must be -1 (by size and gate), 0 (never) or 1 (wherever legal)", store<&gpx_handle::prune>},
     {"chol_w", SHIP, 0, 8, "chol_w must be 0 (by size) or in [2, 8]", store<&gpx_handle::chol_w>, [](int64_t v) { return v != 1; }},
     {"chol_tg", SHIP, -1, 1000000000, TG, store<&gpx_handle::chol_tg>, [](int64_t v) { return v == 0 || v == 1; }, "chol_tg must be 0 or 1"},
     {"chol_tg_chunks", DIAG, -1, 1000000000, TG, store<&gpx_handle::tg_chunks>},
@@ -223,7 +224,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // gpx_chol_tasks, GPX_OPTIONS.  500: timers slot 16.  510: timers slots 17, 18, options trtri_ahead*, chol_tg_fuse.
 // 600: gpx_diagnostics, gpx_chol_tasks -> gpx_chol_tasks2 (gpx_diag.h), the diagnostic options only in the diagnostics
 // build, tile_order default by size (7 below 32 block rows, 19 from there on).
-extern "C" int gpx_version(void) { return 600; }
+// 610: option prune (selection-only sweeps), timers slot 19.
+extern "C" int gpx_version(void) { return 610; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -332,7 +334,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dcZ, h->dcq, h->dbatch, h->dpend, h->drefine, h->dspec};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dcZ, h->dcq, h->dbatch, h->dpend, h->drefine, h->dspec};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -936,7 +938,8 @@ static int staged_sweep(gpx_handle* h, const double* Xc, int64_t M, bool sync_up
         HIPCHK(h, hipMemcpyAsync(dX, Xc, (size_t)nx * 8, hipMemcpyHostToDevice, h->stream));
     }
     if (sync_upload) HIPCHK(h, hipStreamSynchronize(h->stream));
-    if ((rc = core(dX, dacq, mu ? dmu : nullptr, s2 ? ds2 : nullptr))) return rc;
+    // (no staging vector for an output nobody asked for: a sweep that returns only its top-k may then skip candidates)
+    if ((rc = core(dX, acq_all ? dacq : nullptr, mu ? dmu : nullptr, s2 ? ds2 : nullptr))) return rc;
     {
         Span sp(h, T_COPY);
         if (acq_all) HIPCHK(h, hipMemcpyAsync(acq_all, dacq, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
@@ -946,6 +949,13 @@ static int staged_sweep(gpx_handle* h, const double* Xc, int64_t M, bool sync_up
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return GPX_OK;
 }
+
+// Selection-only sweeps (option "prune" = -1): tried from this many candidates and factor rows on -- below them the N*M bound
+// pass and the two extra launch chains are no small part of the sweep they save; abandoned when more than 1 / 4 of the
+// candidates survive the bound (the pruned path then costs bound pass + gather + more than a quarter of the plain loop);
+// gated by a mean s2 / rho of the first generation of at least 1 / 64.
+static const int64_t PRUNE_MIN_M = 32768, PRUNE_MIN_NP = 1024, PRUNE_MAX_SHARE_DIV = 4;
+static const double PRUNE_GATE_S2 = 1.0 / 64.0;
 
 static int sweep_core(gpx_handle* h, int acq_id, const double* params, int nparams, const double* dXc,
                       int64_t M, int64_t k, double* top_val, int64_t* top_idx, double* d_acq,
@@ -964,6 +974,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     if ((rc = ensure(h, h->dKs, h->cap_ks, Np * chunk))) return rc;
     if ((rc = ensure(h, h->dQp, h->cap_part, (int64_t)nP * chunk * 2))) return rc;
     h->dPp = h->dQp + (int64_t)nP * chunk;
+    const bool selection_only = !d_acq && !d_mu && !d_s2;      // the caller reads nothing but the top-k
     if (!d_acq) {
         if ((rc = ensure(h, h->dout, h->cap_out, M))) return rc;
         d_acq = h->dout;
@@ -984,32 +995,128 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             HIPCHK(h, hipMemcpyAsync(h->dcZ, dXc, (size_t)M * h->d * 8, hipMemcpyDeviceToDevice, s));
     }
 
-    for (int64_t m0 = 0; m0 < M; m0 += chunk) {
-        const int64_t valid = std::min(chunk, M - m0);
-        const int64_t cols = (valid + TBH - 1) / TBH * TBH;
-        {
-            Span sp(h, T_XGRAM);
-            launch_cross_gram(s, h->dXs, Np, h->N, (int)h->d, dXc, m0, M, cols, h->dinvell, h->kernel_id,
-                              h->rho, h->dKs, Np);
+    // The exact chain (cross-Gram -> V = T K* -> moments and value) for rows [mb, me) of the candidate array X, in chunks:
+    // out[m] (and mu / s2 / the cache sums, where given) for every m of the range.  A candidate's value depends on its
+    // coordinates alone -- not on the chunk, the tile or the column it is computed in (tests/test_gpu_prune.py).
+    auto run_chunks = [&](const double* X, int64_t mb, int64_t me, double* out, double* mu, double* s2) {
+        for (int64_t m0 = mb; m0 < me; m0 += chunk) {
+            const int64_t valid = std::min(chunk, me - m0);
+            const int64_t cols = (valid + TBH - 1) / TBH * TBH;
+            {
+                Span sp(h, T_XGRAM);
+                launch_cross_gram(s, h->dXs, Np, h->N, (int)h->d, X, m0, me, cols, h->dinvell, h->kernel_id,
+                                  h->rho, h->dKs, Np);
+            }
+            {
+                Span sp(h, T_TRMM);
+                launch_sweep_trmm(s, h->dU, Np, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk,
+                                  // by size: short tiles (fewer than 32 block rows) on the barrier-free loop, long ones on the shared-image loop
+                                  // (crossover measured: profiles/r06_sweep_power_probes.txt, section 6)
+                                  h->tile_order >= 0 ? h->tile_order : (Np / NB < 32 ? 7 : 19), h->super_m, h->dclk);
+            }
+            h->tacc[T_NLAUNCH] += 1.0;
+            // ALGORITHMIC work of this launch: N^2 flop per candidate (N^2/2 multiply-adds of the
+            // triangular product).  The kernel executes Np*(Np+128) per padded column (identity padding and full
+            // diagonal blocks): 1.6 % more at N = 8192 -- not counted.
+            h->tacc[T_FLOP] += (double)h->N * (double)h->N * (double)valid;
+            {
+                Span sp(h, T_ACQ);
+                launch_acq(s, h->dQp, h->dPp, chunk, nP, m0, valid, h->rho, h->bias, acq_id, p0, out, mu, s2, cq, cp);
+            }
         }
-        {
-            Span sp(h, T_TRMM);
-            launch_sweep_trmm(s, h->dU, Np, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk,
-                              // by size: short tiles (fewer than 32 block rows) on the barrier-free loop, long ones on the shared-image loop
-                              // (crossover measured: profiles/r06_sweep_power_probes.txt, section 6)
-                              h->tile_order >= 0 ? h->tile_order : (Np / NB < 32 ? 7 : 19), h->super_m, h->dclk);
+    };
+
+    // ---- selection-only sweep: exact values only where the EI bound can reach the top-k ------------
+    // G: the candidates of one generation of sweep workgroups (512 resident, each a pair of tiles; at most 4096: short
+    // factors would ask for tens of thousands), at least k.
+    const int64_t gen_tiles = std::max<int64_t>(1, 512 / ((nP + 1) / 2));       // candidate tiles of 512 workgroups
+    const int64_t G0 = (int64_t)TBH * std::min<int64_t>(32, gen_tiles);
+    const int64_t G = std::max<int64_t>(G0, (k + TBH - 1) / TBH * TBH);
+    const int64_t cap = std::max<int64_t>(G, M / PRUNE_MAX_SHARE_DIV);     // survivors beyond this: the plain loop is the better path
+    // the gate's generation is a FULL one (a launch that fills half the chip takes as long as one that fills it: config B)
+    const int64_t Gg = (int64_t)TBH * gen_tiles;
+    const bool legal = selection_only && acq_id == GPX_ACQ_EI && k > 0 && !h->cache_on && h->prune != 0 && M >= 3 * G &&
+                       h->rho >= 1e-100 && h->rho < INFINITY;
+    bool pruning = legal && (h->prune == 1 || (M >= PRUNE_MIN_M && Np >= PRUNE_MIN_NP && M >= Gg + 2 * G));
+    int64_t done = 0;            // candidates [0, done) are exactly evaluated already
+    if (pruning) {
+        const int64_t nblk_top = topk_blocks(M), nsel = sel_blocks(M);
+        const int64_t kk = std::min<int64_t>(k, TOPK_PASS);
+        if ((rc = ensure(h, h->dblkv, h->cap_blk, nblk_top * kk))) return rc;
+        if ((rc = ensure(h, h->dblki, h->cap_blki, nblk_top * kk))) return rc;
+        if ((rc = ensure(h, h->dtopv, h->cap_top, (int64_t)TOPK_MAX * 2))) return rc;
+        h->dtopi = reinterpret_cast<int64_t*>(h->dtopv + TOPK_MAX);
+        // workspace: [ub M][vals cap][Xg cap d][idx cap][blk nsel + 1][alpha2 Np][sabs Np][gate s2 Gg][sc 8][hist 2 x 4096 + st 8 (int)]
+        const int64_t words = M + cap + cap * h->d + cap + (nsel + 1) + 2 * Np + Gg + 8 + (2 * 4096 + 8) / 2;
+        if ((rc = ensure(h, h->dprune, h->cap_prune, words * 8))) return rc;
+        double* ub = reinterpret_cast<double*>(h->dprune);
+        double* vals = ub + M;
+        double* Xg = vals + cap;
+        int64_t* idx = reinterpret_cast<int64_t*>(Xg + cap * h->d);
+        int64_t* blk = idx + cap;
+        double* alpha2 = reinterpret_cast<double*>(blk + nsel + 1);
+        double* sabs = alpha2 + Np;
+        double* gs2 = sabs + Np;
+        double* sc = gs2 + Gg;
+        int* hist = reinterpret_cast<int*>(sc + 8);
+        int* st = hist + 2 * 4096;
+
+        if (h->prune < 0) {
+            // Gate, BEFORE the bound pass: the prior variance is a useful bound only where the data leave variance to explain.
+            // The first generation is needed by either path; its mean s2 / rho decides (config B's dense data: declined).
+            // A heuristic that only chooses between two correct paths.
+            run_chunks(dXc, 0, Gg, d_acq, nullptr, gs2);
+            done = Gg;
+            launch_prune_mean(s, gs2, Gg, sc + 4);
+            double mean_s2 = 0.0;
+            HIPCHK(h, hipMemcpyAsync(&mean_s2, sc + 4, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipStreamSynchronize(s));
+            pruning = mean_s2 >= h->rho * PRUNE_GATE_S2;
         }
-        h->tacc[T_NLAUNCH] += 1.0;
-        // ALGORITHMIC work of this launch: N^2 flop per candidate (N^2/2 multiply-adds of the
-        // triangular product).  The kernel executes Np*(Np+128) per padded column (identity padding and full
-        // diagonal blocks): 1.6 % more at N = 8192 -- not counted.
-        h->tacc[T_FLOP] += (double)h->N * (double)h->N * (double)valid;
-        {
-            Span sp(h, T_ACQ);
-            launch_acq(s, h->dQp, h->dPp, chunk, nP, m0, valid, h->rho, h->bias, acq_id, p0, d_acq, d_mu,
-                       d_s2, cq, cp);
+        if (pruning) {
+            {
+                // 1. bound pass: ub[n] = EI(bias + alpha . k(X, z_n) + delta, s2 = rho) >= the value the exact chain returns
+                Span sp(h, T_BOUND);
+                launch_prune_alpha(s, h->dU, Np, h->da, h->rho, h->bias, alpha2, sabs, sc);
+                launch_sweep_rank1_v(s, h->dXs, h->N, (int)h->d, alpha2, Np, sc + 2, dXc, M, h->dinvell, h->kernel_id, h->rho,
+                                     nullptr, ub);
+                launch_prune_ub(s, ub, M, done, sc, h->rho, h->bias, p0);
+            }
+            {
+                // 2. seeds: the G candidates with the largest bound (ties at the threshold: the first by index), exactly
+                Span sp(h, T_ACQ);
+                launch_sel_threshold(s, ub, M, (int)G, hist, st);
+                launch_sel_compact(s, ub, M, 0, st, nullptr, blk, G, dXc, (int)h->d, idx, Xg);
+            }
+            run_chunks(Xg, 0, G, vals, nullptr, nullptr);
+            int64_t nsurv = 0;
+            {
+                // tau = the k-th best seed value; 3. survivors: every candidate not yet evaluated whose bound is not below it
+                Span sp(h, T_ACQ);
+                launch_topk(s, vals, G, (int)k, h->dblkv, h->dblki, topk_blocks(G), h->dtopv, h->dtopi);
+                launch_fill_neg_inf(s, d_acq, done, M);
+                launch_sel_scatter(s, idx, vals, G, d_acq, ub);
+                launch_sel_compact(s, ub, M, 1, st, h->dtopv + (k - 1), blk, cap, dXc, (int)h->d, idx, Xg);
+                HIPCHK(h, hipMemcpyAsync(&nsurv, blk + nsel, 8, hipMemcpyDeviceToHost, s));
+            }
+            HIPCHK(h, hipStreamSynchronize(s));
+            if (nsurv <= cap) {
+                // 4. their exact values to their own positions; everything else stays -inf and the top-k below runs as ever
+                run_chunks(Xg, 0, nsurv, vals, nullptr, nullptr);
+                Span sp(h, T_ACQ);
+                launch_sel_scatter(s, idx, vals, nsurv, d_acq, nullptr);
+                done = M;
+            }
+            // 5. (else) too many survivors -- tau = 0, a flat bound: the plain loop over everything not yet evaluated
         }
     }
+    if (done > 0 && done < std::min(chunk, M)) {
+        // the gate declined: the rest of the first chunk, so that every later launch keeps the plain loop's boundaries (config B:
+        // 1 + 15 full generations instead of 16, where a loop shifted by the gate's candidates would end on a 129th)
+        run_chunks(dXc, done, std::min(chunk, M), d_acq, d_mu, d_s2);
+        done = std::min(chunk, M);
+    }
+    if (done < M) run_chunks(dXc, done, M, d_acq, d_mu, d_s2);
     if (h->cache_on) {
         h->cache_valid = true;
         h->cache_M = M;

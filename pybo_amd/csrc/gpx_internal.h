@@ -20,7 +20,7 @@ constexpr int PEND_MAX = 8;   // appended observations per pass of the sweep-cac
 
 enum Timer {
     T_GRAM = 0, T_CHOL, T_TRTRI, T_ALPHA, T_XGRAM, T_TRMM, T_ACQ, T_RFF, T_NLAUNCH, T_FLOP, T_COPY, T_APPEND,
-    T_RANK1, T_RFFSWEEP, T_RFFOPS, T_TGFALL, T_SCLK, T_RFFCLK, T_AHEAD, T_COUNT
+    T_RANK1, T_RFFSWEEP, T_RFFOPS, T_TGFALL, T_SCLK, T_RFFCLK, T_AHEAD, T_BOUND, T_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int slot; };
@@ -147,6 +147,9 @@ struct gpx_handle {
     int64_t cap_grad = 0;
     double* dens = nullptr;   // ensemble sweep: accumulators + member outputs (5 M)
     int64_t cap_ens = 0;
+    int prune = -1;           // option: selection-only sweeps skip candidates whose EI bound cannot reach the top-k (-1 by size and gate, 0 never, 1 wherever legal)
+    char* dprune = nullptr;   // their workspace (one allocation, laid out in api.hip: sweep_core)
+    int64_t cap_prune = 0;    // ... in bytes
 
     // sweep cache (warm BO step): candidates and their reduced sums q = colsum(V^2), p = V^T a of the last full
     // sweep, kept current by gpx_append's rank-1 correction and re-scored by gpx_sweep_update
@@ -239,6 +242,18 @@ void launch_topk_merge(hipStream_t s, double* vals, int64_t* idx, int64_t n, int
 void launch_topk_rows(hipStream_t s, const double* vals, int64_t M, int64_t S, int k, double* blkv, int64_t* blki,
                       int64_t nblk, double* topv, int64_t* topi);
 int64_t topk_blocks(int64_t M);
+// selection-only sweeps: weights and error bound of the bound pass, the bound itself, radix select of the G-th largest
+// bound, stable compaction (mode 0: seeds by the selected threshold st[2]; mode 1: survivors of the cut *tau), scatter
+void launch_prune_alpha(hipStream_t s, const double* U, int64_t Np, const double* a, double rho, double bias, double* alpha2,
+                        double* sabs, double* sc);
+void launch_prune_ub(hipStream_t s, double* ub, int64_t M, int64_t skip, const double* sc, double rho, double bias, double p0);
+void launch_prune_mean(hipStream_t s, const double* v, int64_t n, double* out);
+void launch_sel_threshold(hipStream_t s, const double* v, int64_t M, int G, int* hist, int* st);
+int64_t sel_blocks(int64_t M);
+void launch_sel_compact(hipStream_t s, const double* v, int64_t M, int mode, const int* st, const double* tau, int64_t* blk,
+                        int64_t cap, const double* Xc, int d, int64_t* idx, double* Xg);
+void launch_sel_scatter(hipStream_t s, const int64_t* idx, const double* vals, int64_t n, double* out, double* mark);
+void launch_fill_neg_inf(hipStream_t s, double* out, int64_t from, int64_t M);
 
 // predict with gradients (small M path)
 int ensemble_predict_grad_host(gpx_handle* const* mem, int n, const double* Xc, int64_t M, double* mu, double* s2,

@@ -393,6 +393,27 @@ __device__ __forceinline__ double norm_pdf(double z) {
     return 0.39894228040143267794 * exp(-0.5 * z * z);
 }
 
+// The acquisition value from the posterior moments: the ONE place this arithmetic lives.  k_acq calls it with a candidate's
+// exact moments, the bound pass of a selection-only sweep (k_prune_ub) with an upper bound of the mean and s2 = rho.
+__device__ __forceinline__ double acq_value(int acq_id, double mu, double s2, double p0) {
+    switch (acq_id) {
+        case GPX_ACQ_EI: {
+            const double s = sqrt(s2);
+            const double dlt = mu - p0;
+            const double z = dlt / s;
+            return dlt * norm_cdf(z) + s * norm_pdf(z);
+        }
+        case GPX_ACQ_PI: {
+            const double z = (mu - p0) / sqrt(s2);
+            return norm_cdf(z);
+        }
+        case GPX_ACQ_UCB:
+            return mu + sqrt(p0 * s2);
+        default:
+            return mu;
+    }
+}
+
 // nrb > 0: Qp/Pp are per-row-block partials (nrb, ldp) of this chunk, reduced here in block order.
 // nrb = 0: Qp/Pp are the already reduced per-candidate sums of the whole grid (the sweep cache), m0 = 0.
 // qsum/psum (optional): the reduced sums are stored per candidate -- the state gpx_append's rank-1 correction
@@ -420,26 +441,7 @@ __global__ __launch_bounds__(256) void k_acq(const double* __restrict__ Qp, cons
     }
     const double mu = bias + p;
     const double s2 = fmax(rho - q, 1e-100);
-    double val;
-    switch (acq_id) {
-        case GPX_ACQ_EI: {
-            const double s = sqrt(s2);
-            const double dlt = mu - p0;
-            const double z = dlt / s;
-            val = dlt * norm_cdf(z) + s * norm_pdf(z);
-            break;
-        }
-        case GPX_ACQ_PI: {
-            const double z = (mu - p0) / sqrt(s2);
-            val = norm_cdf(z);
-            break;
-        }
-        case GPX_ACQ_UCB:
-            val = mu + sqrt(p0 * s2);
-            break;
-        default:
-            val = mu;
-    }
+    const double val = acq_value(acq_id, mu, s2, p0);
     acq_out[m0 + n] = val;
     if (mu_out) mu_out[m0 + n] = mu;
     if (s2_out) s2_out[m0 + n] = s2;
@@ -789,6 +791,290 @@ void launch_topk(hipStream_t s, const double* vals, int64_t M, int k, double* bl
         hipLaunchKernelGGL(k_topk_block, dim3((unsigned)nblk), dim3(256), 0, s, vals, M, kk, blkv, blki, cv, ci);
         hipLaunchKernelGGL(k_topk_merge, dim3(1), dim3(256), 0, s, blkv, blki, nblk * kk, kk, topv + done, topi + done);
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Selection-only sweeps: a caller that asks for the k best candidates and for no per-candidate
+// output needs the exact variance only of candidates that can reach the top-k.  EI is non-decreasing in the mean and in
+// the standard deviation and s2 <= rho, so EI(mu + delta, sqrt(rho)) bounds a candidate's value from above at the cost of
+// one row-dot with alpha (N covariance evaluations) instead of the N^2 flop of its column of V = T K*.
+// ------------------------------------------------------------------------------------------------
+constexpr double PRUNE_TAU_MIN = 1e-280;   // below this the k-th best seed value prunes nothing (relative error bounds need normal numbers)
+constexpr double PRUNE_SLACK = 1e-6;       // relative rounding of acq_value(EI): <= 16 z^4 eps with z^2 <= 1500 wherever EI >= 1e-280, i.e. 4e-9
+
+// alpha2_k = sum_m U[k][m] a_m (row k of U = R^-1 from its diagonal on) and sabs_k = sum_m |U[k][m] a_m|: the weights of the
+// bound pass and the terms of S = || |T|^T |a| ||_1, from the very U and a the sweep kernel multiplies with (whatever
+// fit / append sequence produced them).  One workgroup per row, fixed reduction tree.
+__global__ __launch_bounds__(256) void k_prune_alpha(const double* __restrict__ U, int64_t Np, const double* __restrict__ a,
+                                                     double* __restrict__ alpha2, double* __restrict__ sabs) {
+    __shared__ double r0[256], r1[256];
+    const int64_t k = blockIdx.x;
+    const double* row = U + k * Np;
+    double s = 0.0, t = 0.0;
+    for (int64_t m = k + threadIdx.x; m < Np; m += 256) {
+        const double pr = row[m] * a[m];
+        s += pr;
+        t += fabs(pr);
+    }
+    r0[threadIdx.x] = s;
+    r1[threadIdx.x] = t;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            r0[threadIdx.x] += r0[threadIdx.x + w];
+            r1[threadIdx.x] += r1[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        alpha2[k] = r0[0];
+        sabs[k] = r1[0];
+    }
+}
+
+// sc[0] = S, sc[1] = delta = 8 (Np + 16) 2^-53 (rho S + |bias|), sc[2..3] = {-1, 0}: the `pscal` that makes k_sweep_rankq
+// return the plain dot product.  The bound of |mu_est - (bias + p)| is derived in DESIGN.md section 2.1.
+__global__ __launch_bounds__(256) void k_prune_delta(const double* __restrict__ sabs, int64_t Np, double rho, double bias,
+                                                     double* __restrict__ sc) {
+    __shared__ double r0[256];
+    double s = 0.0;
+    for (int64_t m = threadIdx.x; m < Np; m += 256) s += sabs[m];
+    r0[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) r0[threadIdx.x] += r0[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        sc[0] = r0[0];
+        sc[1] = 8.0 * (double)(Np + 16) * 1.1102230246251565e-16 * (rho * r0[0] + fabs(bias));
+        sc[2] = -1.0;
+        sc[3] = 0.0;
+    }
+}
+
+void launch_prune_alpha(hipStream_t s, const double* U, int64_t Np, const double* a, double rho, double bias, double* alpha2,
+                        double* sabs, double* sc) {
+    hipLaunchKernelGGL(k_prune_alpha, dim3((unsigned)Np), dim3(256), 0, s, U, Np, a, alpha2, sabs);
+    hipLaunchKernelGGL(k_prune_delta, dim3(1), dim3(256), 0, s, sabs, Np, rho, bias, sc);
+}
+
+// ub[n] (in: alpha2 . k(X, z_n)) <- EI((bias + dot) + delta, s2 = rho) by k_acq's own function; -inf for the `skip` leading
+// candidates that are exactly evaluated already.
+__global__ __launch_bounds__(256) void k_prune_ub(double* __restrict__ ub, int64_t M, int64_t skip, const double* __restrict__ sc,
+                                                  double rho, double bias, double p0) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= M) return;
+    ub[n] = (n < skip) ? GPX_NEG_INF : acq_value(GPX_ACQ_EI, (bias + ub[n]) + sc[1], rho, p0);
+}
+
+void launch_prune_ub(hipStream_t s, double* ub, int64_t M, int64_t skip, const double* sc, double rho, double bias, double p0) {
+    hipLaunchKernelGGL(k_prune_ub, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, ub, M, skip, sc, rho, bias, p0);
+}
+
+// out[0] = mean of v[0..n)  (the gate of a selection-only sweep: the mean s2 of its first generation)
+__global__ __launch_bounds__(256) void k_prune_mean(const double* __restrict__ v, int64_t n, double* __restrict__ out) {
+    __shared__ double r0[256];
+    double s = 0.0;
+    for (int64_t m = threadIdx.x; m < n; m += 256) s += v[m];
+    r0[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) r0[threadIdx.x] += r0[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = r0[0] / (double)n;
+}
+
+void launch_prune_mean(hipStream_t s, const double* v, int64_t n, double* out) {
+    hipLaunchKernelGGL(k_prune_mean, dim3(1), dim3(256), 0, s, v, n, out);
+}
+
+// Order-preserving 24-bit key of a double (sign, exponent, 12 mantissa bits): a <= b implies key(a) <= key(b).
+constexpr int SEL_BINS = 4096;
+constexpr int SEL_PER_THREAD = 16;
+constexpr int SEL_PER_BLOCK = 256 * SEL_PER_THREAD;
+__device__ __forceinline__ unsigned sel_key24(double v) {
+    unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    b ^= (b >> 63) ? ~0ull : 0x8000000000000000ull;
+    return (unsigned)(b >> 40);
+}
+
+// Radix select of the G-th largest key in two passes of 12 bits.  st: [0] bin of pass 0, [1] elements in higher bins,
+// [2] the threshold key: at least G elements have key >= st[2].
+__global__ __launch_bounds__(256) void k_sel_hist(const double* __restrict__ v, int64_t M, int pass, const int* __restrict__ st,
+                                                  int* __restrict__ hist) {
+    __shared__ int lh[SEL_BINS];
+    for (int b = threadIdx.x; b < SEL_BINS; b += 256) lh[b] = 0;
+    __syncthreads();
+    const unsigned hi = pass ? (unsigned)st[0] : 0u;
+    const int64_t base = (int64_t)blockIdx.x * SEL_PER_BLOCK;
+    for (int e = 0; e < SEL_PER_THREAD; ++e) {
+        const int64_t n = base + e * 256 + threadIdx.x;
+        if (n >= M) break;
+        const unsigned key = sel_key24(v[n]);
+        if (!pass) atomicAdd(&lh[key >> 12], 1);
+        else if ((key >> 12) == hi) atomicAdd(&lh[key & 4095u], 1);
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < SEL_BINS; b += 256)
+        if (lh[b]) atomicAdd(&hist[b], lh[b]);
+}
+
+__global__ __launch_bounds__(256) void k_sel_pick(const int* __restrict__ hist, int pass, int G, int* __restrict__ st) {
+    __shared__ int ts[256];
+    int s = 0;
+    for (int j = 0; j < 16; ++j) s += hist[threadIdx.x * 16 + j];
+    ts[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int need = pass ? G - st[1] : G;
+        int cum = 0, t = 255;
+        for (; t > 0; --t) {
+            if (cum + ts[t] >= need) break;
+            cum += ts[t];
+        }
+        int b = t * 16 + 15;
+        for (; b > t * 16; --b) {
+            if (cum + hist[b] >= need) break;
+            cum += hist[b];
+        }
+        if (!pass) {
+            st[0] = b;
+            st[1] = cum;
+        } else {
+            st[2] = (st[0] << 12) | b;
+        }
+    }
+}
+
+void launch_sel_threshold(hipStream_t s, const double* v, int64_t M, int G, int* hist, int* st) {
+    const unsigned nblk = (unsigned)((M + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK);
+    (void)hipMemsetAsync(hist, 0, 2 * SEL_BINS * sizeof(int), s);
+    for (int pass = 0; pass < 2; ++pass) {
+        hipLaunchKernelGGL(k_sel_hist, dim3(nblk), dim3(256), 0, s, v, M, pass, st, hist + pass * SEL_BINS);
+        hipLaunchKernelGGL(k_sel_pick, dim3(1), dim3(256), 0, s, hist + pass * SEL_BINS, pass, G, st);
+    }
+}
+
+// Stable compaction.  mode 0 (seeds): key(v) >= st[2].  mode 1 (survivors): NOT v < tau (1 - slack), so a NaN bound survives
+// and an evaluated candidate (v = -inf) does not; a tau that is not a normal positive number prunes nothing.
+__device__ __forceinline__ bool sel_pred(int mode, double v, unsigned thr, double cut) {
+    return mode == 0 ? sel_key24(v) >= thr : !(v < cut);
+}
+__device__ __forceinline__ double sel_cut(int mode, const double* tau) {
+    if (mode == 0) return 0.0;
+    const double t = *tau;
+    return (t >= PRUNE_TAU_MIN) ? t * (1.0 - PRUNE_SLACK) : GPX_NEG_INF;
+}
+
+__global__ __launch_bounds__(256) void k_sel_count(const double* __restrict__ v, int64_t M, int mode, const int* __restrict__ st,
+                                                   const double* __restrict__ tau, int64_t* __restrict__ blk) {
+    __shared__ int cnt;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    const unsigned thr = (unsigned)st[2];
+    const double cut = sel_cut(mode, tau);
+    const int64_t base = (int64_t)blockIdx.x * SEL_PER_BLOCK + (int64_t)threadIdx.x * SEL_PER_THREAD;
+    int c = 0;
+    for (int e = 0; e < SEL_PER_THREAD; ++e)
+        if (base + e < M && sel_pred(mode, v[base + e], thr, cut)) ++c;
+    if (c) atomicAdd(&cnt, c);
+    __syncthreads();
+    if (threadIdx.x == 0) blk[blockIdx.x] = cnt;
+}
+
+// blk[0..nblk) counts -> exclusive offsets in place, blk[nblk] = total (one workgroup walks the blocks 256 at a time)
+__global__ __launch_bounds__(256) void k_sel_scan(int64_t* __restrict__ blk, int64_t nblk) {
+    __shared__ int64_t sh[256];
+    __shared__ int64_t carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (int64_t b0 = 0; b0 < nblk; b0 += 256) {
+        const int64_t i = b0 + threadIdx.x;
+        const int64_t mine = (i < nblk) ? blk[i] : 0;
+        sh[threadIdx.x] = mine;
+        __syncthreads();
+        for (int w = 1; w < 256; w <<= 1) {
+            const int64_t add = ((int)threadIdx.x >= w) ? sh[threadIdx.x - w] : 0;
+            __syncthreads();
+            sh[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (i < nblk) blk[i] = carry + sh[threadIdx.x] - mine;
+        __syncthreads();
+        if (threadIdx.x == 255) carry += sh[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) blk[nblk] = carry;
+}
+
+// the selected candidates in their original order: idx[j] = n and row j of Xg = row n of Xc, for the first `cap` of them
+__global__ __launch_bounds__(256) void k_sel_write(const double* __restrict__ v, int64_t M, int mode, const int* __restrict__ st,
+                                                   const double* __restrict__ tau, const int64_t* __restrict__ blk, int64_t cap,
+                                                   const double* __restrict__ Xc, int d, int64_t* __restrict__ idx,
+                                                   double* __restrict__ Xg) {
+    __shared__ int sh[256];
+    const unsigned thr = (unsigned)st[2];
+    const double cut = sel_cut(mode, tau);
+    const int64_t base = (int64_t)blockIdx.x * SEL_PER_BLOCK + (int64_t)threadIdx.x * SEL_PER_THREAD;
+    unsigned mask = 0;
+    for (int e = 0; e < SEL_PER_THREAD; ++e)
+        if (base + e < M && sel_pred(mode, v[base + e], thr, cut)) mask |= 1u << e;
+    const int mine = __popc(mask);
+    sh[threadIdx.x] = mine;
+    __syncthreads();
+    for (int w = 1; w < 256; w <<= 1) {
+        const int add = ((int)threadIdx.x >= w) ? sh[threadIdx.x - w] : 0;
+        __syncthreads();
+        sh[threadIdx.x] += add;
+        __syncthreads();
+    }
+    int64_t off = blk[blockIdx.x] + sh[threadIdx.x] - mine;
+    for (int e = 0; e < SEL_PER_THREAD; ++e) {
+        if (!((mask >> e) & 1u)) continue;
+        if (off < cap) {
+            idx[off] = base + e;
+            for (int c = 0; c < d; ++c) Xg[off * d + c] = Xc[(base + e) * d + c];
+        }
+        ++off;
+    }
+}
+
+int64_t sel_blocks(int64_t M) { return (M + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK; }
+
+// count only (total -> blk[nblk]) and the offsets the write needs
+void launch_sel_compact(hipStream_t s, const double* v, int64_t M, int mode, const int* st, const double* tau, int64_t* blk,
+                        int64_t cap, const double* Xc, int d, int64_t* idx, double* Xg) {
+    const int64_t nblk = sel_blocks(M);
+    hipLaunchKernelGGL(k_sel_count, dim3((unsigned)nblk), dim3(256), 0, s, v, M, mode, st, tau, blk);
+    hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(256), 0, s, blk, nblk);
+    hipLaunchKernelGGL(k_sel_write, dim3((unsigned)nblk), dim3(256), 0, s, v, M, mode, st, tau, blk, cap, Xc, d, idx, Xg);
+}
+
+// out[idx[j]] = vals[j] for j < n; mark (optional): those candidates' bounds -> -inf (evaluated: never a survivor)
+__global__ __launch_bounds__(256) void k_sel_scatter(const int64_t* __restrict__ idx, const double* __restrict__ vals, int64_t n,
+                                                     double* __restrict__ out, double* __restrict__ mark) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int64_t i = idx[j];
+    out[i] = vals[j];
+    if (mark) mark[i] = GPX_NEG_INF;
+}
+
+void launch_sel_scatter(hipStream_t s, const int64_t* idx, const double* vals, int64_t n, double* out, double* mark) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_sel_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, idx, vals, n, out, mark);
+}
+
+__global__ __launch_bounds__(256) void k_fill_neg_inf(double* __restrict__ out, int64_t from, int64_t M) {
+    const int64_t n = from + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n < M) out[n] = GPX_NEG_INF;
+}
+
+void launch_fill_neg_inf(hipStream_t s, double* out, int64_t from, int64_t M) {
+    if (from >= M) return;
+    hipLaunchKernelGGL(k_fill_neg_inf, dim3((unsigned)((M - from + 255) / 256)), dim3(256), 0, s, out, from, M);
 }
 
 }  // namespace gpx
