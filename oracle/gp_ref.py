@@ -365,3 +365,62 @@ def grid_uniform(seed, bounds, M):
     u[1::2] = ((out[:, 2] << np.uint64(32) | out[:, 3]) >> np.uint64(11)).astype(np.float64) / 9007199254740992.0
     u = u[:total].reshape(M, d)
     return b[:, 0] + u * (b[:, 1] - b[:, 0])
+
+
+# ---------------------------------------------------------------------------------------------------
+# the bound of a selection-only sweep, restated in long double
+# ---------------------------------------------------------------------------------------------------
+U53 = 1.1102230246251565e-16     # 2^-53
+
+
+def prune_delta(S, Np, rho, bias):
+    """delta of kernels_sweep.hip k_prune_delta, the same fp64 expression operation for operation: rho S + |bias| is
+    an explicit fma on the device (rounded once, here through exact rationals); the factor 8 (Np + 16) 2^-53 is exact,
+    so the last product is the only other rounding."""
+    from fractions import Fraction
+    inner = float(Fraction(float(rho)) * Fraction(float(S)) + Fraction(abs(float(bias))))
+    return 8.0 * float(Np + 16) * U53 * inner
+
+
+def prune_truth(T, a, Ks, rho, bias):
+    """From a factor inverse T (N, N; lower, V = T k), a (N,) and cross-covariances Ks (N, m), all taken as exact
+    numbers, in np.longdouble:  mu_true = bias + a.(T k) per column, evaluated as (T^T a).k (the same number; N^2 + N m
+    products instead of N^2 m), and S = || |T|^T |a| ||_1.  Its own rounding is N 2^-64 rho S: 2^-14 of delta."""
+    ld = np.longdouble
+    Tl, al = np.asarray(T, dtype=ld), np.asarray(a, dtype=ld)
+    w = Tl.T @ al
+    S = np.sum(np.abs(Tl).T @ np.abs(al))
+    mu = ld(bias) + np.asarray(Ks, dtype=ld).T @ w
+    return mu, S
+
+
+def prune_S(T, a, rows=512):
+    """S = || |T|^T |a| ||_1 alone in np.longdouble, in slabs of rows (an N = 8192 inverse is 1 GiB as long double)."""
+    ld = np.longdouble
+    al = np.abs(np.asarray(a, dtype=ld))
+    S = ld(0)
+    for i in range(0, len(al), rows):
+        S += np.sum(al[i:i + rows] @ np.abs(np.asarray(T[i:i + rows], dtype=ld)))
+    return S
+
+
+def sel_key24(v):
+    """kernels_sweep.hip sel_key24 in numpy: order-preserving 24-bit key (sign, exponent, 12 mantissa bits)."""
+    b = np.ascontiguousarray(v, dtype=np.float64).view(np.uint64)
+    neg = (b >> np.uint64(63)).astype(bool)
+    b = np.where(neg, ~b, b ^ np.uint64(0x8000000000000000))
+    return (b >> np.uint64(40)).astype(np.int64)
+
+
+def prune_mean_emulations(T, a, Ks, bias):
+    """Plain fp64 numpy versions of the two means a selection-only sweep compares -- the row-dot of the bound pass
+    (alpha~ = T^T a, then alpha~ . k) and the exact chain (V = T k, then V^T a) with the last sum taken forwards,
+    backwards and in 128-row blocks: dict name -> (m,) fp64."""
+    T, a, Ks = np.asarray(T, dtype=float), np.asarray(a, dtype=float), np.asarray(Ks, dtype=float)
+    out = {'rowdot': bias + Ks.T @ (T.T @ a)}
+    W = (T @ Ks) * a[:, None]
+    out['chain_fwd'] = bias + np.cumsum(W, axis=0)[-1]
+    out['chain_bwd'] = bias + np.cumsum(W[::-1], axis=0)[-1]
+    blocks = [W[i:i + 128].sum(axis=0) for i in range(0, len(W), 128)]
+    out['chain_blk'] = bias + np.sum(blocks, axis=0)
+    return out

@@ -47,6 +47,7 @@ _dbl = C.c_double
 DIAG_SYMBOLS = {
     'gpx_chol_trace': (_i64, [_P, _P, _i64]),
     'gpx_chol_tasks2': (_i64, [C.c_int, C.c_int, _P, _i64, _P]),
+    'gpx_prune_report': (C.c_int, [_P, _P, C.c_int, _P, _P, _i64, _P, _P, _i64]),
 }
 SYMBOLS = {
     'gpx_create': (C.c_int, [C.c_int, _P, C.POINTER(_P)]),
@@ -712,6 +713,32 @@ class Engine(object):
         out = np.zeros(len(TIMER_NAMES))
         self._lib.gpx_timers(self._h, _ptr(out), len(out), 1 if reset else 0)
         return dict(zip(TIMER_NAMES, out.tolist()))
+
+    PRUNE_PATHS = ('plain', 'gate declined', 'pruned', 'fell back')
+
+    def prune_report(self, vectors=True):
+        """Diagnostic (gpx_prune_report in csrc/gpx_diag.h): what the last sweep decided about pruning.  dict(path, M, k, G, Gg, done, cap,
+        nsurv, S, delta, tau, gate_s2, thr_key, kept); with `vectors`, where the bound pass ran, also ub (M,) as the survivor pass read
+        it and idx, the survivors in compaction order (empty where it fell back); after a sweep with option prune_keep = 1 also ub_kept
+        and seed_idx, the bounds and the seed list before the scatter."""
+        scal = np.full(14, np.nan)
+        self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), None, None, 0, None, None, 0))
+        names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'S', 'delta', 'tau', 'gate_s2', 'thr_key', 'kept')
+        r = dict(zip(names, scal.tolist()))
+        for n in ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'kept'):
+            r[n] = int(r[n])
+        r['path'] = self.PRUNE_PATHS[r['path']]
+        if vectors and r['path'] in ('pruned', 'fell back'):
+            M = r['M']
+            nidx = r['nsurv'] if r['path'] == 'pruned' else 0
+            r['ub'] = np.empty(M)
+            r['idx'] = np.empty(nidx, dtype=np.int64)
+            kept = bool(r['kept'])
+            r['ub_kept'] = np.empty(M) if kept else None
+            r['seed_idx'] = np.empty(r['G'], dtype=np.int64) if kept else None
+            self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), _ptr(r['ub']), _ptr(r['idx']), nidx,
+                                                   _ptr(r['ub_kept']), _ptr(r['seed_idx']), r['G'] if kept else 0))
+        return r
 
     def chol_trace(self, nblocks, full_log=False):
         """Diagnostic (option chol_tg_trace = 1): the task-graph factorisation's own stamps of the last fit, microseconds

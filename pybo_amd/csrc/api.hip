@@ -148,6 +148,7 @@ static const Option kOptions[] = {
     {"sweep_cache", SHIP, -1, 1, "sweep_cache must be 1, 0 or -1",                                  // -1 also drops a live cache
      [](gpx_handle* h, int64_t v) { h->cache_on = (v == 1); if (v < 0) { h->cache_valid = false; h->npend = 0; } }},
     {"prune", SHIP, -1, 1, "prune must be -1 (by size and gate), 0 (never) or 1 (wherever legal)", store<&gpx_handle::prune>},
+    {"prune_keep", DIAG, 0, 1, "prune_keep must be 0 or 1", store<&gpx_handle::prune_keep>},
     {"chol_w", SHIP, 0, 8, "chol_w must be 0 (by size) or in [2, 8]", store<&gpx_handle::chol_w>, [](int64_t v) { return v != 1; }},
     {"chol_tg", SHIP, -1, 1000000000, TG, store<&gpx_handle::chol_tg>, [](int64_t v) { return v == 0 || v == 1; }, "chol_tg must be 0 or 1"},
     {"chol_tg_chunks", DIAG, -1, 1000000000, TG, store<&gpx_handle::tg_chunks>},
@@ -334,7 +335,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dcZ, h->dcq, h->dbatch, h->dpend, h->drefine, h->dspec};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dpend, h->drefine, h->dspec};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -380,6 +381,42 @@ extern "C" int64_t gpx_chol_trace(gpx_handle* h, int64_t* out, int64_t n) {
     if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return 0;
     static_assert(sizeof(long long) == sizeof(int64_t), "trace words");
     return tg_trace_copy(h, reinterpret_cast<long long*>(out), n);
+}
+
+extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* ub, int64_t* idx, int64_t cap_idx,
+                                double* ub_kept, int64_t* seed_idx, int64_t cap_seed) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        if (!scal || nscal < 0) return fail(h, GPX_EARG, "prune_report: NULL output");
+        const gpx_handle::PruneRecord& r = h->prune_rec;
+        if (r.path < 0) return fail(h, GPX_ESTATE, "prune_report: no sweep has completed its argument checks since the record was last cleared");
+        const bool bound = r.path >= 2;
+        if ((ub || idx || ub_kept || seed_idx) && !bound)
+            return fail(h, GPX_ESTATE, "prune_report: the last sweep did not reach its bound pass");
+        if ((ub_kept || seed_idx) && !r.kept)
+            return fail(h, GPX_ESTATE, "prune_report: the last sweep ran without the option prune_keep");
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        double sc[8];
+        int st[4] = {0, 0, 0, 0};
+        for (double& v : sc) v = NAN;
+        if (bound) {
+            HIPCHK(h, hipMemcpy(sc, r.sc, sizeof sc, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(st, r.st, sizeof st, hipMemcpyDeviceToHost));
+        }
+        const double out[14] = {(double)r.path, (double)r.M,     (double)r.k, (double)r.G, (double)r.Gg,
+                                (double)r.done, (double)r.cap,   (double)r.nsurv, sc[0],   sc[1],
+                                sc[5],          r.mean_s2,       bound ? (double)st[2] : NAN, r.kept ? 1.0 : 0.0};
+        for (int i = 0; i < nscal && i < 14; ++i) scal[i] = out[i];
+        if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
+        const int64_t nidx = std::min(std::min(r.nsurv, r.cap), cap_idx);
+        if (idx && nidx > 0) HIPCHK(h, hipMemcpy(idx, r.idx, (size_t)nidx * 8, hipMemcpyDeviceToHost));
+        if (ub_kept) HIPCHK(h, hipMemcpy(ub_kept, h->dkeep, (size_t)r.M * 8, hipMemcpyDeviceToHost));
+        const int64_t nseed = std::min(r.G, cap_seed);
+        if (seed_idx && nseed > 0)
+            HIPCHK(h, hipMemcpy(seed_idx, h->dkeep + r.M * 8, (size_t)nseed * 8, hipMemcpyDeviceToHost));
+        return GPX_OK;
+    });
 }
 
 extern "C" int gpx_timers(gpx_handle* h, double* out, int n, int reset) {
@@ -960,6 +997,7 @@ static const double PRUNE_GATE_S2 = 1.0 / 64.0;
 static int sweep_core(gpx_handle* h, int acq_id, const double* params, int nparams, const double* dXc,
                       int64_t M, int64_t k, double* top_val, int64_t* top_idx, double* d_acq,
                       double* d_mu, double* d_s2) {
+    h->prune_rec = gpx_handle::PruneRecord();      // every sweep entry, refused ones included, ends the previous sweep's record
     if (!h->fitted) return fail(h, GPX_ESTATE, "sweep: model is not fitted");
     if (!dXc || M < 1) return fail(h, GPX_EARG, "sweep: need M >= 1 candidates");
     int rc;
@@ -1039,6 +1077,10 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
                        h->rho >= 1e-100 && h->rho < INFINITY;
     bool pruning = legal && (h->prune == 1 || (M >= PRUNE_MIN_M && Np >= PRUNE_MIN_NP && M >= Gg + 2 * G));
     int64_t done = 0;            // candidates [0, done) are exactly evaluated already
+    gpx_handle::PruneRecord& rec = h->prune_rec;
+    rec.path = 0;
+    rec.M = M, rec.k = k, rec.G = G, rec.Gg = Gg, rec.cap = cap;
+    rec.mean_s2 = NAN;
     if (pruning) {
         const int64_t nblk_top = topk_blocks(M), nsel = sel_blocks(M);
         const int64_t kk = std::min<int64_t>(k, TOPK_PASS);
@@ -1072,6 +1114,8 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             HIPCHK(h, hipMemcpyAsync(&mean_s2, sc + 4, 8, hipMemcpyDeviceToHost, s));
             HIPCHK(h, hipStreamSynchronize(s));
             pruning = mean_s2 >= h->rho * PRUNE_GATE_S2;
+            rec.mean_s2 = mean_s2;
+            rec.path = 1;
         }
         if (pruning) {
             {
@@ -1082,12 +1126,20 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
                                      nullptr, ub);
                 launch_prune_ub(s, ub, M, done, sc, h->rho, h->bias, p0);
             }
+            int64_t* seed_keep = nullptr;
+            if (h->prune_keep) {
+                // diagnostic: the bound vector (and below the seed list) as they are before the scatter overwrites them
+                if ((rc = ensure(h, h->dkeep, h->cap_keep, (M + G) * 8))) return rc;
+                seed_keep = reinterpret_cast<int64_t*>(h->dkeep) + M;
+                HIPCHK(h, hipMemcpyAsync(h->dkeep, ub, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
+            }
             {
                 // 2. seeds: the G candidates with the largest bound (ties at the threshold: the first by index), exactly
                 Span sp(h, T_ACQ);
                 launch_sel_threshold(s, ub, M, (int)G, hist, st);
                 launch_sel_compact(s, ub, M, 0, st, nullptr, blk, G, dXc, (int)h->d, idx, Xg);
             }
+            if (seed_keep) HIPCHK(h, hipMemcpyAsync(seed_keep, idx, (size_t)G * 8, hipMemcpyDeviceToDevice, s));
             run_chunks(Xg, 0, G, vals, nullptr, nullptr);
             int64_t nsurv = 0;
             {
@@ -1096,10 +1148,14 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
                 launch_topk(s, vals, G, (int)k, h->dblkv, h->dblki, topk_blocks(G), h->dtopv, h->dtopi);
                 launch_fill_neg_inf(s, d_acq, done, M);
                 launch_sel_scatter(s, idx, vals, G, d_acq, ub);
-                launch_sel_compact(s, ub, M, 1, st, h->dtopv + (k - 1), blk, cap, dXc, (int)h->d, idx, Xg);
+                launch_sel_compact(s, ub, M, 1, st, h->dtopv + (k - 1), blk, cap, dXc, (int)h->d, idx, Xg, sc + 5);
                 HIPCHK(h, hipMemcpyAsync(&nsurv, blk + nsel, 8, hipMemcpyDeviceToHost, s));
             }
             HIPCHK(h, hipStreamSynchronize(s));
+            rec.path = nsurv <= cap ? 2 : 3;
+            rec.done = done, rec.nsurv = nsurv;
+            rec.ub = ub, rec.idx = idx, rec.sc = sc, rec.st = st;
+            rec.kept = seed_keep != nullptr;
             if (nsurv <= cap) {
                 // 4. their exact values to their own positions; everything else stays -inf and the top-k below runs as ever
                 run_chunks(Xg, 0, nsurv, vals, nullptr, nullptr);
@@ -1140,6 +1196,7 @@ extern "C" int gpx_sweep(gpx_handle* h, int acq_id, const double* params, int np
                          double* s2) {
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
+        h->prune_rec = gpx_handle::PruneRecord();
         if (!h->fitted) return fail(h, GPX_ESTATE, "sweep: model is not fitted");
         if (!Xc || M < 1) return fail(h, GPX_EARG, "sweep: need M >= 1 candidates");
         return staged_sweep(h, Xc, M, false, acq_all, mu, s2, [&](double* dX, double* dacq, double* dmu, double* ds2) {
@@ -1152,6 +1209,7 @@ extern "C" int gpx_sweep(gpx_handle* h, int acq_id, const double* params, int np
 // "sweep_cache" = 1 and have been kept current by every gpx_append since.
 static int sweep_update_core(gpx_handle* h, int acq_id, const double* params, int nparams, int64_t k,
                              double* top_val, int64_t* top_idx, double* d_acq, double* d_mu, double* d_s2) {
+    h->prune_rec = gpx_handle::PruneRecord();
     if (!h->fitted) return fail(h, GPX_ESTATE, "sweep_update: model is not fitted");
     if (!h->cache_valid)
         return fail(h, GPX_ESTATE, "sweep_update: no valid sweep cache (set option sweep_cache = 1 and run a full "
@@ -1191,6 +1249,7 @@ extern "C" int gpx_sweep_update(gpx_handle* h, int acq_id, const double* params,
                                 double* top_val, int64_t* top_idx, double* acq_all, double* mu, double* s2) {
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
+        h->prune_rec = gpx_handle::PruneRecord();
         if (!h->cache_valid) return fail(h, GPX_ESTATE, "sweep_update: no valid sweep cache");
         return staged_sweep(h, nullptr, h->cache_M, false, acq_all, mu, s2, [&](double*, double* dacq, double* dmu, double* ds2) {
             return sweep_update_core(h, acq_id, params, nparams, k, top_val, top_idx, dacq, dmu, ds2);

@@ -18,6 +18,8 @@
  *                     x_bg_iters rounds) runs beside the factorisation (scripts/chol_bg.py)
  *   "x_skip"          leave out the far updates (bit 0), the chain kernels (bit 1) or the near updates (bit 2) of the stream-scheduled
  *                     factorisation to time its parts alone -- the result is then NOT a factorisation
+ *   "prune_keep"      1: a pruned selection-only sweep keeps a device copy of its bound vector and of its seed list as they are before
+ *                     the seeds are scattered (two device-to-device copies, no other change), for gpx_prune_report [0]
  */
 #ifndef GPX_DIAG_H
 #define GPX_DIAG_H
@@ -47,6 +49,20 @@ int64_t gpx_chol_trace(gpx_handle *h, int64_t *out, int64_t n);
  * links).  chunks as the option "chol_tg_chunks" (<= 0: default).  Returns the total number of entries (written only when
  * cap >= total), -1 on bad arguments.  (Round 5's gpx_chol_tasks had a `split` argument and three counts: renamed, not re-used.) */
 int64_t gpx_chol_tasks2(int nblocks, int chunks, int16_t *out, int64_t cap, int64_t *counts);
+
+/* What the handle's LAST sweep decided about pruning and with what; it only copies what the sweep left behind.
+ * scal[0 .. min(nscal, 14)) = { path: 0 plain (not legal or not tried), 1 the gate declined, 2 pruned, 3 the bound pass ran but more than
+ * cap candidates survived and the plain loop evaluated everything;  M;  k;  G (seeds);  Gg (the gate's generation);  done (leading
+ * candidates evaluated before the bound pass);  cap;  nsurv;  S;  delta;  tau (the k-th best seed value);  the gate's mean s2 (NaN: no
+ * gate);  the seeds' threshold key;  1 if the kept copies exist }.  S .. tau and the key are NaN for paths 0 and 1.
+ * ub (optional, M): the bound vector as the survivor pass read it (-inf where a candidate was evaluated as gate or seed);  idx
+ * (optional, cap_idx): the first min(nsurv, cap, cap_idx) survivors in the order they were compacted;  ub_kept (optional, M) and
+ * seed_idx (optional, cap_seed; G entries): the bound vector and the seed list before the scatter -- only after a sweep that ran with
+ * the option prune_keep = 1.  GPX_ESTATE: no sweep since the record was cleared, a vector was asked for and the last sweep's path is below 2, or a kept vector
+ * was asked for and the sweep kept none.  (Every entry into gpx_sweep[_dev] and gpx_sweep_update[_dev] clears the record, a refused call
+ * included -- the report then answers GPX_ESTATE; a sweep that passes its argument checks starts a new one; nothing else writes the workspace.) */
+int gpx_prune_report(gpx_handle *h, double *scal, int nscal, double *ub, int64_t *idx, int64_t cap_idx, double *ub_kept,
+                     int64_t *seed_idx, int64_t cap_seed);
 
 #ifdef __cplusplus
 }

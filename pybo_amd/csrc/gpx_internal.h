@@ -150,6 +150,20 @@ struct gpx_handle {
     int prune = -1;           // option: selection-only sweeps skip candidates whose EI bound cannot reach the top-k (-1 by size and gate, 0 never, 1 wherever legal)
     char* dprune = nullptr;   // their workspace (one allocation, laid out in api.hip: sweep_core)
     int64_t cap_prune = 0;    // ... in bytes
+    // what the last sweep decided (gpx_prune_report, gpx_diag.h): host scalars and where its vectors lie in dprune
+    struct PruneRecord {
+        int path = -1;            // -1 no sweep yet, 0 plain, 1 the gate declined, 2 pruned, 3 bound pass ran but too many survived
+        int64_t M = 0, k = 0, G = 0, Gg = 0, done = 0, cap = 0, nsurv = 0;
+        double mean_s2 = 0.0;     // the gate's (NaN where it did not run)
+        const double* ub = nullptr;
+        const int64_t* idx = nullptr;
+        const double* sc = nullptr;
+        const int* st = nullptr;
+        bool kept = false;        // dkeep holds this sweep's bound vector and seed list as they were before the scatter
+    } prune_rec;
+    int prune_keep = 0;       // diagnostic option: keep those two device copies
+    char* dkeep = nullptr;    // [ub M][seed idx G]
+    int64_t cap_keep = 0;     // ... in bytes
 
     // sweep cache (warm BO step): candidates and their reduced sums q = colsum(V^2), p = V^T a of the last full
     // sweep, kept current by gpx_append's rank-1 correction and re-scored by gpx_sweep_update
@@ -251,7 +265,7 @@ void launch_prune_mean(hipStream_t s, const double* v, int64_t n, double* out);
 void launch_sel_threshold(hipStream_t s, const double* v, int64_t M, int G, int* hist, int* st);
 int64_t sel_blocks(int64_t M);
 void launch_sel_compact(hipStream_t s, const double* v, int64_t M, int mode, const int* st, const double* tau, int64_t* blk,
-                        int64_t cap, const double* Xc, int d, int64_t* idx, double* Xg);
+                        int64_t cap, const double* Xc, int d, int64_t* idx, double* Xg, double* tau_seen = nullptr);
 void launch_sel_scatter(hipStream_t s, const int64_t* idx, const double* vals, int64_t n, double* out, double* mark);
 void launch_fill_neg_inf(hipStream_t s, double* out, int64_t from, int64_t M);
 

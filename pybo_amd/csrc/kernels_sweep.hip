@@ -847,7 +847,7 @@ __global__ __launch_bounds__(256) void k_prune_delta(const double* __restrict__ 
     }
     if (threadIdx.x == 0) {
         sc[0] = r0[0];
-        sc[1] = 8.0 * (double)(Np + 16) * 1.1102230246251565e-16 * (rho * r0[0] + fabs(bias));
+        sc[1] = 8.0 * (double)(Np + 16) * 1.1102230246251565e-16 * fma(rho, r0[0], fabs(bias));   // (one rounding, whatever -ffp-contract says: gp_ref.prune_delta restates it)
         sc[2] = -1.0;
         sc[3] = 0.0;
     }
@@ -957,10 +957,19 @@ void launch_sel_threshold(hipStream_t s, const double* v, int64_t M, int G, int*
     }
 }
 
-// Stable compaction.  mode 0 (seeds): key(v) >= st[2].  mode 1 (survivors): NOT v < tau (1 - slack), so a NaN bound survives
-// and an evaluated candidate (v = -inf) does not; a tau that is not a normal positive number prunes nothing.
-__device__ __forceinline__ bool sel_pred(int mode, double v, unsigned thr, double cut) {
-    return mode == 0 ? sel_key24(v) >= thr : !(v < cut);
+// Stable compaction.  mode 0 (seeds): the `cap` = G first candidates in (key descending, index ascending) order -- every
+// key above the threshold st[2] (class A: fewer than G by the threshold's definition) and, of the keys equal to it (class E),
+// the first G - |A| by index.  mode 1 (survivors): NOT v < tau (1 - slack), so a NaN bound survives and an evaluated
+// candidate (v = -inf) does not; a tau that is not a normal positive number prunes nothing (all of class E, none of A).
+// A block's two counts travel as one word, E + (A << 40), through the same scan (|A| < 2^23, |E| <= M < 2^40).
+constexpr int SEL_A_SHIFT = 40;
+constexpr long long SEL_E_MASK = (1ll << SEL_A_SHIFT) - 1;
+__device__ __forceinline__ long long sel_class(int mode, double v, unsigned thr, double cut) {
+    if (mode == 0) {
+        const unsigned key = sel_key24(v);
+        return key > thr ? (1ll << SEL_A_SHIFT) : (key == thr ? 1ll : 0ll);
+    }
+    return !(v < cut) ? 1ll : 0ll;
 }
 __device__ __forceinline__ double sel_cut(int mode, const double* tau) {
     if (mode == 0) return 0.0;
@@ -969,19 +978,23 @@ __device__ __forceinline__ double sel_cut(int mode, const double* tau) {
 }
 
 __global__ __launch_bounds__(256) void k_sel_count(const double* __restrict__ v, int64_t M, int mode, const int* __restrict__ st,
-                                                   const double* __restrict__ tau, int64_t* __restrict__ blk) {
-    __shared__ int cnt;
+                                                   const double* __restrict__ tau, int64_t* __restrict__ blk,
+                                                   double* __restrict__ tau_seen) {
+    __shared__ unsigned long long cnt;
     if (threadIdx.x == 0) cnt = 0;
     __syncthreads();
     const unsigned thr = (unsigned)st[2];
     const double cut = sel_cut(mode, tau);
     const int64_t base = (int64_t)blockIdx.x * SEL_PER_BLOCK + (int64_t)threadIdx.x * SEL_PER_THREAD;
-    int c = 0;
+    long long c = 0;
     for (int e = 0; e < SEL_PER_THREAD; ++e)
-        if (base + e < M && sel_pred(mode, v[base + e], thr, cut)) ++c;
-    if (c) atomicAdd(&cnt, c);
+        if (base + e < M) c += sel_class(mode, v[base + e], thr, cut);
+    if (c) atomicAdd(&cnt, (unsigned long long)c);
     __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = cnt;
+    if (threadIdx.x == 0) {
+        blk[blockIdx.x] = (int64_t)cnt;
+        if (tau_seen && blockIdx.x == 0) *tau_seen = *tau;      // the cut's tau, for gpx_prune_report (the top-k reuses its slot)
+    }
 }
 
 // blk[0..nblk) counts -> exclusive offsets in place, blk[nblk] = total (one workgroup walks the blocks 256 at a time)
@@ -1011,45 +1024,58 @@ __global__ __launch_bounds__(256) void k_sel_scan(int64_t* __restrict__ blk, int
 
 // the selected candidates in their original order: idx[j] = n and row j of Xg = row n of Xc, for the first `cap` of them
 __global__ __launch_bounds__(256) void k_sel_write(const double* __restrict__ v, int64_t M, int mode, const int* __restrict__ st,
-                                                   const double* __restrict__ tau, const int64_t* __restrict__ blk, int64_t cap,
-                                                   const double* __restrict__ Xc, int d, int64_t* __restrict__ idx,
+                                                   const double* __restrict__ tau, const int64_t* __restrict__ blk, int64_t nblk,
+                                                   int64_t cap, const double* __restrict__ Xc, int d, int64_t* __restrict__ idx,
                                                    double* __restrict__ Xg) {
-    __shared__ int sh[256];
+    __shared__ long long sh[256];
     const unsigned thr = (unsigned)st[2];
     const double cut = sel_cut(mode, tau);
+    // of class E, the first `need` by index are taken: all of them for the survivors, what the class A leaves of cap for the seeds
+    const long long need = mode == 0 ? cap - (blk[nblk] >> SEL_A_SHIFT) : INT64_MAX;
     const int64_t base = (int64_t)blockIdx.x * SEL_PER_BLOCK + (int64_t)threadIdx.x * SEL_PER_THREAD;
-    unsigned mask = 0;
-    for (int e = 0; e < SEL_PER_THREAD; ++e)
-        if (base + e < M && sel_pred(mode, v[base + e], thr, cut)) mask |= 1u << e;
-    const int mine = __popc(mask);
+    long long cls[SEL_PER_THREAD];
+    long long mine = 0;
+#pragma unroll
+    for (int e = 0; e < SEL_PER_THREAD; ++e) {
+        cls[e] = (base + e < M) ? sel_class(mode, v[base + e], thr, cut) : 0ll;
+        mine += cls[e];
+    }
     sh[threadIdx.x] = mine;
     __syncthreads();
     for (int w = 1; w < 256; w <<= 1) {
-        const int add = ((int)threadIdx.x >= w) ? sh[threadIdx.x - w] : 0;
+        const long long add = ((int)threadIdx.x >= w) ? sh[threadIdx.x - w] : 0;
         __syncthreads();
         sh[threadIdx.x] += add;
         __syncthreads();
     }
-    int64_t off = blk[blockIdx.x] + sh[threadIdx.x] - mine;
+    long long before = blk[blockIdx.x] + sh[threadIdx.x] - mine;      // the two classes' counts ahead of this thread's first element
+#pragma unroll
     for (int e = 0; e < SEL_PER_THREAD; ++e) {
-        if (!((mask >> e) & 1u)) continue;
-        if (off < cap) {
-            idx[off] = base + e;
-            for (int c = 0; c < d; ++c) Xg[off * d + c] = Xc[(base + e) * d + c];
+        const long long c = cls[e];
+        if (c) {
+            const long long nA = before >> SEL_A_SHIFT, nE = before & SEL_E_MASK;
+            const bool take = (c >> SEL_A_SHIFT) || nE < need;
+            const long long off = nA + (nE < need ? nE : need);
+            if (take && off < cap) {
+                idx[off] = base + e;
+                for (int q = 0; q < d; ++q) Xg[off * d + q] = Xc[(base + e) * d + q];
+            }
+            before += c;
         }
-        ++off;
     }
 }
 
 int64_t sel_blocks(int64_t M) { return (M + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK; }
 
-// count only (total -> blk[nblk]) and the offsets the write needs
+// count only (total -> blk[nblk]) and the offsets the write needs.  tau_seen (optional): the survivor pass leaves the tau it cut
+// with there -- one store by one thread, read only by gpx_prune_report; the shipping path carries it so that the diagnostic adds no
+// launch and no copy to a sweep.
 void launch_sel_compact(hipStream_t s, const double* v, int64_t M, int mode, const int* st, const double* tau, int64_t* blk,
-                        int64_t cap, const double* Xc, int d, int64_t* idx, double* Xg) {
+                        int64_t cap, const double* Xc, int d, int64_t* idx, double* Xg, double* tau_seen) {
     const int64_t nblk = sel_blocks(M);
-    hipLaunchKernelGGL(k_sel_count, dim3((unsigned)nblk), dim3(256), 0, s, v, M, mode, st, tau, blk);
+    hipLaunchKernelGGL(k_sel_count, dim3((unsigned)nblk), dim3(256), 0, s, v, M, mode, st, tau, blk, tau_seen);
     hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(256), 0, s, blk, nblk);
-    hipLaunchKernelGGL(k_sel_write, dim3((unsigned)nblk), dim3(256), 0, s, v, M, mode, st, tau, blk, cap, Xc, d, idx, Xg);
+    hipLaunchKernelGGL(k_sel_write, dim3((unsigned)nblk), dim3(256), 0, s, v, M, mode, st, tau, blk, nblk, cap, Xc, d, idx, Xg);
 }
 
 // out[idx[j]] = vals[j] for j < n; mark (optional): those candidates' bounds -> -inf (evaluated: never a survivor)

@@ -32,7 +32,8 @@ I64_MIN, I64_MAX = -2 ** 63, 2 ** 63 - 1
 VALUES = [-2, -1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 15, 16, 17, 31, 32, 33, 100, 127, 128, 129, 255, 256, 65535, 65536, 65537,
           131072, 100000, 100001, 10 ** 6, 10 ** 6 + 1, 10 ** 7, 10 ** 7 + 1, 10 ** 9, 10 ** 9 + 1, 2 ** 31, -2 ** 31 - 1,
           I64_MIN, I64_MAX]
-# every option gpx_set_option knew before the table, then names it must not know
+# every option gpx_set_option knew before the table, then names it must not know ("prune" and "prune_keep" came after it:
+# tests/test_abi.py::test_option_table_agrees_with_the_headers covers every row of the table, those two included)
 OPTIONS = ['chunk', 'super_m', 'tile_order', 'sweep_cache', 'chol_w', 'chol_tg', 'chol_tg_chunks', 'chol_tg_grid',
            'chol_tg_trace', 'chol_tg_tmo_ms', 'chol_tg_min', 'chol_tg_max', 'chol_tg_isolate', 'chol_tg_nap', 'chol_tg_db',
            'chol_tg_db_max', 'chol_tg_fuse', 'trtri_ahead', 'trtri_ahead_min', 'chol_fuse', 'chol_graph', 'chol_merge',

@@ -55,7 +55,7 @@ def test_shipping_and_diagnostics_builds_export_the_same_abi():
 
 # what test_shipping_library_refuses_the_diagnostic_options offers the shipping library (every one must be refused)
 DIAG_PROBES = (('x_skip', 1), ('x_bg', 4), ('x_bg_lds', 8), ('x_bg_iters', 10), ('chol_tg_chunks', 1248), ('chol_tg_nap', 8),
-               ('chol_tg_grid', 64), ('chol_tg_isolate', 0), ('chol_tg_trace', 1), ('grad_rb_cs', 128), ('x_rff', 1))
+               ('chol_tg_grid', 64), ('chol_tg_isolate', 0), ('chol_tg_trace', 1), ('grad_rb_cs', 128), ('x_rff', 1), ('prune_keep', 1))
 
 
 def _option_table():
