@@ -59,8 +59,7 @@ enum gpx_acq {
 };
 
 /* ---- lifetime --------------------------------------------------------------------------- */
-/* `stream` is a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) or NULL for a
- * library-owned stream. */
+/* `stream` is a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) or NULL for a library-owned stream. */
 int gpx_create(int device, void *stream, gpx_handle **out);
 int gpx_destroy(gpx_handle *h);
 const char *gpx_last_error(const gpx_handle *h);
@@ -106,8 +105,7 @@ int gpx_set_option(gpx_handle *h, const char *name, int64_t value);
  * Gram build K = k(X,X) + sn2 I and Cholesky K = R^T R.  The triangular inverse T = R^-T, a = T (y - bias)
  * and alpha follow on FIRST USE (sweep, predict, mean_at_obs, loglik, append, introspection): the Thompson
  * entry points never read them.  X is (N,d), y is (N,), ell is (d,) on the HOST in both variants. */
-int gpx_fit(gpx_handle *h, const double *X, int64_t N, int64_t d, const double *y, int kernel_id,
-            const double *ell, double rho, double sn2, double bias);
+int gpx_fit(gpx_handle *h, const double *X, int64_t N, int64_t d, const double *y, int kernel_id, const double *ell, double rho, double sn2, double bias);
 int gpx_fit_dev(gpx_handle *h, const double *dX, int64_t N, int64_t d, const double *dy,
                 int kernel_id, const double *ell, double rho, double sn2, double bias);
 /* log marginal likelihood of the fitted model, -1/2 a.a - sum log R_ii - N/2 log 2pi: what a
@@ -118,6 +116,10 @@ int gpx_loglik(gpx_handle *h, double *out);
  * where K + sn2 I is not positive definite.  One batched launch chain and one host synchronisation per 64 vectors: what
  * reggie.MCMC(model, n=10, burn=100) [pybo/bayesopt.py:115] repeats per proposal. */
 int gpx_loglik_batch(gpx_handle *h, int64_t B, const double *hypers, double *out);
+/* L = gpx_loglik (loglik may be NULL) and its gradient, grad (d + 3), in the order [sn2, rho, ell_1..d, bias] of gpx_loglik_batch's rows
+ * (natural parameters): what maximum-likelihood / MAP fitting of the hyper-parameters asks for.  From the fitted handle's T, alpha and
+ * scaled inputs: N^3/3 multiply-adds on the tile engine, one host synchronisation, no atomics (same fit, same bits); fit and sweep cache untouched. */
+int gpx_loglik_grad(gpx_handle *h, double *loglik, double *grad);
 /* Incremental fit: absorb ONE more observation x (d,), y into the current factorisation in O(N^2) (two memory-bound passes over
  * T and U) instead of refitting -- the per-iteration `model.add_data(x, y)` of the BO loop [pybo/bayesopt.py:269].  A full
  * 128-block is extended inside buffers allocated with head-room (device copy, no refit).  GPX_ENOTPD like gpx_fit.  A live sweep
@@ -166,9 +168,8 @@ int gpx_predict_mean(gpx_handle *h, const double *Xc, int64_t M, double *mu, dou
 /* Evaluates acq over M candidates, returns the k best (value desc, then index asc) in host
  * buffers top_val[k], top_idx[k] (indices are LOCAL to Xc; add your shard offset).  acq_all, mu,
  * s2 (each (M,), host in gpx_sweep / device in gpx_sweep_dev) are optional (NULL to skip). */
-int gpx_sweep(gpx_handle *h, int acq_id, const double *params, int nparams, const double *Xc,
-              int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *acq_all, double *mu,
-              double *s2);
+int gpx_sweep(gpx_handle *h, int acq_id, const double *params, int nparams, const double *Xc, int64_t M, int64_t k,
+              double *top_val, int64_t *top_idx, double *acq_all, double *mu, double *s2);
 int gpx_sweep_dev(gpx_handle *h, int acq_id, const double *params, int nparams, const double *dXc,
                   int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *d_acq_all,
                   double *d_mu, double *d_s2);
@@ -197,8 +198,7 @@ int gpx_rff_sweep(gpx_handle *h, const double *W, const double *b, const double 
 int gpx_rff_sweep_dev(gpx_handle *h, const double *W, const double *b, const double *theta,
                       int64_t S, int64_t n, int64_t d, double bias, const double *dXc, int64_t M,
                       int64_t k, double *top_val, int64_t *top_idx, double *d_vals_all);
-/* value f (M,) and gradient g (M,d) of ONE draw at M points (host buffers): the
- * `f(x[None], grad=True)` calls of the L-BFGS refinement   [pybo/solvers/lbfgs.py:56-58] */
+/* value f (M,) and gradient g (M,d) of ONE draw at M points (host buffers): `f(x[None], grad=True)` of the L-BFGS refinement [pybo/solvers/lbfgs.py:56-58] */
 int gpx_rff_grad(gpx_handle *h, const double *W, const double *b, const double *theta, int64_t n,
                  int64_t d, double bias, const double *Xc, int64_t M, double *f, double *g);
 /* feature Gram for the weight posterior: Phi = cos(X_obs W^T + b) (N,n) on the device's X_obs;

@@ -59,6 +59,7 @@ SYMBOLS = {
     'gpx_fit_dev': (C.c_int, [_P, _P, _i64, _i64, _P, C.c_int, _P, _dbl, _dbl, _dbl]),
     'gpx_loglik': (C.c_int, [_P, _P]),
     'gpx_loglik_batch': (C.c_int, [_P, _i64, _P, _P]),
+    'gpx_loglik_grad': (C.c_int, [_P, _P, _P]),
     'gpx_append': (C.c_int, [_P, _P, _dbl]),
     'gpx_append_begin': (C.c_int, [_P, _P]),
     'gpx_fail_pivot': (_i64, [_P]),
@@ -480,6 +481,14 @@ class Engine(object):
         out = np.empty(len(hypers))
         self._check(self._lib.gpx_loglik_batch(self._h, len(hypers), _ptr(hypers), _ptr(out)))
         return out
+
+    def loglik_grad(self):
+        """(L, dL/d[sn2, rho, ell_1..d, bias]) of the current fit in NATURAL parameters (gpx_loglik_grad): L is gpx_loglik's value,
+        the gradient comes from one triangular product on the device."""
+        out = C.c_double()
+        grad = np.empty(self.d + 3)
+        self._check(self._lib.gpx_loglik_grad(self._h, C.byref(out), _ptr(grad)))
+        return out.value, grad
 
     def append(self, x, y):
         """Rank-1 extension by one observation; returns False when a refit is needed (block boundary)."""

@@ -335,7 +335,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dpend, h->drefine, h->dspec};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -666,6 +666,13 @@ extern "C" int gpx_loglik(gpx_handle* h, double* out) {
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
         return gpx::loglik_host(h, out);
+    });
+}
+
+extern "C" int gpx_loglik_grad(gpx_handle* h, double* loglik, double* grad) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        return gpx::loglik_grad_host(h, loglik, grad);
     });
 }
 

@@ -194,6 +194,8 @@ struct gpx_handle {
 
     double* dbatch = nullptr;    // gpx_loglik_batch: Gram / factor / scaled inputs / a of the batch (one allocation)
     int64_t cap_batch = 0;
+    double* dhyper = nullptr;    // gpx_loglik_grad: the tiles' partial sums [tiles][d + 2], then [L, d + 3 components] (on first use)
+    int64_t cap_hyper = 0;
 
     // timers
     std::vector<gpx::EventPair> pending;
@@ -280,6 +282,8 @@ int predict_grad_host(gpx_handle* h, const double* Xc, int64_t M, double* mu, do
 int ensure_inverse(gpx_handle* h);
 
 int loglik_host(gpx_handle* h, double* out);
+void launch_loglik(gpx_handle* h, double* out);   // kernels_grad.hip: the evidence of the current fit (a, R formed) -> out[0] on the device
+int loglik_grad_host(gpx_handle* h, double* loglik, double* grad);   // kernels_hyper.hip
 int loglik_batch_host(gpx_handle* h, int64_t B, const double* hyp, double* out);   // kernels_fit.hip
 int append_host(gpx_handle* h, const double* x, double ynew);
 // the y-independent kernels of an append, enqueued on s: k* = k(X, x), r = T k*, {d, 1/d, (resid - r.a)/d, d^2} -> scal

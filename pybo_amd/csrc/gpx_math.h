@@ -90,4 +90,40 @@ __device__ __forceinline__ double kern_eval(int kid, double r2, double rho) {
     }
 }
 
+// k and g = dk/dr2 (the input gradients of kernels_grad.hip, the evidence gradient of kernels_hyper.hip); k is kern_eval's
+// expression, operation for operation (rho * poly * exp, associated from the left), so that K* here and in the cross-Gram /
+// Gram are the same bits
+__device__ __forceinline__ void kern_and_grad(int kid, double r2, double rho, double& k, double& g) {
+    switch (kid) {
+        case GPX_KERN_SE_ARD: {
+            k = rho * exp_nonpos(-0.5 * r2);
+            g = -0.5 * k;
+            break;
+        }
+        case GPX_KERN_MATERN52: {
+            const double s = 2.23606797749978969641 * sqrt_r2(r2, 512.0);
+            const double x = exp_nonpos(-s);
+            k = rho * m52_poly(s) * x;
+            g = -(5.0 / 6.0) * (1.0 + s) * (rho * x);
+            break;
+        }
+        case GPX_KERN_MATERN32: {
+            const double s = 1.73205080756887729353 * sqrt_r2(r2, 512.0);
+            const double x = exp_nonpos(-s);
+            k = rho * m32_poly(s) * x;
+            g = -1.5 * (rho * x);
+            break;
+        }
+        default: {
+            const double r = sqrt_r2(r2, r2);
+            k = rho * exp_nonpos(-r);
+            // exp(-r) has a kink at r = 0 (a candidate on top of an observation: the L-BFGS seeds of the
+            // recommender ARE observations): dk/dx is +-k/ell from either side, take the symmetric value 0.  The same 0 for
+            // every r2 <= 1e-280 (distances below 1e-140 length scales), where sqrt_r2 returns 0: such a candidate is
+            // treated as sitting on the observation (tests/test_gpu_devmath.py pins both sides of that cutoff)
+            g = (r > 0.0) ? -0.5 * k / r : 0.0;
+        }
+    }
+}
+
 }  // namespace gpx

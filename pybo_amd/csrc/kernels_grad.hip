@@ -25,40 +25,7 @@ namespace gpx {
 
 constexpr int GB = 16;  // candidates per pass over T and U (the 10 lock-step L-BFGS seeds of solve_lbfgs fit in one)
 
-// k and g = dk/dr2; k is kern_eval's expression, operation for operation (rho * poly * exp, associated from the left), so
-// that K* here and in the cross-Gram / Gram are the same bits
-__device__ __forceinline__ void kern_and_grad(int kid, double r2, double rho, double& k, double& g) {
-    switch (kid) {
-        case GPX_KERN_SE_ARD: {
-            k = rho * exp_nonpos(-0.5 * r2);
-            g = -0.5 * k;
-            break;
-        }
-        case GPX_KERN_MATERN52: {
-            const double s = 2.23606797749978969641 * sqrt_r2(r2, 512.0);
-            const double x = exp_nonpos(-s);
-            k = rho * m52_poly(s) * x;
-            g = -(5.0 / 6.0) * (1.0 + s) * (rho * x);
-            break;
-        }
-        case GPX_KERN_MATERN32: {
-            const double s = 1.73205080756887729353 * sqrt_r2(r2, 512.0);
-            const double x = exp_nonpos(-s);
-            k = rho * m32_poly(s) * x;
-            g = -1.5 * (rho * x);
-            break;
-        }
-        default: {
-            const double r = sqrt_r2(r2, r2);
-            k = rho * exp_nonpos(-r);
-            // exp(-r) has a kink at r = 0 (a candidate on top of an observation: the L-BFGS seeds of the
-            // recommender ARE observations): dk/dx is +-k/ell from either side, take the symmetric value 0.  The same 0 for
-            // every r2 <= 1e-280 (distances below 1e-140 length scales), where sqrt_r2 returns 0: such a candidate is
-            // treated as sitting on the observation (tests/test_gpu_devmath.py pins both sides of that cutoff)
-            g = (r > 0.0) ? -0.5 * k / r : 0.0;
-        }
-    }
-}
+// (k and g = dk/dr2: kern_and_grad, gpx_math.h)
 
 // ks[m][i], g[m][i] for i < Np (0 beyond N); grid (Np/256, mb)
 __global__ __launch_bounds__(256) void k_kstar(const double* __restrict__ Xs, int64_t N, int64_t Np, int d,
@@ -978,12 +945,16 @@ __global__ __launch_bounds__(256) void k_loglik(const double* __restrict__ R, in
     if (threadIdx.x == 0) out[0] = -0.5 * q - ld - 0.5 * (double)N * 1.83787706640934548356;
 }
 
+void launch_loglik(gpx_handle* h, double* out) {
+    hipLaunchKernelGGL(k_loglik, dim3(1), dim3(256), 0, h->stream, h->dR, h->Np, h->N, h->da, out);
+}
+
 int loglik_host(gpx_handle* h, double* out) {
     if (!h->fitted) { h->err = "loglik: model is not fitted"; return GPX_ESTATE; }
     if (!out) { h->err = "loglik: NULL output"; return GPX_EARG; }
     if (hipSetDevice(h->device) != hipSuccess) { h->err = "hipSetDevice failed"; return GPX_EHIP; }
     if (int rc0 = ensure_inverse(h)) return rc0;     // a = T (y - bias)
-    hipLaunchKernelGGL(k_loglik, dim3(1), dim3(256), 0, h->stream, h->dR, h->Np, h->N, h->da, h->dscal + 8);
+    launch_loglik(h, h->dscal + 8);
     if (hipMemcpyAsync(out, h->dscal + 8, 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
         hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
         h->err = "loglik: kernel or D2H copy failed";

@@ -364,9 +364,19 @@ class GP(object):
         self.bias = float(theta[2 + d])
         self._fitted = False                     # same data, new hyper-parameters: refit on next use
 
-    def loglikelihood(self):
-        """log p(y | X, hyper-parameters) of the current fit, computed on the device."""
-        return self._engine().loglik()
+    def loglikelihood(self, grad=False):
+        """log p(y | X, hyper-parameters) of the current fit, computed on the device.  With `grad`: (L, dL/dtheta) in
+        `hyper_vector()` coordinates [log sn2, log rho, log ell.., bias] -- the device's natural-parameter gradient
+        (gpx_loglik_grad) times [sn2, rho, ell.., 1]."""
+        if not grad:
+            return self._engine().loglik()
+        L, g = self._engine().loglik_grad()
+        return L, g * np.concatenate([[self.sn2, self.rho], self.ell, [1.0]])
+
+    def optimize(self, maxiter=200, rng=None):
+        """Point estimate of the hyper-parameters: maximise likelihood x priors (models/optimize.py); returns self."""
+        from .optimize import optimize
+        return optimize(self, maxiter=maxiter, rng=rng)
 
     def loglik_at(self, thetas):
         """log p(y | X, theta_b) for the rows of `thetas` ([log sn2, log rho, log ell_1..d, bias]) in ONE batched

@@ -14,7 +14,7 @@ import math
 
 import numpy as np
 
-__all__ = ['log_prior']
+__all__ = ['log_prior', 'log_prior_grad', 'prior_bounds']
 
 
 def log_prior(prior, x):
@@ -58,3 +58,35 @@ def log_prior(prior, x):
             return -np.inf
         return float(np.sum(np.log(np.log1p(3.0 * (scale / x) ** 2))))
     raise ValueError('unknown prior {!r}'.format(kind))
+
+
+def log_prior_grad(prior, x):
+    """d log_prior / dx, element-wise (same shape as `x`), for the four densities above; `uniform` is 0 inside its
+    support (its bounds are the caller's business: `prior_bounds`); NaN outside the support of a density."""
+    x = np.asarray(x, dtype=float)
+    if prior is None:
+        return np.zeros_like(x)
+    kind, args = prior[0], prior[1:]
+    if kind == 'uniform':
+        a, b = (np.broadcast_to(np.asarray(v, dtype=float), x.shape) for v in args)
+        return np.where((x >= a) & (x <= b), 0.0, np.nan)
+    if kind == 'normal':
+        mu, s2 = float(args[0]), float(args[1])
+        return -(x - mu) / s2
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if kind == 'lognormal':
+            mu, sigma = float(args[0]), float(args[1])
+            g = -((np.log(x) - mu) / sigma ** 2 + 1.0) / x
+        elif kind == 'horseshoe':
+            u = 3.0 * (float(args[0]) / x) ** 2
+            g = -2.0 * u / (x * (1.0 + u) * np.log1p(u))
+        else:
+            raise ValueError('unknown prior {!r}'.format(kind))
+    return np.where(x > 0, g, np.nan)
+
+
+def prior_bounds(prior, n=1):
+    """(lo, hi) arrays of length n: the support a `uniform` prior confines its parameter to, (-inf, inf) otherwise."""
+    if prior is not None and prior[0] == 'uniform':
+        return tuple(np.broadcast_to(np.asarray(v, dtype=float), (n,)).copy() for v in prior[1:3])
+    return np.full(n, -np.inf), np.full(n, np.inf)

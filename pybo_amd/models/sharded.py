@@ -161,8 +161,12 @@ class ShardedGP(object):
         for r in self._reps:
             r.set_hyper_vector(theta)
 
-    def loglikelihood(self):
-        return self._reps[0].loglikelihood()
+    def loglikelihood(self, grad=False):
+        return self._reps[0].loglikelihood(grad)
+
+    def optimize(self, maxiter=200, rng=None):
+        from .optimize import optimize
+        return optimize(self, maxiter=maxiter, rng=rng)
 
     def loglik_at(self, thetas):
         return self._reps[0].loglik_at(thetas)
