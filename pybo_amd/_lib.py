@@ -48,6 +48,7 @@ DIAG_SYMBOLS = {
     'gpx_chol_trace': (_i64, [_P, _P, _i64]),
     'gpx_chol_tasks2': (_i64, [C.c_int, C.c_int, _P, _i64, _P]),
     'gpx_prune_report': (C.c_int, [_P, _P, C.c_int, _P, _P, _i64, _P, _P, _i64]),
+    'gpx_prune_dots': (C.c_int, [_P, _P]),
 }
 SYMBOLS = {
     'gpx_create': (C.c_int, [C.c_int, _P, C.POINTER(_P)]),
@@ -727,13 +728,16 @@ class Engine(object):
 
     def prune_report(self, vectors=True):
         """Diagnostic (gpx_prune_report in csrc/gpx_diag.h): what the last sweep decided about pruning.  dict(path, M, k, G, Gg, done, cap,
-        nsurv, S, delta, tau, gate_s2, thr_key, kept); with `vectors`, where the bound pass ran, also ub (M,) as the survivor pass read
+        nsurv, S, delta, tau, gate_s2, thr_key, kept, bound_kernel = 'generic' / 'mfma' (None: no bound pass), guard = the matrix-pipe
+        kernel's (d + 4)(R_x + R_z)^2 (NaN where the host chose the generic kernel)); with `vectors`, where the bound pass ran, also ub (M,) as the survivor pass read
         it and idx, the survivors in compaction order (empty where it fell back); after a sweep with option prune_keep = 1 also ub_kept
         and seed_idx, the bounds and the seed list before the scatter."""
-        scal = np.full(14, np.nan)
+        scal = np.full(16, np.nan)
         self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), None, None, 0, None, None, 0))
-        names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'S', 'delta', 'tau', 'gate_s2', 'thr_key', 'kept')
+        names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'S', 'delta', 'tau', 'gate_s2', 'thr_key', 'kept',
+                 'bound_kernel', 'guard')
         r = dict(zip(names, scal.tolist()))
+        r['bound_kernel'] = None if np.isnan(r['bound_kernel']) else ('generic', 'mfma')[int(r['bound_kernel'])]
         for n in ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'kept'):
             r[n] = int(r[n])
         r['path'] = self.PRUNE_PATHS[r['path']]
@@ -748,6 +752,13 @@ class Engine(object):
             self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), _ptr(r['ub']), _ptr(r['idx']), nidx,
                                                    _ptr(r['ub_kept']), _ptr(r['seed_idx']), r['G'] if kept else 0))
         return r
+
+    def prune_dots(self):
+        """Diagnostic (gpx_prune_dots): alpha2 . k(X, z_n) of the last pruned sweep's bound pass (option prune_keep = 1), before EI."""
+        M = self.prune_report(vectors=False)['M']
+        out = np.empty(M)
+        self._check(self._lib.gpx_prune_dots(self._h, _ptr(out)))
+        return out
 
     def chol_trace(self, nblocks, full_log=False):
         """Diagnostic (option chol_tg_trace = 1): the task-graph factorisation's own stamps of the last fit, microseconds

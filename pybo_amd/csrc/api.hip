@@ -149,6 +149,7 @@ static const Option kOptions[] = {
      [](gpx_handle* h, int64_t v) { h->cache_on = (v == 1); if (v < 0) { h->cache_valid = false; h->npend = 0; } }},
     {"prune", SHIP, -1, 1, "prune must be -1 (by size and gate), 0 (never) or 1 (wherever legal)", store<&gpx_handle::prune>},
     {"prune_keep", DIAG, 0, 1, "prune_keep must be 0 or 1", store<&gpx_handle::prune_keep>},
+    {"prune_bound", DIAG, -1, 1, "prune_bound must be -1 (by guard), 0 (generic kernel) or 1 (matrix-pipe kernel)", store<&gpx_handle::prune_bound>},
     {"chol_w", SHIP, 0, 8, "chol_w must be 0 (by size) or in [2, 8]", store<&gpx_handle::chol_w>, [](int64_t v) { return v != 1; }},
     {"chol_tg", SHIP, -1, 1000000000, TG, store<&gpx_handle::chol_tg>, [](int64_t v) { return v == 0 || v == 1; }, "chol_tg must be 0 or 1"},
     {"chol_tg_chunks", DIAG, -1, 1000000000, TG, store<&gpx_handle::tg_chunks>},
@@ -397,17 +398,19 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
             return fail(h, GPX_ESTATE, "prune_report: the last sweep ran without the option prune_keep");
         HIPCHK(h, hipSetDevice(h->device));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        double sc[8];
+        double sc[16];
         int st[4] = {0, 0, 0, 0};
         for (double& v : sc) v = NAN;
         if (bound) {
             HIPCHK(h, hipMemcpy(sc, r.sc, sizeof sc, hipMemcpyDeviceToHost));
             HIPCHK(h, hipMemcpy(st, r.st, sizeof st, hipMemcpyDeviceToHost));
         }
-        const double out[14] = {(double)r.path, (double)r.M,     (double)r.k, (double)r.G, (double)r.Gg,
+        const bool guarded_bound = bound && r.bound_kernel < 0;      // the device chose the bound pass's kernel: sc[8] = guard value, sc[9] = choice
+        const double out[16] = {(double)r.path, (double)r.M,     (double)r.k, (double)r.G, (double)r.Gg,
                                 (double)r.done, (double)r.cap,   (double)r.nsurv, sc[0],   sc[1],
-                                sc[5],          r.mean_s2,       bound ? (double)st[2] : NAN, r.kept ? 1.0 : 0.0};
-        for (int i = 0; i < nscal && i < 14; ++i) scal[i] = out[i];
+                                sc[5],          r.mean_s2,       bound ? (double)st[2] : NAN, r.kept ? 1.0 : 0.0,
+                                bound ? (guarded_bound ? sc[9] : 0.0) : NAN, guarded_bound ? sc[8] : NAN};
+        for (int i = 0; i < nscal && i < 16; ++i) scal[i] = out[i];
         if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
         const int64_t nidx = std::min(std::min(r.nsurv, r.cap), cap_idx);
         if (idx && nidx > 0) HIPCHK(h, hipMemcpy(idx, r.idx, (size_t)nidx * 8, hipMemcpyDeviceToHost));
@@ -415,6 +418,19 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
         const int64_t nseed = std::min(r.G, cap_seed);
         if (seed_idx && nseed > 0)
             HIPCHK(h, hipMemcpy(seed_idx, h->dkeep + r.M * 8, (size_t)nseed * 8, hipMemcpyDeviceToHost));
+        return GPX_OK;
+    });
+}
+
+extern "C" int gpx_prune_dots(gpx_handle* h, double* dots) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        if (!dots) return fail(h, GPX_EARG, "prune_dots: NULL output");
+        const gpx_handle::PruneRecord& r = h->prune_rec;
+        if (r.path < 2 || !r.kept) return fail(h, GPX_ESTATE, "prune_dots: the last sweep kept no bound pass (option prune_keep)");
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(dots, h->dkeep + (r.M + r.G) * 8, (size_t)r.M * 8, hipMemcpyDeviceToHost));
         return GPX_OK;
     });
 }
@@ -1095,8 +1111,10 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
         if ((rc = ensure(h, h->dblki, h->cap_blki, nblk_top * kk))) return rc;
         if ((rc = ensure(h, h->dtopv, h->cap_top, (int64_t)TOPK_MAX * 2))) return rc;
         h->dtopi = reinterpret_cast<int64_t*>(h->dtopv + TOPK_MAX);
-        // workspace: [ub M][vals cap][Xg cap d][idx cap][blk nsel + 1][alpha2 Np][sabs Np][gate s2 Gg][sc 8][hist 2 x 4096 + st 8 (int)]
-        const int64_t words = M + cap + cap * h->d + cap + (nsel + 1) + 2 * Np + Gg + 8 + (2 * 4096 + 8) / 2;
+        // workspace: [ub M][vals cap][Xg cap d][idx cap][blk nsel + 1][alpha2 Np][sabs Np][gate s2 Gg][sc 16][hist 2 x 4096 + st 8 (int)]
+        // [pad to 32 bytes][the matrix-pipe bound kernel's operands]
+        const int64_t words0 = M + cap + cap * h->d + cap + (nsel + 1) + 2 * Np + Gg + 16 + (2 * 4096 + 8) / 2;
+        const int64_t words = (words0 + 3) / 4 * 4 + bound_mfma_ws_words(Np);
         if ((rc = ensure(h, h->dprune, h->cap_prune, words * 8))) return rc;
         double* ub = reinterpret_cast<double*>(h->dprune);
         double* vals = ub + M;
@@ -1107,8 +1125,11 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
         double* sabs = alpha2 + Np;
         double* gs2 = sabs + Np;
         double* sc = gs2 + Gg;
-        int* hist = reinterpret_cast<int*>(sc + 8);
+        int* hist = reinterpret_cast<int*>(sc + 16);
         int* st = hist + 2 * 4096;
+        double* bws = ub + (words0 + 3) / 4 * 4;
+        // the bound pass's kernel: the matrix-pipe form for SE-ARD up to d = 18 where its guard allows (decided on the device)
+        const bool bound_mfma = h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0;
 
         if (h->prune < 0) {
             // Gate, BEFORE the bound pass: the prior variance is a useful bound only where the data leave variance to explain.
@@ -1129,14 +1150,21 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
                 // 1. bound pass: ub[n] = EI(bias + alpha . k(X, z_n) + delta, s2 = rho) >= the value the exact chain returns
                 Span sp(h, T_BOUND);
                 launch_prune_alpha(s, h->dU, Np, h->da, h->rho, h->bias, alpha2, sabs, sc);
+                if (bound_mfma)
+                    launch_bound_mfma(s, h->dXs, h->N, Np, (int)h->d, alpha2, h->rho, dXc, M, h->dinvell, h->prune_bound, bws, sc, ub);
                 launch_sweep_rank1_v(s, h->dXs, h->N, (int)h->d, alpha2, Np, sc + 2, dXc, M, h->dinvell, h->kernel_id, h->rho,
-                                     nullptr, ub);
+                                     nullptr, ub, bound_mfma ? sc + 9 : nullptr);
+                if (h->prune_keep) {
+                    // diagnostic: the dots as the kernel left them (gpx_prune_dots), behind the two copies below
+                    if ((rc = ensure(h, h->dkeep, h->cap_keep, (2 * M + G) * 8))) return rc;
+                    HIPCHK(h, hipMemcpyAsync(h->dkeep + (M + G) * 8, ub, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
+                }
                 launch_prune_ub(s, ub, M, done, sc, h->rho, h->bias, p0);
             }
+            rec.bound_kernel = bound_mfma ? -1 : 0;
             int64_t* seed_keep = nullptr;
             if (h->prune_keep) {
                 // diagnostic: the bound vector (and below the seed list) as they are before the scatter overwrites them
-                if ((rc = ensure(h, h->dkeep, h->cap_keep, (M + G) * 8))) return rc;
                 seed_keep = reinterpret_cast<int64_t*>(h->dkeep) + M;
                 HIPCHK(h, hipMemcpyAsync(h->dkeep, ub, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
             }

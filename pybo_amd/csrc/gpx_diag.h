@@ -19,7 +19,10 @@
  *   "x_skip"          leave out the far updates (bit 0), the chain kernels (bit 1) or the near updates (bit 2) of the stream-scheduled
  *                     factorisation to time its parts alone -- the result is then NOT a factorisation
  *   "prune_keep"      1: a pruned selection-only sweep keeps a device copy of its bound vector and of its seed list as they are before
- *                     the seeds are scattered (two device-to-device copies, no other change), for gpx_prune_report [0]
+ *                     the seeds are scattered, and of the bound pass's dots (three device-to-device copies, no other change), for
+ *                     gpx_prune_report and gpx_prune_dots [0]
+ *   "prune_bound"     the kernel of a pruned sweep's bound pass: 0 the generic k_sweep_rankq<1>; 1 the matrix-pipe kernel wherever it exists
+ *                     (SE-ARD, d <= 18), whatever its guard says; -1 by the guard [-1]
  */
 #ifndef GPX_DIAG_H
 #define GPX_DIAG_H
@@ -51,10 +54,11 @@ int64_t gpx_chol_trace(gpx_handle *h, int64_t *out, int64_t n);
 int64_t gpx_chol_tasks2(int nblocks, int chunks, int16_t *out, int64_t cap, int64_t *counts);
 
 /* What the handle's LAST sweep decided about pruning and with what; it only copies what the sweep left behind.
- * scal[0 .. min(nscal, 14)) = { path: 0 plain (not legal or not tried), 1 the gate declined, 2 pruned, 3 the bound pass ran but more than
+ * scal[0 .. min(nscal, 16)) = { path: 0 plain (not legal or not tried), 1 the gate declined, 2 pruned, 3 the bound pass ran but more than
  * cap candidates survived and the plain loop evaluated everything;  M;  k;  G (seeds);  Gg (the gate's generation);  done (leading
  * candidates evaluated before the bound pass);  cap;  nsurv;  S;  delta;  tau (the k-th best seed value);  the gate's mean s2 (NaN: no
- * gate);  the seeds' threshold key;  1 if the kept copies exist }.  S .. tau and the key are NaN for paths 0 and 1.
+ * gate);  the seeds' threshold key;  1 if the kept copies exist;  the bound pass's kernel, 0 generic / 1 matrix pipe;  the guard's (d + 4) (R_x + R_z)^2
+ * (NaN where the host chose the generic kernel: another covariance, d > 18, prune_bound = 0) }.  S .. tau, the key and the last two are NaN for paths 0 and 1.
  * ub (optional, M): the bound vector as the survivor pass read it (-inf where a candidate was evaluated as gate or seed);  idx
  * (optional, cap_idx): the first min(nsurv, cap, cap_idx) survivors in the order they were compacted;  ub_kept (optional, M) and
  * seed_idx (optional, cap_seed; G entries): the bound vector and the seed list before the scatter -- only after a sweep that ran with
@@ -63,6 +67,10 @@ int64_t gpx_chol_tasks2(int nblocks, int chunks, int16_t *out, int64_t cap, int6
  * included -- the report then answers GPX_ESTATE; a sweep that passes its argument checks starts a new one; nothing else writes the workspace.) */
 int gpx_prune_report(gpx_handle *h, double *scal, int nscal, double *ub, int64_t *idx, int64_t cap_idx, double *ub_kept,
                      int64_t *seed_idx, int64_t cap_seed);
+
+/* dots (M): alpha2 . k(X, z_n) as the bound pass's kernel left them, before EI was taken of them -- only after a pruned sweep (path >= 2)
+ * that ran with the option prune_keep = 1 (GPX_ESTATE otherwise). */
+int gpx_prune_dots(gpx_handle *h, double *dots);
 
 #ifdef __cplusplus
 }

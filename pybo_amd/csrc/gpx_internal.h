@@ -159,10 +159,12 @@ struct gpx_handle {
         const int64_t* idx = nullptr;
         const double* sc = nullptr;
         const int* st = nullptr;
+        int bound_kernel = -1;    // -1: sc[9] says which kernel wrote the dots; 0: the host chose k_sweep_rankq<1> (no guard ran)
         bool kept = false;        // dkeep holds this sweep's bound vector and seed list as they were before the scatter
     } prune_rec;
     int prune_keep = 0;       // diagnostic option: keep those two device copies
-    char* dkeep = nullptr;    // [ub M][seed idx G]
+    int prune_bound = -1;     // diagnostic option: the bound pass's kernel (-1 by guard, 0 k_sweep_rankq<1>, 1 k_bound_mfma wherever SE-ARD, d <= 18)
+    char* dkeep = nullptr;    // [ub M][seed idx G][dots M]
     int64_t cap_keep = 0;     // ... in bytes
 
     // sweep cache (warm BO step): candidates and their reduced sums q = colsum(V^2), p = V^T a of the last full
@@ -246,7 +248,7 @@ void launch_cache_apply(hipStream_t s, const double* v, const double* scal, int6
 void launch_scale_point(hipStream_t s, const double* x, const double* invell, int d, double* xs);
 void launch_sweep_rank1_v(hipStream_t s, const double* Xs, int64_t Ntot, int d, const double* Wq, int64_t ldw,
                           const double* pscal, const double* Z, int64_t M, const double* invell, int kernel_id,
-                          double rho, const double* xlast, double* vout);
+                          double rho, const double* xlast, double* vout, const double* skip = nullptr);
 void launch_sweep_rankq(hipStream_t s, const double* Xs, int64_t Ntot, int d, const double* Wq, int64_t ldw, int q,
                         const double* pscal, const double* Z, int64_t M, const double* invell, int kernel_id,
                         double rho, double* qsum, double* psum);
@@ -262,6 +264,12 @@ int64_t topk_blocks(int64_t M);
 // bound, stable compaction (mode 0: seeds by the selected threshold st[2]; mode 1: survivors of the cut *tau), scatter
 void launch_prune_alpha(hipStream_t s, const double* U, int64_t Np, const double* a, double rho, double bias, double* alpha2,
                         double* sabs, double* sc);
+// the bound pass's dot for SE-ARD with the distances on the matrix pipe: KS = k-steps of its inner product (0: not for this model),
+// workspace words, and prologue + guard + kernel (sc[9] = 1.0: it wrote `out`; 0.0: launch_sweep_rank1_v(.., skip = sc + 9) does)
+int bound_mfma_ks(int kernel_id, int d);
+int64_t bound_mfma_ws_words(int64_t Np);
+void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
+                       const double* Z, int64_t M, const double* invell, int force, double* ws, double* sc, double* out);
 void launch_prune_ub(hipStream_t s, double* ub, int64_t M, int64_t skip, const double* sc, double rho, double bias, double p0);
 void launch_prune_mean(hipStream_t s, const double* v, int64_t n, double* out);
 void launch_sel_threshold(hipStream_t s, const double* v, int64_t M, int G, int* hist, int* st);

@@ -478,7 +478,10 @@ __global__ __launch_bounds__(256, (Q == 1) ? 3 : 2) void k_sweep_rankq(const dou
                                                      const double* __restrict__ Z, int64_t M,
                                                      const double* __restrict__ invell, double rho,
                                                      double* __restrict__ qsum, double* __restrict__ psum,
-                                                     const double* __restrict__ xlast, double* __restrict__ vout) {
+                                                     const double* __restrict__ xlast, double* __restrict__ vout,
+                                                     const double* __restrict__ skip) {
+    // skip (optional, the bound pass of a selection-only sweep): *skip == 1.0 says k_bound_mfma has written vout -- nothing to do.
+    if (skip && *skip == 1.0) return;
     // xlast (optional): the scaled coordinates of row Ntot - 1 when that row is NOT in Xs yet -- an ANNOUNCED
     // observation (gpx_append_begin): its location is known, its value is not, the factor is untouched.
     // vout (optional, q == 1): write v_n instead of updating the sums; gpx_append applies q += v^2, p += v a once the
@@ -601,10 +604,11 @@ void launch_scale_point(hipStream_t s, const double* x, const double* invell, in
 template <int Q>
 static void launch_rankq_kid(hipStream_t s, dim3 grid, const double* Xs, int64_t Ntot, int d, const double* Wq,
                              int64_t ldw, int q, const double* pscal, const double* Z, int64_t M, const double* invell,
-                             int kernel_id, double rho, double* qsum, double* psum, const double* xlast, double* vout) {
+                             int kernel_id, double rho, double* qsum, double* psum, const double* xlast, double* vout,
+                             const double* skip = nullptr) {
 #define GPX_RANKQ(KID)                                                                                              \
     hipLaunchKernelGGL((k_sweep_rankq<Q, KID>), grid, dim3(256), 0, s, Xs, Ntot, d, Wq, ldw, q, pscal, Z, M, invell, \
-                       rho, qsum, psum, xlast, vout)
+                       rho, qsum, psum, xlast, vout, skip)
     switch (kernel_id) {
         case GPX_KERN_SE_ARD: GPX_RANKQ(GPX_KERN_SE_ARD); break;
         case GPX_KERN_MATERN52: GPX_RANKQ(GPX_KERN_MATERN52); break;
@@ -617,10 +621,10 @@ static void launch_rankq_kid(hipStream_t s, dim3 grid, const double* Xs, int64_t
 // the correction pass of ONE announced observation: v_n for every cached candidate -> vout (sums untouched)
 void launch_sweep_rank1_v(hipStream_t s, const double* Xs, int64_t Ntot, int d, const double* Wq, int64_t ldw,
                           const double* pscal, const double* Z, int64_t M, const double* invell, int kernel_id,
-                          double rho, const double* xlast, double* vout) {
+                          double rho, const double* xlast, double* vout, const double* skip) {
     const dim3 grid((unsigned)((M + XN - 1) / XN));
     launch_rankq_kid<1>(s, grid, Xs, Ntot, d, Wq, ldw, 1, pscal, Z, M, invell, kernel_id, rho, nullptr, nullptr, xlast,
-                        vout);
+                        vout, skip);
 }
 
 // row j of the pending-correction table: [w (Nj entries), -1, zeros up to ldw]; pscal_j = {1/d, a_new}
@@ -857,6 +861,235 @@ void launch_prune_alpha(hipStream_t s, const double* U, int64_t Np, const double
                         double* sabs, double* sc) {
     hipLaunchKernelGGL(k_prune_alpha, dim3((unsigned)Np), dim3(256), 0, s, U, Np, a, alpha2, sabs);
     hipLaunchKernelGGL(k_prune_delta, dim3(1), dim3(256), 0, s, sabs, Np, rho, bias, sc);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The bound pass's dot alpha2 . k(X, z_n) for the SE-ARD covariance with the distances on the matrix pipe.
+// With x~, z~ the scaled coordinates minus a common centre c,  -r2 / 2 = x~ . z~ - |x~|^2 / 2 - |z~|^2 / 2  is ONE inner
+// product of length d + 2: observation row [x~_1 .. x~_d, -|x~|^2 / 2, 1] times candidate column [z~_1 .. z~_d, 1, -|z~|^2 / 2],
+// both padded with zeros to 4 KS.  v_mfma_f64_16x16x4_f64 forms it for 16 observations x 16 candidates in KS instructions
+// while the VALU evaluates the exponentials of the tile before: 25 instead of 46 VALU instructions per covariance.
+// The inner-product form cancels where the direct differences do not; sc[] carries the radii of the centred data and the
+// guard k_bound_guard derives from them: sc[9] = 1.0 says this kernel runs, 0.0 says k_sweep_rankq<1> does (both read it).
+// ------------------------------------------------------------------------------------------------
+constexpr int BM_KS_MAX = 5;               // d + 2 <= 20: the candidates' fragments stay in registers (8 KS doubles per lane)
+constexpr int BM_SC_RX2 = 6, BM_SC_RZ2 = 7, BM_SC_GUARD = 8, BM_SC_USE = 9;      // slots of sc[] (0 .. 5: k_prune_delta, gate, tau)
+
+int bound_mfma_ks(int kernel_id, int d) { return (kernel_id == GPX_KERN_SE_ARD && d + 2 <= 4 * BM_KS_MAX) ? (d + 5) / 4 : 0; }
+
+// max of non-negative doubles through their bit patterns (order-preserving for v >= 0); a NaN is not recorded
+__device__ __forceinline__ void block_max_nonneg(double v, double* slot, double* red) {
+    red[threadIdx.x] = (v == v) ? v : 0.0;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        atomicMax(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)__double_as_longlong(red[0]));
+}
+
+// cen[k] = midpoint of the scaled observations' box in dimension k; clears the two radius slots.  One workgroup.
+__global__ __launch_bounds__(256) void k_bound_centre(const double* __restrict__ Xs, int64_t N, int d, double* __restrict__ cen,
+                                                      double* __restrict__ sc) {
+    __shared__ double lo[256], hi[256];
+    for (int k = 0; k < d; ++k) {
+        double a = __builtin_huge_val(), b = -__builtin_huge_val();
+        for (int64_t i = threadIdx.x; i < N; i += 256) {
+            const double x = Xs[i * d + k];
+            a = fmin(a, x);
+            b = fmax(b, x);
+        }
+        lo[threadIdx.x] = a;
+        hi[threadIdx.x] = b;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) {
+                lo[threadIdx.x] = fmin(lo[threadIdx.x], lo[threadIdx.x + w]);
+                hi[threadIdx.x] = fmax(hi[threadIdx.x], hi[threadIdx.x + w]);
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) cen[k] = 0.5 * lo[0] + 0.5 * hi[0];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        sc[BM_SC_RX2] = 0.0;
+        sc[BM_SC_RZ2] = 0.0;
+    }
+}
+
+// The augmented observation array in fragment order: tile t (16 rows), k-step ks, lane l holds element k = 4 ks + (l >> 4) of row
+// 16 t + (l & 15) at A[(t KS + ks) 64 + l] -- one coalesced 512-byte read per wave and k-step.  W4[16 t + 4 g + r] = rho alpha2 of row
+// 16 t + g + 4 r: the four weights of a lane's four results (C/D row = (l >> 4) + 4 r) as one 32-byte read.  Rows from N on: zeros.
+__global__ __launch_bounds__(256) void k_bound_aug(const double* __restrict__ Xs, int64_t N, int64_t Np, int d, int KS,
+                                                   const double* __restrict__ cen, const double* __restrict__ alpha2, double rho,
+                                                   double* __restrict__ A, double* __restrict__ W4, double* __restrict__ sc) {
+    __shared__ double red[256];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;       // (Np is a multiple of 128)
+    double n2 = 0.0;
+    if (i < Np) {
+        const int64_t t = i >> 4;
+        const int row = (int)(i & 15);
+        double* At = A + t * KS * 64 + row;
+        const bool live = i < N;
+        for (int k = 0; k < 4 * KS; ++k) {
+            double v = 0.0;
+            if (live && k < d) {
+                v = Xs[i * d + k] - cen[k];
+                n2 = fma(v, v, n2);
+            }
+            if (live && k == d) v = -0.5 * n2;
+            if (live && k == d + 1) v = 1.0;
+            At[(k >> 2) * 64 + (k & 3) * 16] = v;
+        }
+        const int g = row & 3, r = row >> 2;                          // row = g + 4 r
+        W4[t * 16 + 4 * g + r] = live ? rho * alpha2[i] : 0.0;
+    }
+    block_max_nonneg(n2, sc + BM_SC_RX2, red);
+}
+
+// z~ of one candidate coordinate: the cross-Gram's own scaled value, then the centring -- two roundings, never one fused
+__device__ __forceinline__ double bound_zt(double z, double invell, double c) {
+#pragma clang fp contract(off)
+    const double zs = z * invell;
+    return zs - c;
+}
+
+// sc[RZ2] = max_n |z~_n|^2 over the candidates (NaN rows are not recorded: their bound is NaN whatever the kernel; an infinite
+// coordinate makes the radius infinite and the guard decline)
+__global__ __launch_bounds__(256) void k_bound_rz(const double* __restrict__ Z, int64_t M, int d, const double* __restrict__ invell,
+                                                  const double* __restrict__ cen, double* __restrict__ sc) {
+    __shared__ double red[256];
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double n2 = 0.0;
+    if (n < M)
+        for (int k = 0; k < d; ++k) {
+            const double v = bound_zt(Z[n * d + k], invell[k], cen[k]);
+            n2 = fma(v, v, n2);
+        }
+    block_max_nonneg(n2, sc + BM_SC_RZ2, red);
+}
+
+// The guard: the inner-product form's exponent errs by at most (d + 4) u (R_x + R_z)^2, which the margin
+// delta / 2 has room for while that is at most Np u.  force: -1 by guard, 1 the matrix-pipe kernel whatever the guard says.
+__global__ void k_bound_guard(int d, int64_t Np, int force, double* __restrict__ sc) {
+    const double R = sqrt(sc[BM_SC_RX2]) + sqrt(sc[BM_SC_RZ2]);
+    const double gv = (double)(d + 4) * R * R;
+    sc[BM_SC_GUARD] = gv;
+    sc[BM_SC_USE] = (force > 0 || gv <= (double)Np) ? 1.0 : 0.0;
+}
+
+// One workgroup owns 128 candidates (8 column tiles of 16, their fragments in registers for the whole walk); wave w walks the
+// 16-row tiles w, w + 4, .. of the augmented array in order.  Per tile and column tile: KS MFMAs from a zero accumulator, then per
+// result the exponent limited to <= 0 (compare and select: a NaN stays), exp_nonpos, one FMA with the row's weight into the lane's
+// accumulator of that column.  The four row groups of a wave are combined by two exchanges, the waves through LDS, in a fixed order:
+// the values do not depend on the launch geometry.
+template <int KS>
+__global__ __launch_bounds__(256, 2) void k_bound_mfma(const double* __restrict__ A, const double* __restrict__ W4, int ntile, int d,
+                                                       const double* __restrict__ Z, int64_t M, const double* __restrict__ invell,
+                                                       const double* __restrict__ cen, const double* __restrict__ sc,
+                                                       double* __restrict__ out) {
+    __shared__ double red[4][XN];
+    if (sc[BM_SC_USE] != 1.0) return;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int col = lane & 15, g = lane >> 4;
+    const int64_t n0 = (int64_t)blockIdx.x * XN;
+    double b[8][KS];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int64_t n = n0 + j * 16 + col;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) b[j][ks] = 0.0;
+        if (n < M) {
+            double n2 = 0.0;
+            for (int k = 0; k < d; ++k) {
+                const double v = bound_zt(Z[n * d + k], invell[k], cen[k]);
+                n2 = fma(v, v, n2);
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) b[j][ks] = (k == 4 * ks + g) ? v : b[j][ks];
+            }
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                b[j][ks] = (d == 4 * ks + g) ? 1.0 : b[j][ks];
+                b[j][ks] = (d + 1 == 4 * ks + g) ? -0.5 * n2 : b[j][ks];
+            }
+        }
+    }
+    double acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.0;
+    const double* Ap = A + (int64_t)w * KS * 64 + lane;
+    const double* Wp = W4 + w * 16 + g * 4;
+    double a[KS], an[KS];
+    d4 wv, wn;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) an[ks] = Ap[ks * 64];
+    wn = *reinterpret_cast<const d4*>(Wp);
+#pragma unroll 1
+    for (int t = w; t < ntile; t += 4) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) a[ks] = an[ks];
+        wv = wn;
+        if (t + 4 < ntile) {                  // the next tile's operands while this one computes
+            Ap += 4 * KS * 64;
+            Wp += 4 * 16;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) an[ks] = Ap[ks * 64];
+            wn = *reinterpret_cast<const d4*>(Wp);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            d4 c = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], b[j][ks], c, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                double e = c[r];
+                e = (e > 0.0) ? 0.0 : e;                                // NaN passes through
+                acc[j] = fma(wv[r], exp_nonpos(e), acc[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        double v = acc[j];
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        if (g == 0) red[w][j * 16 + col] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < XN) {
+        const int64_t n = n0 + threadIdx.x;
+        if (n < M) out[n] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    }
+}
+
+// Prologue, guard and the matrix-pipe kernel on stream s.  ws: [A Np x 4 KS][W4 Np][cen 4 BM_KS_MAX]; sc: the bound pass's 16 scalars.
+// The caller launches the generic kernel behind it with sc + BM_SC_USE as its `skip`: exactly one of the two writes `out`.
+int64_t bound_mfma_ws_words(int64_t Np) { return Np * 4 * BM_KS_MAX + Np + 4 * BM_KS_MAX; }
+
+void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
+                       const double* Z, int64_t M, const double* invell, int force, double* ws, double* sc, double* out) {
+    const int KS = (d + 5) / 4;
+    double* A = ws;
+    double* W4 = A + Np * 4 * KS;
+    double* cen = ws + Np * 4 * BM_KS_MAX + Np;
+    hipLaunchKernelGGL(k_bound_centre, dim3(1), dim3(256), 0, s, Xs, N, d, cen, sc);
+    hipLaunchKernelGGL(k_bound_aug, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, Xs, N, Np, d, KS, cen, alpha2, rho, A, W4, sc);
+    hipLaunchKernelGGL(k_bound_rz, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, Z, M, d, invell, cen, sc);
+    hipLaunchKernelGGL(k_bound_guard, dim3(1), dim3(1), 0, s, d, Np, force, sc);
+    const dim3 grid((unsigned)((M + XN - 1) / XN));
+    const int ntile = (int)(Np / 16);
+#define GPX_BM(K) hipLaunchKernelGGL(k_bound_mfma<K>, grid, dim3(256), 0, s, A, W4, ntile, d, Z, M, invell, cen, sc, out)
+    switch (KS) {
+        case 1: GPX_BM(1); break;
+        case 2: GPX_BM(2); break;
+        case 3: GPX_BM(3); break;
+        case 4: GPX_BM(4); break;
+        default: GPX_BM(5); break;
+    }
+#undef GPX_BM
 }
 
 // ub[n] (in: alpha2 . k(X, z_n)) <- EI((bias + dot) + delta, s2 = rho) by k_acq's own function; -inf for the `skip` leading
