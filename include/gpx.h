@@ -75,7 +75,7 @@ int gpx_version(void);
  *                    register-staged loops of rounds 5 / 2 / 1: independently scheduled witnesses) [-1 = by size: 7 below 32 block rows, else 19]
  *   "super_m"        rows of the XCD super-tile of 64 workgroups: 1, 2, 4, 8, 16 [8 -> 8 x 8]
  *   "sweep_cache"    1: full sweeps keep candidates and reduced sums for gpx_sweep_update; 0: leave a live cache alone; -1: drop it [0]
- *   "prune"          EI sweeps returning ONLY their top-k skip candidates whose bound cannot reach it: -1 by size and gate, 0 never, 1 where legal [-1]
+ *   "prune"          EI sweeps for ONLY the top-k (ensembles: members[0]'s value) skip what a bound rules out: -1 by size and gate, 0 never, 1 where legal [-1]
  *   "eager_inverse"  1: form the triangular inverse inside gpx_fit instead of on first use [0]
  *   "trtri_ahead"    1: when the inverse is certain or likely to follow a fit, its part that needs only the factor's leading block
  *                    rows runs on a side stream behind the factorisation's tail, from "trtri_ahead_min" (8) blocks on [1]
@@ -223,7 +223,7 @@ int gpx_rff_posterior(gpx_handle *h, const double *W, const double *b, const dou
  *      EI / PI: value = mean_m acq_m(x).  UCB / MEAN: mixture moments mu = mean_m mu_m,
  *      s2 = mean_m(s2_m + mu_m^2) - mu^2, value = mu + sqrt(params[0] * s2) (UCB) or mu (MEAN); only these
  *      two can return mu / s2.  The member sweeps never leave the device; sums run in member order and are
- *      divided once by n.  Outputs as in gpx_sweep / gpx_sweep_dev. */
+ *      divided once by n.  Outputs as in gpx_sweep / gpx_sweep_dev; an EI call for the top-k alone prunes as they do ("prune" of members[0]). */
 int gpx_ensemble_sweep(gpx_handle *const *members, int n_members, int acq_id, const double *params,
                        int nparams, const double *Xc, int64_t M, int64_t k, double *top_val,
                        int64_t *top_idx, double *acq_all, double *mu, double *s2);

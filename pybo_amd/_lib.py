@@ -49,6 +49,7 @@ DIAG_SYMBOLS = {
     'gpx_chol_tasks2': (_i64, [C.c_int, C.c_int, _P, _i64, _P]),
     'gpx_prune_report': (C.c_int, [_P, _P, C.c_int, _P, _P, _i64, _P, _P, _i64]),
     'gpx_prune_dots': (C.c_int, [_P, _P]),
+    'gpx_ensemble_prune_report': (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _i64]),
 }
 SYMBOLS = {
     'gpx_create': (C.c_int, [C.c_int, _P, C.POINTER(_P)]),
@@ -751,6 +752,29 @@ class Engine(object):
             r['seed_idx'] = np.empty(r['G'], dtype=np.int64) if kept else None
             self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), _ptr(r['ub']), _ptr(r['idx']), nidx,
                                                    _ptr(r['ub_kept']), _ptr(r['seed_idx']), r['G'] if kept else 0))
+        return r
+
+    @staticmethod
+    def ensemble_prune_report(engines, vectors=True):
+        """Diagnostic (gpx_ensemble_prune_report in csrc/gpx_diag.h): what the last ensemble sweep led by engines[0] decided about pruning.
+        dict(path, M, k, G, Gg, done, cap, nsurv, tau, gate, delta (n,)); with `vectors`, where the bound pass ran, also ub (M,), the ensemble
+        bound as the survivor pass read it, and idx, the survivors in compaction order (empty where it fell back)."""
+        lead = engines[0]
+        handles = (_P * len(engines))(*[e._h for e in engines])
+        scal = np.full(10 + len(engines), np.nan)
+        lead._check(lead._lib.gpx_ensemble_prune_report(handles, len(engines), _ptr(scal), len(scal), None, None, 0))
+        names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'tau', 'gate')
+        r = dict(zip(names, scal[:10].tolist()))
+        for n in names[:8]:
+            r[n] = int(r[n])
+        r['path'] = Engine.PRUNE_PATHS[r['path']]
+        r['delta'] = scal[10:].copy()
+        if vectors and r['path'] in ('pruned', 'fell back'):
+            nidx = r['nsurv'] if r['path'] == 'pruned' else 0
+            r['ub'] = np.empty(r['M'])
+            r['idx'] = np.empty(nidx, dtype=np.int64)
+            lead._check(lead._lib.gpx_ensemble_prune_report(handles, len(engines), _ptr(scal), len(scal), _ptr(r['ub']), _ptr(r['idx']),
+                                                            nidx))
         return r
 
     def prune_dots(self):

@@ -226,8 +226,9 @@ static std::string apply_env_options(gpx_handle* h) {
 // gpx_chol_tasks, GPX_OPTIONS.  500: timers slot 16.  510: timers slots 17, 18, options trtri_ahead*, chol_tg_fuse.
 // 600: gpx_diagnostics, gpx_chol_tasks -> gpx_chol_tasks2 (gpx_diag.h), the diagnostic options only in the diagnostics
 // build, tile_order default by size (7 below 32 block rows, 19 from there on).
-// 610: option prune (selection-only sweeps), timers slot 19.
-extern "C" int gpx_version(void) { return 610; }
+// 610: option prune (selection-only sweeps), timers slot 19.  620: the ensemble sweep prunes too (the lead's option prune),
+// gpx_ensemble_prune_report.
+extern "C" int gpx_version(void) { return 620; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -1017,6 +1018,66 @@ static int staged_sweep(gpx_handle* h, const double* Xc, int64_t M, bool sync_up
 static const int64_t PRUNE_MIN_M = 32768, PRUNE_MIN_NP = 1024, PRUNE_MAX_SHARE_DIV = 4;
 static const double PRUNE_GATE_S2 = 1.0 / 64.0;
 
+// Geometry of a selection-only sweep of M candidates for the k best over a factor of nP block rows.
+// G: the candidates of one generation of sweep workgroups (512 resident, each a pair of tiles; at most 4096: short
+// factors would ask for tens of thousands), at least k.
+struct PruneGeom { int64_t G, Gg, cap; };
+static PruneGeom prune_geom(int nP, int64_t k, int64_t M) {
+    const int64_t gen_tiles = std::max<int64_t>(1, 512 / ((nP + 1) / 2));       // candidate tiles of 512 workgroups
+    const int64_t G0 = (int64_t)TBH * std::min<int64_t>(32, gen_tiles);
+    const int64_t G = std::max<int64_t>(G0, (k + TBH - 1) / TBH * TBH);
+    // cap: survivors beyond this: the plain loop is the better path
+    // the gate's generation is a FULL one (a launch that fills half the chip takes as long as one that fills it: config B)
+    return {G, (int64_t)TBH * gen_tiles, std::max<int64_t>(G, M / PRUNE_MAX_SHARE_DIV)};
+}
+
+// The pruning workspace, h->dprune:
+// [ub M][vals cap][Xg cap d][idx cap][blk nsel + 1][alpha2 Np][sabs Np][gate s2 Gg][sc 16][extra][hist 2 x 4096 + st 8 (int)]
+// [pad to 32 bytes][the matrix-pipe bound kernel's operands]
+struct PruneWs {
+    double *ub, *vals, *Xg;
+    int64_t *idx, *blk;
+    double *alpha2, *sabs, *gs2, *sc, *extra;
+    int *hist, *st;
+    double* bws;
+    int64_t nsel;
+};
+static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t extra, PruneWs& w) {
+    const int64_t Np = h->Np;
+    w.nsel = sel_blocks(M);
+    const int64_t words0 = M + cap + cap * h->d + cap + (w.nsel + 1) + 2 * Np + Gg + 16 + extra + (2 * 4096 + 8) / 2;
+    const int64_t words = (words0 + 3) / 4 * 4 + bound_mfma_ws_words(Np);
+    if (!h->dprune || words * 8 > h->cap_prune) h->ens_rec = gpx_handle::EnsPruneRecord();   // (its vectors lie in the old allocation)
+    int rc;
+    if ((rc = ensure(h, h->dprune, h->cap_prune, words * 8))) return rc;
+    w.ub = reinterpret_cast<double*>(h->dprune);
+    w.vals = w.ub + M;
+    w.Xg = w.vals + cap;
+    w.idx = reinterpret_cast<int64_t*>(w.Xg + cap * h->d);
+    w.blk = w.idx + cap;
+    w.alpha2 = reinterpret_cast<double*>(w.blk + w.nsel + 1);
+    w.sabs = w.alpha2 + Np;
+    w.gs2 = w.sabs + Np;
+    w.sc = w.gs2 + Gg;
+    w.extra = w.sc + 16;
+    w.hist = reinterpret_cast<int*>(w.extra + extra);
+    w.st = w.hist + 2 * 4096;
+    w.bws = w.ub + (words0 + 3) / 4 * 4;
+    return GPX_OK;
+}
+
+// The bound pass's dots: out[n] = alpha2 . k(X, z_n) for the M candidates and w.sc[0 .. 1] = S, delta,
+// so that EI((bias + out[n]) + delta, s2 = rho) >= the value the exact chain returns.  bound_mfma: the matrix-pipe form for SE-ARD
+// up to d = 18 where its guard allows (decided on the device).
+static void bound_dots(gpx_handle* h, const double* dXc, int64_t M, const PruneWs& w, bool bound_mfma, double* out) {
+    hipStream_t s = h->stream;
+    launch_prune_alpha(s, h->dU, h->Np, h->da, h->rho, h->bias, w.alpha2, w.sabs, w.sc);
+    if (bound_mfma)
+        launch_bound_mfma(s, h->dXs, h->N, h->Np, (int)h->d, w.alpha2, h->rho, dXc, M, h->dinvell, h->prune_bound, w.bws, w.sc, out);
+    launch_sweep_rank1_v(s, h->dXs, h->N, (int)h->d, w.alpha2, h->Np, w.sc + 2, dXc, M, h->dinvell, h->kernel_id, h->rho,
+                         nullptr, out, bound_mfma ? w.sc + 9 : nullptr);
+}
+
 static int sweep_core(gpx_handle* h, int acq_id, const double* params, int nparams, const double* dXc,
                       int64_t M, int64_t k, double* top_val, int64_t* top_idx, double* d_acq,
                       double* d_mu, double* d_s2) {
@@ -1088,14 +1149,8 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     };
 
     // ---- selection-only sweep: exact values only where the EI bound can reach the top-k ------------
-    // G: the candidates of one generation of sweep workgroups (512 resident, each a pair of tiles; at most 4096: short
-    // factors would ask for tens of thousands), at least k.
-    const int64_t gen_tiles = std::max<int64_t>(1, 512 / ((nP + 1) / 2));       // candidate tiles of 512 workgroups
-    const int64_t G0 = (int64_t)TBH * std::min<int64_t>(32, gen_tiles);
-    const int64_t G = std::max<int64_t>(G0, (k + TBH - 1) / TBH * TBH);
-    const int64_t cap = std::max<int64_t>(G, M / PRUNE_MAX_SHARE_DIV);     // survivors beyond this: the plain loop is the better path
-    // the gate's generation is a FULL one (a launch that fills half the chip takes as long as one that fills it: config B)
-    const int64_t Gg = (int64_t)TBH * gen_tiles;
+    const PruneGeom geom = prune_geom(nP, k, M);
+    const int64_t G = geom.G, Gg = geom.Gg, cap = geom.cap;
     const bool legal = selection_only && acq_id == GPX_ACQ_EI && k > 0 && !h->cache_on && h->prune != 0 && M >= 3 * G &&
                        h->rho >= 1e-100 && h->rho < INFINITY;
     bool pruning = legal && (h->prune == 1 || (M >= PRUNE_MIN_M && Np >= PRUNE_MIN_NP && M >= Gg + 2 * G));
@@ -1105,29 +1160,17 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     rec.M = M, rec.k = k, rec.G = G, rec.Gg = Gg, rec.cap = cap;
     rec.mean_s2 = NAN;
     if (pruning) {
-        const int64_t nblk_top = topk_blocks(M), nsel = sel_blocks(M);
+        const int64_t nblk_top = topk_blocks(M);
         const int64_t kk = std::min<int64_t>(k, TOPK_PASS);
         if ((rc = ensure(h, h->dblkv, h->cap_blk, nblk_top * kk))) return rc;
         if ((rc = ensure(h, h->dblki, h->cap_blki, nblk_top * kk))) return rc;
         if ((rc = ensure(h, h->dtopv, h->cap_top, (int64_t)TOPK_MAX * 2))) return rc;
         h->dtopi = reinterpret_cast<int64_t*>(h->dtopv + TOPK_MAX);
-        // workspace: [ub M][vals cap][Xg cap d][idx cap][blk nsel + 1][alpha2 Np][sabs Np][gate s2 Gg][sc 16][hist 2 x 4096 + st 8 (int)]
-        // [pad to 32 bytes][the matrix-pipe bound kernel's operands]
-        const int64_t words0 = M + cap + cap * h->d + cap + (nsel + 1) + 2 * Np + Gg + 16 + (2 * 4096 + 8) / 2;
-        const int64_t words = (words0 + 3) / 4 * 4 + bound_mfma_ws_words(Np);
-        if ((rc = ensure(h, h->dprune, h->cap_prune, words * 8))) return rc;
-        double* ub = reinterpret_cast<double*>(h->dprune);
-        double* vals = ub + M;
-        double* Xg = vals + cap;
-        int64_t* idx = reinterpret_cast<int64_t*>(Xg + cap * h->d);
-        int64_t* blk = idx + cap;
-        double* alpha2 = reinterpret_cast<double*>(blk + nsel + 1);
-        double* sabs = alpha2 + Np;
-        double* gs2 = sabs + Np;
-        double* sc = gs2 + Gg;
-        int* hist = reinterpret_cast<int*>(sc + 16);
-        int* st = hist + 2 * 4096;
-        double* bws = ub + (words0 + 3) / 4 * 4;
+        PruneWs w;
+        if ((rc = prune_ws(h, M, cap, Gg, 0, w))) return rc;
+        double *const ub = w.ub, *const vals = w.vals, *const Xg = w.Xg, *const gs2 = w.gs2, *const sc = w.sc;
+        int64_t *const idx = w.idx, *const blk = w.blk;
+        int *const hist = w.hist, *const st = w.st;
         // the bound pass's kernel: the matrix-pipe form for SE-ARD up to d = 18 where its guard allows (decided on the device)
         const bool bound_mfma = h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0;
 
@@ -1149,11 +1192,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             {
                 // 1. bound pass: ub[n] = EI(bias + alpha . k(X, z_n) + delta, s2 = rho) >= the value the exact chain returns
                 Span sp(h, T_BOUND);
-                launch_prune_alpha(s, h->dU, Np, h->da, h->rho, h->bias, alpha2, sabs, sc);
-                if (bound_mfma)
-                    launch_bound_mfma(s, h->dXs, h->N, Np, (int)h->d, alpha2, h->rho, dXc, M, h->dinvell, h->prune_bound, bws, sc, ub);
-                launch_sweep_rank1_v(s, h->dXs, h->N, (int)h->d, alpha2, Np, sc + 2, dXc, M, h->dinvell, h->kernel_id, h->rho,
-                                     nullptr, ub, bound_mfma ? sc + 9 : nullptr);
+                bound_dots(h, dXc, M, w, bound_mfma, ub);
                 if (h->prune_keep) {
                     // diagnostic: the dots as the kernel left them (gpx_prune_dots), behind the two copies below
                     if ((rc = ensure(h, h->dkeep, h->cap_keep, (2 * M + G) * 8))) return rc;
@@ -1184,7 +1223,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
                 launch_fill_neg_inf(s, d_acq, done, M);
                 launch_sel_scatter(s, idx, vals, G, d_acq, ub);
                 launch_sel_compact(s, ub, M, 1, st, h->dtopv + (k - 1), blk, cap, dXc, (int)h->d, idx, Xg, sc + 5);
-                HIPCHK(h, hipMemcpyAsync(&nsurv, blk + nsel, 8, hipMemcpyDeviceToHost, s));
+                HIPCHK(h, hipMemcpyAsync(&nsurv, blk + w.nsel, 8, hipMemcpyDeviceToHost, s));
             }
             HIPCHK(h, hipStreamSynchronize(s));
             rec.path = nsurv <= cap ? 2 : 3;
@@ -1600,6 +1639,7 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
                          const double* dXc, int64_t M, int64_t k, double* top_val, int64_t* top_idx,
                          double* d_out, double* d_mu, double* d_s2) {
     gpx_handle* L = mem[0];
+    L->ens_rec = gpx_handle::EnsPruneRecord();     // every ensemble sweep entry, refused ones included, ends the previous one's record
     int rc;
     if ((rc = check_acq(L, "ensemble_sweep", acq_id, params, nparams))) return rc;
     if (!dXc || M < 1) return fail(L, GPX_EARG, "ensemble_sweep: need M >= 1 candidates");
@@ -1618,23 +1658,156 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
     double* t0 = acc1 + M;
     double* t1 = t0 + M;
     double* out = d_out ? d_out : t1 + M;
-    for (int m = 0; m < n; ++m) {
-        gpx_handle* h = mem[m];
-        rc = (mode == 0) ? sweep_core(h, acq_id, params, nparams, dXc, M, 0, nullptr, nullptr, t0, nullptr, nullptr)
-                         : sweep_core(h, GPX_ACQ_MEAN, nullptr, 0, dXc, M, 0, nullptr, nullptr, nullptr, t0, t1);
-        if (rc) {
-            if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
-            return rc;
-        }
-        HIPCHK(L, hipStreamSynchronize(h->stream));
-        launch_ens_accum(L->stream, acc0, acc1, t0, t1, M, mode, m == 0);
-        HIPCHK(L, hipStreamSynchronize(L->stream));    // t0/t1 are reused by the next member
-    }
     const double beta = (acq_id == GPX_ACQ_UCB) ? params[0] : 0.0;
-    if (acq_id == GPX_ACQ_MEAN)     // value = mixture mean
-        launch_ens_finish(L->stream, acc0, acc1, M, 1, (double)n, 0.0, out, d_mu, d_s2);
-    else
-        launch_ens_finish(L->stream, acc0, acc1, M, mode, (double)n, beta, out, d_mu, d_s2);
+
+    // The exact ensemble chain for the `cnt` candidates X: every member's sweep in member order, each folded into the running
+    // sums, then one division -> o[c] (and mu / s2, where given).  A candidate's value depends on its coordinates alone.
+    // gate_mean (mode 0 only): member m's mean s2 over these candidates -> gate_mean[m] (its s2 vector passes through t1).
+    auto exact = [&](const double* X, int64_t cnt, double* o, double* o_mu, double* o_s2, double* gate_mean) -> int {
+        for (int m = 0; m < n; ++m) {
+            gpx_handle* h = mem[m];
+            int rcm = (mode == 0) ? sweep_core(h, acq_id, params, nparams, X, cnt, 0, nullptr, nullptr, t0, nullptr, gate_mean ? t1 : nullptr)
+                                  : sweep_core(h, GPX_ACQ_MEAN, nullptr, 0, X, cnt, 0, nullptr, nullptr, nullptr, t0, t1);
+            if (rcm) {
+                if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
+                return rcm;
+            }
+            if (gate_mean) launch_prune_mean(h->stream, t1, cnt, gate_mean + m);
+            HIPCHK(L, hipStreamSynchronize(h->stream));
+            launch_ens_accum(L->stream, acc0, acc1, t0, t1, cnt, mode, m == 0);
+            HIPCHK(L, hipStreamSynchronize(L->stream));    // t0/t1 are reused by the next member
+        }
+        if (acq_id == GPX_ACQ_MEAN)     // value = mixture mean
+            launch_ens_finish(L->stream, acc0, acc1, cnt, 1, (double)n, 0.0, o, o_mu, o_s2);
+        else
+            launch_ens_finish(L->stream, acc0, acc1, cnt, mode, (double)n, beta, o, o_mu, o_s2);
+        return GPX_OK;
+    };
+
+    // ---- selection-only ensemble sweep: section 2.1 step for step on the MEAN of the members' bounds ----
+    // The sum of the members' bounds, accumulated and divided exactly as `exact` accumulates and divides their values, is >= the
+    // ensemble's value bit for bit (addition and division by n > 0 are monotone).  The lead's option "prune" governs.
+    int nPmax = 0;
+    int64_t Np_min = INT64_MAX;
+    bool members_ok = true;
+    for (int m = 0; m < n; ++m) {
+        nPmax = std::max(nPmax, (int)(mem[m]->Np / NB));
+        Np_min = std::min(Np_min, mem[m]->Np);
+        members_ok = members_ok && !mem[m]->cache_on && mem[m]->rho >= 1e-100 && mem[m]->rho < INFINITY;
+    }
+    const PruneGeom geom = prune_geom(nPmax, k, M);      // (the member with the most block rows: the smallest generation)
+    const int64_t G = geom.G, Gg = geom.Gg, cap = geom.cap;
+    const bool selection_only = !d_out && !d_mu && !d_s2;
+    const bool legal = selection_only && acq_id == GPX_ACQ_EI && k > 0 && members_ok && L->prune != 0 && M >= 3 * G;
+    bool pruning = legal && (L->prune == 1 || (M >= PRUNE_MIN_M && Np_min >= PRUNE_MIN_NP && M >= Gg + 2 * G));
+    int64_t done = 0;            // candidates [0, done) are exactly evaluated already
+    gpx_handle::EnsPruneRecord& rec = L->ens_rec;
+    auto start_rec = [&]() {
+        rec = gpx_handle::EnsPruneRecord();
+        rec.path = 0, rec.n = n;
+        rec.M = M, rec.k = k, rec.G = G, rec.Gg = Gg, rec.cap = cap;
+        rec.gate = NAN;
+    };
+    start_rec();
+    const int64_t d = L->d;
+    if (pruning) {
+        hipStream_t s = L->stream;
+        const int64_t kk = std::min<int64_t>(k, TOPK_PASS);
+        if ((rc = ensure(L, L->dblkv, L->cap_blk, topk_blocks(M) * kk))) return rc;
+        if ((rc = ensure(L, L->dblki, L->cap_blki, topk_blocks(M) * kk))) return rc;
+        if ((rc = ensure(L, L->dtopv, L->cap_top, (int64_t)TOPK_MAX * 2))) return rc;
+        L->dtopi = reinterpret_cast<int64_t*>(L->dtopv + TOPK_MAX);
+        PruneWs w;               // the lead's: the ensemble bound vector, seeds and survivors; extra = [gate means n][delta n]
+        if ((rc = prune_ws(L, M, cap, Gg, 2 * n, w))) return rc;
+        start_rec();             // (a workspace that had to grow clears the record)
+        double *const ub = w.ub, *const vals = w.vals, *const Xg = w.Xg, *const sc = w.sc;
+        double *const gate_mean = w.extra, *const delta = w.extra + n;
+        if (L->prune < 0) {
+            // Gate, as in section 2.1: the first generation is needed by either path; the members' mean s2 / rho decides
+            if ((rc = exact(dXc, Gg, out, nullptr, nullptr, gate_mean))) return rc;
+            done = Gg;
+            std::vector<double> gm((size_t)n);
+            HIPCHK(L, hipMemcpyAsync(gm.data(), gate_mean, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(L, hipStreamSynchronize(s));
+            double g = 0.0;
+            for (int m = 0; m < n; ++m) g += gm[m] / mem[m]->rho;
+            g /= (double)n;
+            pruning = g >= PRUNE_GATE_S2;
+            rec.gate = g;
+            rec.path = 1;
+        }
+        if (pruning) {
+            // 1. bound pass, per member in member order: its dots (own factor, weights and workspace) -> t1, its EI bound folded
+            // into the running sum ub; then ub / n
+            for (int m = 0; m < n; ++m) {
+                gpx_handle* h = mem[m];
+                HIPCHK(L, hipSetDevice(h->device));
+                if ((rc = ensure_inverse(h))) {
+                    if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
+                    return rc;
+                }
+                PruneWs wm = w;
+                if (h != L) {
+                    h->prune_rec = gpx_handle::PruneRecord();      // (the pass overwrites the workspace its last record points into)
+                    if ((rc = prune_ws(h, 0, 0, 0, 0, wm))) {
+                        L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
+                        return rc;
+                    }
+                }
+                {
+                    Span sp(h, T_BOUND);
+                    bound_dots(h, dXc, M, wm, h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0, t1);
+                    launch_prune_ub_fold(h->stream, t1, ub, M, wm.sc, h->rho, h->bias, params[0], m == 0, delta + m);
+                }
+                HIPCHK(L, hipStreamSynchronize(h->stream));      // t1 and ub pass to the next member's stream
+            }
+            {
+                Span sp(L, T_BOUND);
+                launch_prune_ub_mean(s, ub, M, done, (double)n);
+            }
+            {
+                // 2. seeds: the G candidates with the largest bound (ties at the threshold: the first by index), exactly
+                Span sp(L, T_ACQ);
+                launch_sel_threshold(s, ub, M, (int)G, w.hist, w.st);
+                launch_sel_compact(s, ub, M, 0, w.st, nullptr, w.blk, G, dXc, (int)d, w.idx, Xg);
+            }
+            HIPCHK(L, hipStreamSynchronize(s));                  // the members read Xg from their own streams
+            if ((rc = exact(Xg, G, vals, nullptr, nullptr, nullptr))) return rc;
+            int64_t nsurv = 0;
+            {
+                // tau = the k-th best seed value; 3. survivors: every candidate not yet evaluated whose bound is not below it
+                Span sp(L, T_ACQ);
+                launch_topk(s, vals, G, (int)k, L->dblkv, L->dblki, topk_blocks(G), L->dtopv, L->dtopi);
+                launch_fill_neg_inf(s, out, done, M);
+                launch_sel_scatter(s, w.idx, vals, G, out, ub);
+                launch_sel_compact(s, ub, M, 1, w.st, L->dtopv + (k - 1), w.blk, cap, dXc, (int)d, w.idx, Xg, sc + 5);
+                HIPCHK(L, hipMemcpyAsync(&nsurv, w.blk + w.nsel, 8, hipMemcpyDeviceToHost, s));
+            }
+            HIPCHK(L, hipStreamSynchronize(s));
+            rec.path = nsurv <= cap ? 2 : 3;
+            rec.done = done, rec.nsurv = nsurv;
+            rec.ub = ub, rec.idx = w.idx, rec.sc = sc, rec.delta = delta;
+            if (nsurv <= cap) {
+                // 4. their exact values to their own positions; everything else stays -inf and the top-k below runs as ever
+                if (nsurv > 0) {
+                    if ((rc = exact(Xg, nsurv, vals, nullptr, nullptr, nullptr))) return rc;
+                    Span sp(L, T_ACQ);
+                    launch_sel_scatter(s, w.idx, vals, nsurv, out, nullptr);
+                }
+                done = M;
+            }
+            // 5. (else) too many survivors: the plain loop over everything not yet evaluated
+        }
+    }
+    const int64_t chunk_opt = L->chunk > 0 ? L->chunk : (L->Np <= 4096 ? 131072 : 65536);
+    const int64_t chunk1 = std::min(std::min<int64_t>(chunk_opt, (M + TBH - 1) / TBH * TBH), M);
+    if (done > 0 && done < chunk1) {
+        // the gate declined: the rest of the lead's first chunk, so that every later launch keeps the plain loop's boundaries
+        if ((rc = exact(dXc + done * d, chunk1 - done, out + done, nullptr, nullptr, nullptr))) return rc;
+        done = chunk1;
+    }
+    if (done < M && (rc = exact(dXc + done * d, M - done, out + done, d_mu ? d_mu + done : nullptr, d_s2 ? d_s2 + done : nullptr, nullptr)))
+        return rc;
     if (k > 0) {
         if ((rc = topk_core(L, out, M, k, top_val, top_idx))) return rc;
     } else {
@@ -1680,6 +1853,7 @@ extern "C" int gpx_ensemble_sweep(gpx_handle* const* members, int n_members, int
     if (ensemble_check(members, n_members)) return GPX_EARG;
     gpx_handle* h = members[0];
     return guarded(h, [&]() -> int {
+        h->ens_rec = gpx_handle::EnsPruneRecord();
         if (!Xc || M < 1) return fail(h, GPX_EARG, "ensemble_sweep: need M >= 1 candidates");
         if ((mu || s2) && acq_id != GPX_ACQ_UCB && acq_id != GPX_ACQ_MEAN)
             return fail(h, GPX_EARG, "ensemble_sweep: mixture moments are only formed for UCB / mean");
@@ -1687,6 +1861,36 @@ extern "C" int gpx_ensemble_sweep(gpx_handle* const* members, int n_members, int
         return staged_sweep(h, Xc, M, true, acq_all, mu, s2, [&](double* dX, double* dacq, double* dmu, double* ds2) {
             return ensemble_core(members, n_members, acq_id, params, nparams, dX, M, k, top_val, top_idx, dacq, dmu, ds2);
         });
+    });
+}
+
+extern "C" int gpx_ensemble_prune_report(gpx_handle* const* members, int n_members, double* scal, int nscal, double* ub,
+                                         int64_t* idx, int64_t cap_idx) {
+    if (ensemble_check(members, n_members)) return GPX_EARG;
+    gpx_handle* h = members[0];
+    return guarded(h, [&]() -> int {
+        if (!scal || nscal < 0) return fail(h, GPX_EARG, "ensemble_prune_report: NULL output");
+        const gpx_handle::EnsPruneRecord& r = h->ens_rec;
+        if (r.path < 0 || r.n != n_members)
+            return fail(h, GPX_ESTATE, "ensemble_prune_report: no ensemble sweep of these members has completed its argument checks "
+                                       "since the record was last cleared");
+        const bool bound = r.path >= 2;
+        if ((ub || idx) && !bound) return fail(h, GPX_ESTATE, "ensemble_prune_report: the last ensemble sweep did not reach its bound pass");
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        std::vector<double> out((size_t)(10 + n_members), NAN);
+        const double head[10] = {(double)r.path, (double)r.M,   (double)r.k,     (double)r.G, (double)r.Gg,
+                                 (double)r.done, (double)r.cap, (double)r.nsurv, NAN,         r.gate};
+        std::copy(head, head + 10, out.begin());
+        if (bound) {
+            HIPCHK(h, hipMemcpy(&out[8], r.sc + 5, 8, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(&out[10], r.delta, (size_t)n_members * 8, hipMemcpyDeviceToHost));
+        }
+        for (int i = 0; i < nscal && i < 10 + n_members; ++i) scal[i] = out[i];
+        if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
+        const int64_t nidx = std::min(std::min(r.nsurv, r.cap), cap_idx);
+        if (idx && nidx > 0) HIPCHK(h, hipMemcpy(idx, r.idx, (size_t)nidx * 8, hipMemcpyDeviceToHost));
+        return GPX_OK;
     });
 }
 

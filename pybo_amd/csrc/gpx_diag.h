@@ -72,6 +72,17 @@ int gpx_prune_report(gpx_handle *h, double *scal, int nscal, double *ub, int64_t
  * that ran with the option prune_keep = 1 (GPX_ESTATE otherwise). */
 int gpx_prune_dots(gpx_handle *h, double *dots);
 
+/* What the LAST ensemble sweep led by members[0] decided about pruning; `members`, n as in that call.
+ * scal[0 .. min(nscal, 10 + n)) = { path 0 .. 3, M, k, G, Gg, done, cap, nsurv as in gpx_prune_report;  tau (NaN for paths 0 and 1);  the
+ * gate's value, the mean over the members of mean(s2_m) / rho_m of its generation (NaN: no gate);  then delta_m of every member (NaN for
+ * paths 0 and 1) }.  ub (optional, M): the ensemble bound vector -- the members' bounds summed in member order and divided by n -- as the
+ * survivor pass read it (-inf where a candidate was evaluated as gate or seed);  idx (optional, cap_idx): the first min(nsurv, cap,
+ * cap_idx) survivors in the order they were compacted.  GPX_ESTATE: no ensemble sweep of n members since the record was cleared, or a vector
+ * was asked for and the path is below 2.  (Every entry into gpx_ensemble_sweep[_dev] clears the lead's record, a refused call included;
+ * so does a later sweep of the lead alone whose workspace has to grow.  The members' own gpx_prune_report records say path 0 afterwards.) */
+int gpx_ensemble_prune_report(gpx_handle *const *members, int n_members, double *scal, int nscal, double *ub, int64_t *idx,
+                              int64_t cap_idx);
+
 #ifdef __cplusplus
 }
 #endif

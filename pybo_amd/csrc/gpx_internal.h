@@ -162,6 +162,16 @@ struct gpx_handle {
         int bound_kernel = -1;    // -1: sc[9] says which kernel wrote the dots; 0: the host chose k_sweep_rankq<1> (no guard ran)
         bool kept = false;        // dkeep holds this sweep's bound vector and seed list as they were before the scatter
     } prune_rec;
+    // what the last ENSEMBLE sweep led by this handle decided (gpx_ensemble_prune_report): its vectors lie in this handle's dprune
+    struct EnsPruneRecord {
+        int path = -1, n = 0;
+        int64_t M = 0, k = 0, G = 0, Gg = 0, done = 0, cap = 0, nsurv = 0;
+        double gate = 0.0;        // mean over the members of mean(s2_m) / rho_m of the gate's generation (NaN where it did not run)
+        const double* ub = nullptr;
+        const int64_t* idx = nullptr;
+        const double* sc = nullptr;       // sc[5] = tau as the survivor pass cut with it
+        const double* delta = nullptr;    // n: the members' delta_m
+    } ens_rec;
     int prune_keep = 0;       // diagnostic option: keep those two device copies
     int prune_bound = -1;     // diagnostic option: the bound pass's kernel (-1 by guard, 0 k_sweep_rankq<1>, 1 k_bound_mfma wherever SE-ARD, d <= 18)
     char* dkeep = nullptr;    // [ub M][seed idx G][dots M]
@@ -271,6 +281,10 @@ int64_t bound_mfma_ws_words(int64_t Np);
 void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
                        const double* Z, int64_t M, const double* invell, int force, double* ws, double* sc, double* out);
 void launch_prune_ub(hipStream_t s, double* ub, int64_t M, int64_t skip, const double* sc, double rho, double bias, double p0);
+// the ensemble's bound: one member's EI bound folded into the running sum (k_ens_accum's addition), then the sum / n (k_ens_finish's)
+void launch_prune_ub_fold(hipStream_t s, const double* dots, double* acc, int64_t M, const double* sc, double rho, double bias,
+                          double p0, int first, double* delta_out);
+void launch_prune_ub_mean(hipStream_t s, double* acc, int64_t M, int64_t skip, double n);
 void launch_prune_mean(hipStream_t s, const double* v, int64_t n, double* out);
 void launch_sel_threshold(hipStream_t s, const double* v, int64_t M, int G, int* hist, int* st);
 int64_t sel_blocks(int64_t M);

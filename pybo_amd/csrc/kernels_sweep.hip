@@ -1105,6 +1105,47 @@ void launch_prune_ub(hipStream_t s, double* ub, int64_t M, int64_t skip, const d
     hipLaunchKernelGGL(k_prune_ub, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, ub, M, skip, sc, rho, bias, p0);
 }
 
+// The ensemble's bound.  The sum of the members' bounds and its division are the arithmetic of k_ens_accum /
+// k_ens_finish (kernels_ens.hip) literally: one addition per member in member order, one division -- never contracted with
+// the last multiply of acq_value -- so that ub_m >= v_m for every member gives a result >= the exact chain's, bit for bit.
+__device__ __forceinline__ double ens_fold(int first, double acc, double ub) {
+#pragma clang fp contract(off)
+    return first ? ub : acc + ub;
+}
+__device__ __forceinline__ double ens_mean(double acc, double n) {
+#pragma clang fp contract(off)
+    return acc / n;
+}
+
+// acc[c] (+)= EI((bias + dots[c]) + delta, s2 = rho): k_prune_ub's value of one member, folded into the running sum in the same
+// pass; delta_out receives the member's delta = sc[1] (for gpx_ensemble_prune_report).
+__global__ __launch_bounds__(256) void k_prune_ub_fold(const double* __restrict__ dots, double* __restrict__ acc, int64_t M,
+                                                       const double* __restrict__ sc, double rho, double bias, double p0, int first,
+                                                       double* __restrict__ delta_out) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= M) return;
+    const double ub = acq_value(GPX_ACQ_EI, (bias + dots[n]) + sc[1], rho, p0);
+    acc[n] = ens_fold(first, first ? 0.0 : acc[n], ub);
+    if (n == 0) *delta_out = sc[1];
+}
+
+void launch_prune_ub_fold(hipStream_t s, const double* dots, double* acc, int64_t M, const double* sc, double rho, double bias,
+                          double p0, int first, double* delta_out) {
+    hipLaunchKernelGGL(k_prune_ub_fold, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, dots, acc, M, sc, rho, bias, p0, first,
+                       delta_out);
+}
+
+// acc[c] <- acc[c] / n, the ensemble's bound; -inf for the `skip` leading candidates that are exactly evaluated already
+__global__ __launch_bounds__(256) void k_prune_ub_mean(double* __restrict__ acc, int64_t M, int64_t skip, double n) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= M) return;
+    acc[c] = (c < skip) ? GPX_NEG_INF : ens_mean(acc[c], n);
+}
+
+void launch_prune_ub_mean(hipStream_t s, double* acc, int64_t M, int64_t skip, double n) {
+    hipLaunchKernelGGL(k_prune_ub_mean, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, acc, M, skip, n);
+}
+
 // out[0] = mean of v[0..n)  (the gate of a selection-only sweep: the mean s2 of its first generation)
 __global__ __launch_bounds__(256) void k_prune_mean(const double* __restrict__ v, int64_t n, double* __restrict__ out) {
     __shared__ double r0[256];
