@@ -49,6 +49,7 @@ DIAG_SYMBOLS = {
     'gpx_chol_tasks2': (_i64, [C.c_int, C.c_int, _P, _i64, _P]),
     'gpx_prune_report': (C.c_int, [_P, _P, C.c_int, _P, _P, _i64, _P, _P, _i64]),
     'gpx_prune_dots': (C.c_int, [_P, _P]),
+    'gpx_prune_rows': (C.c_int, [_P, _P, _P, _P, _i64]),
     'gpx_ensemble_prune_report': (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _i64]),
 }
 SYMBOLS = {
@@ -732,14 +733,16 @@ class Engine(object):
         nsurv, S, delta, tau, gate_s2, thr_key, kept, bound_kernel = 'generic' / 'mfma' (None: no bound pass), guard = the matrix-pipe
         kernel's (d + 4)(R_x + R_z)^2 (NaN where the host chose the generic kernel)); with `vectors`, where the bound pass ran, also ub (M,) as the survivor pass read
         it and idx, the survivors in compaction order (empty where it fell back); after a sweep with option prune_keep = 1 also ub_kept
-        and seed_idx, the bounds and the seed list before the scatter."""
-        scal = np.full(16, np.nan)
+        and seed_idx, the bounds and the seed list before the scatter.  nR (block rows of the second bound's prefix, 0: it did not
+        run) and nsurv2 (survivors of its cut); with `vectors`, nR > 0 and prune_keep = 1 also ub2, qR (aligned with idx) and idx2 (the
+        second-level list)."""
+        scal = np.full(20, np.nan)
         self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), None, None, 0, None, None, 0))
         names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'S', 'delta', 'tau', 'gate_s2', 'thr_key', 'kept',
-                 'bound_kernel', 'guard')
+                 'bound_kernel', 'guard', 'nR', 'nsurv2')
         r = dict(zip(names, scal.tolist()))
         r['bound_kernel'] = None if np.isnan(r['bound_kernel']) else ('generic', 'mfma')[int(r['bound_kernel'])]
-        for n in ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'kept'):
+        for n in ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'kept', 'nR', 'nsurv2'):
             r[n] = int(r[n])
         r['path'] = self.PRUNE_PATHS[r['path']]
         if vectors and r['path'] in ('pruned', 'fell back'):
@@ -752,6 +755,11 @@ class Engine(object):
             r['seed_idx'] = np.empty(r['G'], dtype=np.int64) if kept else None
             self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), _ptr(r['ub']), _ptr(r['idx']), nidx,
                                                    _ptr(r['ub_kept']), _ptr(r['seed_idx']), r['G'] if kept else 0))
+            if r['nR'] > 0 and kept:
+                r['ub2'] = np.empty(nidx)
+                r['idx2'] = np.empty(r['nsurv2'], dtype=np.int64)
+                r['qR'] = np.empty(nidx)
+                self._check(self._lib.gpx_prune_rows(self._h, _ptr(r['qR']), _ptr(r['ub2']), _ptr(r['idx2']), r['nsurv2']))
         return r
 
     @staticmethod

@@ -150,6 +150,7 @@ static const Option kOptions[] = {
     {"prune", SHIP, -1, 1, "prune must be -1 (by size and gate), 0 (never) or 1 (wherever legal)", store<&gpx_handle::prune>},
     {"prune_keep", DIAG, 0, 1, "prune_keep must be 0 or 1", store<&gpx_handle::prune_keep>},
     {"prune_bound", DIAG, -1, 1, "prune_bound must be -1 (by guard), 0 (generic kernel) or 1 (matrix-pipe kernel)", store<&gpx_handle::prune_bound>},
+    {"prune_rows", DIAG, -1, 1000000, "prune_rows must be -1 (by size), 0 (no second bound) or a number of block rows", store<&gpx_handle::prune_rows>},
     {"chol_w", SHIP, 0, 8, "chol_w must be 0 (by size) or in [2, 8]", store<&gpx_handle::chol_w>, [](int64_t v) { return v != 1; }},
     {"chol_tg", SHIP, -1, 1000000000, TG, store<&gpx_handle::chol_tg>, [](int64_t v) { return v == 0 || v == 1; }, "chol_tg must be 0 or 1"},
     {"chol_tg_chunks", DIAG, -1, 1000000000, TG, store<&gpx_handle::tg_chunks>},
@@ -227,8 +228,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // 600: gpx_diagnostics, gpx_chol_tasks -> gpx_chol_tasks2 (gpx_diag.h), the diagnostic options only in the diagnostics
 // build, tile_order default by size (7 below 32 block rows, 19 from there on).
 // 610: option prune (selection-only sweeps), timers slot 19.  620: the ensemble sweep prunes too (the lead's option prune),
-// gpx_ensemble_prune_report.
-extern "C" int gpx_version(void) { return 620; }
+// gpx_ensemble_prune_report.  630: the second bound of selection-only sweeps (option prune_rows, gpx_prune_rows, gpx_prune_report's scalars 16 .. 19).
+extern "C" int gpx_version(void) { return 630; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -407,11 +408,12 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
             HIPCHK(h, hipMemcpy(st, r.st, sizeof st, hipMemcpyDeviceToHost));
         }
         const bool guarded_bound = bound && r.bound_kernel < 0;      // the device chose the bound pass's kernel: sc[8] = guard value, sc[9] = choice
-        const double out[16] = {(double)r.path, (double)r.M,     (double)r.k, (double)r.G, (double)r.Gg,
+        const double out[20] = {(double)r.path, (double)r.M,     (double)r.k, (double)r.G, (double)r.Gg,
                                 (double)r.done, (double)r.cap,   (double)r.nsurv, sc[0],   sc[1],
                                 sc[5],          r.mean_s2,       bound ? (double)st[2] : NAN, r.kept ? 1.0 : 0.0,
-                                bound ? (guarded_bound ? sc[9] : 0.0) : NAN, guarded_bound ? sc[8] : NAN};
-        for (int i = 0; i < nscal && i < 16; ++i) scal[i] = out[i];
+                                bound ? (guarded_bound ? sc[9] : 0.0) : NAN, guarded_bound ? sc[8] : NAN,
+                                (double)r.nR,   (double)r.nsurv2, NAN, NAN};
+        for (int i = 0; i < nscal && i < 20; ++i) scal[i] = out[i];
         if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
         const int64_t nidx = std::min(std::min(r.nsurv, r.cap), cap_idx);
         if (idx && nidx > 0) HIPCHK(h, hipMemcpy(idx, r.idx, (size_t)nidx * 8, hipMemcpyDeviceToHost));
@@ -419,6 +421,22 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
         const int64_t nseed = std::min(r.G, cap_seed);
         if (seed_idx && nseed > 0)
             HIPCHK(h, hipMemcpy(seed_idx, h->dkeep + r.M * 8, (size_t)nseed * 8, hipMemcpyDeviceToHost));
+        return GPX_OK;
+    });
+}
+
+extern "C" int gpx_prune_rows(gpx_handle* h, double* qR, double* ub2, int64_t* idx2, int64_t cap_idx2) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        const gpx_handle::PruneRecord& r = h->prune_rec;
+        if (r.path != 2 || r.nR <= 0) return fail(h, GPX_ESTATE, "prune_rows: the last sweep ran no second bound");
+        if (!r.kept) return fail(h, GPX_ESTATE, "prune_rows: the last sweep ran without the option prune_keep");
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (qR) HIPCHK(h, hipMemcpy(qR, r.qR, (size_t)r.nsurv * 8, hipMemcpyDeviceToHost));
+        if (ub2) HIPCHK(h, hipMemcpy(ub2, r.ub2, (size_t)r.nsurv * 8, hipMemcpyDeviceToHost));
+        const int64_t n2 = std::min(r.nsurv2, cap_idx2);
+        if (idx2 && n2 > 0) HIPCHK(h, hipMemcpy(idx2, r.idx2, (size_t)n2 * 8, hipMemcpyDeviceToHost));
         return GPX_OK;
     });
 }
@@ -1017,6 +1035,14 @@ static int staged_sweep(gpx_handle* h, const double* Xc, int64_t M, bool sync_up
 // gated by a mean s2 / rho of the first generation of at least 1 / 64.
 static const int64_t PRUNE_MIN_M = 32768, PRUNE_MIN_NP = 1024, PRUNE_MAX_SHARE_DIV = 4;
 static const double PRUNE_GATE_S2 = 1.0 / 64.0;
+// The second bound (option "prune_rows" = -1): the variance bound from the leading nP / 4 block rows
+// (measured on the headline workload against nP / 16 and nP / 8: profiles/prune_rows_ab.md),
+// tried where the first level left more than one generation of survivors -- an exact launch costs a whole generation however few
+// candidates it has, so at or below Gg survivors there is nothing to save -- of at least PRUNE_MIN_M candidates over at least 32
+// block rows: below those the prefix pass's launch chain and its sync are no small part of what it saves (the reasoning of
+// PRUNE_MIN_M / PRUNE_MIN_NP).  These conditions leave the single-bound accounting untouched at every shape
+// tests/test_gpu_prune_bound.py pins (prune = 1: M <= 13288 wherever nP >= 32; its larger M run at nP <= 20).
+static const int PRUNE_ROWS_MIN_NP = 32, PRUNE_ROWS_DIV = 4;
 
 // Geometry of a selection-only sweep of M candidates for the k best over a factor of nP block rows.
 // G: the candidates of one generation of sweep workgroups (512 resident, each a pair of tiles; at most 4096: short
@@ -1034,6 +1060,7 @@ static PruneGeom prune_geom(int nP, int64_t k, int64_t M) {
 // The pruning workspace, h->dprune:
 // [ub M][vals cap][Xg cap d][idx cap][blk nsel + 1][alpha2 Np][sabs Np][gate s2 Gg][sc 16][extra][hist 2 x 4096 + st 8 (int)]
 // [pad to 32 bytes][the matrix-pipe bound kernel's operands]
+// rows (the single model's sweep): [dots M][ub2 cap][qR cap][idx2 cap][Xg2 cap d][blk2 sel_blocks(cap) + 1] -- the second bound's
 struct PruneWs {
     double *ub, *vals, *Xg;
     int64_t *idx, *blk;
@@ -1041,12 +1068,15 @@ struct PruneWs {
     int *hist, *st;
     double* bws;
     int64_t nsel;
+    double *dots, *ub2, *qR, *Xg2;
+    int64_t *idx2, *blk2;
 };
-static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t extra, PruneWs& w) {
+static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t extra, PruneWs& w, bool rows = false) {
     const int64_t Np = h->Np;
     w.nsel = sel_blocks(M);
     const int64_t words0 = M + cap + cap * h->d + cap + (w.nsel + 1) + 2 * Np + Gg + 16 + extra + (2 * 4096 + 8) / 2;
-    const int64_t words = (words0 + 3) / 4 * 4 + bound_mfma_ws_words(Np);
+    const int64_t words1 = (words0 + 3) / 4 * 4 + bound_mfma_ws_words(Np);
+    const int64_t words = words1 + (rows ? M + 3 * cap + cap * h->d + sel_blocks(cap) + 1 : 0);
     if (!h->dprune || words * 8 > h->cap_prune) h->ens_rec = gpx_handle::EnsPruneRecord();   // (its vectors lie in the old allocation)
     int rc;
     if ((rc = ensure(h, h->dprune, h->cap_prune, words * 8))) return rc;
@@ -1063,6 +1093,15 @@ static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t e
     w.hist = reinterpret_cast<int*>(w.extra + extra);
     w.st = w.hist + 2 * 4096;
     w.bws = w.ub + (words0 + 3) / 4 * 4;
+    w.dots = w.ub2 = w.qR = w.Xg2 = nullptr;
+    w.idx2 = w.blk2 = nullptr;
+    if (!rows) return GPX_OK;
+    w.dots = w.ub + words1;
+    w.ub2 = w.dots + M;
+    w.qR = w.ub2 + cap;
+    w.idx2 = reinterpret_cast<int64_t*>(w.qR + cap);
+    w.Xg2 = reinterpret_cast<double*>(w.idx2 + cap);
+    w.blk2 = reinterpret_cast<int64_t*>(w.Xg2 + cap * h->d);
     return GPX_OK;
 }
 
@@ -1117,6 +1156,10 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             HIPCHK(h, hipMemcpyAsync(h->dcZ, dXc, (size_t)M * h->d * 8, hipMemcpyDeviceToDevice, s));
     }
 
+    // by size: short tiles (fewer than 32 block rows) on the barrier-free loop, long ones on the shared-image loop
+    // (crossover measured: profiles/r06_sweep_power_probes.txt, section 6)
+    const int sweep_order = h->tile_order >= 0 ? h->tile_order : (Np / NB < 32 ? 7 : 19);
+
     // The exact chain (cross-Gram -> V = T K* -> moments and value) for rows [mb, me) of the candidate array X, in chunks:
     // out[m] (and mu / s2 / the cache sums, where given) for every m of the range.  A candidate's value depends on its
     // coordinates alone -- not on the chunk, the tile or the column it is computed in (tests/test_gpu_prune.py).
@@ -1131,10 +1174,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             }
             {
                 Span sp(h, T_TRMM);
-                launch_sweep_trmm(s, h->dU, Np, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk,
-                                  // by size: short tiles (fewer than 32 block rows) on the barrier-free loop, long ones on the shared-image loop
-                                  // (crossover measured: profiles/r06_sweep_power_probes.txt, section 6)
-                                  h->tile_order >= 0 ? h->tile_order : (Np / NB < 32 ? 7 : 19), h->super_m, h->dclk);
+                launch_sweep_trmm(s, h->dU, Np, nP, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk);
             }
             h->tacc[T_NLAUNCH] += 1.0;
             // ALGORITHMIC work of this launch: N^2 flop per candidate (N^2/2 multiply-adds of the
@@ -1167,7 +1207,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
         if ((rc = ensure(h, h->dtopv, h->cap_top, (int64_t)TOPK_MAX * 2))) return rc;
         h->dtopi = reinterpret_cast<int64_t*>(h->dtopv + TOPK_MAX);
         PruneWs w;
-        if ((rc = prune_ws(h, M, cap, Gg, 0, w))) return rc;
+        if ((rc = prune_ws(h, M, cap, Gg, 0, w, true))) return rc;
         double *const ub = w.ub, *const vals = w.vals, *const Xg = w.Xg, *const gs2 = w.gs2, *const sc = w.sc;
         int64_t *const idx = w.idx, *const blk = w.blk;
         int *const hist = w.hist, *const st = w.st;
@@ -1192,13 +1232,13 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             {
                 // 1. bound pass: ub[n] = EI(bias + alpha . k(X, z_n) + delta, s2 = rho) >= the value the exact chain returns
                 Span sp(h, T_BOUND);
-                bound_dots(h, dXc, M, w, bound_mfma, ub);
+                bound_dots(h, dXc, M, w, bound_mfma, w.dots);      // (kept: the second bound reads the survivors' dots again)
                 if (h->prune_keep) {
                     // diagnostic: the dots as the kernel left them (gpx_prune_dots), behind the two copies below
                     if ((rc = ensure(h, h->dkeep, h->cap_keep, (2 * M + G) * 8))) return rc;
-                    HIPCHK(h, hipMemcpyAsync(h->dkeep + (M + G) * 8, ub, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
+                    HIPCHK(h, hipMemcpyAsync(h->dkeep + (M + G) * 8, w.dots, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
                 }
-                launch_prune_ub(s, ub, M, done, sc, h->rho, h->bias, p0);
+                launch_prune_ub(s, w.dots, ub, M, done, sc, h->rho, h->bias, p0);
             }
             rec.bound_kernel = bound_mfma ? -1 : 0;
             int64_t* seed_keep = nullptr;
@@ -1231,10 +1271,47 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             rec.ub = ub, rec.idx = idx, rec.sc = sc, rec.st = st;
             rec.kept = seed_keep != nullptr;
             if (nsurv <= cap) {
+                // 4a-4c. the second bound, where the rule above says so: s2 <= rho - q_R, q_R the sum of V^2 over the leading nR block
+                // rows in the exact chain's own bits -- the survivors that EI((bias + dot) + delta, rho - q_R) still lets reach tau
+                const double* Xs = Xg;
+                const int64_t* ids = idx;
+                int64_t ns = nsurv;
+                int nR = 0;
+                if (h->prune_rows > 0) nR = (int)std::min<int64_t>(std::min<int64_t>(h->prune_rows, nP), h->N / NB);
+                else if (h->prune_rows < 0 && M >= PRUNE_MIN_M && nP >= PRUNE_ROWS_MIN_NP && nsurv > Gg) nR = std::max(1, nP / PRUNE_ROWS_DIV);
+                if (nR > 0 && nsurv > 0) {
+                    int64_t nsurv2 = 0;
+                    {
+                        Span sp(h, T_BOUND);
+                        for (int64_t j0 = 0; j0 < nsurv; j0 += chunk) {
+                            const int64_t valid = std::min(chunk, nsurv - j0);
+                            const int64_t cols = (valid + TBH - 1) / TBH * TBH;
+                            // 4a. rows [0, nR 128) of the survivors' cross-Gram panels and the sweep's tiles of those block rows
+                            launch_cross_gram(s, h->dXs, (int64_t)nR * NB, h->N, (int)h->d, Xg, j0, nsurv, cols, h->dinvell,
+                                              h->kernel_id, h->rho, h->dKs, Np);
+                            launch_sweep_trmm(s, h->dU, Np, nR, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order,
+                                              h->super_m, h->dclk);
+                            // 4b. ub2 = EI((bias + dot) + delta, fmax(rho - q_R, 1e-100))
+                            launch_prune_ub2(s, h->dQp, chunk, nR, j0, valid, idx, w.dots, sc, h->rho, h->bias, p0, w.ub2,
+                                             h->prune_keep ? w.qR : nullptr);
+                        }
+                    }
+                    {
+                        // 4c. the cut of step 3 on ub2 (sc[5]: the tau it cut with): positions of the first-level list, stably
+                        Span sp(h, T_ACQ);
+                        launch_sel_compact(s, w.ub2, nsurv, 1, st, sc + 5, w.blk2, cap, Xg, (int)h->d, w.idx2, w.Xg2);
+                        HIPCHK(h, hipMemcpyAsync(&nsurv2, w.blk2 + sel_blocks(nsurv), 8, hipMemcpyDeviceToHost, s));
+                    }
+                    HIPCHK(h, hipStreamSynchronize(s));
+                    rec.nR = nR, rec.nsurv2 = nsurv2;
+                    rec.ub2 = w.ub2, rec.idx2 = w.idx2, rec.qR = h->prune_keep ? w.qR : nullptr;
+                    Xs = w.Xg2, ids = w.idx2, ns = nsurv2;
+                }
                 // 4. their exact values to their own positions; everything else stays -inf and the top-k below runs as ever
-                run_chunks(Xg, 0, nsurv, vals, nullptr, nullptr);
+                run_chunks(Xs, 0, ns, vals, nullptr, nullptr);
                 Span sp(h, T_ACQ);
-                launch_sel_scatter(s, idx, vals, nsurv, d_acq, nullptr);
+                if (ids != idx) launch_sel_remap(s, idx, w.idx2, ns);      // (list positions -> the candidates behind them)
+                launch_sel_scatter(s, ids, vals, ns, d_acq, nullptr);
                 done = M;
             }
             // 5. (else) too many survivors -- tau = 0, a flat bound: the plain loop over everything not yet evaluated

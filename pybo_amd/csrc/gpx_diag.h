@@ -23,6 +23,9 @@
  *                     gpx_prune_report and gpx_prune_dots [0]
  *   "prune_bound"     the kernel of a pruned sweep's bound pass: 0 the generic k_sweep_rankq<1>; 1 the matrix-pipe kernel wherever it exists
  *                     (SE-ARD, d <= 18), whatever its guard says; -1 by the guard [-1]
+ *   "prune_rows"      block rows of the row prefix behind a pruned sweep's second bound: 0 never (the
+ *                     single bound alone); n > 0: min(n, nP, N / 128) rows wherever the first level pruned; -1 by size: nP / 4 rows where
+ *                     M >= 32768, nP >= 32 and more than Gg candidates survived the first bound [-1]
  */
 #ifndef GPX_DIAG_H
 #define GPX_DIAG_H
@@ -54,11 +57,12 @@ int64_t gpx_chol_trace(gpx_handle *h, int64_t *out, int64_t n);
 int64_t gpx_chol_tasks2(int nblocks, int chunks, int16_t *out, int64_t cap, int64_t *counts);
 
 /* What the handle's LAST sweep decided about pruning and with what; it only copies what the sweep left behind.
- * scal[0 .. min(nscal, 16)) = { path: 0 plain (not legal or not tried), 1 the gate declined, 2 pruned, 3 the bound pass ran but more than
+ * scal[0 .. min(nscal, 20)) = { path: 0 plain (not legal or not tried), 1 the gate declined, 2 pruned, 3 the bound pass ran but more than
  * cap candidates survived and the plain loop evaluated everything;  M;  k;  G (seeds);  Gg (the gate's generation);  done (leading
  * candidates evaluated before the bound pass);  cap;  nsurv;  S;  delta;  tau (the k-th best seed value);  the gate's mean s2 (NaN: no
  * gate);  the seeds' threshold key;  1 if the kept copies exist;  the bound pass's kernel, 0 generic / 1 matrix pipe;  the guard's (d + 4) (R_x + R_z)^2
- * (NaN where the host chose the generic kernel: another covariance, d > 18, prune_bound = 0) }.  S .. tau, the key and the last two are NaN for paths 0 and 1.
+ * (NaN where the host chose the generic kernel: another covariance, d > 18, prune_bound = 0);  nR, the block rows of the second bound's
+ * prefix (0: it did not run);  nsurv2, the survivors of its cut (the candidates evaluated exactly on path 2 where nR > 0);  two reserved (NaN) }.  S .. tau, the key and the last two are NaN for paths 0 and 1.
  * ub (optional, M): the bound vector as the survivor pass read it (-inf where a candidate was evaluated as gate or seed);  idx
  * (optional, cap_idx): the first min(nsurv, cap, cap_idx) survivors in the order they were compacted;  ub_kept (optional, M) and
  * seed_idx (optional, cap_seed; G entries): the bound vector and the seed list before the scatter -- only after a sweep that ran with
@@ -71,6 +75,13 @@ int gpx_prune_report(gpx_handle *h, double *scal, int nscal, double *ub, int64_t
 /* dots (M): alpha2 . k(X, z_n) as the bound pass's kernel left them, before EI was taken of them -- only after a pruned sweep (path >= 2)
  * that ran with the option prune_keep = 1 (GPX_ESTATE otherwise). */
 int gpx_prune_dots(gpx_handle *h, double *dots);
+
+/* The second bound of the last sweep, only after a sweep with the option prune_keep = 1 that ran it (path 2 with nR > 0; GPX_ESTATE
+ * otherwise), aligned with the first-level list `idx` of gpx_prune_report: ub2 (optional, nsurv) = EI((bias + dot) + delta,
+ * max(rho - qR, 1e-100));  qR (optional, nsurv) = the sum of V^2 over the leading nR block rows, added block by block as the exact
+ * chain adds them;  idx2 (optional, cap_idx2): the first min(nsurv2, cap_idx2) candidates that survived the second cut, in order.
+ * (An entry point of its own, so that gpx_prune_report keeps the signature its callers were built against.) */
+int gpx_prune_rows(gpx_handle *h, double *qR, double *ub2, int64_t *idx2, int64_t cap_idx2);
 
 /* What the LAST ensemble sweep led by members[0] decided about pruning; `members`, n as in that call.
  * scal[0 .. min(nscal, 10 + n)) = { path 0 .. 3, M, k, G, Gg, done, cap, nsurv as in gpx_prune_report;  tau (NaN for paths 0 and 1);  the

@@ -161,6 +161,11 @@ struct gpx_handle {
         const int* st = nullptr;
         int bound_kernel = -1;    // -1: sc[9] says which kernel wrote the dots; 0: the host chose k_sweep_rankq<1> (no guard ran)
         bool kept = false;        // dkeep holds this sweep's bound vector and seed list as they were before the scatter
+        // the second level (row-prefix bound): nR = 0 where it did not run; its vectors lie in dprune like the first level's
+        int nR = 0;
+        int64_t nsurv2 = 0;
+        const double *qR = nullptr, *ub2 = nullptr;      // aligned with idx (qR only under prune_keep)
+        const int64_t* idx2 = nullptr;
     } prune_rec;
     // what the last ENSEMBLE sweep led by this handle decided (gpx_ensemble_prune_report): its vectors lie in this handle's dprune
     struct EnsPruneRecord {
@@ -174,6 +179,7 @@ struct gpx_handle {
     } ens_rec;
     int prune_keep = 0;       // diagnostic option: keep those two device copies
     int prune_bound = -1;     // diagnostic option: the bound pass's kernel (-1 by guard, 0 k_sweep_rankq<1>, 1 k_bound_mfma wherever SE-ARD, d <= 18)
+    int prune_rows = -1;      // diagnostic option: block rows of the second bound's row prefix (-1 by size: nP / 4, 0 never, n > 0: min(n, nP, N / 128) wherever the first level pruned)
     char* dkeep = nullptr;    // [ub M][seed idx G][dots M]
     int64_t cap_keep = 0;     // ... in bytes
 
@@ -240,10 +246,12 @@ void launch_posterior_wide(hipStream_t s, const double* A, const double* v, cons
                            double sn2, double* B, double* R, double* work, int* flag, double* theta);   // n >= 128 features
 
 // launchers (kernels_sweep.hip)
-void launch_cross_gram(hipStream_t s, const double* Xs, int64_t Np, int64_t N, int d, const double* Xc,
+// rows: the observed rows [0, rows) filled in every panel of pitch ldk (Np, or the leading nR 128 <= N of a row-prefix pass)
+void launch_cross_gram(hipStream_t s, const double* Xs, int64_t rows, int64_t N, int d, const double* Xc,
                        int64_t m0, int64_t M, int64_t cols, const double* invell, int kernel_id,
                        double rho, double* Ks, int64_t ldk);
-void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, const double* Ks, int64_t ldk,
+// nR: the block rows [0, nR) the launch covers (Np / 128: the sweep; fewer: a row-prefix launch, whose Qp / Pp[mt < nR] are the full launch's bits)
+void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const double* Ks, int64_t ldk,
                        int64_t cols, const double* a, double* Qp, double* Pp, int64_t ldp,
                        int tile_order, int super_m, unsigned long long* clk);
 // reduce partials, form mu/s2/acq for columns [0,cols) of this chunk -> global candidate m0+..
@@ -280,7 +288,13 @@ int bound_mfma_ks(int kernel_id, int d);
 int64_t bound_mfma_ws_words(int64_t Np);
 void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
                        const double* Z, int64_t M, const double* invell, int force, double* ws, double* sc, double* out);
-void launch_prune_ub(hipStream_t s, double* ub, int64_t M, int64_t skip, const double* sc, double rho, double bias, double p0);
+void launch_prune_ub(hipStream_t s, const double* dots, double* ub, int64_t M, int64_t skip, const double* sc, double rho,
+                     double bias, double p0);
+// the second bound: ub2[j0 + n] = EI((bias + dots[idx[j0 + n]]) + delta, fmax(rho - sum_{rb < nR} Qp[rb][n], 1e-100)) for the chunk's
+// cols_valid survivors (qR_out, optional: the sums); idx2[j] <- idx[idx2[j]] after the second cut's compaction of list positions
+void launch_prune_ub2(hipStream_t s, const double* Qp, int64_t ldp, int nR, int64_t j0, int64_t cols_valid, const int64_t* idx,
+                      const double* dots, const double* sc, double rho, double bias, double p0, double* ub2, double* qR_out);
+void launch_sel_remap(hipStream_t s, const int64_t* idx, int64_t* idx2, int64_t n);
 // the ensemble's bound: one member's EI bound folded into the running sum (k_ens_accum's addition), then the sum / n (k_ens_finish's)
 void launch_prune_ub_fold(hipStream_t s, const double* dots, double* acc, int64_t M, const double* sc, double rho, double bias,
                           double p0, int first, double* delta_out);

@@ -114,9 +114,12 @@ __global__ __launch_bounds__(256, 3) void k_cross_gram(const double* __restrict_
     }
 }
 
-void launch_cross_gram(hipStream_t s, const double* Xs, int64_t Np, int64_t N, int d, const double* Xc,
+// rows: the observed rows [0, rows) filled in every panel (a multiple of 128), at the pitch ldk -- the factor's Np for the sweep
+// itself, the leading nR 128 <= N for the row-prefix pass of a selection-only sweep.  An entry's bits depend on its two points alone.
+void launch_cross_gram(hipStream_t s, const double* Xs, int64_t rows, int64_t N, int d, const double* Xc,
                        int64_t m0, int64_t M, int64_t cols, const double* invell, int kernel_id,
                        double rho, double* Ks, int64_t ldk) {
+    const int64_t Np = rows;
     const int64_t tiles = Np / XK;
     // row tiles per workgroup: the SE kernel at small d is bound by its 8 B/evaluation of stores (one tile per
     // workgroup interleaves them best: 3.5 vs 4.3 ms per 2^31 evaluations), the others by their VALU work (the
@@ -142,6 +145,8 @@ void launch_cross_gram(hipStream_t s, const double* Xs, int64_t Np, int64_t N, i
 // ------------------------------------------------------------------------------------------------
 // blockIdx -> tile(s) of the launch.  Returns false when the block has nothing to do; mt2 >= 0: the workgroup also
 // computes tile (mt2, nt) afterwards.  RES = workgroups resident per XCD (32 CUs x workgroups per CU): the size of a super-tile.
+// nP here is the number of block rows the MAP covers, [0, nP): the factor's for a full launch, the leading nR of a row-prefix
+// launch (sweep_tiles) -- pairs are then (nR-1-i, i), the odd middle tile alone as ever.
 template <int RES>
 __device__ __forceinline__ bool sweep_tile_of(int b, int order, int sm, int NT, int nP, int& mt, int& nt, int& mt2) {
     mt2 = -1;
@@ -256,14 +261,17 @@ __device__ __forceinline__ void sweep_epilogue(const d4 (&acc)[4][4], const doub
 // The frame of every schedule of the dominant kernel: the workgroup's tile (or tile pair) from the map, per tile the operand
 // pointers, the K-extent and the up/down rule, the k-loop `loop(acc, At, Bt, kend, rev)` of the schedule, the epilogue.
 // (interleaved row blocks in every schedule: the column sums then add a tile's rows in the same order everywhere)
+// Np is the leading dimension of U, the panel pitch of Ks and, as nP, the factor's block rows of the up/down rule; nR <= nP is the
+// number of block rows the map covers.  A tile's arithmetic depends on its rows of U, its panel, its K-extent and the rule -- not
+// on nR: a row-prefix launch (nR < nP) writes into Qp / Pp[mt < nR] the very bits the full launch (nR = nP) writes there.
 template <int RES, class Loop>
 __device__ __forceinline__ void sweep_tiles(int b, const double* __restrict__ U, int64_t Np, const double* __restrict__ Ks, int NT,
-                                            const double* __restrict__ avec, double* __restrict__ Qp, double* __restrict__ Pp,
+                                            int nR, const double* __restrict__ avec, double* __restrict__ Qp, double* __restrict__ Pp,
                                             int64_t ldp, int order, int sm, unsigned long long* clk, double* smem, Loop loop) {
     const LaunchClock lc;
     const int nP = (int)(Np / TB);
     int mt, nt, mt2;
-    if (!sweep_tile_of<RES>(b, order, sm, NT, nP, mt, nt, mt2)) return;
+    if (!sweep_tile_of<RES>(b, order, sm, NT, nR, mt, nt, mt2)) return;
 #pragma unroll 1
     for (int ph = 0; ph < 2; ++ph) {
         if (ph == 1) {
@@ -285,13 +293,13 @@ __device__ __forceinline__ void sweep_tiles(int b, const double* __restrict__ U,
 template <int VAR>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm(const double* __restrict__ U, int64_t Np,
                                                                 const double* __restrict__ Ks,
-                                                                int64_t ldk, int NT,
+                                                                int64_t ldk, int NT, int nR,
                                                                 const double* __restrict__ avec,
                                                                 double* __restrict__ Qp,
                                                                 double* __restrict__ Pp, int64_t ldp,
                                                                 int order, int sm, unsigned long long* clk) {
     __shared__ __attribute__((aligned(16))) double smem[GEMM_LDS_F64];
-    sweep_tiles<64>(blockIdx.x, U, Np, Ks, NT, avec, Qp, Pp, ldp, order, sm, clk, smem,
+    sweep_tiles<64>(blockIdx.x, U, Np, Ks, NT, nR, avec, Qp, Pp, ldp, order, sm, clk, smem,
                     [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev) {
         if (!rev) {
             if (VAR == 2) gemm_tile_128_b<true, true>(acc, At, Np, Bt, TB, 0, kend, smem);
@@ -310,13 +318,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm(const double* __
 // DOWN = false: every tile upwards (probe builds only: the A/B of the order rule -- NOT bit-identical with the shipped schedules)
 template <int BKL, int WGS, int PRIO, int NSET, bool TRI, int AUX = 0, bool DOWN = true>
 __global__ __launch_bounds__(GEMM_THREADS, WGS) void k_sweep_trmm_l(const double* __restrict__ U, int64_t Np,
-                                                                    const double* __restrict__ Ks, int64_t ldk, int NT,
+                                                                    const double* __restrict__ Ks, int64_t ldk, int NT, int nR,
                                                                     const double* __restrict__ avec,
                                                                     double* __restrict__ Qp, double* __restrict__ Pp,
                                                                     int64_t ldp, int order, int sm,
                                                                     unsigned long long* clk, int b0) {
     __shared__ __attribute__((aligned(16))) double smem[gemm_l_lds_f64<BKL>()];
-    sweep_tiles<32 * WGS>((int)blockIdx.x + b0, U, Np, Ks, NT, avec, Qp, Pp, ldp, order, sm, clk, smem,
+    sweep_tiles<32 * WGS>((int)blockIdx.x + b0, U, Np, Ks, NT, nR, avec, Qp, Pp, ldp, order, sm, clk, smem,
                           [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev) {
         if (!(DOWN && rev)) gemm_tile_128_l<BKL, PRIO, NSET, true, TRI, false, AUX>(acc, At, Np, Bt, TB, 0, kend, smem);
         else if constexpr (BKL == 32) gemm_tile_128_l<32, PRIO, NSET, true, TRI, false, AUX, true>(acc, At, Np, Bt, TB, 0, kend, smem);
@@ -327,37 +335,38 @@ __global__ __launch_bounds__(GEMM_THREADS, WGS) void k_sweep_trmm_l(const double
 // The same tiles on the barrier-free loop (gemm_tile_128_w: every wave fetches its own operand halves, one 16-row image per
 // wave, two workgroups per CU), with the diagonal block's zero rows skipped.  Twice the L2 -> LDS bytes of k_sweep_trmm_l.
 __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm_w(const double* __restrict__ U, int64_t Np,
-                                                                  const double* __restrict__ Ks, int64_t ldk, int NT,
+                                                                  const double* __restrict__ Ks, int64_t ldk, int NT, int nR,
                                                                   const double* __restrict__ avec, double* __restrict__ Qp,
                                                                   double* __restrict__ Pp, int64_t ldp, int order, int sm,
                                                                   unsigned long long* clk) {
     __shared__ __attribute__((aligned(16))) double smem[4 * GEMM_W_IMG_F64];
-    sweep_tiles<64>(blockIdx.x, U, Np, Ks, NT, avec, Qp, Pp, ldp, order, sm, clk, smem,
+    sweep_tiles<64>(blockIdx.x, U, Np, Ks, NT, nR, avec, Qp, Pp, ldp, order, sm, clk, smem,
                     [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev) {
         if (!rev) gemm_tile_128_w<1, 1, false, true, 0, true>(acc, At, Np, Bt, TB, 0, kend, smem);
         else gemm_rev32(0, kend, [&](int k0, int k1) { gemm_tile_128_w<1, 1, false, true, 0, false>(acc, At, Np, Bt, TB, k0, k1, smem); });
     });
 }
 
-void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, const double* Ks, int64_t ldk,
+// nR: the block rows [0, nR) the launch covers -- the factor's Np / 128 for the sweep itself, fewer for the row-prefix pass of a
+// selection-only sweep (api.hip: sweep_core, step 4a), which needs rows [0, nR 128) of every Ks panel only.
+void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const double* Ks, int64_t ldk,
                        int64_t cols, const double* a, double* Qp, double* Pp, int64_t ldp,
                        int tile_order, int super_m, unsigned long long* clk) {
     const int NT = (int)(cols / TB);
-    const int nP = (int)(Np / TB);
     // bits 0-1: tile map, bits 2-4: k-loop (4 = default: operands by LDS-DMA, k-step 32, two workgroups per CU, the zero rows of
     // T's diagonal block skipped; 3: the same without the skip; 1: the barrier-free wave-private loop; 7: k-step 16, three workgroups per CU; 6, 5, 2: the
     // register-staged schedules of rounds 5, 2, 1 -- all kept as independently scheduled witnesses of the bit-identity test)
     const int order = tile_order & 3, var = (tile_order >> 2) & 7;
-#define GPX_SW(K) hipLaunchKernelGGL(K, dim3(nblk), dim3(GEMM_THREADS), 0, s, U, Np, Ks, ldk, NT, a, Qp, Pp, ldp, order, super_m, clk)
-#define GPX_SWL(K) hipLaunchKernelGGL(K, dim3(nblk), dim3(GEMM_THREADS), 0, s, U, Np, Ks, ldk, NT, a, Qp, Pp, ldp, order, super_m, clk, 0)
+#define GPX_SW(K) hipLaunchKernelGGL(K, dim3(nblk), dim3(GEMM_THREADS), 0, s, U, Np, Ks, ldk, NT, nR, a, Qp, Pp, ldp, order, super_m, clk)
+#define GPX_SWL(K) hipLaunchKernelGGL(K, dim3(nblk), dim3(GEMM_THREADS), 0, s, U, Np, Ks, ldk, NT, nR, a, Qp, Pp, ldp, order, super_m, clk, 0)
     if (var == 7) {                // three workgroups per CU, k-step 16
-        const unsigned nblk = sweep_grid<96>(order, super_m, NT, nP);
+        const unsigned nblk = sweep_grid<96>(order, super_m, NT, nR);
         GPX_SWL((k_sweep_trmm_l<16, 3, 1, 2, false>));
     } else if (var == 1) {               // barrier-free: every wave keeps its own operands
-        const unsigned nblk = sweep_grid<64>(order, super_m, NT, nP);
+        const unsigned nblk = sweep_grid<64>(order, super_m, NT, nR);
         GPX_SW(k_sweep_trmm_w);
     } else if (var == 4 || var == 3) {   // two workgroups per CU, k-step 32; 4: with the diagonal block's zero rows skipped
-        const unsigned nblk = sweep_grid<64>(order, super_m, NT, nP);
+        const unsigned nblk = sweep_grid<64>(order, super_m, NT, nR);
 #ifdef GPX_SWEEP_PROBES          // scripts/probe/sweep_ab.hip only: variants that are NOT schedules of the library (profiles/r06_sweep_power_probes.txt)
         const int aux = tile_order >> 5;         // (probe builds only: cache policy of the operand loads; gpx_set_option admits 0)
         if (var == 4 && aux == 1) GPX_SWL((k_sweep_trmm_l<32, 2, 1, 2, true, 1>));
@@ -368,7 +377,7 @@ void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, const double*
         else if (var == 4 && aux == 6) GPX_SWL((k_sweep_trmm_l<32, 2, 1, 2, true, 0, false>));      // every tile upwards (round 6's first form)
         else if (var == 4 && aux == 7) {        // probe: one launch per generation of 512 workgroups (every generation starts aligned)
             for (unsigned g0 = 0; g0 < nblk; g0 += 512)
-                hipLaunchKernelGGL((k_sweep_trmm_l<32, 2, 1, 2, true>), dim3(nblk - g0 < 512 ? nblk - g0 : 512), dim3(GEMM_THREADS), 0, s, U, Np, Ks, ldk, NT, a,
+                hipLaunchKernelGGL((k_sweep_trmm_l<32, 2, 1, 2, true>), dim3(nblk - g0 < 512 ? nblk - g0 : 512), dim3(GEMM_THREADS), 0, s, U, Np, Ks, ldk, NT, nR, a,
                                    Qp, Pp, ldp, order, super_m, clk, (int)g0);
         }
         else
@@ -376,7 +385,7 @@ void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, const double*
         if (var == 4) GPX_SWL((k_sweep_trmm_l<32, 2, 1, 2, true>));
         else GPX_SWL((k_sweep_trmm_l<32, 2, 1, 2, false>));
     } else {
-        const unsigned nblk = sweep_grid<64>(order, super_m, NT, nP);
+        const unsigned nblk = sweep_grid<64>(order, super_m, NT, nR);
         if (var == 2) GPX_SW(k_sweep_trmm<2>);
         else if (var == 6) GPX_SW(k_sweep_trmm<6>);
         else GPX_SW(k_sweep_trmm<5>);
@@ -1092,17 +1101,52 @@ void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, i
 #undef GPX_BM
 }
 
-// ub[n] (in: alpha2 . k(X, z_n)) <- EI((bias + dot) + delta, s2 = rho) by k_acq's own function; -inf for the `skip` leading
-// candidates that are exactly evaluated already.
-__global__ __launch_bounds__(256) void k_prune_ub(double* __restrict__ ub, int64_t M, int64_t skip, const double* __restrict__ sc,
-                                                  double rho, double bias, double p0) {
+// ub[n] <- EI((bias + dots[n]) + delta, s2 = rho), dots[n] = alpha2 . k(X, z_n), by k_acq's own function; -inf for the `skip`
+// leading candidates that are exactly evaluated already.  The dots stay where they are: the second bound reads them again.
+__global__ __launch_bounds__(256) void k_prune_ub(const double* __restrict__ dots, double* __restrict__ ub, int64_t M, int64_t skip,
+                                                  const double* __restrict__ sc, double rho, double bias, double p0) {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= M) return;
-    ub[n] = (n < skip) ? GPX_NEG_INF : acq_value(GPX_ACQ_EI, (bias + ub[n]) + sc[1], rho, p0);
+    ub[n] = (n < skip) ? GPX_NEG_INF : acq_value(GPX_ACQ_EI, (bias + dots[n]) + sc[1], rho, p0);
 }
 
-void launch_prune_ub(hipStream_t s, double* ub, int64_t M, int64_t skip, const double* sc, double rho, double bias, double p0) {
-    hipLaunchKernelGGL(k_prune_ub, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, ub, M, skip, sc, rho, bias, p0);
+void launch_prune_ub(hipStream_t s, const double* dots, double* ub, int64_t M, int64_t skip, const double* sc, double rho,
+                     double bias, double p0) {
+    hipLaunchKernelGGL(k_prune_ub, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, dots, ub, M, skip, sc, rho, bias, p0);
+}
+
+// The second bound of a selection-only sweep, for survivor j of the chunk at j0: qR = the sum of the
+// row-prefix launch's Qp[rb][j], rb < nR, in k_acq's order from 0.0 -- every term a sum of squares, so no larger than k_acq's q,
+// bit for bit -- s2R = fmax(rho - qR, 1e-100) >= s2 and ub2 = EI((bias + dot) + delta, s2R) with k_prune_ub's mean bound.
+// qR_out (optional) keeps the sums for gpx_prune_rows.
+__global__ __launch_bounds__(256) void k_prune_ub2(const double* __restrict__ Qp, int64_t ldp, int nR, int64_t j0, int64_t cols_valid,
+                                                   const int64_t* __restrict__ idx, const double* __restrict__ dots,
+                                                   const double* __restrict__ sc, double rho, double bias, double p0,
+                                                   double* __restrict__ ub2, double* __restrict__ qR_out) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= cols_valid) return;
+    double q = 0.0;
+    for (int rb = 0; rb < nR; ++rb) q += Qp[(int64_t)rb * ldp + n];
+    const double s2R = fmax(rho - q, 1e-100);
+    ub2[j0 + n] = acq_value(GPX_ACQ_EI, (bias + dots[idx[j0 + n]]) + sc[1], s2R, p0);
+    if (qR_out) qR_out[j0 + n] = q;
+}
+
+void launch_prune_ub2(hipStream_t s, const double* Qp, int64_t ldp, int nR, int64_t j0, int64_t cols_valid, const int64_t* idx,
+                      const double* dots, const double* sc, double rho, double bias, double p0, double* ub2, double* qR_out) {
+    hipLaunchKernelGGL(k_prune_ub2, dim3((unsigned)((cols_valid + 255) / 256)), dim3(256), 0, s, Qp, ldp, nR, j0, cols_valid, idx,
+                       dots, sc, rho, bias, p0, ub2, qR_out);
+}
+
+// idx2[j] <- idx[idx2[j]]: the second cut compacts positions of the first-level list; these are the candidates behind them
+__global__ __launch_bounds__(256) void k_sel_remap(const int64_t* __restrict__ idx, int64_t* __restrict__ idx2, int64_t n) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < n) idx2[j] = idx[idx2[j]];
+}
+
+void launch_sel_remap(hipStream_t s, const int64_t* idx, int64_t* idx2, int64_t n) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_sel_remap, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, idx, idx2, n);
 }
 
 // The ensemble's bound.  The sum of the members' bounds and its division are the arithmetic of k_ens_accum /

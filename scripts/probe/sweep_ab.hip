@@ -118,7 +118,7 @@ int main(int argc, char** argv) {
                 else { CK(hipFuncSetAttribute((const void*)k_lone<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
                     hipLaunchKernelGGL(k_lone<2>, dim3(nblk), dim3(GEMM_THREADS), lb, 0, U, Np, Ks, (int)(cols / TB), a, Qp, Pp, cols, sm); }
             } else
-            launch_sweep_trmm(0, U, Np, Ks, Np, cols, a, Qp, Pp, cols, to, sm, clk);
+            launch_sweep_trmm(0, U, Np, nP, Ks, Np, cols, a, Qp, Pp, cols, to, sm, clk);
             hipEventRecord(e1);
             CK(hipEventSynchronize(e1));
             CK(hipGetLastError());
