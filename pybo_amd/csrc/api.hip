@@ -151,6 +151,7 @@ static const Option kOptions[] = {
     {"prune_keep", DIAG, 0, 1, "prune_keep must be 0 or 1", store<&gpx_handle::prune_keep>},
     {"prune_bound", DIAG, -1, 1, "prune_bound must be -1 (by guard), 0 (generic kernel) or 1 (matrix-pipe kernel)", store<&gpx_handle::prune_bound>},
     {"prune_rows", DIAG, -1, 1000000, "prune_rows must be -1 (by size), 0 (no second bound) or a number of block rows", store<&gpx_handle::prune_rows>},
+    {"short_map", DIAG, -1, 1, "short_map must be -1 (by size), 0 (never) or 1 (wherever tile map 3 is in use)", store<&gpx_handle::short_map>},
     {"chol_w", SHIP, 0, 8, "chol_w must be 0 (by size) or in [2, 8]", store<&gpx_handle::chol_w>, [](int64_t v) { return v != 1; }},
     {"chol_tg", SHIP, -1, 1000000000, TG, store<&gpx_handle::chol_tg>, [](int64_t v) { return v == 0 || v == 1; }, "chol_tg must be 0 or 1"},
     {"chol_tg_chunks", DIAG, -1, 1000000000, TG, store<&gpx_handle::tg_chunks>},
@@ -1174,7 +1175,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             }
             {
                 Span sp(h, T_TRMM);
-                launch_sweep_trmm(s, h->dU, Np, nP, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk);
+                launch_sweep_trmm(s, h->dU, Np, nP, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk, h->short_map);
             }
             h->tacc[T_NLAUNCH] += 1.0;
             // ALGORITHMIC work of this launch: N^2 flop per candidate (N^2/2 multiply-adds of the
@@ -1290,7 +1291,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
                             launch_cross_gram(s, h->dXs, (int64_t)nR * NB, h->N, (int)h->d, Xg, j0, nsurv, cols, h->dinvell,
                                               h->kernel_id, h->rho, h->dKs, Np);
                             launch_sweep_trmm(s, h->dU, Np, nR, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order,
-                                              h->super_m, h->dclk);
+                                              h->super_m, h->dclk, h->short_map);
                             // 4b. ub2 = EI((bias + dot) + delta, fmax(rho - q_R, 1e-100))
                             launch_prune_ub2(s, h->dQp, chunk, nR, j0, valid, idx, w.dots, sc, h->rho, h->bias, p0, w.ub2,
                                              h->prune_keep ? w.qR : nullptr);

@@ -26,6 +26,9 @@
  *   "prune_rows"      block rows of the row prefix behind a pruned sweep's second bound: 0 never (the
  *                     single bound alone); n > 0: min(n, nP, N / 128) rows wherever the first level pruned; -1 by size: nP / 4 rows where
  *                     M >= 32768, nP >= 32 and more than Gg candidates survived the first bound [-1]
+ *   "short_map"       the short form of tile map 3 (csrc/sweep_map.h: an XCD owns a slice of the candidate tiles AND a slice of the pair rows):
+ *                     0 never; 1 wherever map 3 is in use; -1 by size: launches whose ceil(NT / 8) tiles per XCD are fewer than a
+ *                     super-tile's RES / super_m -- the results are the same bits under every value [-1]
  */
 #ifndef GPX_DIAG_H
 #define GPX_DIAG_H

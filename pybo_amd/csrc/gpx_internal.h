@@ -180,6 +180,7 @@ struct gpx_handle {
     int prune_keep = 0;       // diagnostic option: keep those two device copies
     int prune_bound = -1;     // diagnostic option: the bound pass's kernel (-1 by guard, 0 k_sweep_rankq<1>, 1 k_bound_mfma wherever SE-ARD, d <= 18)
     int prune_rows = -1;      // diagnostic option: block rows of the second bound's row prefix (-1 by size: nP / 4, 0 never, n > 0: min(n, nP, N / 128) wherever the first level pruned)
+    int short_map = -1;       // diagnostic option: the short form of tile map 3 (sweep_map.h) -1 by size (launches that cannot fill the per-XCD patches), 0 never, 1 always
     char* dkeep = nullptr;    // [ub M][seed idx G][dots M]
     int64_t cap_keep = 0;     // ... in bytes
 
@@ -253,7 +254,7 @@ void launch_cross_gram(hipStream_t s, const double* Xs, int64_t rows, int64_t N,
 // nR: the block rows [0, nR) the launch covers (Np / 128: the sweep; fewer: a row-prefix launch, whose Qp / Pp[mt < nR] are the full launch's bits)
 void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const double* Ks, int64_t ldk,
                        int64_t cols, const double* a, double* Qp, double* Pp, int64_t ldp,
-                       int tile_order, int super_m, unsigned long long* clk);
+                       int tile_order, int super_m, unsigned long long* clk, int short_map = -1);
 // reduce partials, form mu/s2/acq for columns [0,cols) of this chunk -> global candidate m0+..
 // nrb = 0: Qp/Pp are reduced per-candidate sums (the sweep cache); qsum/psum (optional) receive the reduced sums
 void launch_acq(hipStream_t s, const double* Qp, const double* Pp, int64_t ldp, int nrb, int64_t m0,

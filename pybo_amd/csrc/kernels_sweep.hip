@@ -17,6 +17,7 @@
 #include "gemm_core.h"
 #include "gpx_internal.h"
 #include "gpx_math.h"
+#include "sweep_map.h"
 
 namespace gpx {
 
@@ -143,65 +144,7 @@ void launch_cross_gram(hipStream_t s, const double* Xs, int64_t rows, int64_t N,
 // Tile (mt, nt): 128 observed rows x 128 candidates, K-extent (mt+1)*128 (T is lower triangular),
 // N^2 * M flop in total.  Heavy tiles (large mt) are dispatched first.
 // ------------------------------------------------------------------------------------------------
-// blockIdx -> tile(s) of the launch.  Returns false when the block has nothing to do; mt2 >= 0: the workgroup also
-// computes tile (mt2, nt) afterwards.  RES = workgroups resident per XCD (32 CUs x workgroups per CU): the size of a super-tile.
-// nP here is the number of block rows the MAP covers, [0, nP): the factor's for a full launch, the leading nR of a row-prefix
-// launch (sweep_tiles) -- pairs are then (nR-1-i, i), the odd middle tile alone as ever.
-template <int RES>
-__device__ __forceinline__ bool sweep_tile_of(int b, int order, int sm, int NT, int nP, int& mt, int& nt, int& mt2) {
-    mt2 = -1;
-    if (order == 1) {
-        // XCD-aware: block b runs on XCD b%8 (observed, speed only).  Give each XCD its own
-        // contiguous slice of candidate tiles so the tiles resident on one XCD walk the
-        // SAME mt (shared T rows in that XCD's L2) over neighbouring nt.
-        const int x = b & 7, q = b >> 3;          // q-th block of XCD x
-        const int per = (NT + 7) / 8;             // candidate tiles per XCD
-        const int lm = q / per, ln = q - lm * per;
-        mt = nP - 1 - lm;
-        nt = x * per + ln;
-        return !(nt >= NT || mt < 0);
-    }
-    if (order == 2 || order == 3) {
-        // XCD-aware 2-D super-tiles: the RES workgroups resident on one XCD form an sm (mt) x SN (nt) patch, so every
-        // T row-panel and every Ks column-panel fetched into that XCD's L2 is used by several tiles.
-        // order 3: PAIRED tiles on the super-tile map: the workgroup computes (nP-1-i, nt) and then (i, nt), so every
-        // workgroup of the launch does the same (nP+1)*128 of K.  Equal durations keep the workgroups
-        // of a super-tile in step for the whole launch: tiles that share a Ks column panel (same nt,
-        // different mt) walk k together instead of drifting apart by their K-extent difference.
-        const int x = b & 7, q = b >> 3;
-        const int SN = RES / sm;                  // super-tile = sm (mt) x SN (nt) = RES workgroups
-        const int per = (NT + 7) / 8;             // candidate tiles per XCD (contiguous slice)
-        const int hper = (per + SN - 1) / SN;     // n-groups per XCD
-        const int s = q / RES, r = q - s * RES;
-        const int G = s / hper, H = s - G * hper;
-        const int i = G * sm + r / SN;
-        const int ln = H * SN + (r - (r / SN) * SN);
-        nt = x * per + ln;
-        mt = nP - 1 - i;
-        if (order == 2) return !(ln >= per || nt >= NT || mt < 0);
-        if (ln >= per || nt >= NT || i > mt) return false;
-        if (i < mt) mt2 = i;
-        return true;
-    }
-    mt = nP - 1 - b / NT;
-    nt = b - (b / NT) * NT;
-    return true;
-}
-
-template <int RES>
-static unsigned sweep_grid(int order, int super_m, int NT, int nP) {
-    const int per = (NT + 7) / 8;
-    if (order == 1) return (unsigned)(8 * per * nP);
-    if (order == 2 || order == 3) {
-        const int SN = RES / super_m;
-        const int hper = (per + SN - 1) / SN;
-        const int rows = (order == 3) ? (nP + 1) / 2 : nP;
-        const int gm = (rows + super_m - 1) / super_m;
-        return (unsigned)(8 * RES * hper * gm);
-    }
-    return (unsigned)(NT * nP);
-}
-
+// The block -> tile maps (sweep_tile_of) and the grid of a launch (sweep_grid): sweep_map.h.
 // The summation order of a tile along k (the SAME in every schedule and every tile map: results stay bit-identical): tiles of the
 // lower half, 2 mt < nP - 1 -- in the paired map exactly the SECOND tile of every pair -- take their 32-row k-steps downwards when
 // the factor has at least 32 block rows.  In the paired map every workgroup of a super-tile then reads the same rows of its Ks
@@ -347,25 +290,38 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm_w(const double* 
     });
 }
 
+// the map of a launch: order 3 in its short form where the option short_map and the launch's size say so
+template <int RES>
+static int sweep_order_of(int order, int short_map, int sm, int NT) {
+    if (order != 3 || short_map == 0) return order;
+    if (short_map < 0 && !sweep_map_is_short<RES>(sm, NT)) return order;
+    return short_map == 2 ? SWEEP_ORDER_SHORT_STRIDED : SWEEP_ORDER_SHORT;
+}
+
 // nR: the block rows [0, nR) the launch covers -- the factor's Np / 128 for the sweep itself, fewer for the row-prefix pass of a
 // selection-only sweep (api.hip: sweep_core, step 4a), which needs rows [0, nR 128) of every Ks panel only.
 void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const double* Ks, int64_t ldk,
                        int64_t cols, const double* a, double* Qp, double* Pp, int64_t ldp,
-                       int tile_order, int super_m, unsigned long long* clk) {
+                       int tile_order, int super_m, unsigned long long* clk, int short_map) {
     const int NT = (int)(cols / TB);
     // bits 0-1: tile map, bits 2-4: k-loop (4 = default: operands by LDS-DMA, k-step 32, two workgroups per CU, the zero rows of
     // T's diagonal block skipped; 3: the same without the skip; 1: the barrier-free wave-private loop; 7: k-step 16, three workgroups per CU; 6, 5, 2: the
     // register-staged schedules of rounds 5, 2, 1 -- all kept as independently scheduled witnesses of the bit-identity test)
-    const int order = tile_order & 3, var = (tile_order >> 2) & 7;
+    // short_map (option "short_map"): map 3 takes its short form (sweep_map.h) -1 where the launch cannot fill the per-XCD patches,
+    // 0 never, 1 always; 2 the strided short form (scripts/probe/sweep_ab.hip only: gpx_set_option admits -1 .. 1)
+    const int order0 = tile_order & 3, var = (tile_order >> 2) & 7;
 #define GPX_SW(K) hipLaunchKernelGGL(K, dim3(nblk), dim3(GEMM_THREADS), 0, s, U, Np, Ks, ldk, NT, nR, a, Qp, Pp, ldp, order, super_m, clk)
 #define GPX_SWL(K) hipLaunchKernelGGL(K, dim3(nblk), dim3(GEMM_THREADS), 0, s, U, Np, Ks, ldk, NT, nR, a, Qp, Pp, ldp, order, super_m, clk, 0)
     if (var == 7) {                // three workgroups per CU, k-step 16
+        const int order = sweep_order_of<96>(order0, short_map, super_m, NT);
         const unsigned nblk = sweep_grid<96>(order, super_m, NT, nR);
         GPX_SWL((k_sweep_trmm_l<16, 3, 1, 2, false>));
     } else if (var == 1) {               // barrier-free: every wave keeps its own operands
+        const int order = sweep_order_of<64>(order0, short_map, super_m, NT);
         const unsigned nblk = sweep_grid<64>(order, super_m, NT, nR);
         GPX_SW(k_sweep_trmm_w);
     } else if (var == 4 || var == 3) {   // two workgroups per CU, k-step 32; 4: with the diagonal block's zero rows skipped
+        const int order = sweep_order_of<64>(order0, short_map, super_m, NT);
         const unsigned nblk = sweep_grid<64>(order, super_m, NT, nR);
 #ifdef GPX_SWEEP_PROBES          // scripts/probe/sweep_ab.hip only: variants that are NOT schedules of the library (profiles/r06_sweep_power_probes.txt)
         const int aux = tile_order >> 5;         // (probe builds only: cache policy of the operand loads; gpx_set_option admits 0)
@@ -385,6 +341,7 @@ void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const
         if (var == 4) GPX_SWL((k_sweep_trmm_l<32, 2, 1, 2, true>));
         else GPX_SWL((k_sweep_trmm_l<32, 2, 1, 2, false>));
     } else {
+        const int order = sweep_order_of<64>(order0, short_map, super_m, NT);
         const unsigned nblk = sweep_grid<64>(order, super_m, NT, nR);
         if (var == 2) GPX_SW(k_sweep_trmm<2>);
         else if (var == 6) GPX_SW(k_sweep_trmm<6>);

@@ -5,6 +5,9 @@
 //   (sc0, nt, sc1, sc0 sc1, sc0 nt), 6 every tile upwards, 7 one launch per generation of 512 workgroups; 1000 / 1001 / 1002: ONE
 //   workgroup per CU on gemm_tile_128_d / _ld / _w<2> (the factorisation's worker loops); 2000 / 2001: the wave-private loop with /
 //   without the diagonal-block skip, every tile upwards.  bash scripts/probe/pmc_fetch.sh adds the L2 -> fabric read bytes.
+//   Suffixes of a variant, in this order: "/S" the launch's short_map (sweep_map.h: 0 never, 1 the short form of map 3, 2 its strided form;
+//   default -1, by size as the library); "c" COLD: a pass over a 1 GiB buffer (larger than the 256 MiB MALL and every L2) before each
+//   timed launch, so that the launch finds neither U nor Ks in a cache (profiles/short_launch_map_ab.md).  Example: 19:8/0c
 #include "../../pybo_amd/csrc/kernels_sweep.hip"
 #include <stdio.h>
 #include <stdlib.h>
@@ -92,17 +95,24 @@ int main(int argc, char** argv) {
     hipLaunchKernelGGL(k_fill, dim3(4096), dim3(256), 0, 0, Ks, (size_t)(cols * Np), 2u, 1.0);
     hipLaunchKernelGGL(k_fill, dim3(64), dim3(256), 0, 0, a, (size_t)Np, 3u, 1.0);
     CK(hipDeviceSynchronize());
+    double* flush = nullptr;         // the cold runs' eviction buffer
+    const size_t nflush = (size_t)1 << 27;
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     std::vector<double> rq, rp;      // the first variant's results: the reference of the others
     for (int v = 4; v < argc; ++v) {
         int to = atoi(argv[v]), sm = 8;
         if (const char* c = strchr(argv[v], ':')) sm = atoi(c + 1);
+        int short_map = -1;
+        if (const char* c = strchr(argv[v], '/')) short_map = atoi(c + 1);
+        const bool cold = argv[v][strlen(argv[v]) - 1] == 'c';
+        if (cold && !flush) CK(hipMalloc(&flush, nflush * 8));
         std::vector<float> ms_all;
         CK(hipMemset(Qp, 0xff, (size_t)nP * cols * 8));
         CK(hipMemset(Pp, 0xff, (size_t)nP * cols * 8));
         double mhz = 0;
         for (int rep = 0; rep < reps + 2; ++rep) {
             CK(hipMemsetAsync(clk, 0, 16, 0));
+            if (cold) hipLaunchKernelGGL(k_fill, dim3(4096), dim3(256), 0, 0, flush, nflush, 7u + (unsigned)rep, 1.0);
             hipEventRecord(e0);
             if (to >= 2000) {
                 const unsigned nblk = sweep_grid<64>(3, sm, (int)(cols / TB), nP);
@@ -118,7 +128,7 @@ int main(int argc, char** argv) {
                 else { CK(hipFuncSetAttribute((const void*)k_lone<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
                     hipLaunchKernelGGL(k_lone<2>, dim3(nblk), dim3(GEMM_THREADS), lb, 0, U, Np, Ks, (int)(cols / TB), a, Qp, Pp, cols, sm); }
             } else
-            launch_sweep_trmm(0, U, Np, nP, Ks, Np, cols, a, Qp, Pp, cols, to, sm, clk);
+            launch_sweep_trmm(0, U, Np, nP, Ks, Np, cols, a, Qp, Pp, cols, to, sm, clk, short_map);
             hipEventRecord(e1);
             CK(hipEventSynchronize(e1));
             CK(hipGetLastError());
@@ -140,8 +150,8 @@ int main(int argc, char** argv) {
             dq = std::max(dq, fabs(hq[i] - rq[i])); sq = std::max(sq, fabs(rq[i]));
             dp = std::max(dp, fabs(hp[i] - rp[i])); sp = std::max(sp, fabs(rp[i]));
         }
-        printf("RESULT tile_order %d super_m %d N %lld cols %lld: min %.3f median %.3f ms  %.2f TFLOP/s  frac %.4f  sclk %.0f MHz  checksum %016llx  maxdiff/scale q %.2e p %.2e\n",
-               to, sm, (long long)N, (long long)cols, ms_all[0], med, (double)N * N * cols / med / 1e9, (double)N * N * cols / med / 1e9 / 78.6, mhz, x, dq / sq, dp / sp);
+        printf("RESULT tile_order %d super_m %d short_map %d %s N %lld cols %lld: min %.3f median %.3f ms  %.2f TFLOP/s  frac %.4f  sclk %.0f MHz  checksum %016llx  maxdiff/scale q %.2e p %.2e\n",
+               to, sm, short_map, cold ? "cold" : "warm", (long long)N, (long long)cols, ms_all[0], med, (double)N * N * cols / med / 1e9, (double)N * N * cols / med / 1e9 / 78.6, mhz, x, dq / sq, dp / sp);
         fflush(stdout);
     }
     return 0;
