@@ -106,8 +106,7 @@ int gpx_set_option(gpx_handle *h, const char *name, int64_t value);
  * and alpha follow on FIRST USE (sweep, predict, mean_at_obs, loglik, append, introspection): the Thompson
  * entry points never read them.  X is (N,d), y is (N,), ell is (d,) on the HOST in both variants. */
 int gpx_fit(gpx_handle *h, const double *X, int64_t N, int64_t d, const double *y, int kernel_id, const double *ell, double rho, double sn2, double bias);
-int gpx_fit_dev(gpx_handle *h, const double *dX, int64_t N, int64_t d, const double *dy,
-                int kernel_id, const double *ell, double rho, double sn2, double bias);
+int gpx_fit_dev(gpx_handle *h, const double *dX, int64_t N, int64_t d, const double *dy, int kernel_id, const double *ell, double rho, double sn2, double bias);
 /* log marginal likelihood of the fitted model, -1/2 a.a - sum log R_ii - N/2 log 2pi: what a
  * hyper-parameter sampler (reggie.MCMC, pybo/bayesopt.py:115) evaluates once per proposal. */
 int gpx_loglik(gpx_handle *h, double *out);
@@ -170,9 +169,8 @@ int gpx_predict_mean(gpx_handle *h, const double *Xc, int64_t M, double *mu, dou
  * s2 (each (M,), host in gpx_sweep / device in gpx_sweep_dev) are optional (NULL to skip). */
 int gpx_sweep(gpx_handle *h, int acq_id, const double *params, int nparams, const double *Xc, int64_t M, int64_t k,
               double *top_val, int64_t *top_idx, double *acq_all, double *mu, double *s2);
-int gpx_sweep_dev(gpx_handle *h, int acq_id, const double *params, int nparams, const double *dXc,
-                  int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *d_acq_all,
-                  double *d_mu, double *d_s2);
+int gpx_sweep_dev(gpx_handle *h, int acq_id, const double *params, int nparams, const double *dXc, int64_t M, int64_t k,
+                  double *top_val, int64_t *top_idx, double *d_acq_all, double *d_mu, double *d_s2);
 
 /* ---- warm BO step: the NEXT iteration's `index(xgrid)` over the SAME grid with the SAME hyper-parameters
  *      [pybo/bayesopt.py:262-269 with a fixed `xgrid=` in pybo/solvers/lbfgs.py:42-50].  The reference pays a full refit and a full
@@ -184,6 +182,11 @@ int gpx_sweep_update(gpx_handle *h, int acq_id, const double *params, int nparam
                      int64_t *top_idx, double *acq_all, double *mu, double *s2);
 int gpx_sweep_update_dev(gpx_handle *h, int acq_id, const double *params, int nparams, int64_t k,
                          double *top_val, int64_t *top_idx, double *d_acq_all, double *d_mu, double *d_s2);
+/* nb greedy picks on the LIVE sweep cache, each conditioned on the ones before it at their posterior mean (mean fixed, variance shrinks).
+ * EI / PI / UCB (GPX_ACQ_MEAN: GPX_EARG).  1 <= nb <= min(64, M).  sel_val, sel_idx (nb) required; sel_s2 (nb) and s2_all (M: the variances
+ * that scored the LAST pick) optional, all host.  Model, cache, queued corrections and a pending announcement are untouched. GPX_ESTATE without a cache. */
+int gpx_sweep_batch(gpx_handle *h, int acq_id, const double *params, int nparams, int64_t nb,
+                    double *sel_val, int64_t *sel_idx, double *sel_s2, double *s2_all);
 /* number of candidates in the live sweep cache (0: none) */
 int64_t gpx_sweep_cache_size(const gpx_handle *h);
 
@@ -192,12 +195,10 @@ int64_t gpx_sweep_cache_size(const gpx_handle *h);
  * (the sqrt(2 rho/n) factor is folded into theta by the caller).  W (S,n,d), b (S,n), theta (S,n)
  * on the host.  For each draw returns the k best candidates: top_val (S,k), top_idx (S,k).
  * vals_all (S,M) optional. */
-int gpx_rff_sweep(gpx_handle *h, const double *W, const double *b, const double *theta, int64_t S,
-                  int64_t n, int64_t d, double bias, const double *Xc, int64_t M, int64_t k,
-                  double *top_val, int64_t *top_idx, double *vals_all);
-int gpx_rff_sweep_dev(gpx_handle *h, const double *W, const double *b, const double *theta,
-                      int64_t S, int64_t n, int64_t d, double bias, const double *dXc, int64_t M,
-                      int64_t k, double *top_val, int64_t *top_idx, double *d_vals_all);
+int gpx_rff_sweep(gpx_handle *h, const double *W, const double *b, const double *theta, int64_t S, int64_t n, int64_t d, double bias,
+                  const double *Xc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *vals_all);
+int gpx_rff_sweep_dev(gpx_handle *h, const double *W, const double *b, const double *theta, int64_t S, int64_t n, int64_t d, double bias,
+                      const double *dXc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *d_vals_all);
 /* value f (M,) and gradient g (M,d) of ONE draw at M points (host buffers): `f(x[None], grad=True)` of the L-BFGS refinement [pybo/solvers/lbfgs.py:56-58] */
 int gpx_rff_grad(gpx_handle *h, const double *W, const double *b, const double *theta, int64_t n,
                  int64_t d, double bias, const double *Xc, int64_t M, double *f, double *g);
@@ -205,8 +206,7 @@ int gpx_rff_grad(gpx_handle *h, const double *W, const double *b, const double *
  * returns A = Phi^T Phi (n,n) and v = Phi^T (y - bias) (n,) in host buffers. */
 int gpx_rff_gram(gpx_handle *h, const double *W, const double *b, int64_t n, double *A, double *v);
 /* the same for S draws in one call: W (S,n,d), b (S,n) -> A (S,n,n), v (S,n) */
-int gpx_rff_gram_batch(gpx_handle *h, const double *W, const double *b, int64_t S, int64_t n, double *A,
-                       double *v);
+int gpx_rff_gram_batch(gpx_handle *h, const double *W, const double *b, int64_t S, int64_t n, double *A, double *v);
 /* the weight posterior of S draws WITHOUT leaving the device (the n x n solve inside sample_f,
  * pybo/policies/simple.py:48): feature Grams as above, then per draw
  *     B = sc^2 A + sn2 I = L L^T,    theta = sc ( B^-1 (sc v) + sqrt(sn2) L^-T z )
@@ -224,12 +224,10 @@ int gpx_rff_posterior(gpx_handle *h, const double *W, const double *b, const dou
  *      s2 = mean_m(s2_m + mu_m^2) - mu^2, value = mu + sqrt(params[0] * s2) (UCB) or mu (MEAN); only these
  *      two can return mu / s2.  The member sweeps never leave the device; sums run in member order and are
  *      divided once by n.  Outputs as in gpx_sweep / gpx_sweep_dev; an EI call for the top-k alone prunes as they do ("prune" of members[0]). */
-int gpx_ensemble_sweep(gpx_handle *const *members, int n_members, int acq_id, const double *params,
-                       int nparams, const double *Xc, int64_t M, int64_t k, double *top_val,
-                       int64_t *top_idx, double *acq_all, double *mu, double *s2);
-int gpx_ensemble_sweep_dev(gpx_handle *const *members, int n_members, int acq_id, const double *params,
-                           int nparams, const double *dXc, int64_t M, int64_t k, double *top_val,
-                           int64_t *top_idx, double *d_acq_all, double *d_mu, double *d_s2);
+int gpx_ensemble_sweep(gpx_handle *const *members, int n_members, int acq_id, const double *params, int nparams, const double *Xc,
+                       int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *acq_all, double *mu, double *s2);
+int gpx_ensemble_sweep_dev(gpx_handle *const *members, int n_members, int acq_id, const double *params, int nparams, const double *dXc,
+                           int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *d_acq_all, double *d_mu, double *d_s2);
 /* per-member posterior moments AND gradients at M points (host buffers), member-major: mu, s2 (n_members, M);
  * dmu, ds2 (n_members, M, d) -- the `f(x, grad=True)` calls of the L-BFGS refinement on the default model
  * [pybo/solvers/lbfgs.py:56-58 over pybo/bayesopt.py:115]; the members' latency-bound kernels run concurrently on
@@ -288,7 +286,8 @@ int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, 
  * [14] its algorithmic fp64 lane operations, S n (d + 20) M per launch [15] fits whose task-graph factorisation gave up and re-ran on
  * the stream schedule [16] the shader clock in MHz the sweep_trmm launches sustained (their workgroups' s_memtime over s_memrealtime
  * ticks) [17] the same for the Thompson sweep kernel [18] inversions whose leading part ran behind the factorisation ("trtri_ahead":
- * for those [2] holds only what was left after the factor was done) [19] bound pass of selection-only sweeps.  Synchronises; returns slots written. */
+ * for those [2] holds only what was left after the factor was done) [19] bound pass of selection-only sweeps [20] batch selection
+ * (gpx_sweep_batch).  Synchronises; returns slots written. */
 int gpx_timers(gpx_handle *h, double *out, int n, int reset);
 /* 1 when the library was built with -DGPX_DIAGNOSTICS (the diagnostic options above are accepted), else 0 */
 int gpx_diagnostics(void);

@@ -78,6 +78,7 @@ SYMBOLS = {
     'gpx_sweep_dev': (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P, _P]),
     'gpx_sweep_update': (C.c_int, [_P, C.c_int, _P, C.c_int, _i64, _P, _P, _P, _P, _P]),
     'gpx_sweep_update_dev': (C.c_int, [_P, C.c_int, _P, C.c_int, _i64, _P, _P, _P, _P, _P]),
+    'gpx_sweep_batch': (C.c_int, [_P, C.c_int, _P, C.c_int, _i64, _P, _P, _P, _P]),
     'gpx_sweep_cache_size': (_i64, [_P]),
     'gpx_rff_sweep': (C.c_int, [_P, _P, _P, _P, _i64, _i64, _i64, _dbl, _P, _i64, _i64, _P, _P, _P]),
     'gpx_rff_sweep_dev': (C.c_int, [_P, _P, _P, _P, _i64, _i64, _i64, _dbl, _P, _i64, _i64, _P, _P, _P]),
@@ -109,7 +110,7 @@ KERNELS = {'se': 0, 'matern5': 1, 'matern3': 2, 'matern1': 3}
 ACQ = {'ei': 0, 'pi': 1, 'ucb': 2, 'mean': 3}
 TIMER_NAMES = ['gram', 'cholesky', 'trtri', 'alpha', 'cross_gram', 'sweep_trmm', 'acq_topk', 'rff',
                'sweep_trmm_launches', 'sweep_trmm_flop', 'copies', 'append', 'rank1', 'rff_sweep', 'rff_sweep_ops',
-               'chol_fallbacks', 'sweep_sclk_mhz', 'rff_sclk_mhz', 'trtri_ahead', 'sweep_bound']
+               'chol_fallbacks', 'sweep_sclk_mhz', 'rff_sclk_mhz', 'trtri_ahead', 'sweep_bound', 'batch']
 TOPK_MAX = 4096
 
 _lib = None
@@ -602,6 +603,19 @@ class Engine(object):
 
     def sweep_cache_size(self):
         return int(self._lib.gpx_sweep_cache_size(self._h))
+
+    def sweep_batch(self, kind, param, nb, want_s2_all=False):
+        """nb greedy picks on the live sweep cache (gpx_sweep_batch), each conditioned on the earlier ones at their posterior
+        mean.  Returns dict(sel_val, sel_idx, sel_s2[, s2_all]); model, cache and a pending announcement are untouched."""
+        aid = ACQ[kind] if isinstance(kind, str) else int(kind)
+        params = _f64([0.0 if param is None else param])
+        n = max(int(nb), 0)
+        out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty(n))
+        if want_s2_all:
+            out['s2_all'] = np.empty(self.sweep_cache_size())
+        self._check(self._lib.gpx_sweep_batch(self._h, aid, _ptr(params), 1, int(nb), _ptr(out['sel_val']), _ptr(out['sel_idx']),
+                                              _ptr(out['sel_s2']), _ptr(out.get('s2_all'))))
+        return out
 
     def sweep_dev(self, acq, param, dXc_ptr, M, k, d_acq=None, d_mu=None, d_s2=None):
         aid = ACQ[acq] if isinstance(acq, str) else int(acq)

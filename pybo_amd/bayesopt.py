@@ -23,6 +23,8 @@ Deliberate differences:
     it in `pybo_amd.models.MCMC(n=10, burn=100)` like the reference (:115) -- but the sampler is this
     build's own (random-direction slice sampling, models/mcmc.py): reggie's is absent and unpinned;
   * checkpoints are binary pickles written atomically (the reference opens the file in text mode);
+  * `solve_bayesopt(..., nbatch=q, batch_grid=)` evaluates q proposed grid points per iteration (pybo_amd/batch.py); nbatch = 1
+    is the reference's loop;
   * a malformed component tuple raises a ValueError with a working message (the reference's '{:r}' format at
     :138 is itself an error).
 """
@@ -336,8 +338,24 @@ def _bo_step(model, trace, objective, bounds, policy, solver, recommender):
     return x, y, xbest
 
 
+def _bo_batch_step(model, trace, objective, bounds, policy, recommender, nb, xgrid, rng):
+    """One batch iteration: propose nb grid points (pybo_amd/batch.py), evaluate them in order, absorb them in ONE add_data,
+    recommend once.  `xbest` is appended once per evaluated point, so the trace keeps counting evaluations."""
+    from .batch import _propose
+    Xq, _, _ = _propose(model, bounds, trace.x, nb, policy, xgrid, 10000, rng)
+    Yq = [objective(x) for x in Xq]
+    model.add_data(Xq, Yq)
+    xbest = recommender(model, bounds, trace.x)     # (trace.x does not contain the batch yet, as in _bo_step)
+    for x, y in zip(Xq, Yq):
+        trace.x.append(x)
+        trace.y.append(y)
+        trace.xbest.append(xbest)
+    return Xq, Yq, xbest
+
+
 def solve_bayesopt(objective, bounds, model=None, niter=100, policy='ei', solver='lbfgs',
-                   recommender='latent', ninit=None, verbose=False, log=None, rng=None, spmd=None):
+                   recommender='latent', ninit=None, verbose=False, log=None, rng=None, spmd=None, nbatch=1,
+                   batch_grid=None):
     """
     Maximise `objective` over the box `bounds` ((d,2) array-like) by Bayesian optimisation.
 
@@ -353,7 +371,19 @@ def solve_bayesopt(objective, bounds, model=None, niter=100, policy='ei', solver
     query point and the value (the reference evaluates once per iteration, bayesopt.py:268), `rng=None` is replaced by
     one broadcast seed, the solver's grid stage is sharded over the ranks (pybo_amd.dist.ShardedIndex), and rank 0
     writes the checkpoints: the replicated models stay bitwise equal.
+
+    `nbatch` (not in the reference): 1 (default) -- the loop above, one point per iteration.  nbatch > 1: every iteration
+    proposes min(nbatch, evaluations left) GRID points at once (`pybo_amd.propose_batch`: greedy picks, each conditioned on the
+    earlier ones at their posterior mean; Thompson: independent draws), evaluates the objective on them in order, absorbs them
+    in one `model.add_data(Xq, Yq)` and recommends once.  `niter` still counts evaluations and a checkpoint still resumes.
+    The points are candidates of `batch_grid` ((M, d) array or DeviceGrid; default: a fresh `init_uniform(bounds, 10000, rng)`
+    per iteration) -- the `solver` plays no part.  Not together with `spmd`.
     """
+    nbatch = int(nbatch)
+    if nbatch < 1:
+        raise ValueError('nbatch must be at least 1')
+    if nbatch > 1 and not (spmd is None or spmd is False):
+        raise ValueError('nbatch > 1 cannot be combined with spmd')
     on, group = _spmd_group(spmd)
     saved = dict(_SPMD)
     if on:
@@ -363,12 +393,13 @@ def solve_bayesopt(objective, bounds, model=None, niter=100, policy='ei', solver
         _SPMD.update(on=True, group=group)
     try:
         return _solve_bayesopt(objective, bounds, model, niter, policy, solver, recommender, ninit, verbose, log, rng,
-                               spmd if on else None)
+                               spmd if on else None, nbatch, batch_grid)
     finally:
         _SPMD.update(saved)
 
 
-def _solve_bayesopt(objective, bounds, model, niter, policy, solver, recommender, ninit, verbose, log, rng, spmd):
+def _solve_bayesopt(objective, bounds, model, niter, policy, solver, recommender, ninit, verbose, log, rng, spmd, nbatch=1,
+                    batch_grid=None):
     rng = rstate(rng)
     bounds = np.array(bounds, dtype=float, ndmin=2)
     policy = get_component(policy, policies, rng)
@@ -393,6 +424,14 @@ def _solve_bayesopt(objective, bounds, model, niter, policy, solver, recommender
         safe_dump(model, trace, filename=log)
 
     xbest = trace.xbest[-1] if trace.xbest else None
+    while nbatch > 1 and len(trace.xbest) < niter:
+        i = len(trace.xbest)
+        Xq, Yq, xbest = _bo_batch_step(model, trace, objective, bounds, policy, recommender, min(nbatch, niter - i), batch_grid,
+                                       rng)
+        safe_dump(model, trace, filename=log)
+        if verbose:
+            for k, (x, y) in enumerate(zip(Xq, Yq)):
+                _report(i + k, x, y, xbest)
     for i in range(len(trace.xbest), niter):
         x, y, xbest = _bo_step(model, trace, objective, bounds, policy, solver, recommender)
         safe_dump(model, trace, filename=log)

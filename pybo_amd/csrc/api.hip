@@ -230,7 +230,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // build, tile_order default by size (7 below 32 block rows, 19 from there on).
 // 610: option prune (selection-only sweeps), timers slot 19.  620: the ensemble sweep prunes too (the lead's option prune),
 // gpx_ensemble_prune_report.  630: the second bound of selection-only sweeps (option prune_rows, gpx_prune_rows, gpx_prune_report's scalars 16 .. 19).
-extern "C" int gpx_version(void) { return 630; }
+// 640: gpx_sweep_batch, timers slot 20.
+extern "C" int gpx_version(void) { return 640; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -339,7 +340,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -1406,6 +1407,81 @@ extern "C" int gpx_sweep_update(gpx_handle* h, int acq_id, const double* params,
         return staged_sweep(h, nullptr, h->cache_M, false, acq_all, mu, s2, [&](double*, double* dacq, double* dmu, double* ds2) {
             return sweep_update_core(h, acq_id, params, nparams, k, top_val, top_idx, dacq, dmu, ds2);
         });
+    });
+}
+
+// Batch proposals: nb greedy picks on the live cache, each conditioned on the earlier ones at their posterior mean (kernels_batch.hip).
+// Per extra pick: launch_append_prepare (k(X, x), r = T k, w = U r -- its scalars and flag land in this call's own words and are
+// not read: d comes from the CONDITIONED variance), the weight row [w, -1], one rank-1 pass over the cached candidates, one fold +
+// scoring pass.  Everything is enqueued on the handle's stream with ONE synchronisation at the end; the picked index never
+// leaves the device, so no launch depends on it.  Scratch (h->dbsel, doubles):
+//   [x xpad][xs xpad][ks ld][g ld][r ld][tu ld][row ld][small 384][partv 1024][parti 1024][q' M][s2 M][taken ceil(M / 8)][V nb M]
+//   small: +0 pscal {1/d, 0}  +8 the prepare's scalars (unused)  +24 scal {d, 1/d, 0, d^2}  +40 its flag word  +64 cross (64)
+//          +128 sel_val (64)  +192 sel_s2 (64)  +256 sel_idx (64 int64)
+extern "C" int gpx_sweep_batch(gpx_handle* h, int acq_id, const double* params, int nparams, int64_t nb, double* sel_val,
+                               int64_t* sel_idx, double* sel_s2, double* s2_all) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        int rc;
+        if ((rc = check_acq(h, "sweep_batch", acq_id, params, nparams))) return rc;
+        if (acq_id == GPX_ACQ_MEAN)
+            return fail(h, GPX_EARG, "sweep_batch: the posterior mean does not change under hallucinated observations (EI, PI or UCB)");
+        if (nb < 1 || nb > 64) return fail(h, GPX_EARG, "sweep_batch: nb must be in [1, 64]");
+        if (!sel_val || !sel_idx) return fail(h, GPX_EARG, "sweep_batch: NULL sel_val / sel_idx output");
+        if (!h->fitted || !h->cache_valid) return fail(h, GPX_ESTATE, "sweep_batch: no live sweep cache (sweep with option sweep_cache = 1 first)");
+        const int64_t M = h->cache_M, d = h->d;
+        if (nb > M) return fail(h, GPX_EARG, "sweep_batch: nb exceeds the number of cached candidates");
+        HIPCHK(h, hipSetDevice(h->device));
+        if ((rc = ensure_inverse(h))) return rc;
+        if ((rc = flush_pending(h))) return rc;                  // queued appends belong in the sums the picks are scored with
+        const int64_t xpad = (h->cap_d + 63) / 64 * 64, ld = h->cap_np + NB;      // N + 1 <= ld whatever the padding holds
+        const int64_t ntaken = (M + 7) / 8;
+        const int64_t need = 2 * xpad + 5 * ld + 384 + 2048 + 2 * M + ntaken + nb * M;
+        if ((rc = ensure(h, h->dbsel, h->cap_bsel, need))) return rc;
+        double* x = h->dbsel;
+        double* xs = x + xpad;
+        double* ks = xs + xpad;
+        double* g = ks + ld;
+        double* r = g + ld;
+        double* tu = r + ld;
+        double* row = tu + ld;
+        double* small = row + ld;
+        double *pscal = small, *scal_prep = small + 8, *scal = small + 24, *cross = small + 64;
+        int* flag = reinterpret_cast<int*>(small + 40);
+        double *dsel_val = small + 128, *dsel_s2 = small + 192;
+        int64_t* dsel_idx = reinterpret_cast<int64_t*>(small + 256);
+        double* partv = small + 384;
+        int64_t* parti = reinterpret_cast<int64_t*>(partv + 1024);
+        double* qp = partv + 2048;
+        double* ds2 = qp + M;
+        unsigned char* taken = reinterpret_cast<unsigned char*>(ds2 + M);
+        double* V = ds2 + M + ntaken;
+        const double p0 = params[0];
+        hipStream_t s = h->stream;
+        {
+            Span sp(h, T_BATCH);
+            HIPCHK(h, hipMemsetAsync(taken, 0, (size_t)ntaken * 8, s));
+            HIPCHK(h, hipMemsetAsync(flag, 0, sizeof(int), s));
+            for (int j = 0; j < (int)nb; ++j) {
+                double* s2_out = (s2_all && j == (int)nb - 1) ? ds2 : nullptr;    // the variances that score the LAST pick
+                launch_batch_score(s, j - 1, M, h->dcq, h->dcp, qp, V, cross, scal, taken, h->rho, h->bias, acq_id, p0,
+                                   s2_out, partv, parti);
+                launch_batch_pick(s, j, M, (int)d, partv, parti, h->dcZ, h->dinvell, qp, V, h->rho, h->sn2, x, xs, scal,
+                                  cross, dsel_val, dsel_idx, dsel_s2, taken);
+                if (j == (int)nb - 1) break;
+                launch_append_prepare(h, s, x, ks, g, r, tu, 0.0, scal_prep, flag);
+                launch_pend_store(s, tu, h->N, ld, scal, row, pscal);
+                launch_sweep_rank1_v(s, h->dXs, h->N + 1, (int)d, row, ld, pscal, h->dcZ, M, h->dinvell, h->kernel_id, h->rho,
+                                     xs, V + (int64_t)j * M);
+            }
+            HIPCHK(h, hipGetLastError());
+        }
+        HIPCHK(h, hipMemcpyAsync(sel_val, dsel_val, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(sel_idx, dsel_idx, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        if (sel_s2) HIPCHK(h, hipMemcpyAsync(sel_s2, dsel_s2, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        if (s2_all) HIPCHK(h, hipMemcpyAsync(s2_all, ds2, (size_t)M * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        return GPX_OK;
     });
 }
 

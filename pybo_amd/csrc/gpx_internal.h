@@ -20,7 +20,7 @@ constexpr int PEND_MAX = 8;   // appended observations per pass of the sweep-cac
 
 enum Timer {
     T_GRAM = 0, T_CHOL, T_TRTRI, T_ALPHA, T_XGRAM, T_TRMM, T_ACQ, T_RFF, T_NLAUNCH, T_FLOP, T_COPY, T_APPEND,
-    T_RANK1, T_RFFSWEEP, T_RFFOPS, T_TGFALL, T_SCLK, T_RFFCLK, T_AHEAD, T_BOUND, T_COUNT
+    T_RANK1, T_RFFSWEEP, T_RFFOPS, T_TGFALL, T_SCLK, T_RFFCLK, T_AHEAD, T_BOUND, T_BATCH, T_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int slot; };
@@ -211,6 +211,10 @@ struct gpx_handle {
     int64_t cap_spec = 0, spec_ld = 0, spec_M = 0;
     hipEvent_t ev_spec_go = nullptr, ev_spec_done = nullptr;
 
+    // batch proposals (gpx_sweep_batch): scratch of its own, laid out in api.hip -- nothing the append / announcement paths own
+    double* dbsel = nullptr;
+    int64_t cap_bsel = 0;
+
     double* dbatch = nullptr;    // gpx_loglik_batch: Gram / factor / scaled inputs / a of the batch (one allocation)
     int64_t cap_batch = 0;
     double* dhyper = nullptr;    // gpx_loglik_grad: the tiles' partial sums [tiles][d + 2], then [L, d + 3 components] (on first use)
@@ -333,6 +337,17 @@ struct SpecBuf { double *x, *xs, *ks, *g, *r, *tu, *row, *pscal, *scal, *v; };
 SpecBuf spec_layout(const gpx_handle* h);
 int rff_grad_host(gpx_handle* h, const double* W, const double* b, const double* theta, int64_t n, int64_t d,
                   double bias, const double* Xc, int64_t M, double* f, double* g);
+
+// launchers (kernels_batch.hip): one scoring pass (j < 0: round 0; else fold row j of V first) with per-block argmax partials
+// (batch_blocks(M) of them), and the one-workgroup pick that merges them and leaves everything round j + 1 needs on the device
+int batch_blocks(int64_t M);
+void launch_batch_score(hipStream_t s, int j, int64_t M, const double* cq, const double* cp, double* qp, double* V,
+                        const double* cross, const double* scal, const unsigned char* taken, double rho, double bias,
+                        int acq_id, double p0, double* s2_out, double* partv, int64_t* parti);
+void launch_batch_pick(hipStream_t s, int j, int64_t M, int d, const double* partv, const int64_t* parti, const double* Z,
+                       const double* invell, const double* qp, const double* V, double rho, double sn2, double* x,
+                       double* xs, double* scal, double* cross, double* sel_val, int64_t* sel_idx, double* sel_s2,
+                       unsigned char* taken);
 
 // launchers (kernels_rff.hip)
 extern int g_rff_variant;

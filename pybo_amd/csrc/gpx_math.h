@@ -1,5 +1,6 @@
 // gpx_math.h -- the covariance functions, shared by every kernel that evaluates one (Gram build, cross-Gram,
 // gradient path) so that K, K* and dK*/dx come from the same arithmetic.
+// Also the acquisition value from the posterior moments (acq_value): the sweep's k_acq and the batch scoring of kernels_batch.hip share it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -123,6 +124,33 @@ __device__ __forceinline__ void kern_and_grad(int kid, double r2, double rho, do
             // treated as sitting on the observation (tests/test_gpu_devmath.py pins both sides of that cutoff)
             g = (r > 0.0) ? -0.5 * k / r : 0.0;
         }
+    }
+}
+
+// ---- acquisition values ----------------------------------------------------------------------------------------
+__device__ __forceinline__ double norm_cdf(double z) { return 0.5 * erfc(-z * 0.70710678118654752440); }
+__device__ __forceinline__ double norm_pdf(double z) {
+    return 0.39894228040143267794 * exp(-0.5 * z * z);
+}
+
+// The acquisition value from the posterior moments: the ONE place this arithmetic lives.  k_acq calls it with a candidate's
+// exact moments, the bound pass of a selection-only sweep (k_prune_ub) with an upper bound of the mean and s2 = rho.
+__device__ __forceinline__ double acq_value(int acq_id, double mu, double s2, double p0) {
+    switch (acq_id) {
+        case GPX_ACQ_EI: {
+            const double s = sqrt(s2);
+            const double dlt = mu - p0;
+            const double z = dlt / s;
+            return dlt * norm_cdf(z) + s * norm_pdf(z);
+        }
+        case GPX_ACQ_PI: {
+            const double z = (mu - p0) / sqrt(s2);
+            return norm_cdf(z);
+        }
+        case GPX_ACQ_UCB:
+            return mu + sqrt(p0 * s2);
+        default:
+            return mu;
     }
 }
 

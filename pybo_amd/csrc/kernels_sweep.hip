@@ -354,31 +354,7 @@ void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const
 // ------------------------------------------------------------------------------------------------
 // acquisition values from the reduced partials (one thread per candidate; coalesced over n)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double norm_cdf(double z) { return 0.5 * erfc(-z * 0.70710678118654752440); }
-__device__ __forceinline__ double norm_pdf(double z) {
-    return 0.39894228040143267794 * exp(-0.5 * z * z);
-}
-
-// The acquisition value from the posterior moments: the ONE place this arithmetic lives.  k_acq calls it with a candidate's
-// exact moments, the bound pass of a selection-only sweep (k_prune_ub) with an upper bound of the mean and s2 = rho.
-__device__ __forceinline__ double acq_value(int acq_id, double mu, double s2, double p0) {
-    switch (acq_id) {
-        case GPX_ACQ_EI: {
-            const double s = sqrt(s2);
-            const double dlt = mu - p0;
-            const double z = dlt / s;
-            return dlt * norm_cdf(z) + s * norm_pdf(z);
-        }
-        case GPX_ACQ_PI: {
-            const double z = (mu - p0) / sqrt(s2);
-            return norm_cdf(z);
-        }
-        case GPX_ACQ_UCB:
-            return mu + sqrt(p0 * s2);
-        default:
-            return mu;
-    }
-}
+// (norm_cdf, norm_pdf and acq_value, the ONE place the acquisition arithmetic lives: gpx_math.h -- kernels_batch.hip scores with them too)
 
 // nrb > 0: Qp/Pp are per-row-block partials (nrb, ldp) of this chunk, reduced here in block order.
 // nrb = 0: Qp/Pp are the already reduced per-candidate sums of the whole grid (the sweep cache), m0 = 0.

@@ -13,7 +13,8 @@ Acquisition policies EI / PI / UCB / Thompson with pybo's signatures
 New: when the model is the device-backed `pybo_amd.models.GP`, the returned index also carries
 `index.topk(xgrid, k)` -- the whole-grid evaluation + top-k done on the GPU in one call -- which
 `pybo_amd.solvers.solve_lbfgs` uses instead of `argsort(f(xgrid))` (pybo/solvers/lbfgs.py:50-51).
-Any other model (e.g. a test stub) gets plain closures, exactly as in the reference.
+Any other model (e.g. a test stub) gets plain closures, exactly as in the reference.  Every EI / PI / UCB index also
+carries `index.acq = (kind, param)` and, for models with `acq_batch`, `index.batch(xgrid, nb)` (pybo_amd/batch.py).
 """
 import numpy as np
 
@@ -21,6 +22,10 @@ __all__ = ['EI', 'PI', 'UCB', 'Thompson']
 
 
 def _attach_topk(index, model, kind, param):
+    index.acq = (kind, param)              # the frozen target / beta: what a batch proposal scores every round with
+    batch = getattr(model, 'acq_batch', None)
+    if batch is not None:                  # device models: nb greedy picks on the swept grid (pybo_amd.propose_batch)
+        index.batch = lambda xgrid, nb: batch(kind, param, xgrid, nb)
     fast = getattr(model, 'acq_topk', None)
     if fast is not None:
         index.topk = lambda xgrid, k: fast(kind, param, xgrid, k)
