@@ -107,8 +107,7 @@ int gpx_set_option(gpx_handle *h, const char *name, int64_t value);
  * entry points never read them.  X is (N,d), y is (N,), ell is (d,) on the HOST in both variants. */
 int gpx_fit(gpx_handle *h, const double *X, int64_t N, int64_t d, const double *y, int kernel_id, const double *ell, double rho, double sn2, double bias);
 int gpx_fit_dev(gpx_handle *h, const double *dX, int64_t N, int64_t d, const double *dy, int kernel_id, const double *ell, double rho, double sn2, double bias);
-/* log marginal likelihood of the fitted model, -1/2 a.a - sum log R_ii - N/2 log 2pi: what a
- * hyper-parameter sampler (reggie.MCMC, pybo/bayesopt.py:115) evaluates once per proposal. */
+/* log marginal likelihood of the fit, -1/2 a.a - sum log R_ii - N/2 log 2pi: what reggie.MCMC [pybo/bayesopt.py:115] evaluates once per proposal */
 int gpx_loglik(gpx_handle *h, double *out);
 /* The same for B hyper-parameter vectors at once on the handle's RESIDENT data, without touching the handle's own fit: hypers
  * (B, d + 3) row-major [sn2, rho, ell_1..d, bias] (the argument order of reggie.make_gp, pybo/bayesopt.py:105), out (B,); -inf
@@ -145,22 +144,26 @@ int gpx_fit_stage(gpx_handle *h, const double *X, int64_t N, int64_t d, const do
 
 /* posterior (latent) mean at the N observed points, closed form y - sn2*alpha = model.predict(X_obs)[0] [pybo/policies/simple.py:21,35] */
 int gpx_mean_at_obs(gpx_handle *h, double *mu_host, double *mu_max);
-/* posterior (latent) variance at the N observed points, closed form sn2 - sn2^2 [K^-1]_ii with
- * [K^-1]_ii = sum_m U[i][m]^2 (one HBM-read pass over U = R^-1; a sweep over X_obs is an N x N x N product).
- * = model.predict(X_obs)[1]                     [pybo/policies/simple.py:21,35; pybo/recommenders.py:34] */
+/* posterior (latent) variance at the N observed points, closed form sn2 - sn2^2 [K^-1]_ii with [K^-1]_ii = sum_m U[i][m]^2 (one HBM-read pass over
+ * U = R^-1; a sweep over X_obs is an N x N x N product) = model.predict(X_obs)[1] [pybo/policies/simple.py:21,35; pybo/recommenders.py:34] */
 int gpx_var_at_obs(gpx_handle *h, double *s2_host);
-/* rows (a multiple of 128) the handle's factor buffers are allocated for: 4 matrices of capacity^2 doubles stay
- * on the device until gpx_destroy -- what a pool of handles should be sized by. */
+/* rows (a multiple of 128) the factor buffers are allocated for: 4 matrices of capacity^2 doubles stay on the device until gpx_destroy (size pools by it) */
 int64_t gpx_capacity(const gpx_handle *h);
 
 /* ---- posterior moments = model.predict(X, grad) [pybo/policies/simple.py:64] ------------- */
 /* Xc (M,d) -> mu (M,), s2 (M,) latent variance; dmu, ds2 (M,d) optional (NULL to skip).  With gradients a single point
  * (M = 1) is answered in the one-pass form, batches in the two-pass form: option "grad_form" above. */
 int gpx_predict(gpx_handle *h, const double *Xc, int64_t M, double *mu, double *s2, double *dmu, double *ds2);
-/* The mean alone, mu (M,) and optionally dmu (M,d) (NULL to skip): mu = bias + k(x, X).alpha reads neither the
- * factor nor its inverse -- what the latent recommender maximises, model.predict(X, True)[0::2]
- * [pybo/recommenders.py:17-24], without the two triangular passes per point the variance costs. */
+/* The mean alone, mu (M,) and optionally dmu (M,d) (NULL to skip): mu = bias + k(x, X).alpha reads neither the factor nor its inverse -- what the latent
+ * recommender maximises, model.predict(X, True)[0::2] [pybo/recommenders.py:17-24], without the two triangular passes per point the variance costs. */
 int gpx_predict_mean(gpx_handle *h, const double *Xc, int64_t M, double *mu, double *dmu);
+/* The JOINT latent posterior at M points, 1 <= M <= 4096, all buffers on the host -- the reference's demos call model.sample(X, ...).  mu (M,)
+ * optional; cov (M,M) row-major, the FULL matrix k(Z,Z) - V^T V with V = T k(X,Z): raw (no clamp on the diagonal), symmetric bit for bit.  Both
+ * calls: one host synchronisation; the fit, a live sweep cache, queued corrections and a pending gpx_append_begin are left as they are. */
+int gpx_predict_cov(gpx_handle *h, const double *Xc, int64_t M, double *mu, double *cov);
+/* S joint draws from the caller's standard normals z (S,M): out (S,M), out[s] = mu + R^T z[s], R^T R = cov + (noisy ? sn2 : 0) I + jitter I (R upper;
+ * jitter finite, >= 0).  A draw's bits do not depend on S.  GPX_ENOTPD (out undefined): gpx_last_error names the pivot; gpx_fail_pivot still describes fits. */
+int gpx_sample_joint(gpx_handle *h, const double *Xc, int64_t M, const double *z, int64_t S, int noisy, double jitter, double *out);
 
 /* ---- acquisition sweep + top-k = the batched index call and argsort of the solver
  *      finit = f(xgrid); idx = argsort(finit)[::-1]       [pybo/solvers/lbfgs.py:50-51] ---- */
@@ -202,8 +205,7 @@ int gpx_rff_sweep_dev(gpx_handle *h, const double *W, const double *b, const dou
 /* value f (M,) and gradient g (M,d) of ONE draw at M points (host buffers): `f(x[None], grad=True)` of the L-BFGS refinement [pybo/solvers/lbfgs.py:56-58] */
 int gpx_rff_grad(gpx_handle *h, const double *W, const double *b, const double *theta, int64_t n,
                  int64_t d, double bias, const double *Xc, int64_t M, double *f, double *g);
-/* feature Gram for the weight posterior: Phi = cos(X_obs W^T + b) (N,n) on the device's X_obs;
- * returns A = Phi^T Phi (n,n) and v = Phi^T (y - bias) (n,) in host buffers. */
+/* feature Gram for the weight posterior: Phi = cos(X_obs W^T + b) (N,n) on the device's X_obs; host outputs A = Phi^T Phi (n,n), v = Phi^T (y - bias) (n,) */
 int gpx_rff_gram(gpx_handle *h, const double *W, const double *b, int64_t n, double *A, double *v);
 /* the same for S draws in one call: W (S,n,d), b (S,n) -> A (S,n,n), v (S,n) */
 int gpx_rff_gram_batch(gpx_handle *h, const double *W, const double *b, int64_t S, int64_t n, double *A, double *v);
@@ -214,8 +216,7 @@ int gpx_rff_gram_batch(gpx_handle *h, const double *W, const double *b, int64_t 
  * theta (S,n) comes back ready for gpx_rff_sweep* / gpx_rff_grad.  n <= 127: all S draws in one launch chain (the n x n
  * posterior of a draw lives in LDS); 128 <= n <= 4096: per draw the blocked Cholesky kernels of the fit + two vector
  * substitutions (`n` is a free keyword of the reference's sample_f, pybo/policies/simple.py:44).  GPX_ENOTPD if a B is not PD. */
-int gpx_rff_posterior(gpx_handle *h, const double *W, const double *b, const double *z, int64_t S, int64_t n,
-                      double sc, double *theta);
+int gpx_rff_posterior(gpx_handle *h, const double *W, const double *b, const double *z, int64_t S, int64_t n, double sc, double *theta);
 
 /* ---- hyper-parameter ensemble = pybo's DEFAULT model, reggie.MCMC(gp, n=10)
  *      [pybo/bayesopt.py:115]: every index is the average over the n member GPs.  `members` are fitted
@@ -233,8 +234,7 @@ int gpx_ensemble_sweep_dev(gpx_handle *const *members, int n_members, int acq_id
  * [pybo/solvers/lbfgs.py:56-58 over pybo/bayesopt.py:115]; the members' latency-bound kernels run concurrently on
  * their own streams (one call instead of n_members gpx_predict calls) and the caller forms the average it needs
  * (mixture moments for UCB / mean, the mean of the members' EI / PI and their gradients). */
-int gpx_ensemble_predict(gpx_handle *const *members, int n_members, const double *Xc, int64_t M, double *mu,
-                         double *s2, double *dmu, double *ds2);
+int gpx_ensemble_predict(gpx_handle *const *members, int n_members, const double *Xc, int64_t M, double *mu, double *s2, double *dmu, double *ds2);
 
 /* ---- candidate grid generated and kept in HBM = the solver's grid
  *      xgrid = init_uniform(bounds, ngrid, rng)   [pybo/solvers/lbfgs.py:45; pybo/inits/methods.py:24-38]
@@ -276,8 +276,7 @@ const char *gpx_comm_last_error(void);
  *          = the global argsort(finit)[::-1][:k] of pybo/solvers/lbfgs.py:51 over the sharded grid.
  *   k = 0: no merge; out_val / out_idx receive all nranks*n pairs in rank order (batch-BO: one recommendation
  *          per Thompson draw, draws sharded over ranks). */
-int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, double *out_val,
-                       int64_t *out_idx);
+int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, double *out_val, int64_t *out_idx);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* Stage timers in milliseconds accumulated since the last reset (HIP events on the handle's stream): [0] gram [1] cholesky
@@ -287,7 +286,7 @@ int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, 
  * the stream schedule [16] the shader clock in MHz the sweep_trmm launches sustained (their workgroups' s_memtime over s_memrealtime
  * ticks) [17] the same for the Thompson sweep kernel [18] inversions whose leading part ran behind the factorisation ("trtri_ahead":
  * for those [2] holds only what was left after the factor was done) [19] bound pass of selection-only sweeps [20] batch selection
- * (gpx_sweep_batch).  Synchronises; returns slots written. */
+ * (gpx_sweep_batch) [21] joint posterior (gpx_predict_cov / gpx_sample_joint: everything between their copies).  Synchronises; returns slots written. */
 int gpx_timers(gpx_handle *h, double *out, int n, int reset);
 /* 1 when the library was built with -DGPX_DIAGNOSTICS (the diagnostic options above are accepted), else 0 */
 int gpx_diagnostics(void);

@@ -74,6 +74,8 @@ SYMBOLS = {
     'gpx_capacity': (_i64, [_P]),
     'gpx_predict': (C.c_int, [_P, _P, _i64, _P, _P, _P, _P]),
     'gpx_predict_mean': (C.c_int, [_P, _P, _i64, _P, _P]),
+    'gpx_predict_cov': (C.c_int, [_P, _P, _i64, _P, _P]),
+    'gpx_sample_joint': (C.c_int, [_P, _P, _i64, _P, _i64, C.c_int, _dbl, _P]),
     'gpx_sweep': (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P, _P]),
     'gpx_sweep_dev': (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P, _P]),
     'gpx_sweep_update': (C.c_int, [_P, C.c_int, _P, C.c_int, _i64, _P, _P, _P, _P, _P]),
@@ -110,8 +112,9 @@ KERNELS = {'se': 0, 'matern5': 1, 'matern3': 2, 'matern1': 3}
 ACQ = {'ei': 0, 'pi': 1, 'ucb': 2, 'mean': 3}
 TIMER_NAMES = ['gram', 'cholesky', 'trtri', 'alpha', 'cross_gram', 'sweep_trmm', 'acq_topk', 'rff',
                'sweep_trmm_launches', 'sweep_trmm_flop', 'copies', 'append', 'rank1', 'rff_sweep', 'rff_sweep_ops',
-               'chol_fallbacks', 'sweep_sclk_mhz', 'rff_sclk_mhz', 'trtri_ahead', 'sweep_bound', 'batch']
+               'chol_fallbacks', 'sweep_sclk_mhz', 'rff_sclk_mhz', 'trtri_ahead', 'sweep_bound', 'batch', 'joint']
 TOPK_MAX = 4096
+JOINT_MAX = 4096     # points of a joint posterior (gpx_predict_cov / gpx_sample_joint)
 
 _lib = None
 
@@ -569,6 +572,26 @@ class Engine(object):
         dmu = np.empty((M, self.d)) if grad else None
         self._check(self._lib.gpx_predict_mean(self._h, _ptr(Xc), M, _ptr(mu), _ptr(dmu) if grad else None))
         return (mu, dmu) if grad else mu
+
+    def predict_cov(self, Xc):
+        """Joint latent posterior at the rows of Xc (at most JOINT_MAX): (mu (M,), cov (M, M)), cov = k(Z, Z) - V^T V raw and symmetric
+        bit for bit (gpx_predict_cov)."""
+        Xc = _f64(Xc).reshape(-1, self.d)
+        M = len(Xc)
+        mu = np.empty(M)
+        cov = np.empty((M, M))
+        self._check(self._lib.gpx_predict_cov(self._h, _ptr(Xc), M, _ptr(mu), _ptr(cov)))
+        return mu, cov
+
+    def sample_joint(self, Xc, z, noisy=False, jitter=0.0):
+        """Joint draws at the rows of Xc from the standard normals z (S, M): out[s] = mu + R^T z[s] with R^T R = cov + (noisy ? sn2 : 0) I
+        + jitter I, factored on the device (gpx_sample_joint); LinAlgError when that matrix is not positive definite."""
+        Xc = _f64(Xc).reshape(-1, self.d)
+        M = len(Xc)
+        z = _f64(z).reshape(-1, M)
+        out = np.empty(z.shape)
+        self._check(self._lib.gpx_sample_joint(self._h, _ptr(Xc), M, _ptr(z), len(z), int(bool(noisy)), float(jitter), _ptr(out)))
+        return out
 
     def sweep(self, acq, param, Xc, k=0, want_all=True, want_moments=False):
         """Host-buffer sweep.  Returns dict(top_val, top_idx, acq, mu, s2)."""

@@ -340,7 +340,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -1504,6 +1504,104 @@ extern "C" int gpx_predict_mean(gpx_handle* h, const double* Xc, int64_t M, doub
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
         return gpx::predict_mean_host(h, Xc, M, mu, dmu);
+    });
+}
+
+// ---- joint posterior at a point set (kernels_cov.hip): full covariance, exact draws -------------------------------------
+// The chain of both entry points: Ks = k(X, Z) by the sweep's own cross-Gram kernel (into dKs), V = T Ks STORED panel-major,
+// mu = bias + V^T a, Kss = k(Z, Z) by the cross-Gram kernel on the scaled points, C = Kss - V^T V; for draws B = C + c I,
+// B = R^T R by launch_cholesky_small under a flag word of its own (dflag[10]), out = mu + z R.  One stream, one synchronisation.
+// Reads the fit only: no flush of queued corrections, the sweep cache, an announcement and their buffers are not touched.
+// Scratch (h->djoint, doubles): [X M d (padded to 32)][Zs Mp d][mu Mp][Pp nP Mp][V Np Mp][Kss Mp Mp][C Mp Mp] + draws: [B Mp Mp][R Mp Mp][z S M][out S M]
+static const int64_t JOINT_MAX_M = 4096;
+
+static int joint_core(gpx_handle* h, const char* what, const double* Xc, int64_t M, const double* z, int64_t S, int noisy,
+                      double jitter, double* mu, double* cov, double* out) {
+    char msg[256];
+    const bool draw = out != nullptr;
+    if (!h->fitted) {
+        snprintf(msg, sizeof msg, "%s: model is not fitted", what);
+        return fail(h, GPX_ESTATE, msg);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure_inverse(h))) return rc;
+    hipStream_t s = h->stream;
+    const int64_t Np = h->Np, d = h->d, Mp = (M + TBH - 1) / TBH * TBH;
+    const int nP = (int)(Np / NB);
+    const int64_t nx = (M * d + 31) / 32 * 32;                  // every part below starts on a 256-byte boundary
+    const int64_t need = nx + Mp * d + Mp + nP * Mp + Np * Mp + 2 * Mp * Mp + (draw ? 2 * Mp * Mp + 2 * S * M : 0);
+    if ((rc = ensure(h, h->dKs, h->cap_ks, Np * Mp))) return rc;
+    if ((rc = ensure(h, h->djoint, h->cap_joint, need))) return rc;
+    double* dX = h->djoint;
+    double* dZs = dX + nx;
+    double* dmu = dZs + Mp * d;
+    double* dPp = dmu + Mp;
+    double* dV = dPp + nP * Mp;
+    double* dKss = dV + Np * Mp;
+    double* dC = dKss + Mp * Mp;
+    double* dB = dC + Mp * Mp;
+    double* dRj = dB + Mp * Mp;
+    double* dz = dRj + Mp * Mp;
+    double* dout = dz + S * M;
+    int* flag = h->dflag + 10;                // its own word: the fit's flag, the RFF posterior's and an announcement's stay untouched
+    {
+        Span sp(h, T_COPY);
+        HIPCHK(h, hipMemcpyAsync(dX, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, s));
+        if (draw) HIPCHK(h, hipMemcpyAsync(dz, z, (size_t)S * M * 8, hipMemcpyHostToDevice, s));
+    }
+    {
+        Span sp(h, T_JOINT);
+        launch_cross_gram(s, h->dXs, Np, h->N, (int)d, dX, 0, M, Mp, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
+        launch_cov_trmm(s, h->dU, Np, h->dKs, Mp, dV);
+        launch_cov_mu(s, dV, Np, Mp, h->da, h->bias, dPp, dmu);
+        launch_scale_x(s, dX, M, Mp, (int)d, h->dinvell, dZs);
+        launch_cross_gram(s, dZs, Mp, M, (int)d, dX, 0, M, Mp, h->dinvell, h->kernel_id, h->rho, dKss, Mp);
+        launch_cov_syrk(s, dV, Np, dKss, Mp, dC);
+        if (draw) {
+            launch_cov_form(s, dC, M, Mp, (noisy ? h->sn2 : 0.0) + jitter, dB);
+            launch_cholesky_small(s, dB, dRj, Mp, flag);
+            launch_cov_draw(s, dRj, Mp, M, dz, S, dmu, flag, dout);
+        }
+        HIPCHK(h, hipGetLastError());
+    }
+    int fl = 0;
+    {
+        Span sp(h, T_COPY);
+        if (mu) HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)M * 8, hipMemcpyDeviceToHost, s));
+        if (cov) HIPCHK(h, hipMemcpy2DAsync(cov, (size_t)M * 8, dC, (size_t)Mp * 8, (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost, s));
+        if (draw) {
+            HIPCHK(h, hipMemcpyAsync(out, dout, (size_t)S * M * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipMemcpyAsync(&fl, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+        }
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (fl != 0) {
+        snprintf(msg, sizeof msg, "%s: cov + (%s + jitter) I is not positive definite: pivot %d of %lld failed (out is undefined)", what,
+                 noisy ? "sn2" : "0", fl - 1, (long long)M);
+        return fail(h, GPX_ENOTPD, msg);
+    }
+    return GPX_OK;
+}
+
+extern "C" int gpx_predict_cov(gpx_handle* h, const double* Xc, int64_t M, double* mu, double* cov) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        if (!Xc || !cov) return fail(h, GPX_EARG, "predict_cov: NULL Xc / cov");
+        if (M < 1 || M > JOINT_MAX_M) return fail(h, GPX_EARG, "predict_cov: M must be in [1, 4096]");
+        return joint_core(h, "predict_cov", Xc, M, nullptr, 0, 0, 0.0, mu, cov, nullptr);
+    });
+}
+
+extern "C" int gpx_sample_joint(gpx_handle* h, const double* Xc, int64_t M, const double* z, int64_t S, int noisy, double jitter,
+                                double* out) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        if (!Xc || !z || !out) return fail(h, GPX_EARG, "sample_joint: NULL Xc / z / out");
+        if (M < 1 || M > JOINT_MAX_M) return fail(h, GPX_EARG, "sample_joint: M must be in [1, 4096]");
+        if (S < 1) return fail(h, GPX_EARG, "sample_joint: S must be >= 1");
+        if (!(jitter >= 0.0) || !std::isfinite(jitter)) return fail(h, GPX_EARG, "sample_joint: jitter must be finite and >= 0");
+        return joint_core(h, "sample_joint", Xc, M, z, S, noisy, jitter, nullptr, nullptr, out);
     });
 }
 

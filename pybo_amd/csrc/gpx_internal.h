@@ -20,7 +20,7 @@ constexpr int PEND_MAX = 8;   // appended observations per pass of the sweep-cac
 
 enum Timer {
     T_GRAM = 0, T_CHOL, T_TRTRI, T_ALPHA, T_XGRAM, T_TRMM, T_ACQ, T_RFF, T_NLAUNCH, T_FLOP, T_COPY, T_APPEND,
-    T_RANK1, T_RFFSWEEP, T_RFFOPS, T_TGFALL, T_SCLK, T_RFFCLK, T_AHEAD, T_BOUND, T_BATCH, T_COUNT
+    T_RANK1, T_RFFSWEEP, T_RFFOPS, T_TGFALL, T_SCLK, T_RFFCLK, T_AHEAD, T_BOUND, T_BATCH, T_JOINT, T_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int slot; };
@@ -215,6 +215,11 @@ struct gpx_handle {
     double* dbsel = nullptr;
     int64_t cap_bsel = 0;
 
+    // joint posterior (gpx_predict_cov / gpx_sample_joint): scratch of its own, laid out in api.hip (joint_core); the cross-Gram
+    // of the points goes through dKs like a sweep's
+    double* djoint = nullptr;
+    int64_t cap_joint = 0;
+
     double* dbatch = nullptr;    // gpx_loglik_batch: Gram / factor / scaled inputs / a of the batch (one allocation)
     int64_t cap_batch = 0;
     double* dhyper = nullptr;    // gpx_loglik_grad: the tiles' partial sums [tiles][d + 2], then [L, d + 3 components] (on first use)
@@ -247,6 +252,7 @@ void launch_refine_inverse(gpx_handle* h, double* tmp);   // option refine_inver
 void launch_alpha(gpx_handle* h);      // a = T (y - bias); alpha = U a
 void launch_kinv_diag(gpx_handle* h, double* out);   // out[i] = [K^-1]_ii = sum_m U[i][m]^2
 void launch_transpose_lower(hipStream_t s, const double* R, int64_t Np, double* out, int64_t N);
+void launch_cholesky_small(hipStream_t s, double* S, double* R, int64_t np, int* flag);   // S (upper 128-block triangle, identity padding; consumed) = R^T R
 void launch_posterior_wide(hipStream_t s, const double* A, const double* v, const double* z, int n, int64_t np, double sc,
                            double sn2, double* B, double* R, double* work, int* flag, double* theta);   // n >= 128 features
 
@@ -348,6 +354,16 @@ void launch_batch_pick(hipStream_t s, int j, int64_t M, int d, const double* par
                        const double* invell, const double* qp, const double* V, double rho, double sn2, double* x,
                        double* xs, double* scal, double* cross, double* sel_val, int64_t* sel_idx, double* sel_s2,
                        unsigned char* taken);
+
+// launchers (kernels_cov.hip): the joint posterior at cols = Mp padded points -- V = T Ks stored panel-major [cols / 128][Np][128],
+// mu = bias + V^T a (Pp: Np / 128 x cols partial sums), C = Kss - V^T V (Mp, Mp) symmetric bit for bit, B = C + add I with identity
+// padding, out[s][j] = mu[j] + sum_{i <= j} z[s][i] R[i][j] (skipped when *flag != 0)
+void launch_cov_trmm(hipStream_t s, const double* U, int64_t Np, const double* Ks, int64_t cols, double* V);
+void launch_cov_mu(hipStream_t s, const double* V, int64_t Np, int64_t cols, const double* a, double bias, double* Pp, double* mu);
+void launch_cov_syrk(hipStream_t s, const double* V, int64_t Np, const double* Kss, int64_t Mp, double* C);
+void launch_cov_form(hipStream_t s, const double* C, int64_t M, int64_t Mp, double add, double* B);
+void launch_cov_draw(hipStream_t s, const double* R, int64_t Mp, int64_t M, const double* z, int64_t S, const double* mu,
+                     const int* flag, double* out);
 
 // launchers (kernels_rff.hip)
 extern int g_rff_variant;

@@ -3,7 +3,7 @@ Device-backed exact GP with the duck-typed protocol pybo expects from `reggie` m
 (call sites: /root/reference/pybo/bayesopt.py:105-115,258,269; pybo/policies/simple.py:20-64;
 pybo/recommenders.py:22-34):
 
-    make_gp(sn2, rho, ell, bias)   copy()   add_data(X, Y)   predict(X, grad=False)
+    make_gp(sn2, rho, ell, bias)   copy()   add_data(X, Y)   predict(X, grad=False)   sample(X, size, latent, rng)
     get_improvement(target, X, grad)   get_tail(target, X, grad)   sample_f(n, rng).get(X, grad)
     params[name].set_prior(kind, *args)   picklable
 
@@ -35,6 +35,25 @@ def _is_small(engine):
     """Pool class of a handle by what it keeps allocated (gpx_capacity), not by its last fit: buffers never shrink,
     so a handle that once held a large model stays large however small its current one is."""
     return engine.capacity() <= _POOL_SMALL_N + 256
+
+
+def _prior_cov(kernel, X, ell, rho):
+    """k(X, X) of the four kernels on the host: the joint PRIOR of a model without data (no device call).  Scaled by 1 / ell first,
+    squared distances by direct differences -- the order the device uses."""
+    Xs = X / ell
+    r2 = np.zeros((len(X), len(X)))
+    for k in range(X.shape[1]):
+        df = Xs[:, k][:, None] - Xs[:, k][None, :]
+        r2 += df * df
+    if kernel == 'se':
+        return rho * np.exp(-0.5 * r2)
+    if kernel == 'matern5':
+        s = 2.23606797749978969641 * np.sqrt(r2)
+        return rho * (1.0 + s + (5.0 / 3.0) * r2) * np.exp(-s)
+    if kernel == 'matern3':
+        s = 1.73205080756887729353 * np.sqrt(r2)
+        return rho * (1.0 + s) * np.exp(-s)
+    return rho * np.exp(-np.sqrt(r2))
 
 
 class _DeviceState(object):
@@ -302,6 +321,48 @@ class GP(object):
                 # recommenders once per iteration (recommenders.py:22-34).
                 return eng.mean_at_obs()[0][rows], eng.var_at_obs()[rows]
         return eng.predict(X, grad=grad)
+
+    JITTER = 1e-10      # default jitter of `sample` in units of rho: the absolute variance tolerance
+
+    def _joint_points(self, X):
+        X = np.array(X, ndmin=2, dtype=float)
+        if X.shape[0] > _lib.JOINT_MAX:
+            raise ValueError('a joint posterior takes at most %d points (got %d)' % (_lib.JOINT_MAX, X.shape[0]))
+        return X
+
+    def predict_cov(self, X):
+        """Joint latent posterior at the rows of X (at most 4096): (mu (M,), Sigma (M, M)), Sigma = k(X, X) - V^T V as the device
+        forms it (gpx_predict_cov): raw -- no clamp, no jitter -- and symmetric bit for bit."""
+        X = self._joint_points(X)
+        if X.shape[0] == 0:
+            return np.zeros(0), np.zeros((0, 0))
+        if self.ndata == 0:
+            return np.full(len(X), self.bias), _prior_cov(self.kernel, X, self.ell, self.rho)
+        return self._engine().predict_cov(X)
+
+    def sample(self, X, size=None, latent=True, rng=None, jitter=None):
+        """Joint draws of the function at the rows of X (at most 4096) -- `model.sample` of the reference's demos: (M,) for
+        size=None, else (size, M).  `latent=False` adds the observation noise sn2 to the covariance.  The normals are ONE
+        rstate(rng).randn(S, M); mu + R^T z with R^T R = Sigma + c I is formed on the device (gpx_sample_joint), c = jitter
+        (default 1e-10 rho) [+ sn2].  LinAlgError when that matrix is not positive definite: pass a larger jitter."""
+        X = self._joint_points(X)
+        S, M = (1 if size is None else int(size)), X.shape[0]
+        if S < 0:
+            raise ValueError('size must be >= 0')
+        jitter = self.JITTER * self.rho if jitter is None else float(jitter)
+        if not (jitter >= 0.0 and np.isfinite(jitter)):
+            raise ValueError('jitter must be finite and >= 0')
+        if M == 0 or S == 0:
+            out = np.zeros((S, M))
+        else:
+            z = rstate(rng).randn(S, M)
+            if self.ndata == 0:
+                K = _prior_cov(self.kernel, X, self.ell, self.rho)
+                K[np.diag_indices_from(K)] += jitter + (0.0 if latent else self.sn2)
+                out = self.bias + z @ np.linalg.cholesky(K).T
+            else:
+                out = self._engine().sample_joint(X, z, noisy=not latent, jitter=jitter)
+        return out[0] if size is None else out
 
     def _data_rows(self, X):
         """Row range of `X` in the model's data when X is a contiguous run of the data rows, else None.  The trace of

@@ -356,6 +356,19 @@ class MCMC(object):
         members = self._need()
         return members[rng.randint(len(members))].sample_f(n, rng)
 
+    def sample(self, X, size=None, latent=True, rng=None, jitter=None):
+        """Joint draws at the rows of X from the MIXTURE: every draw comes from a member chosen uniformly by `rng` (as `sample_f`
+        does for its one draw), then from that member's joint posterior with the same stream.  (M,) for size=None, else (size, M)."""
+        rng = rstate(rng)
+        members = self._need()
+        n = 1 if size is None else int(size)
+        if n == 0:
+            return np.zeros((0, np.array(X, ndmin=2).shape[0]))
+        rows = [members[rng.randint(len(members))].sample(X, size=None, latent=latent, rng=rng, jitter=jitter) for _ in range(n)]
+        if size is None:
+            return rows[0]
+        return np.array(rows).reshape(n, -1)
+
     def _engines(self):
         """The members' device engines when every member is a device GP (pybo_amd.models.GP), else None."""
         members = self._need()

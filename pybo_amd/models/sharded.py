@@ -199,6 +199,13 @@ class ShardedGP(object):
     def predict_mean(self, X, grad=False):
         return self._reps[0].predict_mean(X, grad)
 
+    def predict_cov(self, X):
+        """Joint posterior at a point set: one replica's (every replica holds the same fit; V is not sharded)."""
+        return self._reps[0].predict_cov(X)
+
+    def sample(self, X, size=None, latent=True, rng=None, jitter=None):
+        return self._reps[0].sample(X, size=size, latent=latent, rng=rng, jitter=jitter)
+
     def mean_topk(self, xgrid, k):
         if not isinstance(xgrid, (DeviceGrid, ShardedDeviceGrid)):
             xgrid = np.array(xgrid, ndmin=2, dtype=float)
