@@ -17,6 +17,7 @@
 #include "gemm_core.h"
 #include "gpx_internal.h"
 #include "gpx_math.h"
+#include "bound_exp.h"
 #include "sweep_map.h"
 
 namespace gpx {
@@ -810,7 +811,11 @@ void launch_prune_alpha(hipStream_t s, const double* U, int64_t Np, const double
 // With x~, z~ the scaled coordinates minus a common centre c,  -r2 / 2 = x~ . z~ - |x~|^2 / 2 - |z~|^2 / 2  is ONE inner
 // product of length d + 2: observation row [x~_1 .. x~_d, -|x~|^2 / 2, 1] times candidate column [z~_1 .. z~_d, 1, -|z~|^2 / 2],
 // both padded with zeros to 4 KS.  v_mfma_f64_16x16x4_f64 forms it for 16 observations x 16 candidates in KS instructions
-// while the VALU evaluates the exponentials of the tile before: 25 instead of 46 VALU instructions per covariance.
+// while the VALU evaluates the exponentials of the tile before.  Where the two norm slots would cost an MFMA of their own
+// (d mod 4 in {0, 3}) the inner product keeps its d terms and the norms arrive through the accumulator: it starts from
+// (-|x~|^2 / 2) + (-|z~|^2 / 2), one addition per result instead of a quarter MFMA (64 cycles per 256 results).
+// The exponential is bound_exp.h's table form: 18.3 VALU instructions per covariance in the walk's loop (19.2 with the addition)
+// and one LDS read, where exp_nonpos made it 25.3; 46 in the generic kernel.
 // The inner-product form cancels where the direct differences do not; sc[] carries the radii of the centred data and the
 // guard k_bound_guard derives from them: sc[9] = 1.0 says this kernel runs, 0.0 says k_sweep_rankq<1> does (both read it).
 // ------------------------------------------------------------------------------------------------
@@ -818,6 +823,10 @@ constexpr int BM_KS_MAX = 5;               // d + 2 <= 20: the candidates' fragm
 constexpr int BM_SC_RX2 = 6, BM_SC_RZ2 = 7, BM_SC_GUARD = 8, BM_SC_USE = 9;      // slots of sc[] (0 .. 5: k_prune_delta, gate, tau)
 
 int bound_mfma_ks(int kernel_id, int d) { return (kernel_id == GPX_KERN_SE_ARD && d + 2 <= 4 * BM_KS_MAX) ? (d + 5) / 4 : 0; }
+
+// the norms go through the accumulator where that saves an MFMA per tile; the k-steps of the kernel either way
+static bool bound_mfma_normc(int d) { return d > 0 && (d + 3) / 4 < (d + 5) / 4; }
+static int bound_mfma_steps(int d) { return bound_mfma_normc(d) ? (d + 3) / 4 : (d + 5) / 4; }
 
 // max of non-negative doubles through their bit patterns (order-preserving for v >= 0); a NaN is not recorded
 __device__ __forceinline__ void block_max_nonneg(double v, double* slot, double* red) {
@@ -864,9 +873,11 @@ __global__ __launch_bounds__(256) void k_bound_centre(const double* __restrict__
 // The augmented observation array in fragment order: tile t (16 rows), k-step ks, lane l holds element k = 4 ks + (l >> 4) of row
 // 16 t + (l & 15) at A[(t KS + ks) 64 + l] -- one coalesced 512-byte read per wave and k-step.  W4[16 t + 4 g + r] = rho alpha2 of row
 // 16 t + g + 4 r: the four weights of a lane's four results (C/D row = (l >> 4) + 4 r) as one 32-byte read.  Rows from N on: zeros.
+// NX4 (non-null: the norms go through the accumulator): -|x~|^2 / 2 in W4's order, and the rows are [x~_1 .. x~_d] alone.
 __global__ __launch_bounds__(256) void k_bound_aug(const double* __restrict__ Xs, int64_t N, int64_t Np, int d, int KS,
                                                    const double* __restrict__ cen, const double* __restrict__ alpha2, double rho,
-                                                   double* __restrict__ A, double* __restrict__ W4, double* __restrict__ sc) {
+                                                   double* __restrict__ A, double* __restrict__ W4, double* __restrict__ NX4,
+                                                   double* __restrict__ sc) {
     __shared__ double red[256];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;       // (Np is a multiple of 128)
     double n2 = 0.0;
@@ -881,12 +892,13 @@ __global__ __launch_bounds__(256) void k_bound_aug(const double* __restrict__ Xs
                 v = Xs[i * d + k] - cen[k];
                 n2 = fma(v, v, n2);
             }
-            if (live && k == d) v = -0.5 * n2;
-            if (live && k == d + 1) v = 1.0;
+            if (live && !NX4 && k == d) v = -0.5 * n2;
+            if (live && !NX4 && k == d + 1) v = 1.0;
             At[(k >> 2) * 64 + (k & 3) * 16] = v;
         }
         const int g = row & 3, r = row >> 2;                          // row = g + 4 r
         W4[t * 16 + 4 * g + r] = live ? rho * alpha2[i] : 0.0;
+        if (NX4) NX4[t * 16 + 4 * g + r] = live ? -0.5 * n2 : 0.0;
     }
     block_max_nonneg(n2, sc + BM_SC_RX2, red);
 }
@@ -923,74 +935,94 @@ __global__ void k_bound_guard(int d, int64_t Np, int force, double* __restrict__
 }
 
 // One workgroup owns 128 candidates (8 column tiles of 16, their fragments in registers for the whole walk); wave w walks the
-// 16-row tiles w, w + 4, .. of the augmented array in order.  Per tile and column tile: KS MFMAs from a zero accumulator, then per
-// result the exponent limited to <= 0 (compare and select: a NaN stays), exp_nonpos, one FMA with the row's weight into the lane's
-// accumulator of that column.  The four row groups of a wave are combined by two exchanges, the waves through LDS, in a fixed order:
-// the values do not depend on the launch geometry.
-template <int KS>
-__global__ __launch_bounds__(256, 2) void k_bound_mfma(const double* __restrict__ A, const double* __restrict__ W4, int ntile, int d,
-                                                       const double* __restrict__ Z, int64_t M, const double* __restrict__ invell,
-                                                       const double* __restrict__ cen, const double* __restrict__ sc,
-                                                       double* __restrict__ out) {
+// 16-row tiles w, w + 4, .. of the augmented array in order.  Per tile and column tile: KS MFMAs from a zero accumulator (NC: from
+// the sum of the two norms), then per result the exponent limited to <= 0, bound_exp from the table in LDS, one FMA with the row's
+// weight into the lane's accumulator of that column.  The two limits are v_min_f64 / v_max_f64, which drop a NaN: a candidate whose
+// |z~|^2 is not finite (a NaN or infinite coordinate, an overflow) gets its NaN back once, after the walk.  The four row groups of a
+// wave are combined by two exchanges, the waves through LDS, in a fixed order: the values do not depend on the launch geometry.
+template <int KS, bool NC>
+__global__ __launch_bounds__(256, (KS + (NC ? 1 : 0) <= 3) ? 4 : 3) void k_bound_mfma(const double* __restrict__ A, const double* __restrict__ W4,
+                                                       const double* __restrict__ NX4, int ntile, int d, const double* __restrict__ Z,
+                                                       int64_t M, const double* __restrict__ invell, const double* __restrict__ cen,
+                                                       const double* __restrict__ sc, double* __restrict__ out) {
     __shared__ double red[4][XN];
+    __shared__ double tab[BEXP_NT];
     if (sc[BM_SC_USE] != 1.0) return;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (threadIdx.x < BEXP_NT) tab[threadIdx.x] = kBoundExpTab[threadIdx.x];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (w in a scalar register: the walk's loop is uniform)
     const int col = lane & 15, g = lane >> 4;
     const int64_t n0 = (int64_t)blockIdx.x * XN;
-    double b[8][KS];
+    double b[8][KS], nz[NC ? 8 : 1];
+    unsigned lost = 0;                        // bit j: column tile j's candidate has no finite |z~|^2
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int64_t n = n0 + j * 16 + col;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) b[j][ks] = 0.0;
+        double n2 = 0.0;
         if (n < M) {
-            double n2 = 0.0;
             for (int k = 0; k < d; ++k) {
                 const double v = bound_zt(Z[n * d + k], invell[k], cen[k]);
                 n2 = fma(v, v, n2);
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) b[j][ks] = (k == 4 * ks + g) ? v : b[j][ks];
             }
+            if (!NC) {
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                b[j][ks] = (d == 4 * ks + g) ? 1.0 : b[j][ks];
-                b[j][ks] = (d + 1 == 4 * ks + g) ? -0.5 * n2 : b[j][ks];
+                for (int ks = 0; ks < KS; ++ks) {
+                    b[j][ks] = (d == 4 * ks + g) ? 1.0 : b[j][ks];
+                    b[j][ks] = (d + 1 == 4 * ks + g) ? -0.5 * n2 : b[j][ks];
+                }
             }
         }
+        if (NC) nz[j] = -0.5 * n2;
+        lost |= (n2 < __builtin_huge_val()) ? 0u : (1u << j);
     }
+    __syncthreads();
     double acc[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = 0.0;
-    const double* Ap = A + (int64_t)w * KS * 64 + lane;
-    const double* Wp = W4 + w * 16 + g * 4;
+    // byte offsets in 32 bits from the kernel's (scalar) pointers: one register each where a pointer takes two (A: 32 KS Np bytes)
+    unsigned ao = ((unsigned)w * KS * 64 + lane) * 8, wo = ((unsigned)w * 16 + g * 4) * 8, xo = wo;
+    const auto ld1 = [](const double* p, unsigned o) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(p) + o); };
+    const auto ld4 = [](const double* p, unsigned o) { return *reinterpret_cast<const d4*>(reinterpret_cast<const char*>(p) + o); };
     double a[KS], an[KS];
-    d4 wv, wn;
+    d4 wv, wn = {0.0, 0.0, 0.0, 0.0}, xv = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) an[ks] = Ap[ks * 64];
-    wn = *reinterpret_cast<const d4*>(Wp);
+    for (int ks = 0; ks < KS; ++ks) an[ks] = ld1(A, ao + ks * 512);
+    if (NC)
+        xv = ld4(NX4, xo);
+    else
+        wn = ld4(W4, wo);
 #pragma unroll 1
     for (int t = w; t < ntile; t += 4) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) a[ks] = an[ks];
-        wv = wn;
+        // NC keeps 8 norms where the other form keeps 8 more fragments, and the row norms besides: no second buffer for either vector.
+        // The weights are first wanted a whole exponential into the tile, the norms (below) are read behind their last use.
+        wv = NC ? ld4(W4, wo) : wn;
+        wo += 4 * 16 * 8;
         if (t + 4 < ntile) {                  // the next tile's operands while this one computes
-            Ap += 4 * KS * 64;
-            Wp += 4 * 16;
+            ao += 4 * KS * 64 * 8;
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) an[ks] = Ap[ks * 64];
-            wn = *reinterpret_cast<const d4*>(Wp);
+            for (int ks = 0; ks < KS; ++ks) an[ks] = ld1(A, ao + ks * 512);
+            if (!NC) wn = ld4(W4, wo);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             d4 c = {0.0, 0.0, 0.0, 0.0};
+            if (NC) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) c[r] = xv[r] + nz[j];
+                if (j == 7) {                 // the last use of this tile's norms: the next tile's take their place
+                    xo += (t + 4 < ntile) ? 4 * 16 * 8 : 0;
+                    xv = ld4(NX4, xo);
+                }
+            }
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], b[j][ks], c, 0, 0, 0);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double e = c[r];
-                e = (e > 0.0) ? 0.0 : e;                                // NaN passes through
-                acc[j] = fma(wv[r], exp_nonpos(e), acc[j]);
-            }
+            for (int r = 0; r < 4; ++r) acc[j] = fma(wv[r], bound_exp<false>(__builtin_fmin(c[r], 0.0), tab), acc[j]);
         }
     }
 #pragma unroll
@@ -998,7 +1030,7 @@ __global__ __launch_bounds__(256, 2) void k_bound_mfma(const double* __restrict_
         double v = acc[j];
         v += __shfl_xor(v, 16);
         v += __shfl_xor(v, 32);
-        if (g == 0) red[w][j * 16 + col] = v;
+        if (g == 0) red[w][j * 16 + col] = ((lost >> j) & 1u) ? __builtin_nan("") : v;
     }
     __syncthreads();
     if (threadIdx.x < XN) {
@@ -1007,29 +1039,36 @@ __global__ __launch_bounds__(256, 2) void k_bound_mfma(const double* __restrict_
     }
 }
 
-// Prologue, guard and the matrix-pipe kernel on stream s.  ws: [A Np x 4 KS][W4 Np][cen 4 BM_KS_MAX]; sc: the bound pass's 16 scalars.
+// Prologue, guard and the matrix-pipe kernel on stream s.  ws: [A Np x 4 KS][W4 Np][NX4 Np, where the norms go through the accumulator:
+// KS <= 4 there][cen 4 BM_KS_MAX at its fixed place]; sc: the bound pass's 16 scalars.
 // The caller launches the generic kernel behind it with sc + BM_SC_USE as its `skip`: exactly one of the two writes `out`.
 int64_t bound_mfma_ws_words(int64_t Np) { return Np * 4 * BM_KS_MAX + Np + 4 * BM_KS_MAX; }
 
 void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
                        const double* Z, int64_t M, const double* invell, int force, double* ws, double* sc, double* out) {
-    const int KS = (d + 5) / 4;
+    const int KS = bound_mfma_steps(d);
+    const bool nc = bound_mfma_normc(d);
     double* A = ws;
     double* W4 = A + Np * 4 * KS;
+    double* NX4 = nc ? W4 + Np : nullptr;
     double* cen = ws + Np * 4 * BM_KS_MAX + Np;
     hipLaunchKernelGGL(k_bound_centre, dim3(1), dim3(256), 0, s, Xs, N, d, cen, sc);
-    hipLaunchKernelGGL(k_bound_aug, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, Xs, N, Np, d, KS, cen, alpha2, rho, A, W4, sc);
+    hipLaunchKernelGGL(k_bound_aug, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, Xs, N, Np, d, KS, cen, alpha2, rho, A, W4, NX4, sc);
     hipLaunchKernelGGL(k_bound_rz, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, Z, M, d, invell, cen, sc);
     hipLaunchKernelGGL(k_bound_guard, dim3(1), dim3(1), 0, s, d, Np, force, sc);
     const dim3 grid((unsigned)((M + XN - 1) / XN));
     const int ntile = (int)(Np / 16);
-#define GPX_BM(K) hipLaunchKernelGGL(k_bound_mfma<K>, grid, dim3(256), 0, s, A, W4, ntile, d, Z, M, invell, cen, sc, out)
-    switch (KS) {
-        case 1: GPX_BM(1); break;
-        case 2: GPX_BM(2); break;
-        case 3: GPX_BM(3); break;
-        case 4: GPX_BM(4); break;
-        default: GPX_BM(5); break;
+#define GPX_BM(K, C) hipLaunchKernelGGL((k_bound_mfma<K, C>), grid, dim3(256), 0, s, A, W4, NX4, ntile, d, Z, M, invell, cen, sc, out)
+    switch (2 * KS + (nc ? 1 : 0)) {
+        case 2: GPX_BM(1, false); break;
+        case 3: GPX_BM(1, true); break;
+        case 4: GPX_BM(2, false); break;
+        case 5: GPX_BM(2, true); break;
+        case 6: GPX_BM(3, false); break;
+        case 7: GPX_BM(3, true); break;
+        case 8: GPX_BM(4, false); break;
+        case 9: GPX_BM(4, true); break;
+        default: GPX_BM(5, false); break;
     }
 #undef GPX_BM
 }
