@@ -218,22 +218,24 @@ int gpx_rff_gram_batch(gpx_handle *h, const double *W, const double *b, int64_t 
  * substitutions (`n` is a free keyword of the reference's sample_f, pybo/policies/simple.py:44).  GPX_ENOTPD if a B is not PD. */
 int gpx_rff_posterior(gpx_handle *h, const double *W, const double *b, const double *z, int64_t S, int64_t n, double sc, double *theta);
 
-/* ---- hyper-parameter ensemble = pybo's DEFAULT model, reggie.MCMC(gp, n=10)
- *      [pybo/bayesopt.py:115]: every index is the average over the n member GPs.  `members` are fitted
- *      handles on ONE device with the same input dimension (members[0] owns the scratch and the error text).
- *      EI / PI: value = mean_m acq_m(x).  UCB / MEAN: mixture moments mu = mean_m mu_m,
- *      s2 = mean_m(s2_m + mu_m^2) - mu^2, value = mu + sqrt(params[0] * s2) (UCB) or mu (MEAN); only these
- *      two can return mu / s2.  The member sweeps never leave the device; sums run in member order and are
- *      divided once by n.  Outputs as in gpx_sweep / gpx_sweep_dev; an EI call for the top-k alone prunes as they do ("prune" of members[0]). */
+/* ---- hyper-parameter ensemble = pybo's DEFAULT model, reggie.MCMC(gp, n=10) [pybo/bayesopt.py:115]: every index is the average over the n member
+ *      GPs.  `members` are fitted handles on ONE device with the same input dimension (members[0] owns the scratch and the error text).
+ *      EI / PI: value = mean_m acq_m(x).  UCB / MEAN: mixture moments mu = mean_m mu_m, s2 = mean_m(s2_m + mu_m^2) - mu^2, value = mu + sqrt(params[0] * s2)
+ *      (UCB) or mu (MEAN); only these two can return mu / s2.  The member sweeps never leave the device; sums run in member order and are divided once
+ *      by n.  Outputs as in gpx_sweep / gpx_sweep_dev; an EI call for the top-k alone prunes as they do ("prune" of members[0]). */
 int gpx_ensemble_sweep(gpx_handle *const *members, int n_members, int acq_id, const double *params, int nparams, const double *Xc,
                        int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *acq_all, double *mu, double *s2);
 int gpx_ensemble_sweep_dev(gpx_handle *const *members, int n_members, int acq_id, const double *params, int nparams, const double *dXc,
                            int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *d_acq_all, double *d_mu, double *d_s2);
-/* per-member posterior moments AND gradients at M points (host buffers), member-major: mu, s2 (n_members, M);
- * dmu, ds2 (n_members, M, d) -- the `f(x, grad=True)` calls of the L-BFGS refinement on the default model
- * [pybo/solvers/lbfgs.py:56-58 over pybo/bayesopt.py:115]; the members' latency-bound kernels run concurrently on
- * their own streams (one call instead of n_members gpx_predict calls) and the caller forms the average it needs
- * (mixture moments for UCB / mean, the mean of the members' EI / PI and their gradients). */
+/* gpx_sweep_batch on the ensemble: nb greedy picks scored by the rule above, the members FROZEN (1 <= n_members <= 64, each handle once), every member
+ * conditioned on a pick at its own posterior mean.  Every member holds a live sweep cache of the same candidates (none: GPX_ESTATE; other sizes or
+ * rows: GPX_EARG, outputs undefined).  sel_val, sel_idx (nb) required; sel_s2 (n_members, nb) optional: the member's conditioned variance at its pick. */
+int gpx_ensemble_sweep_batch(gpx_handle *const *members, int n_members, int acq_id, const double *params, int nparams, int64_t nb,
+                             double *sel_val, int64_t *sel_idx, double *sel_s2);
+/* per-member posterior moments AND gradients at M points (host buffers), member-major: mu, s2 (n_members, M); dmu, ds2 (n_members, M, d) -- the
+ * `f(x, grad=True)` calls of the L-BFGS refinement on the default model [pybo/solvers/lbfgs.py:56-58 over pybo/bayesopt.py:115]; the members'
+ * latency-bound kernels run concurrently on their own streams (one call instead of n_members gpx_predict calls) and the caller forms the average it
+ * needs (mixture moments for UCB / mean, the mean of the members' EI / PI and their gradients). */
 int gpx_ensemble_predict(gpx_handle *const *members, int n_members, const double *Xc, int64_t M, double *mu, double *s2, double *dmu, double *ds2);
 
 /* ---- candidate grid generated and kept in HBM = the solver's grid
@@ -286,7 +288,7 @@ int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, 
  * the stream schedule [16] the shader clock in MHz the sweep_trmm launches sustained (their workgroups' s_memtime over s_memrealtime
  * ticks) [17] the same for the Thompson sweep kernel [18] inversions whose leading part ran behind the factorisation ("trtri_ahead":
  * for those [2] holds only what was left after the factor was done) [19] bound pass of selection-only sweeps [20] batch selection
- * (gpx_sweep_batch) [21] joint posterior (gpx_predict_cov / gpx_sample_joint: everything between their copies).  Synchronises; returns slots written. */
+ * (gpx_[ensemble_]sweep_batch) [21] joint posterior (gpx_predict_cov / gpx_sample_joint: all between their copies).  Synchronises; returns slots written. */
 int gpx_timers(gpx_handle *h, double *out, int n, int reset);
 /* 1 when the library was built with -DGPX_DIAGNOSTICS (the diagnostic options above are accepted), else 0 */
 int gpx_diagnostics(void);

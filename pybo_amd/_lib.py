@@ -90,6 +90,7 @@ SYMBOLS = {
     'gpx_rff_posterior': (C.c_int, [_P, _P, _P, _P, _i64, _i64, _dbl, _P]),
     'gpx_ensemble_sweep': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P, _P]),
     'gpx_ensemble_sweep_dev': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P, _P]),
+    'gpx_ensemble_sweep_batch': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _i64, _P, _P, _P]),
     'gpx_ensemble_predict': (C.c_int, [_P, C.c_int, _P, _i64, _P, _P, _P, _P]),
     'gpx_grid_create': (C.c_int, [C.c_int, C.c_int, _P, _i64, _i64, C.c_uint64, _i64, _P, C.c_int, C.POINTER(_P)]),
     'gpx_grid_data': (_P, [_P]),
@@ -676,6 +677,21 @@ class Engine(object):
                                                  _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out),
                                                  _ptr(mu), _ptr(s2)))
         return dict(top_val=tv, top_idx=ti, acq=out, mu=mu, s2=s2)
+
+    @staticmethod
+    def ensemble_batch(engines, kind, param, nb):
+        """nb greedy picks of the ensemble on its members' live sweep caches (gpx_ensemble_sweep_batch): the members frozen, each
+        conditioned on a pick at its own posterior mean.  Returns dict(sel_val (nb,), sel_idx (nb,), sel_s2 (n, nb)); the members
+        are left as they were."""
+        lead = engines[0]
+        handles = (_P * len(engines))(*[e._h for e in engines])
+        aid = ACQ[kind] if isinstance(kind, str) else int(kind)
+        params = _f64([0.0 if param is None else param])
+        n = max(int(nb), 0)
+        out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty((len(engines), n)))
+        lead._check(lead._lib.gpx_ensemble_sweep_batch(handles, len(engines), aid, _ptr(params), 1, int(nb), _ptr(out['sel_val']),
+                                                       _ptr(out['sel_idx']), _ptr(out['sel_s2'])))
+        return out
 
     @staticmethod
     def ensemble_predict(engines, Xc):

@@ -9,10 +9,13 @@ only the variance shrinks -- and pick again, with the acquisition parameter (EI 
     propose_batch(model, bounds, X, nb, policy='ei', xgrid=None, ngrid=10000, rng=None) -> (Xq (nb, d), values (nb,), idx (nb,))
 
 Three paths, chosen by what the policy's index carries:
-  * `index.batch` (device models, `pybo_amd.models.GP`): every round runs on the GPU over the warm sweep cache
-    (gpx_sweep_batch); one O(N M) pass per extra point, the model untouched;
-  * `index.acq` only (the MCMC ensemble, ShardedGP, the oracle's GPRef, stubs): the generic host path below -- score the grid,
-    pick, `copy()` the model once and `add_data(x, predict(x)[0])` per round;
+  * `index.batch` (device models: `pybo_amd.models.GP`, and `pybo_amd.models.MCMC` over such members): every round runs on the
+    GPU over the warm sweep cache (gpx_sweep_batch / gpx_ensemble_sweep_batch); one O(N M) pass per member and extra point, the
+    model untouched.  The ensemble's members are FROZEN for the batch -- no chain step, no refit: each member is conditioned on a
+    pick at its own posterior mean and the ensemble's index (mean of the members' EI / PI, mixture moments for UCB) is re-scored;
+  * `index.acq` only (an MCMC ensemble over other members, ShardedGP, the oracle's GPRef, stubs): the generic host path below --
+    score the grid, pick, `copy()` the model once and `add_data(x, predict(x)[0])` per round.  On an `MCMC` that `add_data`
+    advances the chain: the hyper-parameters are RE-SAMPLED on the hallucinated observation every round, unlike the device path;
   * neither (Thompson, or any sampled policy): nb independent policy calls, each one's best grid point; duplicates are allowed.
 Picks are grid candidates, ranked value descending, then index ascending, NaN last -- the device top-k's order.
 """

@@ -230,8 +230,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // build, tile_order default by size (7 below 32 block rows, 19 from there on).
 // 610: option prune (selection-only sweeps), timers slot 19.  620: the ensemble sweep prunes too (the lead's option prune),
 // gpx_ensemble_prune_report.  630: the second bound of selection-only sweeps (option prune_rows, gpx_prune_rows, gpx_prune_report's scalars 16 .. 19).
-// 640: gpx_sweep_batch, timers slot 20.
-extern "C" int gpx_version(void) { return 640; }
+// 640: gpx_sweep_batch, timers slot 20.  650: gpx_ensemble_sweep_batch.
+extern "C" int gpx_version(void) { return 650; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -1414,10 +1414,57 @@ extern "C" int gpx_sweep_update(gpx_handle* h, int acq_id, const double* params,
 // Per extra pick: launch_append_prepare (k(X, x), r = T k, w = U r -- its scalars and flag land in this call's own words and are
 // not read: d comes from the CONDITIONED variance), the weight row [w, -1], one rank-1 pass over the cached candidates, one fold +
 // scoring pass.  Everything is enqueued on the handle's stream with ONE synchronisation at the end; the picked index never
-// leaves the device, so no launch depends on it.  Scratch (h->dbsel, doubles):
-//   [x xpad][xs xpad][ks ld][g ld][r ld][tu ld][row ld][small 384][partv 1024][parti 1024][q' M][s2 M][taken ceil(M / 8)][V nb M]
-//   small: +0 pscal {1/d, 0}  +8 the prepare's scalars (unused)  +24 scal {d, 1/d, 0, d^2}  +40 its flag word  +64 cross (64)
-//          +128 sel_val (64)  +192 sel_s2 (64)  +256 sel_idx (64 int64)
+// leaves the device, so no launch depends on it.  Scratch (h->dbsel, doubles), shared by gpx_sweep_batch and, per member, by
+// gpx_ensemble_sweep_batch (whose lead keeps `extra` more words behind V):
+//   [x xpad][xs xpad][ks ld][g ld][r ld][tu ld][row ld][small 384][partv 1024][parti 1024][q' M][s2 M][taken ceil(M / 8)][V nb M][extra]
+//   small: +0 pscal {1/d, 0}  +8 the prepare's scalars (unused)  +24 scal {d, 1/d, 0, d^2}  +40 its flag word  +48 the same-grid
+//          flag word (ensemble lead)  +64 cross (64)  +128 sel_val (64)  +192 sel_s2 (64)  +256 sel_idx (64 int64)
+struct BatchBuf {
+    int64_t ld;
+    double *x, *xs, *ks, *g, *r, *tu, *row, *pscal, *scal_prep, *scal, *cross, *sel_val, *sel_s2, *partv, *qp, *s2, *V, *extra;
+    int *flag, *same;
+    int64_t *sel_idx, *parti;
+    unsigned char* taken;
+    int64_t ntaken;
+};
+static int batch_layout(gpx_handle* h, int64_t M, int64_t nb, int64_t extra, BatchBuf& b) {
+    const int64_t xpad = (h->cap_d + 63) / 64 * 64, ld = h->cap_np + NB;      // N + 1 <= ld whatever the padding holds
+    const int64_t ntaken = (M + 7) / 8;
+    const int64_t need = 2 * xpad + 5 * ld + 384 + 2048 + 2 * M + ntaken + nb * M + extra;
+    if (int rc = ensure(h, h->dbsel, h->cap_bsel, need)) return rc;
+    b.ld = ld;
+    b.x = h->dbsel;
+    b.xs = b.x + xpad;
+    b.ks = b.xs + xpad;
+    b.g = b.ks + ld;
+    b.r = b.g + ld;
+    b.tu = b.r + ld;
+    b.row = b.tu + ld;
+    double* small = b.row + ld;
+    b.pscal = small, b.scal_prep = small + 8, b.scal = small + 24, b.cross = small + 64;
+    b.flag = reinterpret_cast<int*>(small + 40);
+    b.same = reinterpret_cast<int*>(small + 48);
+    b.sel_val = small + 128, b.sel_s2 = small + 192;
+    b.sel_idx = reinterpret_cast<int64_t*>(small + 256);
+    b.partv = small + 384;
+    b.parti = reinterpret_cast<int64_t*>(b.partv + 1024);
+    b.qp = b.partv + 2048;
+    b.s2 = b.qp + M;
+    b.taken = reinterpret_cast<unsigned char*>(b.s2 + M);
+    b.ntaken = ntaken;
+    b.V = b.s2 + M + ntaken;
+    b.extra = b.V + nb * M;
+    return GPX_OK;
+}
+
+// one extra pick's conditioning of member h on the point x (raw) / xs (scaled by h's 1/ell), enqueued on s: row j of V
+static void batch_condition(gpx_handle* h, hipStream_t s, const BatchBuf& b, const double* x, const double* Z, int64_t M, int j) {
+    launch_append_prepare(h, s, x, b.ks, b.g, b.r, b.tu, 0.0, b.scal_prep, b.flag);
+    launch_pend_store(s, b.tu, h->N, b.ld, b.scal, b.row, b.pscal);
+    launch_sweep_rank1_v(s, h->dXs, h->N + 1, (int)h->d, b.row, b.ld, b.pscal, Z, M, h->dinvell, h->kernel_id, h->rho, b.xs,
+                         b.V + (int64_t)j * M);
+}
+
 extern "C" int gpx_sweep_batch(gpx_handle* h, int acq_id, const double* params, int nparams, int64_t nb, double* sel_val,
                                int64_t* sel_idx, double* sel_s2, double* s2_all) {
     return guarded(h, [&]() -> int {
@@ -1434,52 +1481,29 @@ extern "C" int gpx_sweep_batch(gpx_handle* h, int acq_id, const double* params, 
         HIPCHK(h, hipSetDevice(h->device));
         if ((rc = ensure_inverse(h))) return rc;
         if ((rc = flush_pending(h))) return rc;                  // queued appends belong in the sums the picks are scored with
-        const int64_t xpad = (h->cap_d + 63) / 64 * 64, ld = h->cap_np + NB;      // N + 1 <= ld whatever the padding holds
-        const int64_t ntaken = (M + 7) / 8;
-        const int64_t need = 2 * xpad + 5 * ld + 384 + 2048 + 2 * M + ntaken + nb * M;
-        if ((rc = ensure(h, h->dbsel, h->cap_bsel, need))) return rc;
-        double* x = h->dbsel;
-        double* xs = x + xpad;
-        double* ks = xs + xpad;
-        double* g = ks + ld;
-        double* r = g + ld;
-        double* tu = r + ld;
-        double* row = tu + ld;
-        double* small = row + ld;
-        double *pscal = small, *scal_prep = small + 8, *scal = small + 24, *cross = small + 64;
-        int* flag = reinterpret_cast<int*>(small + 40);
-        double *dsel_val = small + 128, *dsel_s2 = small + 192;
-        int64_t* dsel_idx = reinterpret_cast<int64_t*>(small + 256);
-        double* partv = small + 384;
-        int64_t* parti = reinterpret_cast<int64_t*>(partv + 1024);
-        double* qp = partv + 2048;
-        double* ds2 = qp + M;
-        unsigned char* taken = reinterpret_cast<unsigned char*>(ds2 + M);
-        double* V = ds2 + M + ntaken;
+        BatchBuf b;
+        if ((rc = batch_layout(h, M, nb, 0, b))) return rc;
         const double p0 = params[0];
         hipStream_t s = h->stream;
         {
             Span sp(h, T_BATCH);
-            HIPCHK(h, hipMemsetAsync(taken, 0, (size_t)ntaken * 8, s));
-            HIPCHK(h, hipMemsetAsync(flag, 0, sizeof(int), s));
+            HIPCHK(h, hipMemsetAsync(b.taken, 0, (size_t)b.ntaken * 8, s));
+            HIPCHK(h, hipMemsetAsync(b.flag, 0, sizeof(int), s));
             for (int j = 0; j < (int)nb; ++j) {
-                double* s2_out = (s2_all && j == (int)nb - 1) ? ds2 : nullptr;    // the variances that score the LAST pick
-                launch_batch_score(s, j - 1, M, h->dcq, h->dcp, qp, V, cross, scal, taken, h->rho, h->bias, acq_id, p0,
-                                   s2_out, partv, parti);
-                launch_batch_pick(s, j, M, (int)d, partv, parti, h->dcZ, h->dinvell, qp, V, h->rho, h->sn2, x, xs, scal,
-                                  cross, dsel_val, dsel_idx, dsel_s2, taken);
+                double* s2_out = (s2_all && j == (int)nb - 1) ? b.s2 : nullptr;    // the variances that score the LAST pick
+                launch_batch_score(s, j - 1, M, h->dcq, h->dcp, b.qp, b.V, b.cross, b.scal, b.taken, h->rho, h->bias, acq_id, p0,
+                                   s2_out, b.partv, b.parti);
+                launch_batch_pick(s, j, M, (int)d, b.partv, b.parti, h->dcZ, h->dinvell, b.qp, b.V, h->rho, h->sn2, b.x, b.xs,
+                                  b.scal, b.cross, b.sel_val, b.sel_idx, b.sel_s2, b.taken);
                 if (j == (int)nb - 1) break;
-                launch_append_prepare(h, s, x, ks, g, r, tu, 0.0, scal_prep, flag);
-                launch_pend_store(s, tu, h->N, ld, scal, row, pscal);
-                launch_sweep_rank1_v(s, h->dXs, h->N + 1, (int)d, row, ld, pscal, h->dcZ, M, h->dinvell, h->kernel_id, h->rho,
-                                     xs, V + (int64_t)j * M);
+                batch_condition(h, s, b, b.x, h->dcZ, M, j);
             }
             HIPCHK(h, hipGetLastError());
         }
-        HIPCHK(h, hipMemcpyAsync(sel_val, dsel_val, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(sel_idx, dsel_idx, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        if (sel_s2) HIPCHK(h, hipMemcpyAsync(sel_s2, dsel_s2, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        if (s2_all) HIPCHK(h, hipMemcpyAsync(s2_all, ds2, (size_t)M * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(sel_val, b.sel_val, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(sel_idx, b.sel_idx, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        if (sel_s2) HIPCHK(h, hipMemcpyAsync(sel_s2, b.sel_s2, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        if (s2_all) HIPCHK(h, hipMemcpyAsync(s2_all, b.s2, (size_t)M * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
         return GPX_OK;
     });
@@ -2113,6 +2137,94 @@ extern "C" int gpx_ensemble_sweep(gpx_handle* const* members, int n_members, int
         return staged_sweep(h, Xc, M, true, acq_all, mu, s2, [&](double* dX, double* dacq, double* dmu, double* ds2) {
             return ensemble_core(members, n_members, acq_id, params, nparams, dX, M, k, top_val, top_idx, dacq, dmu, ds2);
         });
+    });
+}
+
+// Batch proposals on the ensemble: the members frozen, every round scored with ensemble_core's rule, every member conditioned on the
+// pick at its own posterior mean (gpx_sweep_batch's recurrence per member, in that member's dbsel).  The lead's dbsel also holds what
+// the members share: taken, the argmax partials, sel_val / sel_idx, the raw x, and behind its V [sel_s2 n nb][descriptors n].
+// The members' streams are drained on entry; from there on everything runs on the lead's stream with ONE synchronisation.
+extern "C" int gpx_ensemble_sweep_batch(gpx_handle* const* members, int n_members, int acq_id, const double* params,
+                                        int nparams, int64_t nb, double* sel_val, int64_t* sel_idx, double* sel_s2) {
+    if (members && members[0] && (n_members < 1 || n_members > 64)) {
+        members[0]->err = "ensemble_sweep_batch: n_members must be in [1, 64]";
+        return GPX_EARG;
+    }
+    if (ensemble_check(members, n_members)) return GPX_EARG;
+    gpx_handle* L = members[0];
+    return guarded(L, [&]() -> int {
+        const int n = n_members;
+        int rc;
+        if ((rc = check_acq(L, "ensemble_sweep_batch", acq_id, params, nparams))) return rc;
+        if (acq_id == GPX_ACQ_MEAN)
+            return fail(L, GPX_EARG, "ensemble_sweep_batch: the posterior mean does not change under hallucinated observations (EI, PI or UCB)");
+        if (nb < 1 || nb > 64) return fail(L, GPX_EARG, "ensemble_sweep_batch: nb must be in [1, 64]");
+        if (!sel_val || !sel_idx) return fail(L, GPX_EARG, "ensemble_sweep_batch: NULL sel_val / sel_idx output");
+        for (int m = 0; m < n; ++m) {
+            if (!members[m]->fitted) return fail(L, GPX_ESTATE, "ensemble_sweep_batch: a member model is not fitted");
+            if (members[m]->device != L->device || members[m]->d != L->d)
+                return fail(L, GPX_EARG, "ensemble_sweep_batch: members must share the device and the input dimension");
+            for (int o = 0; o < m; ++o)
+                if (members[o] == members[m])
+                    return fail(L, GPX_EARG, "ensemble_sweep_batch: a handle is listed twice (every member needs its own scratch)");
+        }
+        for (int m = 0; m < n; ++m)
+            if (!members[m]->cache_valid)
+                return fail(L, GPX_ESTATE, ("ensemble member " + std::to_string(m) + ": ensemble_sweep_batch: no live sweep cache (sweep with "
+                                            "option sweep_cache = 1 first)").c_str());
+        const int64_t M = L->cache_M, d = L->d;
+        for (int m = 1; m < n; ++m)
+            if (members[m]->cache_M != M) return fail(L, GPX_EARG, "ensemble_sweep_batch: the members' caches differ in size");
+        if (nb > M) return fail(L, GPX_EARG, "ensemble_sweep_batch: nb exceeds the number of cached candidates");
+        HIPCHK(L, hipSetDevice(L->device));
+        const int64_t desc_words = ((int64_t)n * (int64_t)sizeof(EnsBatchMember) + 7) / 8;
+        std::vector<BatchBuf> bufs((size_t)n);
+        L->bsel_desc.assign((size_t)n, EnsBatchMember());
+        for (int m = 0; m < n; ++m) {
+            gpx_handle* h = members[m];
+            if ((rc = ensure_inverse(h)) || (rc = flush_pending(h)) ||      // queued appends belong in the sums, on the member's own stream
+                (rc = batch_layout(h, M, nb, m == 0 ? (int64_t)n * nb + desc_words : 0, bufs[m]))) {
+                if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
+                return rc;
+            }
+            HIPCHK(L, hipStreamSynchronize(h->stream));
+            const BatchBuf& b = bufs[m];
+            EnsBatchMember& e = L->bsel_desc[m];
+            e.cq = h->dcq, e.cp = h->dcp, e.invell = h->dinvell;
+            e.qp = b.qp, e.V = b.V, e.cross = b.cross, e.scal = b.scal, e.xs = b.xs;
+            e.rho = h->rho, e.bias = h->bias, e.sn2 = h->sn2;
+        }
+        const BatchBuf& lb = bufs[0];
+        double* dsel_s2 = lb.extra;
+        EnsBatchMember* ddesc = reinterpret_cast<EnsBatchMember*>(lb.extra + (int64_t)n * nb);
+        const double p0 = params[0];
+        hipStream_t s = L->stream;
+        int differ = 0;
+        {
+            Span sp(L, T_BATCH);
+            HIPCHK(L, hipMemcpyAsync(ddesc, L->bsel_desc.data(), (size_t)n * sizeof(EnsBatchMember), hipMemcpyHostToDevice, s));
+            HIPCHK(L, hipMemsetAsync(lb.taken, 0, (size_t)lb.ntaken * 8, s));
+            HIPCHK(L, hipMemsetAsync(lb.same, 0, sizeof(int), s));
+            for (int m = 0; m < n; ++m) {
+                HIPCHK(L, hipMemsetAsync(bufs[m].flag, 0, sizeof(int), s));
+                if (m > 0) launch_ens_same_grid(s, L->dcZ, members[m]->dcZ, M * d, lb.same);
+            }
+            for (int j = 0; j < (int)nb; ++j) {
+                launch_ens_batch_score(s, j - 1, n, M, ddesc, lb.taken, acq_id, p0, lb.partv, lb.parti);
+                launch_ens_batch_pick(s, j, n, nb, M, (int)d, lb.partv, lb.parti, L->dcZ, ddesc, lb.x, lb.sel_val, lb.sel_idx,
+                                      dsel_s2, lb.taken);
+                if (j == (int)nb - 1) break;
+                for (int m = 0; m < n; ++m) batch_condition(members[m], s, bufs[m], lb.x, L->dcZ, M, j);
+            }
+            HIPCHK(L, hipGetLastError());
+        }
+        HIPCHK(L, hipMemcpyAsync(sel_val, lb.sel_val, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(L, hipMemcpyAsync(sel_idx, lb.sel_idx, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        if (sel_s2) HIPCHK(L, hipMemcpyAsync(sel_s2, dsel_s2, (size_t)n * nb * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(L, hipMemcpyAsync(&differ, lb.same, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(L, hipStreamSynchronize(s));
+        if (differ) return fail(L, GPX_EARG, "ensemble_sweep_batch: the members' caches hold different candidates");
+        return GPX_OK;
     });
 }
 

@@ -25,6 +25,14 @@ enum Timer {
 
 struct EventPair { hipEvent_t a, b; int slot; };
 
+// one member of an ensemble batch (gpx_ensemble_sweep_batch) as the kernels of kernels_batch.hip see it: the member's cached sums,
+// its model constants, and where its batch state lies in its own handle's dbsel (batch_layout, api.hip)
+struct EnsBatchMember {
+    const double *cq, *cp, *invell;
+    double *qp, *V, *cross, *scal, *xs;
+    double rho, bias, sn2;
+};
+
 }  // namespace gpx
 
 struct CholGraphKey {             // what a captured factorisation depends on (compared bytewise: zero-filled before use)
@@ -214,6 +222,7 @@ struct gpx_handle {
     // batch proposals (gpx_sweep_batch): scratch of its own, laid out in api.hip -- nothing the append / announcement paths own
     double* dbsel = nullptr;
     int64_t cap_bsel = 0;
+    std::vector<gpx::EnsBatchMember> bsel_desc;   // host source of the lead's descriptor table (gpx_ensemble_sweep_batch): outlives its copy
 
     // joint posterior (gpx_predict_cov / gpx_sample_joint): scratch of its own, laid out in api.hip (joint_core); the cross-Gram
     // of the points goes through dKs like a sweep's
@@ -354,6 +363,15 @@ void launch_batch_pick(hipStream_t s, int j, int64_t M, int d, const double* par
                        const double* invell, const double* qp, const double* V, double rho, double sn2, double* x,
                        double* xs, double* scal, double* cross, double* sel_val, int64_t* sel_idx, double* sel_s2,
                        unsigned char* taken);
+// the ensemble forms (gpx_ensemble_sweep_batch): ONE scoring pass over the candidates with all n members inside it (each member's
+// fold as above, its value or moments summed in member order, one division), the pick that leaves every member's next round on the
+// device (sel_s2: (n, nb) member-major), and the bitwise compare of two candidate sets (*flag <- 1 where a 64-bit word differs)
+void launch_ens_batch_score(hipStream_t s, int j, int n, int64_t M, const EnsBatchMember* mem, const unsigned char* taken,
+                            int acq_id, double p0, double* partv, int64_t* parti);
+void launch_ens_batch_pick(hipStream_t s, int j, int n, int64_t nb, int64_t M, int d, const double* partv, const int64_t* parti,
+                           const double* Z, const EnsBatchMember* mem, double* x, double* sel_val, int64_t* sel_idx,
+                           double* sel_s2, unsigned char* taken);
+void launch_ens_same_grid(hipStream_t s, const double* Za, const double* Zb, int64_t words, int* flag);
 
 // launchers (kernels_cov.hip): the joint posterior at cols = Mp padded points -- V = T Ks stored panel-major [cols / 128][Np][128],
 // mu = bias + V^T a (Pp: Np / 128 x cols partial sums), C = Kss - V^T V (Mp, Mp) symmetric bit for bit, B = C + add I with identity

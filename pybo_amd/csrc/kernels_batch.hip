@@ -13,6 +13,13 @@
 //   k_batch_score  one pass over the candidates: folds the raw row into v_j and q' (round 0: q' <- q), the next round's values,
 //                  and a per-block argmax partial
 // The argmax runs over a total order and every candidate's arithmetic is its own thread's: results do not depend on the grid.
+//
+// The ensemble forms (gpx_ensemble_sweep_batch: n members frozen for the batch, every member conditioned on the pick at ITS OWN
+// posterior mean) keep the recurrence per member -- its own w, d, cross terms, 1/ell, V and q' -- and share the pick:
+//   k_ens_batch_score  one pass with all members inside it: per member batch_fold (k_batch_score's statements), its value (EI / PI)
+//                      or moments (UCB), summed in member order with k_ens_accum's statements and divided once with k_ens_finish's
+//   k_ens_batch_pick   the pick, the raw x once, and per member s2, d, the cross terms, x / ell_m and sel_s2[m][j]
+//   k_ens_same_grid    the members' caches hold the same candidates, bit for bit (one flag word, read at the call's only sync)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -46,6 +53,23 @@ __device__ __forceinline__ void batch_block_argmax(double& v, int64_t& i, double
         if (batch_better(sv[ww], si[ww], v, i)) { v = sv[ww]; i = si[ww]; }
 }
 
+// The fold of round j >= 0, shared by both scoring kernels: vraw = V[j][n] as the rank-1 pass left it, qprev = q'_n.  Stores v_j[n],
+// returns the new q'_n.
+__device__ __forceinline__ double batch_fold(int j, int64_t M, int64_t n, double* __restrict__ V, const double* __restrict__ cross,
+                                             double invd, double vraw, double qprev) {
+#pragma clang fp contract(off)
+    double t = 0.0;
+    for (int l = 0; l < j; ++l) {
+        const double prod = cross[l] * V[(int64_t)l * M + n];
+        t = t + prod;
+    }
+    const double td = t * invd;
+    const double v = vraw - td;
+    V[(int64_t)j * M + n] = v;
+    const double vv = v * v;
+    return qprev + vv;
+}
+
 // j < 0: round 0, q' <- q of the cache.  j >= 0: row j of V holds the rank-1 pass's (k(x, z_n) - w . k(X, z_n)) / d; the cross
 // terms are taken off it in pick order, each product rounded before it is added (no contraction), then divided once by d.
 __global__ __launch_bounds__(256) void k_batch_score(int j, int64_t M, const double* __restrict__ cq,
@@ -65,18 +89,7 @@ __global__ __launch_bounds__(256) void k_batch_score(int j, int64_t M, const dou
         if (j < 0) {
             q = cq[n];
         } else {
-#pragma clang fp contract(off)
-            const double invd = scal[1];
-            double t = 0.0;
-            for (int l = 0; l < j; ++l) {
-                const double prod = cross[l] * V[(int64_t)l * M + n];
-                t = t + prod;
-            }
-            const double td = t * invd;
-            const double v = V[(int64_t)j * M + n] - td;
-            V[(int64_t)j * M + n] = v;
-            const double vv = v * v;
-            q = qp[n] + vv;
+            q = batch_fold(j, M, n, V, cross, scal[1], V[(int64_t)j * M + n], qp[n]);
         }
         qp[n] = q;
         const double mu = bias + cp[n];
@@ -137,6 +150,134 @@ __global__ __launch_bounds__(256) void k_batch_pick(int j, int nblk, const doubl
     }
 }
 
+// ---- the ensemble forms ---------------------------------------------------------------------------------------------------
+// k_ens_accum's statements on registers (mode 0: t0 = the member's value; mode 1: t0 = mu_m, t1 = s2_m) ...
+__device__ __forceinline__ void ens_fold(int mode, bool first, double t0, double t1, double& acc0, double& acc1) {
+#pragma clang fp contract(off)
+    if (mode == 0) {
+        acc0 = first ? t0 : acc0 + t0;
+    } else {
+        const double m2 = t0 * t0;
+        const double q = t1 + m2;
+        acc0 = first ? t0 : acc0 + t0;
+        acc1 = first ? q : acc1 + q;
+    }
+}
+
+// ... and k_ens_finish's
+__device__ __forceinline__ double ens_value(int mode, double acc0, double acc1, double n, double beta) {
+#pragma clang fp contract(off)
+    const double mu = acc0 / n;
+    if (mode == 0) return mu;
+    const double mu2 = mu * mu;
+    double s2 = acc1 / n - mu2;
+    s2 = fmax(s2, 0.0);
+    return mu + sqrt(beta * s2);
+}
+
+// One thread per candidate, the members in order inside it.  HBM-bound, n (j + 4) 8 M bytes per round: member m + 1's three
+// streaming loads (q', p, the raw row) are issued before member m's arithmetic, its cross-term rows follow as that retires.
+__global__ __launch_bounds__(256) void k_ens_batch_score(int j, int nmem, int64_t M, const EnsBatchMember* __restrict__ mem,
+                                                         const unsigned char* __restrict__ taken, int acq_id, double p0,
+                                                         double* __restrict__ partv, int64_t* __restrict__ parti) {
+    __shared__ double sv[4];
+    __shared__ int64_t si[4];
+    double bv = GPX_NEG_INF;
+    int64_t bi = GPX_IDX_NONE;
+    const int mode = (acq_id == GPX_ACQ_UCB) ? 1 : 0;
+    const double nd = (double)nmem;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < M; n += stride) {
+        double acc0 = 0.0, acc1 = 0.0;
+        double qn = (j < 0) ? mem[0].cq[n] : mem[0].qp[n];
+        double pn = mem[0].cp[n];
+        double vn = (j < 0) ? 0.0 : mem[0].V[(int64_t)j * M + n];
+        for (int m = 0; m < nmem; ++m) {
+            const EnsBatchMember& e = mem[m];
+            const double qprev = qn, p = pn, vraw = vn;
+            if (m + 1 < nmem) {
+                const EnsBatchMember& f = mem[m + 1];
+                qn = (j < 0) ? f.cq[n] : f.qp[n];
+                pn = f.cp[n];
+                if (j >= 0) vn = f.V[(int64_t)j * M + n];
+            }
+            const double q = (j < 0) ? qprev : batch_fold(j, M, n, e.V, e.cross, e.scal[1], vraw, qprev);
+            e.qp[n] = q;
+            const double mu = e.bias + p;
+            const double s2 = fmax(e.rho - q, 1e-100);
+            if (mode == 0)
+                ens_fold(0, m == 0, acq_value(acq_id, mu, s2, p0), 0.0, acc0, acc1);
+            else
+                ens_fold(1, m == 0, mu, s2, acc0, acc1);
+        }
+        if (!taken[n]) {
+            double val = ens_value(mode, acc0, acc1, nd, p0);
+            if (val != val) val = GPX_NEG_INF;
+            if (batch_better(val, n, bv, bi)) { bv = val; bi = n; }
+        }
+    }
+    batch_block_argmax(bv, bi, sv, si);
+    if (threadIdx.x == 0) {
+        partv[blockIdx.x] = bv;
+        parti[blockIdx.x] = bi;
+    }
+}
+
+// One workgroup.  Every member's scal: k_batch_pick's four words, from ITS conditioned variance at the pick.
+__global__ __launch_bounds__(256) void k_ens_batch_pick(int j, int nblk, const double* __restrict__ partv,
+                                                        const int64_t* __restrict__ parti, int64_t M, int d,
+                                                        const double* __restrict__ Z, int nmem, int64_t nb,
+                                                        const EnsBatchMember* __restrict__ mem, double* __restrict__ x,
+                                                        double* __restrict__ sel_val, int64_t* __restrict__ sel_idx,
+                                                        double* __restrict__ sel_s2, unsigned char* __restrict__ taken) {
+    __shared__ double sv[4];
+    __shared__ int64_t si[4];
+    double bv = GPX_NEG_INF;
+    int64_t bi = GPX_IDX_NONE;
+    for (int e = threadIdx.x; e < nblk; e += 256) {
+        const int64_t idx = parti[e];
+        if (idx != GPX_IDX_NONE && batch_better(partv[e], idx, bv, bi)) { bv = partv[e]; bi = idx; }
+    }
+    batch_block_argmax(bv, bi, sv, si);
+    const bool none = (bi == GPX_IDX_NONE) || bi < 0 || bi >= M;      // (cannot happen while nb <= M; never index with it)
+    const int64_t row = none ? 0 : bi;
+    const int t = threadIdx.x;
+    if (t == 0) {
+        sel_val[j] = bv;
+        sel_idx[j] = none ? -1 : bi;
+        if (!none) taken[row] = 1;
+    }
+    for (int m = t; m < nmem; m += 256) {
+        const EnsBatchMember& e = mem[m];
+        const double s2 = fmax(e.rho - e.qp[row], 1e-100);
+        const double d2 = s2 + e.sn2;
+        const double dd = sqrt(d2);
+        sel_s2[(int64_t)m * nb + j] = s2;
+        e.scal[0] = dd;
+        e.scal[1] = 1.0 / dd;
+        e.scal[2] = 0.0;
+        e.scal[3] = d2;
+    }
+    for (int c = t; c < nmem * j; c += 256) {
+        const int m = c / j, l = c - m * j;
+        mem[m].cross[l] = mem[m].V[(int64_t)l * M + row];
+    }
+    for (int k = t; k < d; k += 256) {
+        const double xv = Z[row * d + k];
+        x[k] = xv;
+        for (int m = 0; m < nmem; ++m) mem[m].xs[k] = xv * mem[m].invell[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ens_same_grid(const unsigned long long* __restrict__ a,
+                                                       const unsigned long long* __restrict__ b, int64_t words,
+                                                       int* __restrict__ flag) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    bool differ = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += stride) differ = differ || (a[i] != b[i]);
+    if (differ) *flag = 1;
+}
+
 int batch_blocks(int64_t M) {
     const int64_t b = (M + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
@@ -155,6 +296,25 @@ void launch_batch_pick(hipStream_t s, int j, int64_t M, int d, const double* par
                        unsigned char* taken) {
     hipLaunchKernelGGL(k_batch_pick, dim3(1), dim3(256), 0, s, j, batch_blocks(M), partv, parti, M, d, Z, invell, qp, V,
                        rho, sn2, x, xs, scal, cross, sel_val, sel_idx, sel_s2, taken);
+}
+
+void launch_ens_batch_score(hipStream_t s, int j, int n, int64_t M, const EnsBatchMember* mem, const unsigned char* taken,
+                            int acq_id, double p0, double* partv, int64_t* parti) {
+    hipLaunchKernelGGL(k_ens_batch_score, dim3((unsigned)batch_blocks(M)), dim3(256), 0, s, j, n, M, mem, taken, acq_id, p0,
+                       partv, parti);
+}
+
+void launch_ens_batch_pick(hipStream_t s, int j, int n, int64_t nb, int64_t M, int d, const double* partv, const int64_t* parti,
+                           const double* Z, const EnsBatchMember* mem, double* x, double* sel_val, int64_t* sel_idx,
+                           double* sel_s2, unsigned char* taken) {
+    hipLaunchKernelGGL(k_ens_batch_pick, dim3(1), dim3(256), 0, s, j, batch_blocks(M), partv, parti, M, d, Z, n, nb, mem, x,
+                       sel_val, sel_idx, sel_s2, taken);
+}
+
+void launch_ens_same_grid(hipStream_t s, const double* Za, const double* Zb, int64_t words, int* flag) {
+    hipLaunchKernelGGL(k_ens_same_grid, dim3((unsigned)batch_blocks(words)), dim3(256), 0, s,
+                       reinterpret_cast<const unsigned long long*>(Za), reinterpret_cast<const unsigned long long*>(Zb), words,
+                       flag);
 }
 
 }  // namespace gpx

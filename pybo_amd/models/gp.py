@@ -514,11 +514,10 @@ class GP(object):
         out = self._engine().sweep(kind, param, xgrid, k=int(k), want_all=False)
         return out['top_val'], out['top_idx']
 
-    def acq_batch(self, kind, param, xgrid, nb):
-        """nb grid points to evaluate in parallel: greedy EI / PI / UCB picks, each conditioned on the earlier ones at their
-        posterior mean (gpx_sweep_batch).  Returns dict(sel_val, sel_idx, sel_s2).  The cache is handled as in `acq_topk`: a
-        `DeviceGrid` this device state has swept before is only re-used, anything else (a host array too) is swept once with the
-        sweep cache on; the picks then cost one O(N M) pass each and leave model and cache as they were."""
+    def _cache_grid(self, kind, param, xgrid):
+        """Make `xgrid` the live sweep cache of this model's device state and return the engine.  As in `acq_topk`: a `DeviceGrid`
+        this device state has swept before is only re-used, anything else (a host array too) is swept once with the sweep cache
+        on."""
         eng = self._engine()
         st = self._state
         if isinstance(xgrid, DeviceGrid) and int(xgrid.device) != int(eng.device):
@@ -534,7 +533,13 @@ class GP(object):
                     eng.sweep(kind, param, np.array(xgrid, ndmin=2, dtype=float), k=1, want_all=False)
             finally:
                 eng.set_option('sweep_cache', 0)      # other sweeps of this engine must not overwrite the cache
-        return eng.sweep_batch(kind, param, int(nb))
+        return eng
+
+    def acq_batch(self, kind, param, xgrid, nb):
+        """nb grid points to evaluate in parallel: greedy EI / PI / UCB picks, each conditioned on the earlier ones at their
+        posterior mean (gpx_sweep_batch).  Returns dict(sel_val, sel_idx, sel_s2).  The cache is handled by `_cache_grid`; the
+        picks then cost one O(N M) pass each and leave model and cache as they were."""
+        return self._cache_grid(kind, param, xgrid).sweep_batch(kind, param, int(nb))
 
     def topk_engine(self):
         """The device handle whose HBM holds the (value, index) pairs of the last `acq_topk`."""

@@ -203,6 +203,12 @@ class MCMC(object):
             raise AttributeError('mean_topk')
         return self._mean_topk
 
+    @property
+    def acq_batch(self):
+        if not hasattr(self._proto, '_engine'):      # ShardedGP and stub members keep the generic path of pybo_amd.batch
+            raise AttributeError('acq_batch')
+        return self._acq_batch
+
     def predict_mean(self, X, grad=False):
         """Mixture mean only (= predict(X)[0]): the members' closed forms at the data where they have one
         (EI / PI targets and the recommenders ask for the mean at the observed points, pybo/policies/simple.py:21,35,
@@ -385,6 +391,19 @@ class MCMC(object):
             xgrid = np.array(xgrid, ndmin=2, dtype=float)
         out = Engine.ensemble_sweep(self._engines(), kind, param, xgrid, k=int(k), want_all=False)
         return out['top_val'], out['top_idx']
+
+    def _acq_batch(self, kind, param, xgrid, nb):
+        """nb grid points to evaluate in parallel, on the device (gpx_ensemble_sweep_batch): greedy picks of the ENSEMBLE's EI / PI /
+        UCB with the members FROZEN for the batch -- no chain step, no refit -- and every member conditioned on a pick at its own
+        posterior mean.  Every member's sweep cache is brought onto `xgrid` first (`GP._cache_grid`: a `DeviceGrid` that member's
+        state has swept before is re-used, anything else is swept once with the cache on).  Returns dict(sel_val (nb,), sel_idx
+        (nb,), sel_s2 (n, nb))."""
+        from .._lib import Engine, DeviceGrid
+        members = self._need()
+        if not isinstance(xgrid, DeviceGrid) or int(xgrid.device) != int(members[0].device):
+            xgrid = np.array(xgrid, ndmin=2, dtype=float)        # one host copy for all members
+        engines = [m._cache_grid(kind, param, xgrid) for m in members]
+        return Engine.ensemble_batch(engines, kind, param, int(nb))
 
     # -- pickling: hyper-parameter states + data, members are rebuilt on load -------------------------
     def __getstate__(self):
