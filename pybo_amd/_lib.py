@@ -783,18 +783,18 @@ class Engine(object):
 
     def prune_report(self, vectors=True):
         """Diagnostic (gpx_prune_report in csrc/gpx_diag.h): what the last sweep decided about pruning.  dict(path, M, k, G, Gg, done, cap,
-        nsurv, S, delta, tau, gate_s2, thr_key, kept, bound_kernel = 'generic' / 'mfma' (None: no bound pass), guard = the matrix-pipe
+        nsurv, S, delta, tau, gate_s2, thr_key, kept, bound_kernel = 'generic' / 'mfma' / 'mfma32' (None: no bound pass), guard = the matrix-pipe
         kernel's (d + 4)(R_x + R_z)^2 (NaN where the host chose the generic kernel)); with `vectors`, where the bound pass ran, also ub (M,) as the survivor pass read
         it and idx, the survivors in compaction order (empty where it fell back); after a sweep with option prune_keep = 1 also ub_kept
         and seed_idx, the bounds and the seed list before the scatter.  nR (block rows of the second bound's prefix, 0: it did not
         run) and nsurv2 (survivors of its cut); with `vectors`, nR > 0 and prune_keep = 1 also ub2, qR (aligned with idx) and idx2 (the
-        second-level list)."""
+        second-level list).  E: the fp32 kernel's relative margin (NaN where it was not considered)."""
         scal = np.full(20, np.nan)
         self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), None, None, 0, None, None, 0))
         names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'S', 'delta', 'tau', 'gate_s2', 'thr_key', 'kept',
-                 'bound_kernel', 'guard', 'nR', 'nsurv2')
+                 'bound_kernel', 'guard', 'nR', 'nsurv2', 'E')
         r = dict(zip(names, scal.tolist()))
-        r['bound_kernel'] = None if np.isnan(r['bound_kernel']) else ('generic', 'mfma')[int(r['bound_kernel'])]
+        r['bound_kernel'] = None if np.isnan(r['bound_kernel']) else ('generic', 'mfma', 'mfma32')[int(r['bound_kernel'])]
         for n in ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'kept', 'nR', 'nsurv2'):
             r[n] = int(r[n])
         r['path'] = self.PRUNE_PATHS[r['path']]

@@ -149,7 +149,7 @@ static const Option kOptions[] = {
      [](gpx_handle* h, int64_t v) { h->cache_on = (v == 1); if (v < 0) { h->cache_valid = false; h->npend = 0; } }},
     {"prune", SHIP, -1, 1, "prune must be -1 (by size and gate), 0 (never) or 1 (wherever legal)", store<&gpx_handle::prune>},
     {"prune_keep", DIAG, 0, 1, "prune_keep must be 0 or 1", store<&gpx_handle::prune_keep>},
-    {"prune_bound", DIAG, -1, 1, "prune_bound must be -1 (by guard), 0 (generic kernel) or 1 (matrix-pipe kernel)", store<&gpx_handle::prune_bound>},
+    {"prune_bound", DIAG, -1, 2, "prune_bound must be -1 (by guard), 0 (generic kernel), 1 (matrix-pipe kernel) or 2 (fp32 matrix-pipe kernel)", store<&gpx_handle::prune_bound>},
     {"prune_rows", DIAG, -1, 1000000, "prune_rows must be -1 (by size), 0 (no second bound) or a number of block rows", store<&gpx_handle::prune_rows>},
     {"short_map", DIAG, -1, 1, "short_map must be -1 (by size), 0 (never) or 1 (wherever tile map 3 is in use)", store<&gpx_handle::short_map>},
     {"chol_w", SHIP, 0, 8, "chol_w must be 0 (by size) or in [2, 8]", store<&gpx_handle::chol_w>, [](int64_t v) { return v != 1; }},
@@ -409,12 +409,13 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
             HIPCHK(h, hipMemcpy(sc, r.sc, sizeof sc, hipMemcpyDeviceToHost));
             HIPCHK(h, hipMemcpy(st, r.st, sizeof st, hipMemcpyDeviceToHost));
         }
-        const bool guarded_bound = bound && r.bound_kernel < 0;      // the device chose the bound pass's kernel: sc[8] = guard value, sc[9] = choice
+        // the device chose the bound pass's kernel: sc[8] = guard value, sc[9] = a matrix-pipe kernel ran, sc[12] = the fp32 one, sc[10] = its E
+        const bool guarded_bound = bound && r.bound_kernel < 0;
         const double out[20] = {(double)r.path, (double)r.M,     (double)r.k, (double)r.G, (double)r.Gg,
                                 (double)r.done, (double)r.cap,   (double)r.nsurv, sc[0],   sc[1],
                                 sc[5],          r.mean_s2,       bound ? (double)st[2] : NAN, r.kept ? 1.0 : 0.0,
-                                bound ? (guarded_bound ? sc[9] : 0.0) : NAN, guarded_bound ? sc[8] : NAN,
-                                (double)r.nR,   (double)r.nsurv2, NAN, NAN};
+                                bound ? (guarded_bound ? sc[9] + sc[12] : 0.0) : NAN, guarded_bound ? sc[8] : NAN,
+                                (double)r.nR,   (double)r.nsurv2, guarded_bound ? sc[10] : NAN, NAN};
         for (int i = 0; i < nscal && i < 20; ++i) scal[i] = out[i];
         if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
         const int64_t nidx = std::min(std::min(r.nsurv, r.cap), cap_idx);
@@ -1109,12 +1110,15 @@ static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t e
 
 // The bound pass's dots: out[n] = alpha2 . k(X, z_n) for the M candidates and w.sc[0 .. 1] = S, delta,
 // so that EI((bias + out[n]) + delta, s2 = rho) >= the value the exact chain returns.  bound_mfma: the matrix-pipe form for SE-ARD
-// up to d = 18 where its guard allows (decided on the device).
+// up to d = 18 where its guard allows (decided on the device), in fp32 with its own margin added (out[n] = dot_hi, bound_f32.h) where
+// that link's guards allow as well and the pass is long enough to matter (option prune_bound = 2: wherever the kernel exists).
+static const int64_t BOUND_F32_MIN_M = 131072;
 static void bound_dots(gpx_handle* h, const double* dXc, int64_t M, const PruneWs& w, bool bound_mfma, double* out) {
     hipStream_t s = h->stream;
     launch_prune_alpha(s, h->dU, h->Np, h->da, h->rho, h->bias, w.alpha2, w.sabs, w.sc);
     if (bound_mfma)
-        launch_bound_mfma(s, h->dXs, h->N, h->Np, (int)h->d, w.alpha2, h->rho, dXc, M, h->dinvell, h->prune_bound, w.bws, w.sc, out);
+        launch_bound_mfma(s, h->dXs, h->N, h->Np, (int)h->d, w.alpha2, h->rho, dXc, M, h->dinvell, h->prune_bound, M >= BOUND_F32_MIN_M, w.bws,
+                          w.sc, out);
     launch_sweep_rank1_v(s, h->dXs, h->N, (int)h->d, w.alpha2, h->Np, w.sc + 2, dXc, M, h->dinvell, h->kernel_id, h->rho,
                          nullptr, out, bound_mfma ? w.sc + 9 : nullptr);
 }

@@ -2,7 +2,7 @@
 # Build libgpx.so and libgpx_diag.so for gfx950 in-tree (the .so files are git-ignored).
 #   build.sh          compile the objects that are older than their inputs (incremental: development)
 #   build.sh --force  compile EVERY object from source (what __graft_entry__.build() runs: the driver's build check must
-#                     compile all twelve translation units, also on a snapshot that shipped up-to-date .o files)
+#                     compile all thirteen translation units, also on a snapshot that shipped up-to-date .o files)
 # The two libraries link the same objects but one: diag_flag.cpp, compiled twice (diag_flag.o, and diag_flag_diag.o with
 # -DGPX_DIAGNOSTICS), decides whether gpx_set_option accepts the diagnostic knobs of gpx_diag.h.  The test-suite drives
 # libgpx_diag.so (tests/conftest.py: GPX_DIAGNOSTICS=1); everything else loads libgpx.so.
@@ -14,7 +14,7 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-const-variable $EXTRA"
 SRCS="kernels_fit kernels_chol_tg kernels_sweep kernels_rff kernels_grad kernels_hyper kernels_ens kernels_batch kernels_cov comm api"
-HDRS="bound_exp.h gemm_core.h sweep_map.h gpx_internal.h gpx_diag.h gpx_math.h fit_tiles.h ../../include/gpx.h"
+HDRS="bound_exp.h bound_f32.h gemm_core.h sweep_map.h gpx_internal.h gpx_diag.h gpx_math.h fit_tiles.h ../../include/gpx.h"
 FORCE=0
 [ "$1" = "--force" ] && FORCE=1
 pids=()
@@ -36,9 +36,11 @@ for f in $SRCS; do
   compile $f.o $f.hip
   OBJS="$OBJS $f.o"
 done
+compile kernels_bound32.o kernels_bound32.hip -fno-slp-vectorize      # (why: the file's header)
+OBJS="$OBJS kernels_bound32.o"
 compile diag_flag.o diag_flag.cpp -x c++                      # host code only (as HIP it would export one more symbol)
 compile diag_flag_diag.o diag_flag.cpp -x c++ -DGPX_DIAGNOSTICS
 for p in "${pids[@]}"; do wait $p; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o libgpx.so $OBJS diag_flag.o -ldl
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o libgpx_diag.so $OBJS diag_flag_diag.o -ldl
-echo "built $(pwd)/libgpx.so and libgpx_diag.so ($n of $(($(echo $SRCS | wc -w) + 2)) objects compiled)"
+echo "built $(pwd)/libgpx.so and libgpx_diag.so ($n of $(($(echo $SRCS | wc -w) + 3)) objects compiled)"

@@ -22,7 +22,9 @@
  *                     the seeds are scattered, and of the bound pass's dots (three device-to-device copies, no other change), for
  *                     gpx_prune_report and gpx_prune_dots [0]
  *   "prune_bound"     the kernel of a pruned sweep's bound pass: 0 the generic k_sweep_rankq<1>; 1 the matrix-pipe kernel wherever it exists
- *                     (SE-ARD, d <= 18), whatever its guard says; -1 by the guard [-1]
+ *                     (SE-ARD, d <= 18), whatever its guard says; 2 the fp32 matrix-pipe kernel, which adds its own error margin to each
+ *                     dot (csrc/bound_f32.h), wherever it exists, whatever the guards say; -1 by the guards, the fp32 kernel only from
+ *                     131072 candidates on [-1]
  *   "prune_rows"      block rows of the row prefix behind a pruned sweep's second bound: 0 never (the
  *                     single bound alone); n > 0: min(n, nP, N / 128) rows wherever the first level pruned; -1 by size: nP / 4 rows where
  *                     M >= 32768, nP >= 32 and more than Gg candidates survived the first bound [-1]
@@ -63,9 +65,10 @@ int64_t gpx_chol_tasks2(int nblocks, int chunks, int16_t *out, int64_t cap, int6
  * scal[0 .. min(nscal, 20)) = { path: 0 plain (not legal or not tried), 1 the gate declined, 2 pruned, 3 the bound pass ran but more than
  * cap candidates survived and the plain loop evaluated everything;  M;  k;  G (seeds);  Gg (the gate's generation);  done (leading
  * candidates evaluated before the bound pass);  cap;  nsurv;  S;  delta;  tau (the k-th best seed value);  the gate's mean s2 (NaN: no
- * gate);  the seeds' threshold key;  1 if the kept copies exist;  the bound pass's kernel, 0 generic / 1 matrix pipe;  the guard's (d + 4) (R_x + R_z)^2
+ * gate);  the seeds' threshold key;  1 if the kept copies exist;  the bound pass's kernel, 0 generic / 1 matrix pipe / 2 matrix pipe in fp32;  the guard's (d + 4) (R_x + R_z)^2
  * (NaN where the host chose the generic kernel: another covariance, d > 18, prune_bound = 0);  nR, the block rows of the second bound's
- * prefix (0: it did not run);  nsurv2, the survivors of its cut (the candidates evaluated exactly on path 2 where nR > 0);  two reserved (NaN) }.  S .. tau, the key and the last two are NaN for paths 0 and 1.
+ * prefix (0: it did not run);  nsurv2, the survivors of its cut (the candidates evaluated exactly on path 2 where nR > 0);  E, the relative margin of the
+ * fp32 kernel (csrc/bound_f32.h; NaN where that kernel was not considered);  one reserved (NaN) }.  S .. tau, the key and the last two are NaN for paths 0 and 1.
  * ub (optional, M): the bound vector as the survivor pass read it (-inf where a candidate was evaluated as gate or seed);  idx
  * (optional, cap_idx): the first min(nsurv, cap, cap_idx) survivors in the order they were compacted;  ub_kept (optional, M) and
  * seed_idx (optional, cap_seed; G entries): the bound vector and the seed list before the scatter -- only after a sweep that ran with

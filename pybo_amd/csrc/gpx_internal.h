@@ -186,7 +186,7 @@ struct gpx_handle {
         const double* delta = nullptr;    // n: the members' delta_m
     } ens_rec;
     int prune_keep = 0;       // diagnostic option: keep those two device copies
-    int prune_bound = -1;     // diagnostic option: the bound pass's kernel (-1 by guard, 0 k_sweep_rankq<1>, 1 k_bound_mfma wherever SE-ARD, d <= 18)
+    int prune_bound = -1;     // diagnostic option: the bound pass's kernel (-1 by guard, 0 k_sweep_rankq<1>, 1 k_bound_mfma / 2 k_bound_mfma32 wherever SE-ARD, d <= 18)
     int prune_rows = -1;      // diagnostic option: block rows of the second bound's row prefix (-1 by size: nP / 4, 0 never, n > 0: min(n, nP, N / 128) wherever the first level pruned)
     int short_map = -1;       // diagnostic option: the short form of tile map 3 (sweep_map.h) -1 by size (launches that cannot fill the per-XCD patches), 0 never, 1 always
     char* dkeep = nullptr;    // [ub M][seed idx G][dots M]
@@ -303,11 +303,18 @@ int64_t topk_blocks(int64_t M);
 void launch_prune_alpha(hipStream_t s, const double* U, int64_t Np, const double* a, double rho, double bias, double* alpha2,
                         double* sabs, double* sc);
 // the bound pass's dot for SE-ARD with the distances on the matrix pipe: KS = k-steps of its inner product (0: not for this model),
-// workspace words, and prologue + guard + kernel (sc[9] = 1.0: it wrote `out`; 0.0: launch_sweep_rank1_v(.., skip = sc + 9) does)
+// workspace words, and prologue + guard + kernel (sc[9] = 1.0: one of them wrote `out`; 0.0: launch_sweep_rank1_v(.., skip = sc + 9) does)
+constexpr int BM_SC_RX2 = 6, BM_SC_RZ2 = 7, BM_SC_GUARD = 8, BM_SC_USE = 9;      // slots of sc[] (0 .. 5: k_prune_delta, gate, tau)
+// the fp32 link (bound_f32.h): E, 1.0 where a weight is outside fp32's normal range, 1.0 where k_bound_mfma32 writes the dots
+// (sc[USE] is 1.0 then as well: the generic kernel skips on it, k_bound_mfma on this one), the margin's factor and flush term
+constexpr int BM_SC_E32 = 10, BM_SC_BADW = 11, BM_SC_USE32 = 12, BM_SC_FAC32 = 13, BM_SC_FLUSH32 = 14;
 int bound_mfma_ks(int kernel_id, int d);
 int64_t bound_mfma_ws_words(int64_t Np);
 void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
-                       const double* Z, int64_t M, const double* invell, int force, double* ws, double* sc, double* out);
+                       const double* Z, int64_t M, const double* invell, int force, bool allow32, double* ws, double* sc, double* out);
+// the fp32 link's kernel alone (kernels_bound32.hip; launch_bound_mfma calls it behind its guard): operands as k_bound_aug wrote them
+void launch_bound_mfma32(hipStream_t s, const float* A32, const float* W32, const float* NX32, int KS, bool nc, int ntile, int d,
+                         const double* Z, int64_t M, const double* invell, const double* cen, const double* sc, double* out);
 void launch_prune_ub(hipStream_t s, const double* dots, double* ub, int64_t M, int64_t skip, const double* sc, double rho,
                      double bias, double p0);
 // the second bound: ub2[j0 + n] = EI((bias + dots[idx[j0 + n]]) + delta, fmax(rho - sum_{rb < nR} Qp[rb][n], 1e-100)) for the chunk's

@@ -154,4 +154,12 @@ __device__ __forceinline__ double acq_value(int acq_id, double mu, double s2, do
     }
 }
 
+// (the bound pass's matrix-pipe kernels, kernels_sweep.hip and kernels_bound32.hip)
+// z~ of one candidate coordinate: the cross-Gram's own scaled value, then the centring -- two roundings, never one fused
+__device__ __forceinline__ double bound_zt(double z, double invell, double c) {
+#pragma clang fp contract(off)
+    const double zs = z * invell;
+    return zs - c;
+}
+
 }  // namespace gpx

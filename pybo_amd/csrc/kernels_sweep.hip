@@ -18,6 +18,7 @@
 #include "gpx_internal.h"
 #include "gpx_math.h"
 #include "bound_exp.h"
+#include "bound_f32.h"
 #include "sweep_map.h"
 
 namespace gpx {
@@ -820,8 +821,6 @@ void launch_prune_alpha(hipStream_t s, const double* U, int64_t Np, const double
 // guard k_bound_guard derives from them: sc[9] = 1.0 says this kernel runs, 0.0 says k_sweep_rankq<1> does (both read it).
 // ------------------------------------------------------------------------------------------------
 constexpr int BM_KS_MAX = 5;               // d + 2 <= 20: the candidates' fragments stay in registers (8 KS doubles per lane)
-constexpr int BM_SC_RX2 = 6, BM_SC_RZ2 = 7, BM_SC_GUARD = 8, BM_SC_USE = 9;      // slots of sc[] (0 .. 5: k_prune_delta, gate, tau)
-
 int bound_mfma_ks(int kernel_id, int d) { return (kernel_id == GPX_KERN_SE_ARD && d + 2 <= 4 * BM_KS_MAX) ? (d + 5) / 4 : 0; }
 
 // the norms go through the accumulator where that saves an MFMA per tile; the k-steps of the kernel either way
@@ -867,6 +866,7 @@ __global__ __launch_bounds__(256) void k_bound_centre(const double* __restrict__
     if (threadIdx.x == 0) {
         sc[BM_SC_RX2] = 0.0;
         sc[BM_SC_RZ2] = 0.0;
+        sc[BM_SC_BADW] = 0.0;
     }
 }
 
@@ -874,13 +874,16 @@ __global__ __launch_bounds__(256) void k_bound_centre(const double* __restrict__
 // 16 t + (l & 15) at A[(t KS + ks) 64 + l] -- one coalesced 512-byte read per wave and k-step.  W4[16 t + 4 g + r] = rho alpha2 of row
 // 16 t + g + 4 r: the four weights of a lane's four results (C/D row = (l >> 4) + 4 r) as one 32-byte read.  Rows from N on: zeros.
 // NX4 (non-null: the norms go through the accumulator): -|x~|^2 / 2 in W4's order, and the rows are [x~_1 .. x~_d] alone.
+// A32 (non-null: the fp32 link may run): the same three arrays once more in fp32, at A32, A32 + 4 KS Np and, with NX4, Np behind that --
+// the coordinates and the norm times log2(e), each rounded once from the fp64 value; weights and norms in row order -- and sc[BADW] = 1.0 where a weight is neither 0
+// nor a normal fp32 number.
 __global__ __launch_bounds__(256) void k_bound_aug(const double* __restrict__ Xs, int64_t N, int64_t Np, int d, int KS,
                                                    const double* __restrict__ cen, const double* __restrict__ alpha2, double rho,
                                                    double* __restrict__ A, double* __restrict__ W4, double* __restrict__ NX4,
-                                                   double* __restrict__ sc) {
+                                                   float* __restrict__ A32, double* __restrict__ sc) {
     __shared__ double red[256];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;       // (Np is a multiple of 128)
-    double n2 = 0.0;
+    double n2 = 0.0, badw = 0.0;
     if (i < Np) {
         const int64_t t = i >> 4;
         const int row = (int)(i & 15);
@@ -895,19 +898,21 @@ __global__ __launch_bounds__(256) void k_bound_aug(const double* __restrict__ Xs
             if (live && !NX4 && k == d) v = -0.5 * n2;
             if (live && !NX4 && k == d + 1) v = 1.0;
             At[(k >> 2) * 64 + (k & 3) * 16] = v;
+            if (A32) A32[t * KS * 64 + row + (k >> 2) * 64 + (k & 3) * 16] = (float)((live && k <= d) ? B32_LOG2E * v : v);
         }
         const int g = row & 3, r = row >> 2;                          // row = g + 4 r
-        W4[t * 16 + 4 * g + r] = live ? rho * alpha2[i] : 0.0;
+        const double wt = live ? rho * alpha2[i] : 0.0;
+        W4[t * 16 + 4 * g + r] = wt;
         if (NX4) NX4[t * 16 + 4 * g + r] = live ? -0.5 * n2 : 0.0;
+        if (A32) {
+            float* W32 = A32 + Np * 4 * KS;
+            W32[i] = (float)wt;      // (row order: the fp32 MFMA's C/D row is 4 (l >> 4) + r, a lane's four results are four neighbouring rows)
+            if (NX4) W32[Np + i] = live ? (float)(B32_LOG2E * (-0.5 * n2)) : 0.0f;
+            badw = bound32_bad_weight(wt);
+        }
     }
     block_max_nonneg(n2, sc + BM_SC_RX2, red);
-}
-
-// z~ of one candidate coordinate: the cross-Gram's own scaled value, then the centring -- two roundings, never one fused
-__device__ __forceinline__ double bound_zt(double z, double invell, double c) {
-#pragma clang fp contract(off)
-    const double zs = z * invell;
-    return zs - c;
+    if (A32) block_max_nonneg(badw, sc + BM_SC_BADW, red);
 }
 
 // sc[RZ2] = max_n |z~_n|^2 over the candidates (NaN rows are not recorded: their bound is NaN whatever the kernel; an infinite
@@ -927,11 +932,25 @@ __global__ __launch_bounds__(256) void k_bound_rz(const double* __restrict__ Z, 
 
 // The guard: the inner-product form's exponent errs by at most (d + 4) u (R_x + R_z)^2, which the margin
 // delta / 2 has room for while that is at most Np u.  force: -1 by guard, 1 the matrix-pipe kernel whatever the guard says.
-__global__ void k_bound_guard(int d, int64_t Np, int force, double* __restrict__ sc) {
+// The fp32 link (want32: its operands exist and the host's size rule allows it; force 2: whatever the guards say) runs where the fp64
+// guard passes, E <= 2^-10 and every weight is 0 or a normal fp32 number; sc[E32] is NaN where it was not considered.
+__global__ void k_bound_guard(int d, int64_t Np, int force, int want32, double rho, double* __restrict__ sc) {
     const double R = sqrt(sc[BM_SC_RX2]) + sqrt(sc[BM_SC_RZ2]);
     const double gv = (double)(d + 4) * R * R;
+    const bool use64 = force > 0 || gv <= (double)Np;
     sc[BM_SC_GUARD] = gv;
-    sc[BM_SC_USE] = (force > 0 || gv <= (double)Np) ? 1.0 : 0.0;
+    sc[BM_SC_USE] = use64 ? 1.0 : 0.0;
+    double E = __builtin_nan(""), use32 = 0.0, fac = 0.0, fl = 0.0;
+    if (want32) {
+        E = bound32_E(d, (double)(Np / 16), gv);
+        use32 = (force == 2 || (use64 && E <= B32_E_MAX && sc[BM_SC_BADW] == 0.0)) ? 1.0 : 0.0;
+        fac = bound32_factor(E, sc[BM_SC_BADW]);
+        fl = bound32_flush(rho * sc[0] * (1.0 + 0x1p-20), (double)Np);
+    }
+    sc[BM_SC_E32] = E;
+    sc[BM_SC_USE32] = use32;
+    sc[BM_SC_FAC32] = fac;
+    sc[BM_SC_FLUSH32] = fl;
 }
 
 // One workgroup owns 128 candidates (8 column tiles of 16, their fragments in registers for the whole walk); wave w walks the
@@ -947,7 +966,7 @@ __global__ __launch_bounds__(256, (KS + (NC ? 1 : 0) <= 3) ? 4 : 3) void k_bound
                                                        const double* __restrict__ sc, double* __restrict__ out) {
     __shared__ double red[4][XN];
     __shared__ double tab[BEXP_NT];
-    if (sc[BM_SC_USE] != 1.0) return;
+    if (sc[BM_SC_USE] != 1.0 || sc[BM_SC_USE32] == 1.0) return;
     if (threadIdx.x < BEXP_NT) tab[threadIdx.x] = kBoundExpTab[threadIdx.x];
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (w in a scalar register: the walk's loop is uniform)
     const int col = lane & 15, g = lane >> 4;
@@ -1039,23 +1058,28 @@ __global__ __launch_bounds__(256, (KS + (NC ? 1 : 0) <= 3) ? 4 : 3) void k_bound
     }
 }
 
-// Prologue, guard and the matrix-pipe kernel on stream s.  ws: [A Np x 4 KS][W4 Np][NX4 Np, where the norms go through the accumulator:
-// KS <= 4 there][cen 4 BM_KS_MAX at its fixed place]; sc: the bound pass's 16 scalars.
-// The caller launches the generic kernel behind it with sc + BM_SC_USE as its `skip`: exactly one of the two writes `out`.
-int64_t bound_mfma_ws_words(int64_t Np) { return Np * 4 * BM_KS_MAX + Np + 4 * BM_KS_MAX; }
+// Prologue, guard and the matrix-pipe kernels on stream s.  ws: [A Np x 4 KS][W4 Np][NX4 Np, where the norms go through the accumulator:
+// KS <= 4 there][cen 4 BM_KS_MAX at its fixed place][the fp32 copies: A Np x 4 KS, W4 Np, NX4 Np floats]; sc: the bound pass's 16 scalars.
+// force: the option prune_bound (-1, 1, 2); allow32: the host's size rule lets the fp32 link run by its guards.
+// The caller launches the generic kernel behind it with sc + BM_SC_USE as its `skip`: exactly one of the three writes `out`.
+int64_t bound_mfma_ws_words(int64_t Np) { return Np * 4 * BM_KS_MAX + Np + 4 * BM_KS_MAX + Np * 2 * BM_KS_MAX + Np; }
 
 void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
-                       const double* Z, int64_t M, const double* invell, int force, double* ws, double* sc, double* out) {
+                       const double* Z, int64_t M, const double* invell, int force, bool allow32, double* ws, double* sc, double* out) {
     const int KS = bound_mfma_steps(d);
     const bool nc = bound_mfma_normc(d);
     double* A = ws;
     double* W4 = A + Np * 4 * KS;
     double* NX4 = nc ? W4 + Np : nullptr;
     double* cen = ws + Np * 4 * BM_KS_MAX + Np;
+    const bool want32 = force == 2 || (force < 0 && allow32);
+    float* A32 = want32 ? reinterpret_cast<float*>(cen + 4 * BM_KS_MAX) : nullptr;
+    const float* W32 = want32 ? A32 + Np * 4 * KS : nullptr;
+    const float* NX32 = (want32 && nc) ? W32 + Np : nullptr;
     hipLaunchKernelGGL(k_bound_centre, dim3(1), dim3(256), 0, s, Xs, N, d, cen, sc);
-    hipLaunchKernelGGL(k_bound_aug, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, Xs, N, Np, d, KS, cen, alpha2, rho, A, W4, NX4, sc);
+    hipLaunchKernelGGL(k_bound_aug, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, Xs, N, Np, d, KS, cen, alpha2, rho, A, W4, NX4, A32, sc);
     hipLaunchKernelGGL(k_bound_rz, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, Z, M, d, invell, cen, sc);
-    hipLaunchKernelGGL(k_bound_guard, dim3(1), dim3(1), 0, s, d, Np, force, sc);
+    hipLaunchKernelGGL(k_bound_guard, dim3(1), dim3(1), 0, s, d, Np, force, want32 ? 1 : 0, rho, sc);
     const dim3 grid((unsigned)((M + XN - 1) / XN));
     const int ntile = (int)(Np / 16);
 #define GPX_BM(K, C) hipLaunchKernelGGL((k_bound_mfma<K, C>), grid, dim3(256), 0, s, A, W4, NX4, ntile, d, Z, M, invell, cen, sc, out)
@@ -1071,6 +1095,8 @@ void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, i
         default: GPX_BM(5, false); break;
     }
 #undef GPX_BM
+    if (!want32) return;
+    launch_bound_mfma32(s, A32, W32, NX32, KS, nc, ntile, d, Z, M, invell, cen, sc, out);
 }
 
 // ub[n] <- EI((bias + dots[n]) + delta, s2 = rho), dots[n] = alpha2 . k(X, z_n), by k_acq's own function; -inf for the `skip`
