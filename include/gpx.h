@@ -67,15 +67,15 @@ int gpx_version(void);
 /* Options (int64 values).  Every option below selects among schedules that give BIT-IDENTICAL results unless it says
  * otherwise; defaults in brackets.  The measurements behind the defaults: DESIGN.md section 4.
  *   "chunk"          candidate columns per sweep chunk, a multiple of 128 [by size: 65536; 131072 up to N = 4096]
- *   "tile_order"     sweep-kernel schedule: bits 0-1 blockIdx->tile map (0 linear heavy-first, 1 per-XCD candidate slices, 2 per-XCD
- *                    8x8 super-tiles, 3 the same with every workgroup computing the PAIR of tiles (nP-1-i, nt), (i, nt): equal work),
- *                    bits 2-4 k-loop (4 = operands by LDS-DMA, k-step 32, two workgroups per CU, the all-zero quarter-rows of T's
- *                    diagonal block skipped; 3 = the same without the skip; 1 = barrier-free, every wave fetching its own operand
- *                    halves; 7 = k-step 16, three workgroups per CU; 6 / 5 / 2 = the
- *                    register-staged loops of rounds 5 / 2 / 1: independently scheduled witnesses) [-1 = by size: 7 below 32 block rows, else 19]
+ *   "tile_order"     sweep-kernel schedule: bits 0-1 blockIdx->tile map (0 linear heavy-first, 1 per-XCD candidate slices, 2 per-XCD 8x8 super-tiles, 3 the
+ *                    same with every workgroup computing the PAIR of tiles (nP-1-i, nt), (i, nt): equal work), bits 2-4 k-loop (4 = operands by LDS-DMA,
+ *                    k-step 32, two workgroups per CU, the all-zero quarter-rows of T's diagonal block skipped; 3 = the same without the skip; 1 =
+ *                    barrier-free, every wave fetching its own operand halves; 7 = k-step 16, three workgroups per CU; 6 / 5 / 2 = the register-staged loops
+ *                    of rounds 5 / 2 / 1: independently scheduled witnesses) [-1 = by size: 7 below 32 block rows, else 19]
  *   "super_m"        rows of the XCD super-tile of 64 workgroups: 1, 2, 4, 8, 16 [8 -> 8 x 8]
  *   "sweep_cache"    1: full sweeps keep candidates and reduced sums for gpx_sweep_update; 0: leave a live cache alone; -1: drop it [0]
  *   "prune"          EI sweeps for ONLY the top-k (ensembles: members[0]'s value) skip what a bound rules out: -1 by size and gate, 0 never, 1 where legal [-1]
+ *                    (-1: a sweep whose pruning paid lets the next of the same shape skip the gate: kept across fits / appends, dropped by ANY gpx_set_option)
  *   "eager_inverse"  1: form the triangular inverse inside gpx_fit instead of on first use [0]
  *   "trtri_ahead"    1: when the inverse is certain or likely to follow a fit, its part that needs only the factor's leading block
  *                    rows runs on a side stream behind the factorisation's tail, from "trtri_ahead_min" (8) blocks on [1]

@@ -788,12 +788,14 @@ class Engine(object):
         it and idx, the survivors in compaction order (empty where it fell back); after a sweep with option prune_keep = 1 also ub_kept
         and seed_idx, the bounds and the seed list before the scatter.  nR (block rows of the second bound's prefix, 0: it did not
         run) and nsurv2 (survivors of its cut); with `vectors`, nR > 0 and prune_keep = 1 also ub2, qR (aligned with idx) and idx2 (the
-        second-level list).  E: the fp32 kernel's relative margin (NaN where it was not considered)."""
+        second-level list).  E: the fp32 kernel's relative margin (NaN where it was not considered).  gate_hint: this sweep skipped its gate
+        on the decision carried from the last one (csrc/prune_hint.h; then done = 0 and gate_s2 is NaN)."""
         scal = np.full(20, np.nan)
         self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), None, None, 0, None, None, 0))
         names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'S', 'delta', 'tau', 'gate_s2', 'thr_key', 'kept',
-                 'bound_kernel', 'guard', 'nR', 'nsurv2', 'E')
+                 'bound_kernel', 'guard', 'nR', 'nsurv2', 'E', 'gate_hint')
         r = dict(zip(names, scal.tolist()))
+        r['gate_hint'] = r['gate_hint'] == 1.0
         r['bound_kernel'] = None if np.isnan(r['bound_kernel']) else ('generic', 'mfma', 'mfma32')[int(r['bound_kernel'])]
         for n in ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'kept', 'nR', 'nsurv2'):
             r[n] = int(r[n])
@@ -818,18 +820,19 @@ class Engine(object):
     @staticmethod
     def ensemble_prune_report(engines, vectors=True):
         """Diagnostic (gpx_ensemble_prune_report in csrc/gpx_diag.h): what the last ensemble sweep led by engines[0] decided about pruning.
-        dict(path, M, k, G, Gg, done, cap, nsurv, tau, gate, delta (n,)); with `vectors`, where the bound pass ran, also ub (M,), the ensemble
+        dict(path, M, k, G, Gg, done, cap, nsurv, tau, gate, delta (n,), gate_hint: the gate was skipped on the carried decision); with `vectors`, where the bound pass ran, also ub (M,), the ensemble
         bound as the survivor pass read it, and idx, the survivors in compaction order (empty where it fell back)."""
         lead = engines[0]
         handles = (_P * len(engines))(*[e._h for e in engines])
-        scal = np.full(10 + len(engines), np.nan)
+        scal = np.full(11 + len(engines), np.nan)
         lead._check(lead._lib.gpx_ensemble_prune_report(handles, len(engines), _ptr(scal), len(scal), None, None, 0))
         names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'tau', 'gate')
         r = dict(zip(names, scal[:10].tolist()))
         for n in names[:8]:
             r[n] = int(r[n])
         r['path'] = Engine.PRUNE_PATHS[r['path']]
-        r['delta'] = scal[10:].copy()
+        r['delta'] = scal[10:10 + len(engines)].copy()
+        r['gate_hint'] = scal[10 + len(engines)] == 1.0
         if vectors and r['path'] in ('pruned', 'fell back'):
             nidx = r['nsurv'] if r['path'] == 'pruned' else 0
             r['ub'] = np.empty(r['M'])

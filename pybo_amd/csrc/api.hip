@@ -187,7 +187,11 @@ static const Option kOptions[] = {
 
 extern "C" int gpx_set_option(gpx_handle* h, const char* name, int64_t value) {
     return guarded(h, [&]() -> int {
-        if (!h || !name) return GPX_EARG;
+        if (!h) return GPX_EARG;
+        // any option call, refused ones included, drops the carried gate decisions (prune_hint.h): whoever sets an option before a
+        // sweep gets that sweep decided from scratch
+        h->prune_hint = h->ens_hint = PruneHint();
+        if (!name) return GPX_EARG;
         for (const Option& o : kOptions) {
             if (strcmp(name, o.name)) continue;
             if (o.diag && !gpx_diagnostics())
@@ -231,7 +235,9 @@ static std::string apply_env_options(gpx_handle* h) {
 // 610: option prune (selection-only sweeps), timers slot 19.  620: the ensemble sweep prunes too (the lead's option prune),
 // gpx_ensemble_prune_report.  630: the second bound of selection-only sweeps (option prune_rows, gpx_prune_rows, gpx_prune_report's scalars 16 .. 19).
 // 640: gpx_sweep_batch, timers slot 20.  650: gpx_ensemble_sweep_batch.
-extern "C" int gpx_version(void) { return 650; }
+// 660: the gate's decision of a selection-only sweep is carried to the next one (prune_hint.h; any gpx_set_option drops it),
+// gpx_prune_report's scalar 19 and gpx_ensemble_prune_report's scalar 10 + n say whether the sweep skipped its gate on it.
+extern "C" int gpx_version(void) { return 660; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -415,7 +421,7 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
                                 (double)r.done, (double)r.cap,   (double)r.nsurv, sc[0],   sc[1],
                                 sc[5],          r.mean_s2,       bound ? (double)st[2] : NAN, r.kept ? 1.0 : 0.0,
                                 bound ? (guarded_bound ? sc[9] + sc[12] : 0.0) : NAN, guarded_bound ? sc[8] : NAN,
-                                (double)r.nR,   (double)r.nsurv2, guarded_bound ? sc[10] : NAN, NAN};
+                                (double)r.nR,   (double)r.nsurv2, guarded_bound ? sc[10] : NAN, r.hinted ? 1.0 : 0.0};
         for (int i = 0; i < nscal && i < 20; ++i) scal[i] = out[i];
         if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
         const int64_t nidx = std::min(std::min(r.nsurv, r.cap), cap_idx);
@@ -1220,7 +1226,13 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
         // the bound pass's kernel: the matrix-pipe form for SE-ARD up to d = 18 where its guard allows (decided on the device)
         const bool bound_mfma = h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0;
 
-        if (h->prune < 0) {
+        PruneHint key;
+        key.kernel_id = h->kernel_id, key.n = 1, key.d = h->d, key.nP = nP, key.Np_min = Np, key.M = M, key.k = k;
+        const bool automatic = h->prune < 0;       // only these sweeps read or write the carried decision
+        if (automatic && prune_hint_matches(h->prune_hint, key)) {
+            // The last sweep of this shape pruned and it paid (prune_hint_after): no gate, on into the bound pass as prune = 1 does
+            rec.hinted = true;
+        } else if (automatic) {
             // Gate, BEFORE the bound pass: the prior variance is a useful bound only where the data leave variance to explain.
             // The first generation is needed by either path; its mean s2 / rho decides (config B's dense data: declined).
             // A heuristic that only chooses between two correct paths.
@@ -1234,6 +1246,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             rec.mean_s2 = mean_s2;
             rec.path = 1;
         }
+        if (automatic) h->prune_hint = PruneHint();      // re-earned below from this sweep's own outcome, or gone
         if (pruning) {
             {
                 // 1. bound pass: ub[n] = EI(bias + alpha . k(X, z_n) + delta, s2 = rho) >= the value the exact chain returns
@@ -1276,6 +1289,10 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             rec.done = done, rec.nsurv = nsurv;
             rec.ub = ub, rec.idx = idx, rec.sc = sc, rec.st = st;
             rec.kept = seed_keep != nullptr;
+            if (automatic) {
+                h->prune_hint = key;
+                h->prune_hint.armed = prune_hint_after(rec.path, nsurv, cap);
+            }
             if (nsurv <= cap) {
                 // 4a-4c. the second bound, where the rule above says so: s2 <= rho - q_R, q_R the sum of V^2 over the leading nR block
                 // rows in the exact chain's own bits -- the survivors that EI((bias + dot) + delta, rho - q_R) still lets reach tau
@@ -2002,7 +2019,13 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
         start_rec();             // (a workspace that had to grow clears the record)
         double *const ub = w.ub, *const vals = w.vals, *const Xg = w.Xg, *const sc = w.sc;
         double *const gate_mean = w.extra, *const delta = w.extra + n;
-        if (L->prune < 0) {
+        PruneHint key;
+        key.kernel_id = L->kernel_id, key.n = n, key.d = d, key.nP = nPmax, key.Np_min = Np_min, key.M = M, key.k = k;
+        const bool automatic = L->prune < 0;       // only these sweeps read or write the lead's carried decision
+        if (automatic && prune_hint_matches(L->ens_hint, key)) {
+            // as in section 2.1: the last ensemble sweep of this shape pruned and it paid -- no gate, no member generations for it
+            rec.hinted = true;
+        } else if (automatic) {
             // Gate, as in section 2.1: the first generation is needed by either path; the members' mean s2 / rho decides
             if ((rc = exact(dXc, Gg, out, nullptr, nullptr, gate_mean))) return rc;
             done = Gg;
@@ -2016,6 +2039,7 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
             rec.gate = g;
             rec.path = 1;
         }
+        if (automatic) L->ens_hint = PruneHint();        // re-earned below from this sweep's own outcome, or gone
         if (pruning) {
             // 1. bound pass, per member in member order: its dots (own factor, weights and workspace) -> t1, its EI bound folded
             // into the running sum ub; then ub / n
@@ -2067,6 +2091,10 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
             rec.path = nsurv <= cap ? 2 : 3;
             rec.done = done, rec.nsurv = nsurv;
             rec.ub = ub, rec.idx = w.idx, rec.sc = sc, rec.delta = delta;
+            if (automatic) {
+                L->ens_hint = key;
+                L->ens_hint.armed = prune_hint_after(rec.path, nsurv, cap);
+            }
             if (nsurv <= cap) {
                 // 4. their exact values to their own positions; everything else stays -inf and the top-k below runs as ever
                 if (nsurv > 0) {
@@ -2246,7 +2274,8 @@ extern "C" int gpx_ensemble_prune_report(gpx_handle* const* members, int n_membe
         if ((ub || idx) && !bound) return fail(h, GPX_ESTATE, "ensemble_prune_report: the last ensemble sweep did not reach its bound pass");
         HIPCHK(h, hipSetDevice(h->device));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::vector<double> out((size_t)(10 + n_members), NAN);
+        std::vector<double> out((size_t)(11 + n_members), NAN);
+        out[10 + n_members] = r.hinted ? 1.0 : 0.0;      // behind the deltas: head[8] is tau, and callers built against 10 + n read on as before
         const double head[10] = {(double)r.path, (double)r.M,   (double)r.k,     (double)r.G, (double)r.Gg,
                                  (double)r.done, (double)r.cap, (double)r.nsurv, NAN,         r.gate};
         std::copy(head, head + 10, out.begin());
@@ -2254,7 +2283,7 @@ extern "C" int gpx_ensemble_prune_report(gpx_handle* const* members, int n_membe
             HIPCHK(h, hipMemcpy(&out[8], r.sc + 5, 8, hipMemcpyDeviceToHost));
             HIPCHK(h, hipMemcpy(&out[10], r.delta, (size_t)n_members * 8, hipMemcpyDeviceToHost));
         }
-        for (int i = 0; i < nscal && i < 10 + n_members; ++i) scal[i] = out[i];
+        for (int i = 0; i < nscal && i < 11 + n_members; ++i) scal[i] = out[i];
         if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
         const int64_t nidx = std::min(std::min(r.nsurv, r.cap), cap_idx);
         if (idx && nidx > 0) HIPCHK(h, hipMemcpy(idx, r.idx, (size_t)nidx * 8, hipMemcpyDeviceToHost));

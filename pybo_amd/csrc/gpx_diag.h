@@ -68,7 +68,8 @@ int64_t gpx_chol_tasks2(int nblocks, int chunks, int16_t *out, int64_t cap, int6
  * gate);  the seeds' threshold key;  1 if the kept copies exist;  the bound pass's kernel, 0 generic / 1 matrix pipe / 2 matrix pipe in fp32;  the guard's (d + 4) (R_x + R_z)^2
  * (NaN where the host chose the generic kernel: another covariance, d > 18, prune_bound = 0);  nR, the block rows of the second bound's
  * prefix (0: it did not run);  nsurv2, the survivors of its cut (the candidates evaluated exactly on path 2 where nR > 0);  E, the relative margin of the
- * fp32 kernel (csrc/bound_f32.h; NaN where that kernel was not considered);  one reserved (NaN) }.  S .. tau, the key and the last two are NaN for paths 0 and 1.
+ * fp32 kernel (csrc/bound_f32.h; NaN where that kernel was not considered);  1 if this sweep skipped its gate on the decision carried from the last one
+ * (csrc/prune_hint.h; then done = 0 and the gate's mean is NaN), else 0 }.  S .. tau, the key, the guard and E are NaN for paths 0 and 1.
  * ub (optional, M): the bound vector as the survivor pass read it (-inf where a candidate was evaluated as gate or seed);  idx
  * (optional, cap_idx): the first min(nsurv, cap, cap_idx) survivors in the order they were compacted;  ub_kept (optional, M) and
  * seed_idx (optional, cap_seed; G entries): the bound vector and the seed list before the scatter -- only after a sweep that ran with
@@ -90,9 +91,9 @@ int gpx_prune_dots(gpx_handle *h, double *dots);
 int gpx_prune_rows(gpx_handle *h, double *qR, double *ub2, int64_t *idx2, int64_t cap_idx2);
 
 /* What the LAST ensemble sweep led by members[0] decided about pruning; `members`, n as in that call.
- * scal[0 .. min(nscal, 10 + n)) = { path 0 .. 3, M, k, G, Gg, done, cap, nsurv as in gpx_prune_report;  tau (NaN for paths 0 and 1);  the
+ * scal[0 .. min(nscal, 11 + n)) = { path 0 .. 3, M, k, G, Gg, done, cap, nsurv as in gpx_prune_report;  tau (NaN for paths 0 and 1);  the
  * gate's value, the mean over the members of mean(s2_m) / rho_m of its generation (NaN: no gate);  then delta_m of every member (NaN for
- * paths 0 and 1) }.  ub (optional, M): the ensemble bound vector -- the members' bounds summed in member order and divided by n -- as the
+ * paths 0 and 1);  then, at 10 + n, 1 if this sweep skipped its gate on the lead's carried decision, else 0 }.  ub (optional, M): the ensemble bound vector -- the members' bounds summed in member order and divided by n -- as the
  * survivor pass read it (-inf where a candidate was evaluated as gate or seed);  idx (optional, cap_idx): the first min(nsurv, cap,
  * cap_idx) survivors in the order they were compacted.  GPX_ESTATE: no ensemble sweep of n members since the record was cleared, or a vector
  * was asked for and the path is below 2.  (Every entry into gpx_ensemble_sweep[_dev] clears the lead's record, a refused call included;

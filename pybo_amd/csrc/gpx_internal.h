@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/gpx.h"
+#include "prune_hint.h"
 
 namespace gpx {
 
@@ -163,6 +164,7 @@ struct gpx_handle {
         int path = -1;            // -1 no sweep yet, 0 plain, 1 the gate declined, 2 pruned, 3 bound pass ran but too many survived
         int64_t M = 0, k = 0, G = 0, Gg = 0, done = 0, cap = 0, nsurv = 0;
         double mean_s2 = 0.0;     // the gate's (NaN where it did not run)
+        bool hinted = false;      // the gate was skipped on the carried decision (prune_hint.h)
         const double* ub = nullptr;
         const int64_t* idx = nullptr;
         const double* sc = nullptr;
@@ -180,11 +182,15 @@ struct gpx_handle {
         int path = -1, n = 0;
         int64_t M = 0, k = 0, G = 0, Gg = 0, done = 0, cap = 0, nsurv = 0;
         double gate = 0.0;        // mean over the members of mean(s2_m) / rho_m of the gate's generation (NaN where it did not run)
+        bool hinted = false;      // the gate was skipped on the carried decision
         const double* ub = nullptr;
         const int64_t* idx = nullptr;
         const double* sc = nullptr;       // sc[5] = tau as the survivor pass cut with it
         const double* delta = nullptr;    // n: the members' delta_m
     } ens_rec;
+    // the gate's decision carried to the next sweep of the same shape (prune_hint.h): this handle's own sweeps / the ensemble sweeps it
+    // leads.  NOT part of the records: those are reset by every sweep entry and by a growing workspace.  Dropped by any gpx_set_option.
+    gpx::PruneHint prune_hint, ens_hint;
     int prune_keep = 0;       // diagnostic option: keep those two device copies
     int prune_bound = -1;     // diagnostic option: the bound pass's kernel (-1 by guard, 0 k_sweep_rankq<1>, 1 k_bound_mfma / 2 k_bound_mfma32 wherever SE-ARD, d <= 18)
     int prune_rows = -1;      // diagnostic option: block rows of the second bound's row prefix (-1 by size: nP / 4, 0 never, n > 0: min(n, nP, N / 128) wherever the first level pruned)
