@@ -22,13 +22,10 @@
  */
 #ifndef GPX_H
 #define GPX_H
-
 #include <stdint.h>
-
 #ifdef __cplusplus
 extern "C" {
 #endif
-
 typedef struct gpx_handle gpx_handle;
 
 enum gpx_status {
@@ -55,7 +52,10 @@ enum gpx_acq {
     GPX_ACQ_EI = 0,   /* model.get_improvement(target, X)  [pybo/policies/simple.py:25]  params = {target} */
     GPX_ACQ_PI = 1,   /* model.get_tail(target, X)         [pybo/policies/simple.py:39]  params = {target} */
     GPX_ACQ_UCB = 2,  /* mu + sqrt(beta*s2)                [pybo/policies/simple.py:62-73] params = {beta} */
-    GPX_ACQ_MEAN = 3  /* posterior mean                    [pybo/recommenders.py:19-25]  no params */
+    GPX_ACQ_MEAN = 3, /* posterior mean                    [pybo/recommenders.py:19-25]  no params */
+    GPX_ACQ_MES = 16  /* max-value entropy search: mean_s g((y*_s - mu) / sqrt(s2)), g(c) = c phi(c) / (2 Phi(c)) - log Phi(c); ids 4 .. 15: refused.
+                       * params = the S sampled maxima y*_s, 1 <= nparams = S <= 64, all finite (else GPX_EARG); gpx_ensemble_sweep*: n_members * S of them,
+                       * member-major, member m scores with its slice.  Taken by gpx_sweep*, gpx_sweep_update*, gpx_ensemble_sweep*; never pruned; no batch. */
 };
 
 /* ---- lifetime --------------------------------------------------------------------------- */

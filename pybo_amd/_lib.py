@@ -110,7 +110,7 @@ SYMBOLS = {
 GPX_OK, GPX_EARG, GPX_ENOTPD, GPX_EHIP, GPX_EOOM, GPX_ESTATE, GPX_ERCCL = 0, -1, -2, -3, -4, -5, -6
 COMM_ID_BYTES = 128
 KERNELS = {'se': 0, 'matern5': 1, 'matern3': 2, 'matern1': 3}
-ACQ = {'ei': 0, 'pi': 1, 'ucb': 2, 'mean': 3}
+ACQ = {'ei': 0, 'pi': 1, 'ucb': 2, 'mean': 3, 'mes': 16}       # (ids 4 .. 15 are refused by the library)
 TIMER_NAMES = ['gram', 'cholesky', 'trtri', 'alpha', 'cross_gram', 'sweep_trmm', 'acq_topk', 'rff',
                'sweep_trmm_launches', 'sweep_trmm_flop', 'copies', 'append', 'rank1', 'rff_sweep', 'rff_sweep_ops',
                'chol_fallbacks', 'sweep_sclk_mhz', 'rff_sclk_mhz', 'trtri_ahead', 'sweep_bound', 'batch', 'joint']
@@ -165,6 +165,15 @@ def _f64(a, shape=None):
     if shape is not None:
         a = a.reshape(shape)
     return a
+
+
+def _acq_params(param):
+    """The (params, nparams) pair of a sweep entry from an acquisition parameter: a scalar (EI / PI target, UCB beta) or None (the
+    mean) is one double; an array (the maximum samples of 'mes', (S,) or member-major (n, S)) passes through flattened, untouched."""
+    if param is None or np.ndim(param) == 0:
+        return _f64([0.0 if param is None else param]), 1
+    params = _f64(param).reshape(-1)
+    return params, len(params)
 
 
 def sobol_direction_numbers(d, nbits):
@@ -600,13 +609,13 @@ class Engine(object):
         Xc = Xc.reshape(-1, self.d) if self.d else np.atleast_2d(Xc)
         M = len(Xc)
         aid = ACQ[acq] if isinstance(acq, str) else int(acq)
-        params = _f64([0.0 if param is None else param])
+        params, nparams = _acq_params(param)
         tv = np.empty(k)
         ti = np.empty(k, dtype=np.int64)
         out = np.empty(M) if want_all else None
         mu = np.empty(M) if want_moments else None
         s2 = np.empty(M) if want_moments else None
-        self._check(self._lib.gpx_sweep(self._h, aid, _ptr(params), 1, _ptr(Xc), M, k,
+        self._check(self._lib.gpx_sweep(self._h, aid, _ptr(params), nparams, _ptr(Xc), M, k,
                                         _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out),
                                         _ptr(mu), _ptr(s2)))
         return dict(top_val=tv, top_idx=ti, acq=out, mu=mu, s2=s2)
@@ -615,13 +624,13 @@ class Engine(object):
         """Re-score the cached candidate set (option sweep_cache, kept current by append): O(M)."""
         M = self.sweep_cache_size()
         aid = ACQ[acq] if isinstance(acq, str) else int(acq)
-        params = _f64([0.0 if param is None else param])
+        params, nparams = _acq_params(param)
         tv = np.empty(k)
         ti = np.empty(k, dtype=np.int64)
         out = np.empty(M) if want_all else None
         mu = np.empty(M) if want_moments else None
         s2 = np.empty(M) if want_moments else None
-        self._check(self._lib.gpx_sweep_update(self._h, aid, _ptr(params), 1, k, _ptr(tv) if k else None,
+        self._check(self._lib.gpx_sweep_update(self._h, aid, _ptr(params), nparams, k, _ptr(tv) if k else None,
                                                _ptr(ti) if k else None, _ptr(out), _ptr(mu), _ptr(s2)))
         return dict(top_val=tv, top_idx=ti, acq=out, mu=mu, s2=s2)
 
@@ -632,21 +641,21 @@ class Engine(object):
         """nb greedy picks on the live sweep cache (gpx_sweep_batch), each conditioned on the earlier ones at their posterior
         mean.  Returns dict(sel_val, sel_idx, sel_s2[, s2_all]); model, cache and a pending announcement are untouched."""
         aid = ACQ[kind] if isinstance(kind, str) else int(kind)
-        params = _f64([0.0 if param is None else param])
+        params, nparams = _acq_params(param)
         n = max(int(nb), 0)
         out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty(n))
         if want_s2_all:
             out['s2_all'] = np.empty(self.sweep_cache_size())
-        self._check(self._lib.gpx_sweep_batch(self._h, aid, _ptr(params), 1, int(nb), _ptr(out['sel_val']), _ptr(out['sel_idx']),
+        self._check(self._lib.gpx_sweep_batch(self._h, aid, _ptr(params), nparams, int(nb), _ptr(out['sel_val']), _ptr(out['sel_idx']),
                                               _ptr(out['sel_s2']), _ptr(out.get('s2_all'))))
         return out
 
     def sweep_dev(self, acq, param, dXc_ptr, M, k, d_acq=None, d_mu=None, d_s2=None):
         aid = ACQ[acq] if isinstance(acq, str) else int(acq)
-        params = _f64([0.0 if param is None else param])
+        params, nparams = _acq_params(param)
         tv = np.empty(k)
         ti = np.empty(k, dtype=np.int64)
-        self._check(self._lib.gpx_sweep_dev(self._h, aid, _ptr(params), 1, _P(dXc_ptr), M, k,
+        self._check(self._lib.gpx_sweep_dev(self._h, aid, _ptr(params), nparams, _P(dXc_ptr), M, k,
                                             _ptr(tv) if k else None, _ptr(ti) if k else None,
                                             _P(d_acq) if d_acq else None, _P(d_mu) if d_mu else None,
                                             _P(d_s2) if d_s2 else None))
@@ -659,12 +668,12 @@ class Engine(object):
         lead = engines[0]
         handles = (_P * len(engines))(*[e._h for e in engines])
         aid = ACQ[acq] if isinstance(acq, str) else int(acq)
-        params = _f64([0.0 if param is None else param])
+        params, nparams = _acq_params(param)
         tv = np.empty(k)
         ti = np.empty(k, dtype=np.int64)
         if isinstance(Xc, DeviceGrid):
             M = len(Xc)
-            lead._check(lead._lib.gpx_ensemble_sweep_dev(handles, len(engines), aid, _ptr(params), 1, Xc.ptr, M,
+            lead._check(lead._lib.gpx_ensemble_sweep_dev(handles, len(engines), aid, _ptr(params), nparams, Xc.ptr, M,
                                                          k, _ptr(tv) if k else None, _ptr(ti) if k else None,
                                                          None, None, None))
             return dict(top_val=tv, top_idx=ti, acq=None, mu=None, s2=None)
@@ -673,7 +682,7 @@ class Engine(object):
         out = np.empty(M) if want_all else None
         mu = np.empty(M) if want_moments else None
         s2 = np.empty(M) if want_moments else None
-        lead._check(lead._lib.gpx_ensemble_sweep(handles, len(engines), aid, _ptr(params), 1, _ptr(Xc), M, k,
+        lead._check(lead._lib.gpx_ensemble_sweep(handles, len(engines), aid, _ptr(params), nparams, _ptr(Xc), M, k,
                                                  _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out),
                                                  _ptr(mu), _ptr(s2)))
         return dict(top_val=tv, top_idx=ti, acq=out, mu=mu, s2=s2)
@@ -686,10 +695,10 @@ class Engine(object):
         lead = engines[0]
         handles = (_P * len(engines))(*[e._h for e in engines])
         aid = ACQ[kind] if isinstance(kind, str) else int(kind)
-        params = _f64([0.0 if param is None else param])
+        params, nparams = _acq_params(param)
         n = max(int(nb), 0)
         out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty((len(engines), n)))
-        lead._check(lead._lib.gpx_ensemble_sweep_batch(handles, len(engines), aid, _ptr(params), 1, int(nb), _ptr(out['sel_val']),
+        lead._check(lead._lib.gpx_ensemble_sweep_batch(handles, len(engines), aid, _ptr(params), nparams, int(nb), _ptr(out['sel_val']),
                                                        _ptr(out['sel_idx']), _ptr(out['sel_s2'])))
         return out
 

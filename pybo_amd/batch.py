@@ -17,6 +17,8 @@ Three paths, chosen by what the policy's index carries:
     score the grid, pick, `copy()` the model once and `add_data(x, predict(x)[0])` per round.  On an `MCMC` that `add_data`
     advances the chain: the hyper-parameters are RE-SAMPLED on the hallucinated observation every round, unlike the device path;
   * neither (Thompson, or any sampled policy): nb independent policy calls, each one's best grid point; duplicates are allowed.
+`policy='mes'` is refused: its index carries `.acq = ('mes', ystar)` but no `.batch`, and `_score` below raises the ValueError for any kind
+but EI, PI and UCB -- scoring the believer rounds with max-value entropy search is not built (the sampled maxima would have to follow them).
 Picks are grid candidates, ranked value descending, then index ascending, NaN last -- the device top-k's order.
 """
 import numpy as np

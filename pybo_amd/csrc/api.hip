@@ -7,10 +7,12 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 
 #include "gpx_internal.h"
 #include "gpx_diag.h"
+#include "mes_math.h"
 
 using namespace gpx;
 
@@ -237,7 +239,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // 640: gpx_sweep_batch, timers slot 20.  650: gpx_ensemble_sweep_batch.
 // 660: the gate's decision of a selection-only sweep is carried to the next one (prune_hint.h; any gpx_set_option drops it),
 // gpx_prune_report's scalar 19 and gpx_ensemble_prune_report's scalar 10 + n say whether the sweep skipped its gate on it.
-extern "C" int gpx_version(void) { return 660; }
+// 670: GPX_ACQ_MES = 16 (max-value entropy search: gpx_sweep*, gpx_sweep_update*, gpx_ensemble_sweep*; params = the sampled maxima).
+extern "C" int gpx_version(void) { return 670; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -994,11 +997,41 @@ static int topk_core(gpx_handle* h, const double* d_vals, int64_t M, int64_t k, 
 
 // The acquisition arguments of every sweep (`what` prefixes the message): the id and its parameter, then k and the top-k
 // outputs (two calls: ensemble_sweep checks its candidates between them).
-static int check_acq(gpx_handle* h, const char* what, int acq_id, const double* params, int nparams) {
-    if (acq_id < GPX_ACQ_EI || acq_id > GPX_ACQ_MEAN) return fail(h, GPX_EARG, (std::string(what) + ": unknown acquisition id").c_str());
-    if (acq_id != GPX_ACQ_MEAN && (nparams < 1 || !params))
+// One row per acquisition: how many parameters it takes at least (vec: a vector of maximum samples, 1 .. MES_MAX_S per member,
+// every entry finite).  Ids without a row -- 4 .. 15 among them -- are unknown.
+struct AcqRule { int id, min_params; bool vec; };
+static const AcqRule ACQ_RULES[] = {
+    {GPX_ACQ_EI, 1, false}, {GPX_ACQ_PI, 1, false}, {GPX_ACQ_UCB, 1, false}, {GPX_ACQ_MEAN, 0, false}, {GPX_ACQ_MES, 1, true},
+};
+static int check_acq(gpx_handle* h, const char* what, int acq_id, const double* params, int nparams, int n_members = 0) {
+    const AcqRule* rule = nullptr;
+    for (const AcqRule& r : ACQ_RULES)
+        if (r.id == acq_id) rule = &r;
+    if (!rule) return fail(h, GPX_EARG, (std::string(what) + ": unknown acquisition id").c_str());
+    if (rule->vec) {
+        // n_members > 0: an ensemble entry, member m scores with params[m S .. m S + S)
+        if (n_members > 0 && (!params || nparams < n_members || nparams % n_members != 0 || nparams / n_members > MES_MAX_S))
+            return fail(h, GPX_EARG, (std::string(what) + ": MES takes n_members * S maximum samples, S in [1, 64]").c_str());
+        bool ok = params && nparams >= 1 && (n_members > 0 || nparams <= MES_MAX_S);
+        for (int i = 0; ok && i < nparams; ++i) ok = std::isfinite(params[i]);
+        if (!ok) return fail(h, GPX_EARG, (std::string(what) + ": MES takes 1 to 64 finite maximum samples").c_str());
+        return GPX_OK;
+    }
+    if (rule->min_params > 0 && (nparams < rule->min_params || !params))
         return fail(h, GPX_EARG, (std::string(what) + ": missing acquisition parameter").c_str());
     return GPX_OK;
+}
+// the batch entries: the believer rounds are scored by acq_value (kernels_batch.hip), which MES is not part of
+static int check_acq_batch(gpx_handle* h, const char* what, int acq_id) {
+    if (acq_id == GPX_ACQ_MES) return fail(h, GPX_EARG, (std::string(what) + ": MES is not supported").c_str());
+    return GPX_OK;
+}
+// the maxima of one sweep as k_acq_mes takes them (checked by check_acq)
+static MesArg mes_arg(const double* params, int nparams) {
+    MesArg a;
+    a.S = nparams;
+    for (int i = 0; i < MES_MAX_S; ++i) a.y[i] = i < nparams ? params[i] : 0.0;
+    return a;
 }
 
 static int check_topk(gpx_handle* h, const char* what, int64_t k, const double* top_val, const int64_t* top_idx) {
@@ -1152,6 +1185,8 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
         if ((rc = ensure(h, h->dout, h->cap_out, M))) return rc;
         d_acq = h->dout;
     }
+    const bool mes = acq_id == GPX_ACQ_MES;          // its parameters are a vector: k_acq_mes, never pruned
+    const MesArg ys = mes_arg(params, mes ? nparams : 0);
     const double p0 = (acq_id == GPX_ACQ_MEAN) ? 0.0 : params[0];
     double* cq = nullptr;
     double* cp = nullptr;
@@ -1195,7 +1230,8 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             h->tacc[T_FLOP] += (double)h->N * (double)h->N * (double)valid;
             {
                 Span sp(h, T_ACQ);
-                launch_acq(s, h->dQp, h->dPp, chunk, nP, m0, valid, h->rho, h->bias, acq_id, p0, out, mu, s2, cq, cp);
+                if (mes) launch_acq_mes(s, h->dQp, h->dPp, chunk, nP, m0, valid, h->rho, h->bias, ys, out, mu, s2, cq, cp);
+                else launch_acq(s, h->dQp, h->dPp, chunk, nP, m0, valid, h->rho, h->bias, acq_id, p0, out, mu, s2, cq, cp);
             }
         }
     };
@@ -1401,8 +1437,11 @@ static int sweep_update_core(gpx_handle* h, int acq_id, const double* params, in
     const double p0 = (acq_id == GPX_ACQ_MEAN) ? 0.0 : params[0];
     {
         Span sp(h, T_ACQ);
-        launch_acq(h->stream, h->dcq, h->dcp, 0, 0, 0, M, h->rho, h->bias, acq_id, p0, d_acq, d_mu, d_s2, nullptr,
-                   nullptr);
+        if (acq_id == GPX_ACQ_MES)
+            launch_acq_mes(h->stream, h->dcq, h->dcp, 0, 0, 0, M, h->rho, h->bias, mes_arg(params, nparams), d_acq, d_mu, d_s2, nullptr,
+                           nullptr);
+        else
+            launch_acq(h->stream, h->dcq, h->dcp, 0, 0, 0, M, h->rho, h->bias, acq_id, p0, d_acq, d_mu, d_s2, nullptr, nullptr);
     }
     if (k > 0 && (rc = topk_core(h, d_acq, M, k, top_val, top_idx))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1491,7 +1530,7 @@ extern "C" int gpx_sweep_batch(gpx_handle* h, int acq_id, const double* params, 
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
         int rc;
-        if ((rc = check_acq(h, "sweep_batch", acq_id, params, nparams))) return rc;
+        if ((rc = check_acq_batch(h, "sweep_batch", acq_id)) || (rc = check_acq(h, "sweep_batch", acq_id, params, nparams))) return rc;
         if (acq_id == GPX_ACQ_MEAN)
             return fail(h, GPX_EARG, "sweep_batch: the posterior mean does not change under hallucinated observations (EI, PI or UCB)");
         if (nb < 1 || nb > 64) return fail(h, GPX_EARG, "sweep_batch: nb must be in [1, 64]");
@@ -1938,7 +1977,8 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
     gpx_handle* L = mem[0];
     L->ens_rec = gpx_handle::EnsPruneRecord();     // every ensemble sweep entry, refused ones included, ends the previous one's record
     int rc;
-    if ((rc = check_acq(L, "ensemble_sweep", acq_id, params, nparams))) return rc;
+    if ((rc = check_acq(L, "ensemble_sweep", acq_id, params, nparams, n))) return rc;
+    const int mesS = (acq_id == GPX_ACQ_MES) ? nparams / n : 0;      // MES: member m scores with its own slice of the maxima
     if (!dXc || M < 1) return fail(L, GPX_EARG, "ensemble_sweep: need M >= 1 candidates");
     if ((rc = check_topk(L, "ensemble_sweep", k, top_val, top_idx))) return rc;
     for (int m = 0; m < n; ++m) {
@@ -1963,7 +2003,8 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
     auto exact = [&](const double* X, int64_t cnt, double* o, double* o_mu, double* o_s2, double* gate_mean) -> int {
         for (int m = 0; m < n; ++m) {
             gpx_handle* h = mem[m];
-            int rcm = (mode == 0) ? sweep_core(h, acq_id, params, nparams, X, cnt, 0, nullptr, nullptr, t0, nullptr, gate_mean ? t1 : nullptr)
+            int rcm = (mode == 0) ? sweep_core(h, acq_id, mesS ? params + (size_t)m * mesS : params, mesS ? mesS : nparams, X, cnt, 0, nullptr,
+                                               nullptr, t0, nullptr, gate_mean ? t1 : nullptr)
                                   : sweep_core(h, GPX_ACQ_MEAN, nullptr, 0, X, cnt, 0, nullptr, nullptr, nullptr, t0, t1);
             if (rcm) {
                 if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
@@ -2187,7 +2228,8 @@ extern "C" int gpx_ensemble_sweep_batch(gpx_handle* const* members, int n_member
     return guarded(L, [&]() -> int {
         const int n = n_members;
         int rc;
-        if ((rc = check_acq(L, "ensemble_sweep_batch", acq_id, params, nparams))) return rc;
+        if ((rc = check_acq_batch(L, "ensemble_sweep_batch", acq_id)) || (rc = check_acq(L, "ensemble_sweep_batch", acq_id, params, nparams)))
+            return rc;
         if (acq_id == GPX_ACQ_MEAN)
             return fail(L, GPX_EARG, "ensemble_sweep_batch: the posterior mean does not change under hallucinated observations (EI, PI or UCB)");
         if (nb < 1 || nb > 64) return fail(L, GPX_EARG, "ensemble_sweep_batch: nb must be in [1, 64]");

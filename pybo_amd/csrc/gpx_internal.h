@@ -285,6 +285,11 @@ void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const
 void launch_acq(hipStream_t s, const double* Qp, const double* Pp, int64_t ldp, int nrb, int64_t m0,
                 int64_t cols_valid, double rho, double bias, int acq_id, double p0, double* acq_out,
                 double* mu_out, double* s2_out, double* qsum, double* psum);
+// the same for GPX_ACQ_MES (kernels_mes.hip): the sampled maxima by value (MesArg: mes_math.h)
+struct MesArg;
+void launch_acq_mes(hipStream_t s, const double* Qp, const double* Pp, int64_t ldp, int nrb, int64_t m0,
+                    int64_t cols_valid, double rho, double bias, const MesArg& ys, double* acq_out,
+                    double* mu_out, double* s2_out, double* qsum, double* psum);
 // correction of the cached sums after q <= 8 appended observations in one pass (see kernels_sweep.hip)
 void launch_pend_store(hipStream_t s, const double* w, int64_t Nj, int64_t ldw, const double* scal, double* row,
                        double* pscal_j);

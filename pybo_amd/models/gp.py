@@ -488,6 +488,20 @@ class GP(object):
     def get_tail(self, target, X, grad=False):
         return self._acq('pi', target, X, grad)
 
+    def get_entropy(self, ystar, X, grad=False):
+        """Max-value entropy search at the rows of X for the sampled maxima `ystar` (S,), 1 <= S <= 64 (pybo_amd/mes.py).  Without
+        `grad` a device sweep ('mes': k_acq_mes); with it the values and dMES/dx, formed on the host from predict(X, grad=True)."""
+        ystar = np.array(ystar, dtype=float).reshape(-1)
+        if not grad:
+            return self._acq('mes', ystar, X, False)
+        X = np.array(X, ndmin=2, dtype=float)
+        if self.ndata == 0:
+            raise RuntimeError('the model has no data yet')
+        if X.shape[0] == 0:
+            return np.zeros(0), np.zeros((0, X.shape[1]))
+        from ..mes import mes_value_grad
+        return mes_value_grad(*self._engine().predict(X, grad=True), ystar)
+
     def acq_topk(self, kind, param, xgrid, k):
         """Whole-grid acquisition + top-k on the device: (values (k,), grid indices (k,)).  `xgrid` is a
         host array (uploaded) or a `DeviceGrid` (already in HBM)."""

@@ -260,6 +260,11 @@ class MCMC(object):
         """(n, 3 + d) array of the kept hyper-parameter states [log sn2, log rho, log ell.., bias]."""
         return np.array([m.hyper_vector() for m in self._members])
 
+    @property
+    def members(self):
+        """The kept member models, in ensemble order (policies that sample per member read their moments: policies.MES)."""
+        return list(self._need())
+
     # -- model protocol ----------------------------------------------------------------------------
     @property
     def ndata(self):
@@ -356,6 +361,34 @@ class MCMC(object):
 
     def get_tail(self, target, X, grad=False):
         return self._mean_of('get_tail', target, X, grad)
+
+    def get_entropy(self, ystar, X, grad=False):
+        """Max-value entropy search over the members: `ystar` is (n, S), member m scores with its own row (the paper's treatment of
+        hyper-parameter samples), the value is the mean of the members' values.  Device members: one ensemble sweep (the maxima travel
+        member-major); gradients follow `_mean_of`."""
+        from ..mes import mes_value, mes_value_grad
+        members = self._need()
+        ystar = np.array(ystar, dtype=float, ndmin=2)
+        if ystar.shape[0] != len(members):
+            raise ValueError('get_entropy: ystar must be (n_members, S) = (%d, S)' % len(members))
+        engines = None if grad else self._engines()
+        if engines is not None:
+            from .._lib import Engine
+            return Engine.ensemble_sweep(engines, 'mes', ystar, np.array(X, ndmin=2, dtype=float), k=0)['acq']
+        if grad and self._engines() is not None and len(np.atleast_2d(X)):
+            outs = [mes_value_grad(mu, s2, dmu, ds2, ys) for mu, s2, dmu, ds2, ys in zip(*self._member_grads(X), ystar)]
+        else:
+            outs = []
+            for m, ys in zip(members, ystar):
+                if hasattr(m, 'get_entropy'):
+                    outs.append(m.get_entropy(ys, X, grad))
+                elif grad:
+                    outs.append(mes_value_grad(*m.predict(X, True), ys))
+                else:
+                    outs.append(mes_value(*m.predict(X), ys))
+        if not grad:
+            return np.mean(outs, axis=0)
+        return np.mean([o[0] for o in outs], axis=0), np.mean([o[1] for o in outs], axis=0)
 
     def sample_f(self, n, rng=None):
         rng = rstate(rng)

@@ -1,4 +1,4 @@
-"""Acquisition policies; the exported names match pybo.policies (`EI`, `PI`, `UCB`, `Thompson`)."""
-from .simple import EI, PI, UCB, Thompson
+"""Acquisition policies; the exported names match pybo.policies (`EI`, `PI`, `UCB`, `Thompson`), plus `MES`."""
+from .simple import EI, PI, UCB, Thompson, MES
 
-__all__ = ['EI', 'PI', 'UCB', 'Thompson']
+__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES']

@@ -15,10 +15,11 @@ New: when the model is the device-backed `pybo_amd.models.GP`, the returned inde
 `pybo_amd.solvers.solve_lbfgs` uses instead of `argsort(f(xgrid))` (pybo/solvers/lbfgs.py:50-51).
 Any other model (e.g. a test stub) gets plain closures, exactly as in the reference.  Every EI / PI / UCB index also
 carries `index.acq = (kind, param)` and, for models with `acq_batch`, `index.batch(xgrid, nb)` (pybo_amd/batch.py).
+`MES` (max-value entropy search) is this build's own: the reference has no information-theoretic policy.
 """
 import numpy as np
 
-__all__ = ['EI', 'PI', 'UCB', 'Thompson']
+__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES']
 
 
 def _attach_topk(index, model, kind, param):
@@ -74,6 +75,56 @@ def Thompson(model, _, __, n=100, rng=None):
         return sample.get(X, grad)
 
     index.topk = fast                     # device sample: grid evaluation + top-k stay on the GPU
+    return index
+
+
+def _noise(model):
+    """The model's noise variance: its `sn2`, its 'like.sn2' parameter, or 0 for a stub that has neither."""
+    sn2 = getattr(model, 'sn2', None)
+    if sn2 is None:
+        prm = getattr(model, 'params', {}).get('like.sn2')
+        sn2 = 0.0 if prm is None else prm.value
+    return float(sn2)
+
+
+def MES(model, bounds, X, nmax=16, ngrid=10000, xi=0.0, rng=None):
+    """Max-value entropy search (Wang & Jegelka 2017): mean over nmax sampled maxima y* of g((y* - mu) / s), g(c) = c phi(c) /
+    (2 Phi(c)) - log Phi(c) (pybo_amd/mes.py).  The maxima come from the paper's Gumbel approximation on the support set
+    `init_uniform(bounds, ngrid, rng)` stacked on X (one `predict` there), floored at (best posterior mean at the data) + xi +
+    5 sqrt(sn2).  An ensemble (`models.MCMC`) draws one set per member from that member's own moments: ystar is (n, nmax).
+    The index carries `.acq = ('mes', ystar)` and, for device models, `.topk`; never `.batch` (pybo_amd/batch.py)."""
+    from ..inits import init_uniform
+    from ..mes import mes_value, mes_value_grad, sample_maxima
+    from ..utils import rstate
+    rng = rstate(rng)
+    model = model.copy()
+    X = np.array(X, ndmin=2, dtype=float)
+    support = np.vstack([init_uniform(bounds, ngrid, rng), X])
+
+    def maxima(member):
+        mu, s2 = member.predict(support)
+        floor = mu[len(support) - len(X):].max() + xi + 5.0 * np.sqrt(_noise(member))
+        return sample_maxima(mu, np.sqrt(s2), nmax, floor, rng)
+
+    members = getattr(model, 'members', None)
+    ystar = maxima(model) if members is None else np.array([maxima(m) for m in members])
+
+    if getattr(model, 'get_entropy', None) is not None:
+        def index(X, grad=False):
+            return model.get_entropy(ystar, X, grad)
+    else:
+        def index(X, grad=False):
+            if not grad:
+                return mes_value(*model.predict(X), ystar)
+            return mes_value_grad(*model.predict(X, grad=True), ystar)
+
+    index.acq = ('mes', ystar)
+    fast = getattr(model, 'acq_topk', None)
+    if fast is not None:
+        index.topk = lambda xgrid, k: fast('mes', ystar, xgrid, k)
+        owner = getattr(model, 'topk_engine', None)
+        if owner is not None:
+            index.topk_engine = owner
     return index
 
 
