@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <new>
 
 #include "gpx_internal.h"
@@ -397,6 +398,19 @@ extern "C" int64_t gpx_chol_trace(gpx_handle* h, int64_t* out, int64_t n) {
     return tg_trace_copy(h, reinterpret_cast<long long*>(out), n);
 }
 
+// What gpx_prune_report and gpx_ensemble_prune_report share, from the records' common head: the first eight scalars, and the bound
+// vector with the survivor list
+static void report_head(const gpx_handle::SelectRecord& r, double* out) {
+    const double head[8] = {(double)r.path, (double)r.M, (double)r.k, (double)r.G, (double)r.Gg, (double)r.done, (double)r.cap, (double)r.nsurv};
+    std::copy(head, head + 8, out);
+}
+static int report_vectors(gpx_handle* h, const gpx_handle::SelectRecord& r, double* ub, int64_t* idx, int64_t cap_idx) {
+    if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
+    const int64_t nidx = std::min(std::min(r.nsurv, r.cap), cap_idx);
+    if (idx && nidx > 0) HIPCHK(h, hipMemcpy(idx, r.idx, (size_t)nidx * 8, hipMemcpyDeviceToHost));
+    return GPX_OK;
+}
+
 extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* ub, int64_t* idx, int64_t cap_idx,
                                 double* ub_kept, int64_t* seed_idx, int64_t cap_seed) {
     return guarded(h, [&]() -> int {
@@ -420,15 +434,16 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
         }
         // the device chose the bound pass's kernel: sc[8] = guard value, sc[9] = a matrix-pipe kernel ran, sc[12] = the fp32 one, sc[10] = its E
         const bool guarded_bound = bound && r.bound_kernel < 0;
-        const double out[20] = {(double)r.path, (double)r.M,     (double)r.k, (double)r.G, (double)r.Gg,
-                                (double)r.done, (double)r.cap,   (double)r.nsurv, sc[0],   sc[1],
-                                sc[5],          r.mean_s2,       bound ? (double)st[2] : NAN, r.kept ? 1.0 : 0.0,
-                                bound ? (guarded_bound ? sc[9] + sc[12] : 0.0) : NAN, guarded_bound ? sc[8] : NAN,
-                                (double)r.nR,   (double)r.nsurv2, guarded_bound ? sc[10] : NAN, r.hinted ? 1.0 : 0.0};
+        double out[20];
+        report_head(r, out);
+        // (slot 11: the gate's mean s2 as it is, not divided by rho)
+        const double tail[12] = {sc[0], sc[1], sc[5], r.gate, bound ? (double)st[2] : NAN, r.kept ? 1.0 : 0.0,
+                                 bound ? (guarded_bound ? sc[9] + sc[12] : 0.0) : NAN, guarded_bound ? sc[8] : NAN,
+                                 (double)r.nR, (double)r.nsurv2, guarded_bound ? sc[10] : NAN, r.hinted ? 1.0 : 0.0};
+        std::copy(tail, tail + 12, out + 8);
         for (int i = 0; i < nscal && i < 20; ++i) scal[i] = out[i];
-        if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
-        const int64_t nidx = std::min(std::min(r.nsurv, r.cap), cap_idx);
-        if (idx && nidx > 0) HIPCHK(h, hipMemcpy(idx, r.idx, (size_t)nidx * 8, hipMemcpyDeviceToHost));
+        int rc;
+        if ((rc = report_vectors(h, r, ub, idx, cap_idx))) return rc;
         if (ub_kept) HIPCHK(h, hipMemcpy(ub_kept, h->dkeep, (size_t)r.M * 8, hipMemcpyDeviceToHost));
         const int64_t nseed = std::min(r.G, cap_seed);
         if (seed_idx && nseed > 0)
@@ -1162,6 +1177,165 @@ static void bound_dots(gpx_handle* h, const double* dXc, int64_t M, const PruneW
                          nullptr, out, bound_mfma ? w.sc + 9 : nullptr);
 }
 
+// candidate columns of one chunk of a sweep of M candidates on h
+static int64_t sweep_chunk(const gpx_handle* h, int64_t M) {
+    const int64_t chunk_opt = h->chunk > 0 ? h->chunk : (h->Np <= 4096 ? 131072 : 65536);
+    return std::min<int64_t>(chunk_opt, (M + TBH - 1) / TBH * TBH);
+}
+
+// What the single model's sweep (sweep_core) and the ensemble's (ensemble_core) plug into select_topk_pruned:
+//   exact        the path's exact chain for rows [mb, me) of the candidate array X: out[m] (and mu / s2, where given) for every m of the range
+//   gate         the first generation [0, Gg) of the sweep's own candidates, exactly, into its output; *value for the record and *go, the
+//                decision.  The two gates are NOT the same arithmetic (rho on the right of the comparison / inside the sum) and stay apart
+//   bound        ub[n] >= the value `exact` returns for candidate n, for every n >= done
+//   after_seeds  (optional) between the seeds' compaction and their exact pass
+//   refine       (optional) a second cut of the survivor list: replaces `list` by a list of positions of the first one
+struct SelectList { const double* X; int64_t* idx; int64_t n; };
+struct SelectOps {
+    std::function<int(const double* X, int64_t mb, int64_t me, double* out, double* mu, double* s2)> exact;
+    std::function<int(int64_t Gg, double* value, bool* go)> gate;
+    std::function<int(double* ub, int64_t done)> bound;
+    std::function<int()> after_seeds;
+    std::function<int(SelectList& list)> refine;
+};
+
+// The selection-only sweep of the n members led by L: exact values only where the EI bound
+// can reach the top-k.  `legal`: the path's own conditions; the shared ones and the automatic rule are applied here.  On return candidates
+// [0, *done) of `out` are final -- exact values, or -inf where the bound rules a candidate out -- and the caller runs the plain loop
+// over the rest (plain_rest).  `rec` arrives as its owner started it (the fields behind the common head); the head is filled here.
+// `w`: the lead's workspace, laid out here before any callback runs.  `hint`: read, reset and re-armed by "prune" = -1 sweeps only.
+template <typename Rec>
+static int select_topk_pruned(gpx_handle* L, bool legal, bool selection_only, int acq_id, int n, int nP, int64_t Np_min, const double* dXc,
+                              int64_t M, int64_t k, int64_t ws_extra, bool ws_rows, PruneWs& w, PruneHint& hint, Rec& rec, double* out,
+                              const SelectOps& ops, int64_t* done) {
+    const PruneGeom geom = prune_geom(nP, k, M);
+    const int64_t G = geom.G, Gg = geom.Gg, cap = geom.cap;
+    const Rec fresh = rec;
+    auto start_rec = [&]() {
+        rec = fresh;
+        rec.path = 0, rec.M = M, rec.k = k, rec.G = G, rec.Gg = Gg, rec.cap = cap, rec.gate = NAN;
+    };
+    start_rec();
+    *done = 0;                   // candidates [0, *done) are exactly evaluated already
+    legal = legal && selection_only && acq_id == GPX_ACQ_EI && k > 0 && L->prune != 0 && M >= 3 * G;
+    bool pruning = legal && (L->prune == 1 || (M >= PRUNE_MIN_M && Np_min >= PRUNE_MIN_NP && M >= Gg + 2 * G));
+    if (!pruning) return GPX_OK;
+    hipStream_t s = L->stream;
+    int rc;
+    const int64_t kk = std::min<int64_t>(k, TOPK_PASS);
+    if ((rc = ensure(L, L->dblkv, L->cap_blk, topk_blocks(M) * kk))) return rc;
+    if ((rc = ensure(L, L->dblki, L->cap_blki, topk_blocks(M) * kk))) return rc;
+    if ((rc = ensure(L, L->dtopv, L->cap_top, (int64_t)TOPK_MAX * 2))) return rc;
+    L->dtopi = reinterpret_cast<int64_t*>(L->dtopv + TOPK_MAX);
+    if ((rc = prune_ws(L, M, cap, Gg, ws_extra, w, ws_rows))) return rc;
+    start_rec();                 // (a workspace that had to grow clears the lead's ensemble record)
+    PruneHint key;
+    key.kernel_id = L->kernel_id, key.n = n, key.d = L->d, key.nP = nP, key.Np_min = Np_min, key.M = M, key.k = k;
+    const bool automatic = L->prune < 0;       // only these sweeps read or write the carried decision
+    if (automatic && prune_hint_matches(hint, key)) {
+        // The last sweep of this shape pruned and it paid (prune_hint_after): no gate, on into the bound pass as prune = 1 does
+        rec.hinted = true;
+    } else if (automatic) {
+        // Gate, BEFORE the bound pass: the prior variance is a useful bound only where the data leave variance to explain.
+        // The first generation is needed by either path; its mean s2 / rho decides (config B's dense data: declined).
+        // A heuristic that only chooses between two correct paths.
+        if ((rc = ops.gate(Gg, &rec.gate, &pruning))) return rc;
+        *done = Gg;
+        rec.path = 1;
+    }
+    if (automatic) hint = PruneHint();         // re-earned below from this sweep's own outcome, or gone
+    if (!pruning) return GPX_OK;
+    double *const ub = w.ub, *const vals = w.vals, *const Xg = w.Xg;
+    // 1. bound pass
+    if ((rc = ops.bound(ub, *done))) return rc;
+    {
+        // 2. seeds: the G candidates with the largest bound (ties at the threshold: the first by index), exactly
+        Span sp(L, T_ACQ);
+        launch_sel_threshold(s, ub, M, (int)G, w.hist, w.st);
+        launch_sel_compact(s, ub, M, 0, w.st, nullptr, w.blk, G, dXc, (int)L->d, w.idx, Xg);
+    }
+    if (ops.after_seeds && (rc = ops.after_seeds())) return rc;
+    if ((rc = ops.exact(Xg, 0, G, vals, nullptr, nullptr))) return rc;
+    int64_t nsurv = 0;
+    {
+        // tau = the k-th best seed value; 3. survivors: every candidate not yet evaluated whose bound is not below it
+        Span sp(L, T_ACQ);
+        launch_topk(s, vals, G, (int)k, L->dblkv, L->dblki, topk_blocks(G), L->dtopv, L->dtopi);
+        launch_fill_neg_inf(s, out, *done, M);
+        launch_sel_scatter(s, w.idx, vals, G, out, ub);
+        launch_sel_compact(s, ub, M, 1, w.st, L->dtopv + (k - 1), w.blk, cap, dXc, (int)L->d, w.idx, Xg, w.sc + 5);
+        HIPCHK(L, hipMemcpyAsync(&nsurv, w.blk + w.nsel, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(L, hipStreamSynchronize(s));
+    rec.path = nsurv <= cap ? 2 : 3, rec.done = *done, rec.nsurv = nsurv;
+    rec.ub = ub, rec.idx = w.idx, rec.sc = w.sc;
+    if (automatic) hint = key, hint.armed = prune_hint_after(rec.path, nsurv, cap);
+    // 5. too many survivors -- tau = 0, a flat bound: the plain loop over everything not yet evaluated
+    if (nsurv > cap) return GPX_OK;
+    SelectList list = {Xg, w.idx, nsurv};
+    if (ops.refine && (rc = ops.refine(list))) return rc;
+    if (list.n > 0) {
+        // 4. their exact values to their own positions; everything else stays -inf and the caller's top-k runs as ever
+        if ((rc = ops.exact(list.X, 0, list.n, vals, nullptr, nullptr))) return rc;
+        Span sp(L, T_ACQ);
+        if (list.idx != w.idx) launch_sel_remap(s, w.idx, list.idx, list.n);      // (list positions -> the candidates behind them)
+        launch_sel_scatter(s, list.idx, vals, list.n, out, nullptr);
+    }
+    *done = M;
+    return GPX_OK;
+}
+
+// What the selection left: after a declined gate the rest of the lead's first chunk, so that every later launch keeps the plain loop's
+// boundaries (config B: 1 + 15 full generations instead of 16, where a loop shifted by the gate's candidates would end on a 129th);
+// then the plain loop over everything not yet evaluated
+static int plain_rest(const SelectOps& ops, const double* dXc, int64_t done, int64_t chunk, int64_t M, double* out, double* mu, double* s2) {
+    const int64_t chunk1 = std::min(chunk, M);
+    int rc;
+    if (done > 0 && done < chunk1) {
+        if ((rc = ops.exact(dXc, done, chunk1, out, mu, s2))) return rc;
+        done = chunk1;
+    }
+    return done < M ? ops.exact(dXc, done, M, out, mu, s2) : GPX_OK;
+}
+
+// Steps 4a-4c of a single model's selection-only sweep, where the rule says so: s2 <= rho - q_R, q_R the sum of
+// V^2 over the leading nR block rows in the exact chain's own bits -- the survivors that EI((bias + dot) + delta, rho - q_R) still lets
+// reach tau replace `list` (positions of the first-level list, which select_topk_pruned maps back).  nsurv <= cap of them lie in w.Xg / w.idx.
+static int second_bound(gpx_handle* h, const PruneWs& w, int64_t chunk, int sweep_order, double p0, SelectList& list) {
+    hipStream_t s = h->stream;
+    gpx_handle::PruneRecord& rec = h->prune_rec;
+    const int64_t Np = h->Np, M = rec.M, Gg = rec.Gg, cap = rec.cap, nsurv = list.n;
+    const int nP = (int)(Np / NB);
+    int nR = 0;
+    if (h->prune_rows > 0) nR = (int)std::min<int64_t>(std::min<int64_t>(h->prune_rows, nP), h->N / NB);
+    else if (h->prune_rows < 0 && M >= PRUNE_MIN_M && nP >= PRUNE_ROWS_MIN_NP && nsurv > Gg) nR = std::max(1, nP / PRUNE_ROWS_DIV);
+    if (nR <= 0 || nsurv <= 0) return GPX_OK;
+    int64_t nsurv2 = 0;
+    {
+        Span sp(h, T_BOUND);
+        for (int64_t j0 = 0; j0 < nsurv; j0 += chunk) {
+            const int64_t valid = std::min(chunk, nsurv - j0);
+            const int64_t cols = (valid + TBH - 1) / TBH * TBH;
+            // 4a. rows [0, nR 128) of the survivors' cross-Gram panels and the sweep's tiles of those block rows
+            launch_cross_gram(s, h->dXs, (int64_t)nR * NB, h->N, (int)h->d, w.Xg, j0, nsurv, cols, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
+            launch_sweep_trmm(s, h->dU, Np, nR, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk, h->short_map);
+            // 4b. ub2 = EI((bias + dot) + delta, fmax(rho - q_R, 1e-100))
+            launch_prune_ub2(s, h->dQp, chunk, nR, j0, valid, w.idx, w.dots, w.sc, h->rho, h->bias, p0, w.ub2, h->prune_keep ? w.qR : nullptr);
+        }
+    }
+    {
+        // 4c. the cut of step 3 on ub2 (sc[5]: the tau it cut with): positions of the first-level list, stably
+        Span sp(h, T_ACQ);
+        launch_sel_compact(s, w.ub2, nsurv, 1, w.st, w.sc + 5, w.blk2, cap, w.Xg, (int)h->d, w.idx2, w.Xg2);
+        HIPCHK(h, hipMemcpyAsync(&nsurv2, w.blk2 + sel_blocks(nsurv), 8, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
+    rec.nR = nR, rec.nsurv2 = nsurv2;
+    rec.ub2 = w.ub2, rec.idx2 = w.idx2, rec.qR = h->prune_keep ? w.qR : nullptr;
+    list = {w.Xg2, w.idx2, nsurv2};
+    return GPX_OK;
+}
+
 static int sweep_core(gpx_handle* h, int acq_id, const double* params, int nparams, const double* dXc,
                       int64_t M, int64_t k, double* top_val, int64_t* top_idx, double* d_acq,
                       double* d_mu, double* d_s2) {
@@ -1175,8 +1349,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     hipStream_t s = h->stream;
     const int64_t Np = h->Np;
     const int nP = (int)(Np / NB);
-    const int64_t chunk_opt = h->chunk > 0 ? h->chunk : (Np <= 4096 ? 131072 : 65536);
-    const int64_t chunk = std::min<int64_t>(chunk_opt, (M + TBH - 1) / TBH * TBH);
+    const int64_t chunk = sweep_chunk(h, M);
     if ((rc = ensure(h, h->dKs, h->cap_ks, Np * chunk))) return rc;
     if ((rc = ensure(h, h->dQp, h->cap_part, (int64_t)nP * chunk * 2))) return rc;
     h->dPp = h->dQp + (int64_t)nP * chunk;
@@ -1210,7 +1383,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     // The exact chain (cross-Gram -> V = T K* -> moments and value) for rows [mb, me) of the candidate array X, in chunks:
     // out[m] (and mu / s2 / the cache sums, where given) for every m of the range.  A candidate's value depends on its
     // coordinates alone -- not on the chunk, the tile or the column it is computed in (tests/test_gpu_prune.py).
-    auto run_chunks = [&](const double* X, int64_t mb, int64_t me, double* out, double* mu, double* s2) {
+    auto run_chunks = [&](const double* X, int64_t mb, int64_t me, double* out, double* mu, double* s2) -> int {
         for (int64_t m0 = mb; m0 < me; m0 += chunk) {
             const int64_t valid = std::min(chunk, me - m0);
             const int64_t cols = (valid + TBH - 1) / TBH * TBH;
@@ -1234,155 +1407,53 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
                 else launch_acq(s, h->dQp, h->dPp, chunk, nP, m0, valid, h->rho, h->bias, acq_id, p0, out, mu, s2, cq, cp);
             }
         }
+        return GPX_OK;
     };
 
-    // ---- selection-only sweep: exact values only where the EI bound can reach the top-k ------------
-    const PruneGeom geom = prune_geom(nP, k, M);
-    const int64_t G = geom.G, Gg = geom.Gg, cap = geom.cap;
-    const bool legal = selection_only && acq_id == GPX_ACQ_EI && k > 0 && !h->cache_on && h->prune != 0 && M >= 3 * G &&
-                       h->rho >= 1e-100 && h->rho < INFINITY;
-    bool pruning = legal && (h->prune == 1 || (M >= PRUNE_MIN_M && Np >= PRUNE_MIN_NP && M >= Gg + 2 * G));
-    int64_t done = 0;            // candidates [0, done) are exactly evaluated already
+    // ---- selection-only sweep: select_topk_pruned with this model's exact chain, gate, bound and second bound ----
     gpx_handle::PruneRecord& rec = h->prune_rec;
-    rec.path = 0;
-    rec.M = M, rec.k = k, rec.G = G, rec.Gg = Gg, rec.cap = cap;
-    rec.mean_s2 = NAN;
-    if (pruning) {
-        const int64_t nblk_top = topk_blocks(M);
-        const int64_t kk = std::min<int64_t>(k, TOPK_PASS);
-        if ((rc = ensure(h, h->dblkv, h->cap_blk, nblk_top * kk))) return rc;
-        if ((rc = ensure(h, h->dblki, h->cap_blki, nblk_top * kk))) return rc;
-        if ((rc = ensure(h, h->dtopv, h->cap_top, (int64_t)TOPK_MAX * 2))) return rc;
-        h->dtopi = reinterpret_cast<int64_t*>(h->dtopv + TOPK_MAX);
-        PruneWs w;
-        if ((rc = prune_ws(h, M, cap, Gg, 0, w, true))) return rc;
-        double *const ub = w.ub, *const vals = w.vals, *const Xg = w.Xg, *const gs2 = w.gs2, *const sc = w.sc;
-        int64_t *const idx = w.idx, *const blk = w.blk;
-        int *const hist = w.hist, *const st = w.st;
+    PruneWs w;
+    SelectOps ops;
+    ops.exact = run_chunks;
+    ops.gate = [&](int64_t Gg, double* value, bool* go) -> int {
+        run_chunks(dXc, 0, Gg, d_acq, nullptr, w.gs2);
+        launch_prune_mean(s, w.gs2, Gg, w.sc + 4);
+        double mean_s2 = 0.0;
+        HIPCHK(h, hipMemcpyAsync(&mean_s2, w.sc + 4, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        *go = mean_s2 >= h->rho * PRUNE_GATE_S2;
+        *value = mean_s2;
+        return GPX_OK;
+    };
+    // ub[n] = EI(bias + alpha . k(X, z_n) + delta, s2 = rho) >= the value the exact chain returns
+    ops.bound = [&](double* ub, int64_t done) -> int {
         // the bound pass's kernel: the matrix-pipe form for SE-ARD up to d = 18 where its guard allows (decided on the device)
         const bool bound_mfma = h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0;
-
-        PruneHint key;
-        key.kernel_id = h->kernel_id, key.n = 1, key.d = h->d, key.nP = nP, key.Np_min = Np, key.M = M, key.k = k;
-        const bool automatic = h->prune < 0;       // only these sweeps read or write the carried decision
-        if (automatic && prune_hint_matches(h->prune_hint, key)) {
-            // The last sweep of this shape pruned and it paid (prune_hint_after): no gate, on into the bound pass as prune = 1 does
-            rec.hinted = true;
-        } else if (automatic) {
-            // Gate, BEFORE the bound pass: the prior variance is a useful bound only where the data leave variance to explain.
-            // The first generation is needed by either path; its mean s2 / rho decides (config B's dense data: declined).
-            // A heuristic that only chooses between two correct paths.
-            run_chunks(dXc, 0, Gg, d_acq, nullptr, gs2);
-            done = Gg;
-            launch_prune_mean(s, gs2, Gg, sc + 4);
-            double mean_s2 = 0.0;
-            HIPCHK(h, hipMemcpyAsync(&mean_s2, sc + 4, 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipStreamSynchronize(s));
-            pruning = mean_s2 >= h->rho * PRUNE_GATE_S2;
-            rec.mean_s2 = mean_s2;
-            rec.path = 1;
-        }
-        if (automatic) h->prune_hint = PruneHint();      // re-earned below from this sweep's own outcome, or gone
-        if (pruning) {
-            {
-                // 1. bound pass: ub[n] = EI(bias + alpha . k(X, z_n) + delta, s2 = rho) >= the value the exact chain returns
-                Span sp(h, T_BOUND);
-                bound_dots(h, dXc, M, w, bound_mfma, w.dots);      // (kept: the second bound reads the survivors' dots again)
-                if (h->prune_keep) {
-                    // diagnostic: the dots as the kernel left them (gpx_prune_dots), behind the two copies below
-                    if ((rc = ensure(h, h->dkeep, h->cap_keep, (2 * M + G) * 8))) return rc;
-                    HIPCHK(h, hipMemcpyAsync(h->dkeep + (M + G) * 8, w.dots, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
-                }
-                launch_prune_ub(s, w.dots, ub, M, done, sc, h->rho, h->bias, p0);
-            }
-            rec.bound_kernel = bound_mfma ? -1 : 0;
-            int64_t* seed_keep = nullptr;
+        {
+            Span sp(h, T_BOUND);
+            bound_dots(h, dXc, M, w, bound_mfma, w.dots);      // (kept: the second bound reads the survivors' dots again)
             if (h->prune_keep) {
-                // diagnostic: the bound vector (and below the seed list) as they are before the scatter overwrites them
-                seed_keep = reinterpret_cast<int64_t*>(h->dkeep) + M;
-                HIPCHK(h, hipMemcpyAsync(h->dkeep, ub, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
+                // diagnostic: the dots as the kernel left them (gpx_prune_dots), behind the two copies below
+                if ((rc = ensure(h, h->dkeep, h->cap_keep, (2 * M + rec.G) * 8))) return rc;
+                HIPCHK(h, hipMemcpyAsync(h->dkeep + (M + rec.G) * 8, w.dots, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
             }
-            {
-                // 2. seeds: the G candidates with the largest bound (ties at the threshold: the first by index), exactly
-                Span sp(h, T_ACQ);
-                launch_sel_threshold(s, ub, M, (int)G, hist, st);
-                launch_sel_compact(s, ub, M, 0, st, nullptr, blk, G, dXc, (int)h->d, idx, Xg);
-            }
-            if (seed_keep) HIPCHK(h, hipMemcpyAsync(seed_keep, idx, (size_t)G * 8, hipMemcpyDeviceToDevice, s));
-            run_chunks(Xg, 0, G, vals, nullptr, nullptr);
-            int64_t nsurv = 0;
-            {
-                // tau = the k-th best seed value; 3. survivors: every candidate not yet evaluated whose bound is not below it
-                Span sp(h, T_ACQ);
-                launch_topk(s, vals, G, (int)k, h->dblkv, h->dblki, topk_blocks(G), h->dtopv, h->dtopi);
-                launch_fill_neg_inf(s, d_acq, done, M);
-                launch_sel_scatter(s, idx, vals, G, d_acq, ub);
-                launch_sel_compact(s, ub, M, 1, st, h->dtopv + (k - 1), blk, cap, dXc, (int)h->d, idx, Xg, sc + 5);
-                HIPCHK(h, hipMemcpyAsync(&nsurv, blk + w.nsel, 8, hipMemcpyDeviceToHost, s));
-            }
-            HIPCHK(h, hipStreamSynchronize(s));
-            rec.path = nsurv <= cap ? 2 : 3;
-            rec.done = done, rec.nsurv = nsurv;
-            rec.ub = ub, rec.idx = idx, rec.sc = sc, rec.st = st;
-            rec.kept = seed_keep != nullptr;
-            if (automatic) {
-                h->prune_hint = key;
-                h->prune_hint.armed = prune_hint_after(rec.path, nsurv, cap);
-            }
-            if (nsurv <= cap) {
-                // 4a-4c. the second bound, where the rule above says so: s2 <= rho - q_R, q_R the sum of V^2 over the leading nR block
-                // rows in the exact chain's own bits -- the survivors that EI((bias + dot) + delta, rho - q_R) still lets reach tau
-                const double* Xs = Xg;
-                const int64_t* ids = idx;
-                int64_t ns = nsurv;
-                int nR = 0;
-                if (h->prune_rows > 0) nR = (int)std::min<int64_t>(std::min<int64_t>(h->prune_rows, nP), h->N / NB);
-                else if (h->prune_rows < 0 && M >= PRUNE_MIN_M && nP >= PRUNE_ROWS_MIN_NP && nsurv > Gg) nR = std::max(1, nP / PRUNE_ROWS_DIV);
-                if (nR > 0 && nsurv > 0) {
-                    int64_t nsurv2 = 0;
-                    {
-                        Span sp(h, T_BOUND);
-                        for (int64_t j0 = 0; j0 < nsurv; j0 += chunk) {
-                            const int64_t valid = std::min(chunk, nsurv - j0);
-                            const int64_t cols = (valid + TBH - 1) / TBH * TBH;
-                            // 4a. rows [0, nR 128) of the survivors' cross-Gram panels and the sweep's tiles of those block rows
-                            launch_cross_gram(s, h->dXs, (int64_t)nR * NB, h->N, (int)h->d, Xg, j0, nsurv, cols, h->dinvell,
-                                              h->kernel_id, h->rho, h->dKs, Np);
-                            launch_sweep_trmm(s, h->dU, Np, nR, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order,
-                                              h->super_m, h->dclk, h->short_map);
-                            // 4b. ub2 = EI((bias + dot) + delta, fmax(rho - q_R, 1e-100))
-                            launch_prune_ub2(s, h->dQp, chunk, nR, j0, valid, idx, w.dots, sc, h->rho, h->bias, p0, w.ub2,
-                                             h->prune_keep ? w.qR : nullptr);
-                        }
-                    }
-                    {
-                        // 4c. the cut of step 3 on ub2 (sc[5]: the tau it cut with): positions of the first-level list, stably
-                        Span sp(h, T_ACQ);
-                        launch_sel_compact(s, w.ub2, nsurv, 1, st, sc + 5, w.blk2, cap, Xg, (int)h->d, w.idx2, w.Xg2);
-                        HIPCHK(h, hipMemcpyAsync(&nsurv2, w.blk2 + sel_blocks(nsurv), 8, hipMemcpyDeviceToHost, s));
-                    }
-                    HIPCHK(h, hipStreamSynchronize(s));
-                    rec.nR = nR, rec.nsurv2 = nsurv2;
-                    rec.ub2 = w.ub2, rec.idx2 = w.idx2, rec.qR = h->prune_keep ? w.qR : nullptr;
-                    Xs = w.Xg2, ids = w.idx2, ns = nsurv2;
-                }
-                // 4. their exact values to their own positions; everything else stays -inf and the top-k below runs as ever
-                run_chunks(Xs, 0, ns, vals, nullptr, nullptr);
-                Span sp(h, T_ACQ);
-                if (ids != idx) launch_sel_remap(s, idx, w.idx2, ns);      // (list positions -> the candidates behind them)
-                launch_sel_scatter(s, ids, vals, ns, d_acq, nullptr);
-                done = M;
-            }
-            // 5. (else) too many survivors -- tau = 0, a flat bound: the plain loop over everything not yet evaluated
+            launch_prune_ub(s, w.dots, ub, M, done, w.sc, h->rho, h->bias, p0);
         }
-    }
-    if (done > 0 && done < std::min(chunk, M)) {
-        // the gate declined: the rest of the first chunk, so that every later launch keeps the plain loop's boundaries (config B:
-        // 1 + 15 full generations instead of 16, where a loop shifted by the gate's candidates would end on a 129th)
-        run_chunks(dXc, done, std::min(chunk, M), d_acq, d_mu, d_s2);
-        done = std::min(chunk, M);
-    }
-    if (done < M) run_chunks(dXc, done, M, d_acq, d_mu, d_s2);
+        rec.bound_kernel = bound_mfma ? -1 : 0, rec.st = w.st, rec.kept = h->prune_keep != 0;
+        // diagnostic: the bound vector (and after_seeds: the seed list) as they are before the scatter overwrites them
+        if (rec.kept) HIPCHK(h, hipMemcpyAsync(h->dkeep, ub, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
+        return GPX_OK;
+    };
+    ops.after_seeds = [&]() -> int {
+        if (rec.kept) HIPCHK(h, hipMemcpyAsync(h->dkeep + M * 8, w.idx, (size_t)rec.G * 8, hipMemcpyDeviceToDevice, s));
+        return GPX_OK;
+    };
+    ops.refine = [&](SelectList& list) -> int { return second_bound(h, w, chunk, sweep_order, p0, list); };
+    int64_t done = 0;
+    const bool legal = !h->cache_on && h->rho >= 1e-100 && h->rho < INFINITY;
+    if ((rc = select_topk_pruned(h, legal, selection_only, acq_id, 1, nP, Np, dXc, M, k, 0, true, w, h->prune_hint, rec, d_acq, ops, &done)))
+        return rc;
+    if ((rc = plain_rest(ops, dXc, done, chunk, M, d_acq, d_mu, d_s2))) return rc;
     if (h->cache_on) {
         h->cache_valid = true;
         h->cache_M = M;
@@ -1971,6 +2042,12 @@ extern "C" int gpx_rff_gram(gpx_handle* h, const double* W, const double* b, int
 }
 
 // ---- ensemble sweep (hyper-parameter marginalisation; pybo/bayesopt.py:115) ------------------------------
+// member m's failure as the lead reports it
+static int member_fail(gpx_handle* L, const gpx_handle* h, int m, int rc) {
+    if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
+    return rc;
+}
+
 static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double* params, int nparams,
                          const double* dXc, int64_t M, int64_t k, double* top_val, int64_t* top_idx,
                          double* d_out, double* d_mu, double* d_s2) {
@@ -2000,16 +2077,13 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
     // The exact ensemble chain for the `cnt` candidates X: every member's sweep in member order, each folded into the running
     // sums, then one division -> o[c] (and mu / s2, where given).  A candidate's value depends on its coordinates alone.
     // gate_mean (mode 0 only): member m's mean s2 over these candidates -> gate_mean[m] (its s2 vector passes through t1).
-    auto exact = [&](const double* X, int64_t cnt, double* o, double* o_mu, double* o_s2, double* gate_mean) -> int {
+    auto members = [&](const double* X, int64_t cnt, double* o, double* o_mu, double* o_s2, double* gate_mean) -> int {
         for (int m = 0; m < n; ++m) {
             gpx_handle* h = mem[m];
             int rcm = (mode == 0) ? sweep_core(h, acq_id, mesS ? params + (size_t)m * mesS : params, mesS ? mesS : nparams, X, cnt, 0, nullptr,
                                                nullptr, t0, nullptr, gate_mean ? t1 : nullptr)
                                   : sweep_core(h, GPX_ACQ_MEAN, nullptr, 0, X, cnt, 0, nullptr, nullptr, nullptr, t0, t1);
-            if (rcm) {
-                if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
-                return rcm;
-            }
+            if (rcm) return member_fail(L, h, m, rcm);
             if (gate_mean) launch_prune_mean(h->stream, t1, cnt, gate_mean + m);
             HIPCHK(L, hipStreamSynchronize(h->stream));
             launch_ens_accum(L->stream, acc0, acc1, t0, t1, cnt, mode, m == 0);
@@ -2022,10 +2096,10 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
         return GPX_OK;
     };
 
-    // ---- selection-only ensemble sweep: section 2.1 step for step on the MEAN of the members' bounds ----
-    // The sum of the members' bounds, accumulated and divided exactly as `exact` accumulates and divides their values, is >= the
+    // ---- selection-only ensemble sweep: select_topk_pruned on the MEAN of the members' bounds ----
+    // The sum of the members' bounds, accumulated and divided exactly as `members` accumulates and divides their values, is >= the
     // ensemble's value bit for bit (addition and division by n > 0 are monotone).  The lead's option "prune" governs.
-    int nPmax = 0;
+    int nPmax = 0;               // (the member with the most block rows: the smallest generation)
     int64_t Np_min = INT64_MAX;
     bool members_ok = true;
     for (int m = 0; m < n; ++m) {
@@ -2033,130 +2107,59 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
         Np_min = std::min(Np_min, mem[m]->Np);
         members_ok = members_ok && !mem[m]->cache_on && mem[m]->rho >= 1e-100 && mem[m]->rho < INFINITY;
     }
-    const PruneGeom geom = prune_geom(nPmax, k, M);      // (the member with the most block rows: the smallest generation)
-    const int64_t G = geom.G, Gg = geom.Gg, cap = geom.cap;
-    const bool selection_only = !d_out && !d_mu && !d_s2;
-    const bool legal = selection_only && acq_id == GPX_ACQ_EI && k > 0 && members_ok && L->prune != 0 && M >= 3 * G;
-    bool pruning = legal && (L->prune == 1 || (M >= PRUNE_MIN_M && Np_min >= PRUNE_MIN_NP && M >= Gg + 2 * G));
-    int64_t done = 0;            // candidates [0, done) are exactly evaluated already
-    gpx_handle::EnsPruneRecord& rec = L->ens_rec;
-    auto start_rec = [&]() {
-        rec = gpx_handle::EnsPruneRecord();
-        rec.path = 0, rec.n = n;
-        rec.M = M, rec.k = k, rec.G = G, rec.Gg = Gg, rec.cap = cap;
-        rec.gate = NAN;
-    };
-    start_rec();
     const int64_t d = L->d;
-    if (pruning) {
-        hipStream_t s = L->stream;
-        const int64_t kk = std::min<int64_t>(k, TOPK_PASS);
-        if ((rc = ensure(L, L->dblkv, L->cap_blk, topk_blocks(M) * kk))) return rc;
-        if ((rc = ensure(L, L->dblki, L->cap_blki, topk_blocks(M) * kk))) return rc;
-        if ((rc = ensure(L, L->dtopv, L->cap_top, (int64_t)TOPK_MAX * 2))) return rc;
-        L->dtopi = reinterpret_cast<int64_t*>(L->dtopv + TOPK_MAX);
-        PruneWs w;               // the lead's: the ensemble bound vector, seeds and survivors; extra = [gate means n][delta n]
-        if ((rc = prune_ws(L, M, cap, Gg, 2 * n, w))) return rc;
-        start_rec();             // (a workspace that had to grow clears the record)
-        double *const ub = w.ub, *const vals = w.vals, *const Xg = w.Xg, *const sc = w.sc;
-        double *const gate_mean = w.extra, *const delta = w.extra + n;
-        PruneHint key;
-        key.kernel_id = L->kernel_id, key.n = n, key.d = d, key.nP = nPmax, key.Np_min = Np_min, key.M = M, key.k = k;
-        const bool automatic = L->prune < 0;       // only these sweeps read or write the lead's carried decision
-        if (automatic && prune_hint_matches(L->ens_hint, key)) {
-            // as in section 2.1: the last ensemble sweep of this shape pruned and it paid -- no gate, no member generations for it
-            rec.hinted = true;
-        } else if (automatic) {
-            // Gate, as in section 2.1: the first generation is needed by either path; the members' mean s2 / rho decides
-            if ((rc = exact(dXc, Gg, out, nullptr, nullptr, gate_mean))) return rc;
-            done = Gg;
-            std::vector<double> gm((size_t)n);
-            HIPCHK(L, hipMemcpyAsync(gm.data(), gate_mean, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(L, hipStreamSynchronize(s));
-            double g = 0.0;
-            for (int m = 0; m < n; ++m) g += gm[m] / mem[m]->rho;
-            g /= (double)n;
-            pruning = g >= PRUNE_GATE_S2;
-            rec.gate = g;
-            rec.path = 1;
+    hipStream_t s = L->stream;
+    gpx_handle::EnsPruneRecord& rec = L->ens_rec;
+    rec.n = n;
+    PruneWs w;                   // the lead's: the ensemble bound vector, seeds and survivors; extra = [gate means n][delta n]
+    SelectOps ops;
+    ops.exact = [&](const double* X, int64_t mb, int64_t me, double* o, double* o_mu, double* o_s2) -> int {
+        return members(X + mb * d, me - mb, o + mb, o_mu ? o_mu + mb : nullptr, o_s2 ? o_s2 + mb : nullptr, nullptr);
+    };
+    // the members' mean s2 / rho over the first generation decides
+    ops.gate = [&](int64_t Gg, double* value, bool* go) -> int {
+        if ((rc = members(dXc, Gg, out, nullptr, nullptr, w.extra))) return rc;
+        std::vector<double> gm((size_t)n);
+        HIPCHK(L, hipMemcpyAsync(gm.data(), w.extra, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(L, hipStreamSynchronize(s));
+        double g = 0.0;
+        for (int m = 0; m < n; ++m) g += gm[m] / mem[m]->rho;
+        *value = g / (double)n;
+        *go = *value >= PRUNE_GATE_S2;
+        return GPX_OK;
+    };
+    // per member in member order: its dots (own factor, weights and workspace) -> t1, its EI bound folded into the running sum ub; then ub / n
+    ops.bound = [&](double* ub, int64_t done) -> int {
+        double* const delta = w.extra + n;
+        for (int m = 0; m < n; ++m) {
+            gpx_handle* h = mem[m];
+            HIPCHK(L, hipSetDevice(h->device));
+            if ((rc = ensure_inverse(h))) return member_fail(L, h, m, rc);
+            PruneWs wm = w;
+            if (h != L) {
+                h->prune_rec = gpx_handle::PruneRecord();      // (the pass overwrites the workspace its last record points into)
+                if ((rc = prune_ws(h, 0, 0, 0, 0, wm))) return member_fail(L, h, m, rc);
+            }
+            {
+                Span sp(h, T_BOUND);
+                bound_dots(h, dXc, M, wm, h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0, t1);
+                launch_prune_ub_fold(h->stream, t1, ub, M, wm.sc, h->rho, h->bias, params[0], m == 0, delta + m);
+            }
+            HIPCHK(L, hipStreamSynchronize(h->stream));      // t1 and ub pass to the next member's stream
         }
-        if (automatic) L->ens_hint = PruneHint();        // re-earned below from this sweep's own outcome, or gone
-        if (pruning) {
-            // 1. bound pass, per member in member order: its dots (own factor, weights and workspace) -> t1, its EI bound folded
-            // into the running sum ub; then ub / n
-            for (int m = 0; m < n; ++m) {
-                gpx_handle* h = mem[m];
-                HIPCHK(L, hipSetDevice(h->device));
-                if ((rc = ensure_inverse(h))) {
-                    if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
-                    return rc;
-                }
-                PruneWs wm = w;
-                if (h != L) {
-                    h->prune_rec = gpx_handle::PruneRecord();      // (the pass overwrites the workspace its last record points into)
-                    if ((rc = prune_ws(h, 0, 0, 0, 0, wm))) {
-                        L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
-                        return rc;
-                    }
-                }
-                {
-                    Span sp(h, T_BOUND);
-                    bound_dots(h, dXc, M, wm, h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0, t1);
-                    launch_prune_ub_fold(h->stream, t1, ub, M, wm.sc, h->rho, h->bias, params[0], m == 0, delta + m);
-                }
-                HIPCHK(L, hipStreamSynchronize(h->stream));      // t1 and ub pass to the next member's stream
-            }
-            {
-                Span sp(L, T_BOUND);
-                launch_prune_ub_mean(s, ub, M, done, (double)n);
-            }
-            {
-                // 2. seeds: the G candidates with the largest bound (ties at the threshold: the first by index), exactly
-                Span sp(L, T_ACQ);
-                launch_sel_threshold(s, ub, M, (int)G, w.hist, w.st);
-                launch_sel_compact(s, ub, M, 0, w.st, nullptr, w.blk, G, dXc, (int)d, w.idx, Xg);
-            }
-            HIPCHK(L, hipStreamSynchronize(s));                  // the members read Xg from their own streams
-            if ((rc = exact(Xg, G, vals, nullptr, nullptr, nullptr))) return rc;
-            int64_t nsurv = 0;
-            {
-                // tau = the k-th best seed value; 3. survivors: every candidate not yet evaluated whose bound is not below it
-                Span sp(L, T_ACQ);
-                launch_topk(s, vals, G, (int)k, L->dblkv, L->dblki, topk_blocks(G), L->dtopv, L->dtopi);
-                launch_fill_neg_inf(s, out, done, M);
-                launch_sel_scatter(s, w.idx, vals, G, out, ub);
-                launch_sel_compact(s, ub, M, 1, w.st, L->dtopv + (k - 1), w.blk, cap, dXc, (int)d, w.idx, Xg, sc + 5);
-                HIPCHK(L, hipMemcpyAsync(&nsurv, w.blk + w.nsel, 8, hipMemcpyDeviceToHost, s));
-            }
-            HIPCHK(L, hipStreamSynchronize(s));
-            rec.path = nsurv <= cap ? 2 : 3;
-            rec.done = done, rec.nsurv = nsurv;
-            rec.ub = ub, rec.idx = w.idx, rec.sc = sc, rec.delta = delta;
-            if (automatic) {
-                L->ens_hint = key;
-                L->ens_hint.armed = prune_hint_after(rec.path, nsurv, cap);
-            }
-            if (nsurv <= cap) {
-                // 4. their exact values to their own positions; everything else stays -inf and the top-k below runs as ever
-                if (nsurv > 0) {
-                    if ((rc = exact(Xg, nsurv, vals, nullptr, nullptr, nullptr))) return rc;
-                    Span sp(L, T_ACQ);
-                    launch_sel_scatter(s, w.idx, vals, nsurv, out, nullptr);
-                }
-                done = M;
-            }
-            // 5. (else) too many survivors: the plain loop over everything not yet evaluated
+        {
+            Span sp(L, T_BOUND);
+            launch_prune_ub_mean(s, ub, M, done, (double)n);
         }
-    }
-    const int64_t chunk_opt = L->chunk > 0 ? L->chunk : (L->Np <= 4096 ? 131072 : 65536);
-    const int64_t chunk1 = std::min(std::min<int64_t>(chunk_opt, (M + TBH - 1) / TBH * TBH), M);
-    if (done > 0 && done < chunk1) {
-        // the gate declined: the rest of the lead's first chunk, so that every later launch keeps the plain loop's boundaries
-        if ((rc = exact(dXc + done * d, chunk1 - done, out + done, nullptr, nullptr, nullptr))) return rc;
-        done = chunk1;
-    }
-    if (done < M && (rc = exact(dXc + done * d, M - done, out + done, d_mu ? d_mu + done : nullptr, d_s2 ? d_s2 + done : nullptr, nullptr)))
+        rec.delta = delta;
+        return GPX_OK;
+    };
+    ops.after_seeds = [&]() -> int { HIPCHK(L, hipStreamSynchronize(s)); return GPX_OK; };      // the members read the seeds from their own streams
+    int64_t done = 0;
+    if ((rc = select_topk_pruned(L, members_ok, !d_out && !d_mu && !d_s2, acq_id, n, nPmax, Np_min, dXc, M, k, 2 * n, false, w, L->ens_hint, rec,
+                                 out, ops, &done)))
         return rc;
+    if ((rc = plain_rest(ops, dXc, done, sweep_chunk(L, M), M, out, d_mu, d_s2))) return rc;
     if (k > 0) {
         if ((rc = topk_core(L, out, M, k, top_val, top_idx))) return rc;
     } else {
@@ -2318,18 +2321,14 @@ extern "C" int gpx_ensemble_prune_report(gpx_handle* const* members, int n_membe
         HIPCHK(h, hipStreamSynchronize(h->stream));
         std::vector<double> out((size_t)(11 + n_members), NAN);
         out[10 + n_members] = r.hinted ? 1.0 : 0.0;      // behind the deltas: head[8] is tau, and callers built against 10 + n read on as before
-        const double head[10] = {(double)r.path, (double)r.M,   (double)r.k,     (double)r.G, (double)r.Gg,
-                                 (double)r.done, (double)r.cap, (double)r.nsurv, NAN,         r.gate};
-        std::copy(head, head + 10, out.begin());
+        report_head(r, out.data());
+        out[9] = r.gate;
         if (bound) {
             HIPCHK(h, hipMemcpy(&out[8], r.sc + 5, 8, hipMemcpyDeviceToHost));
             HIPCHK(h, hipMemcpy(&out[10], r.delta, (size_t)n_members * 8, hipMemcpyDeviceToHost));
         }
         for (int i = 0; i < nscal && i < 11 + n_members; ++i) scal[i] = out[i];
-        if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
-        const int64_t nidx = std::min(std::min(r.nsurv, r.cap), cap_idx);
-        if (idx && nidx > 0) HIPCHK(h, hipMemcpy(idx, r.idx, (size_t)nidx * 8, hipMemcpyDeviceToHost));
-        return GPX_OK;
+        return report_vectors(h, r, ub, idx, cap_idx);
     });
 }
 

@@ -157,17 +157,22 @@ struct gpx_handle {
     double* dens = nullptr;   // ensemble sweep: accumulators + member outputs (5 M)
     int64_t cap_ens = 0;
     int prune = -1;           // option: selection-only sweeps skip candidates whose EI bound cannot reach the top-k (-1 by size and gate, 0 never, 1 wherever legal)
-    char* dprune = nullptr;   // their workspace (one allocation, laid out in api.hip: sweep_core)
+    char* dprune = nullptr;   // their workspace (one allocation, laid out in api.hip: prune_ws)
     int64_t cap_prune = 0;    // ... in bytes
-    // what the last sweep decided (gpx_prune_report, gpx_diag.h): host scalars and where its vectors lie in dprune
-    struct PruneRecord {
+    // What the last selection-only sweep decided: the head both records share, filled by select_topk_pruned (api.hip) -- host scalars and
+    // where the sweep's vectors lie in the lead's dprune
+    struct SelectRecord {
         int path = -1;            // -1 no sweep yet, 0 plain, 1 the gate declined, 2 pruned, 3 bound pass ran but too many survived
         int64_t M = 0, k = 0, G = 0, Gg = 0, done = 0, cap = 0, nsurv = 0;
-        double mean_s2 = 0.0;     // the gate's (NaN where it did not run)
+        double gate = 0.0;        // the gate's value (NaN where it did not run): the single model's mean s2, NOT divided by rho; the ensemble's
+                                  // mean over the members of mean(s2_m) / rho_m
         bool hinted = false;      // the gate was skipped on the carried decision (prune_hint.h)
         const double* ub = nullptr;
         const int64_t* idx = nullptr;
-        const double* sc = nullptr;
+        const double* sc = nullptr;       // sc[5] = tau as the survivor pass cut with it
+    };
+    // the last sweep of this handle (gpx_prune_report, gpx_diag.h)
+    struct PruneRecord : SelectRecord {
         const int* st = nullptr;
         int bound_kernel = -1;    // -1: sc[9] says which kernel wrote the dots; 0: the host chose k_sweep_rankq<1> (no guard ran)
         bool kept = false;        // dkeep holds this sweep's bound vector and seed list as they were before the scatter
@@ -177,15 +182,9 @@ struct gpx_handle {
         const double *qR = nullptr, *ub2 = nullptr;      // aligned with idx (qR only under prune_keep)
         const int64_t* idx2 = nullptr;
     } prune_rec;
-    // what the last ENSEMBLE sweep led by this handle decided (gpx_ensemble_prune_report): its vectors lie in this handle's dprune
-    struct EnsPruneRecord {
-        int path = -1, n = 0;
-        int64_t M = 0, k = 0, G = 0, Gg = 0, done = 0, cap = 0, nsurv = 0;
-        double gate = 0.0;        // mean over the members of mean(s2_m) / rho_m of the gate's generation (NaN where it did not run)
-        bool hinted = false;      // the gate was skipped on the carried decision
-        const double* ub = nullptr;
-        const int64_t* idx = nullptr;
-        const double* sc = nullptr;       // sc[5] = tau as the survivor pass cut with it
+    // the last ENSEMBLE sweep led by this handle (gpx_ensemble_prune_report): its vectors lie in this handle's dprune
+    struct EnsPruneRecord : SelectRecord {
+        int n = 0;
         const double* delta = nullptr;    // n: the members' delta_m
     } ens_rec;
     // the gate's decision carried to the next sweep of the same shape (prune_hint.h): this handle's own sweeps / the ensemble sweeps it

@@ -301,7 +301,7 @@ static int sweep_order_of(int order, int short_map, int sm, int NT) {
 }
 
 // nR: the block rows [0, nR) the launch covers -- the factor's Np / 128 for the sweep itself, fewer for the row-prefix pass of a
-// selection-only sweep (api.hip: sweep_core, step 4a), which needs rows [0, nR 128) of every Ks panel only.
+// selection-only sweep (api.hip: second_bound, step 4a), which needs rows [0, nR 128) of every Ks panel only.
 void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const double* Ks, int64_t ldk,
                        int64_t cols, const double* a, double* Qp, double* Pp, int64_t ldp,
                        int tile_order, int super_m, unsigned long long* clk, int short_map) {

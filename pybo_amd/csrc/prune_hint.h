@@ -1,7 +1,7 @@
 // prune_hint.h -- the gate's decision of a selection-only sweep, carried from one sweep to the next.
 // Plain C++, no HIP: tests/c/prune_hint_check.cpp compiles it with the host compiler alone.
 //
-// The gate (api.hip: sweep_core, ensemble_core under option "prune" = -1) spends a whole exact generation on a yes / no answer.  A sweep
+// The gate (api.hip: select_topk_pruned under option "prune" = -1, with sweep_core's or ensemble_core's `gate`) spends a whole exact generation on a yes / no answer.  A sweep
 // that pruned reports afterwards how well pruning paid -- its first-level survivor count against cap -- which is better evidence than the
 // gate's proxy; where it paid clearly, the next sweep of the same shape on the same handle skips the gate and goes straight into the
 // bound pass, exactly as "prune" = 1 does (done = 0).  The decision is re-earned from every sweep's own outcome; a stale one costs one

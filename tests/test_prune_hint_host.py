@@ -43,14 +43,19 @@ def test_the_check_is_clean_under_the_address_and_undefined_behaviour_sanitizers
 
 
 def test_the_library_includes_the_header_the_check_includes():
-    """One definition of the key, the match and the rule: the handle, both sweep paths and the host program use prune_hint.h."""
+    """One definition of the key, the match and the rule: the handle, both sweep paths and the host program use prune_hint.h.  The
+    library consults them in ONE place, the selection driver, and both sweep paths go through that driver."""
     csrc = os.path.join(ROOT, 'pybo_amd', 'csrc')
     hdr = open(os.path.join(csrc, 'prune_hint.h')).read()
     assert 'threadIdx' not in hdr and 'hip_runtime' not in hdr and 'gpx_internal' not in hdr      # plain C++
     assert '#include "prune_hint.h"' in open(os.path.join(csrc, 'gpx_internal.h')).read()
     api = open(os.path.join(csrc, 'api.hip')).read()
-    for body in (api[api.index('static int sweep_core('):api.index('extern "C" int gpx_sweep_dev(')],
-                 api[api.index('static int ensemble_core('):api.index('static int ensemble_check(')]):
-        assert 'prune_hint_matches(' in body and 'prune_hint_after(' in body
+    driver = api[api.index('static int select_topk_pruned('):api.index('static int plain_rest(')]
+    for call in ('prune_hint_matches(', 'prune_hint_after('):
+        assert api.count(call) == 1 and driver.count(call) == 1, call
+    assert api.count('select_topk_pruned(') == 3                                      # its definition and the two calls below
+    for body, hint in ((api[api.index('static int sweep_core('):api.index('extern "C" int gpx_sweep_dev(')], 'h->prune_hint'),
+                       (api[api.index('static int ensemble_core('):api.index('static int ensemble_check(')], 'L->ens_hint')):
+        assert body.count('select_topk_pruned(') == 1 and body.count(hint) == 1        # each hands its own hint object to the driver
     assert '#include "../../pybo_amd/csrc/prune_hint.h"' in open(SRC).read()
     assert 'prune_hint.h' in open(os.path.join(csrc, 'build.sh')).read()              # a dependency of the incremental build
