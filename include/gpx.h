@@ -53,9 +53,12 @@ enum gpx_acq {
     GPX_ACQ_PI = 1,   /* model.get_tail(target, X)         [pybo/policies/simple.py:39]  params = {target} */
     GPX_ACQ_UCB = 2,  /* mu + sqrt(beta*s2)                [pybo/policies/simple.py:62-73] params = {beta} */
     GPX_ACQ_MEAN = 3, /* posterior mean                    [pybo/recommenders.py:19-25]  no params */
-    GPX_ACQ_MES = 16  /* max-value entropy search: mean_s g((y*_s - mu) / sqrt(s2)), g(c) = c phi(c) / (2 Phi(c)) - log Phi(c); ids 4 .. 15: refused.
+    GPX_ACQ_MES = 16, /* max-value entropy search: mean_s g((y*_s - mu) / sqrt(s2)), g(c) = c phi(c) / (2 Phi(c)) - log Phi(c); ids 4 .. 15: refused.
                        * params = the S sampled maxima y*_s, 1 <= nparams = S <= 64, all finite (else GPX_EARG); gpx_ensemble_sweep*: n_members * S of them,
                        * member-major, member m scores with its slice.  Taken by gpx_sweep*, gpx_sweep_update*, gpx_ensemble_sweep*; never pruned; no batch. */
+    GPX_ACQ_KG = 32   /* knowledge gradient over a support set A (Frazier 2009): E_Z max(mu(z) + b_0 Z, max_j mu(a_j) + b_j Z) - max(mu(z), max_j mu(a_j)),
+                       * b_0 = s2 / D, b_j = Sigma(a_j, z) / D, D = sqrt(s2 + sn2).  params = A, raw coordinates (m, d) row-major on the HOST, nparams = m d,
+                       * 1 <= m <= 127, finite (else GPX_EARG).  Taken by gpx_sweep* ONLY (every output, cache seeding); never pruned.  Ids 17 .. 31: refused */
 };
 
 /* ---- lifetime --------------------------------------------------------------------------- */
@@ -136,9 +139,8 @@ int64_t gpx_fail_pivot(const gpx_handle *h);
 /* introspection for parity tests (host outputs): which = 0: L (N,N) lower Cholesky factor, row-major (K + sn2 I = L L^T);
  * 1: T = L^-1 (N,N) lower; 2: K + sn2 I, upper triangle (only after gpx_fit_stage(.., 1): the factorisation consumes it) */
 int gpx_get_matrix(gpx_handle *h, int which, double *out);
-/* a = L^-1 (y - bias) (N,) and alpha = (K + sn2 I)^-1 (y - bias) (N,) */
+/* a = L^-1 (y - bias), alpha = (K + sn2 I)^-1 (y - bias), both (N,); gpx_fit_stage (parity): the fit, stopped after the Gram build (stage 1) or Cholesky (2) */
 int gpx_get_vectors(gpx_handle *h, double *a, double *alpha);
-/* debugging/parity: run the fit but stop after the Gram build (stage=1) or Cholesky (stage=2) */
 int gpx_fit_stage(gpx_handle *h, const double *X, int64_t N, int64_t d, const double *y,
                   int kernel_id, const double *ell, double rho, double sn2, double bias, int stage);
 
@@ -165,11 +167,9 @@ int gpx_predict_cov(gpx_handle *h, const double *Xc, int64_t M, double *mu, doub
  * jitter finite, >= 0).  A draw's bits do not depend on S.  GPX_ENOTPD (out undefined): gpx_last_error names the pivot; gpx_fail_pivot still describes fits. */
 int gpx_sample_joint(gpx_handle *h, const double *Xc, int64_t M, const double *z, int64_t S, int noisy, double jitter, double *out);
 
-/* ---- acquisition sweep + top-k = the batched index call and argsort of the solver
- *      finit = f(xgrid); idx = argsort(finit)[::-1]       [pybo/solvers/lbfgs.py:50-51] ---- */
-/* Evaluates acq over M candidates, returns the k best (value desc, then index asc) in host
- * buffers top_val[k], top_idx[k] (indices are LOCAL to Xc; add your shard offset).  acq_all, mu,
- * s2 (each (M,), host in gpx_sweep / device in gpx_sweep_dev) are optional (NULL to skip). */
+/* ---- acquisition sweep + top-k = the solver's batched index call and argsort: finit = f(xgrid); idx = argsort(finit)[::-1] [pybo/solvers/lbfgs.py:50-51] */
+/* Evaluates acq over M candidates, returns the k best (value desc, then index asc) in host buffers top_val[k], top_idx[k] (indices are LOCAL to Xc;
+ * add your shard offset).  acq_all, mu, s2 (each (M,), host in gpx_sweep / device in gpx_sweep_dev) are optional (NULL to skip). */
 int gpx_sweep(gpx_handle *h, int acq_id, const double *params, int nparams, const double *Xc, int64_t M, int64_t k,
               double *top_val, int64_t *top_idx, double *acq_all, double *mu, double *s2);
 int gpx_sweep_dev(gpx_handle *h, int acq_id, const double *params, int nparams, const double *dXc, int64_t M, int64_t k,
@@ -186,18 +186,18 @@ int gpx_sweep_update(gpx_handle *h, int acq_id, const double *params, int nparam
 int gpx_sweep_update_dev(gpx_handle *h, int acq_id, const double *params, int nparams, int64_t k,
                          double *top_val, int64_t *top_idx, double *d_acq_all, double *d_mu, double *d_s2);
 /* nb greedy picks on the LIVE sweep cache, each conditioned on the ones before it at their posterior mean (mean fixed, variance shrinks).
- * EI / PI / UCB (GPX_ACQ_MEAN: GPX_EARG).  1 <= nb <= min(64, M).  sel_val, sel_idx (nb) required; sel_s2 (nb) and s2_all (M: the variances
+ * EI / PI / UCB (GPX_ACQ_MEAN: GPX_EARG).  1 <= nb <= min(64, M).  sel_val, sel_idx (nb) required; sel_s2 (nb) and s2all (M: the variances
  * that scored the LAST pick) optional, all host.  Model, cache, queued corrections and a pending announcement are untouched. GPX_ESTATE without a cache. */
-int gpx_sweep_batch(gpx_handle *h, int acq_id, const double *params, int nparams, int64_t nb,
-                    double *sel_val, int64_t *sel_idx, double *sel_s2, double *s2_all);
+int gpx_sweep_batch(gpx_handle *h, int acq_id, const double *params, int nparams, int64_t nb, double *sel_val, int64_t *sel_idx, double *sel_s2, double *s2all);
+/* Knowledge gradient (GPX_ACQ_KG) and its gradient at M <= 4096 points, host buffers: A (m, d) the support set as for the sweep, f (M,), g (M, d) -- the
+ * `f(x, grad=True)` of the L-BFGS refinement.  f agrees with the sweep's value to rounding.  One host synchronisation; fit, sweep cache and queue untouched. */
+int gpx_kg_grad(gpx_handle *h, const double *A, int64_t m, const double *Xc, int64_t M, double *f, double *g);
 /* number of candidates in the live sweep cache (0: none) */
 int64_t gpx_sweep_cache_size(const gpx_handle *h);
 
 /* ---- Thompson sampling = model.sample_f(n, rng).get(X)   [pybo/policies/simple.py:44-48] -- */
-/* S random-Fourier-feature posterior draws f_s(x) = bias + sum_j theta[s][j] cos(W[s][j].x + b[s][j])
- * (the sqrt(2 rho/n) factor is folded into theta by the caller).  W (S,n,d), b (S,n), theta (S,n)
- * on the host.  For each draw returns the k best candidates: top_val (S,k), top_idx (S,k).
- * vals_all (S,M) optional. */
+/* S random-Fourier-feature posterior draws f_s(x) = bias + sum_j theta[s][j] cos(W[s][j].x + b[s][j]) (the sqrt(2 rho/n) factor is folded into theta by the
+ * caller).  W (S,n,d), b (S,n), theta (S,n) on the host.  Per draw returns the k best candidates: top_val (S,k), top_idx (S,k).  vals_all (S,M) optional. */
 int gpx_rff_sweep(gpx_handle *h, const double *W, const double *b, const double *theta, int64_t S, int64_t n, int64_t d, double bias,
                   const double *Xc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *vals_all);
 int gpx_rff_sweep_dev(gpx_handle *h, const double *W, const double *b, const double *theta, int64_t S, int64_t n, int64_t d, double bias,

@@ -82,6 +82,7 @@ SYMBOLS = {
     'gpx_sweep_update_dev': (C.c_int, [_P, C.c_int, _P, C.c_int, _i64, _P, _P, _P, _P, _P]),
     'gpx_sweep_batch': (C.c_int, [_P, C.c_int, _P, C.c_int, _i64, _P, _P, _P, _P]),
     'gpx_sweep_cache_size': (_i64, [_P]),
+    'gpx_kg_grad': (C.c_int, [_P, _P, _i64, _P, _i64, _P, _P]),
     'gpx_rff_sweep': (C.c_int, [_P, _P, _P, _P, _i64, _i64, _i64, _dbl, _P, _i64, _i64, _P, _P, _P]),
     'gpx_rff_sweep_dev': (C.c_int, [_P, _P, _P, _P, _i64, _i64, _i64, _dbl, _P, _i64, _i64, _P, _P, _P]),
     'gpx_rff_grad': (C.c_int, [_P, _P, _P, _P, _i64, _i64, _dbl, _P, _i64, _P, _P]),
@@ -111,6 +112,11 @@ GPX_OK, GPX_EARG, GPX_ENOTPD, GPX_EHIP, GPX_EOOM, GPX_ESTATE, GPX_ERCCL = 0, -1,
 COMM_ID_BYTES = 128
 KERNELS = {'se': 0, 'matern5': 1, 'matern3': 2, 'matern1': 3}
 ACQ = {'ei': 0, 'pi': 1, 'ucb': 2, 'mean': 3, 'mes': 16}       # (ids 4 .. 15 are refused by the library)
+# The acquisitions that are NOT a function of a candidate's own moments, in a table of their own (tests/test_mes_cpu.py pins ACQ's
+# values): 'kg', the knowledge gradient over a support set -- param = the set (m, d), m <= KG_MAX_SUPPORT; cold sweeps only; ids
+# 17 .. 31 are refused by the library
+ACQ_SUPPORT = {'kg': 32}
+KG_MAX_SUPPORT = 127
 TIMER_NAMES = ['gram', 'cholesky', 'trtri', 'alpha', 'cross_gram', 'sweep_trmm', 'acq_topk', 'rff',
                'sweep_trmm_launches', 'sweep_trmm_flop', 'copies', 'append', 'rank1', 'rff_sweep', 'rff_sweep_ops',
                'chol_fallbacks', 'sweep_sclk_mhz', 'rff_sclk_mhz', 'trtri_ahead', 'sweep_bound', 'batch', 'joint']
@@ -118,6 +124,13 @@ TOPK_MAX = 4096
 JOINT_MAX = 4096     # points of a joint posterior (gpx_predict_cov / gpx_sample_joint)
 
 _lib = None
+
+
+def acq_id(acq):
+    """The library's id of an acquisition given by name (ACQ, ACQ_SUPPORT) or by number."""
+    if not isinstance(acq, str):
+        return int(acq)
+    return ACQ[acq] if acq in ACQ else ACQ_SUPPORT[acq]
 
 
 def chol_tasks(nblocks, chunks=0):
@@ -593,6 +606,17 @@ class Engine(object):
         self._check(self._lib.gpx_predict_cov(self._h, _ptr(Xc), M, _ptr(mu), _ptr(cov)))
         return mu, cov
 
+    def kg_grad(self, A, Xc):
+        """Knowledge gradient over the support set A (m, d), m <= KG_MAX_SUPPORT, and its gradient at the rows of Xc (at most JOINT_MAX):
+        (f (M,), g (M, d)) (gpx_kg_grad); f agrees with sweep('kg', A, Xc) to rounding."""
+        A = _f64(A).reshape(-1, self.d)
+        Xc = _f64(Xc).reshape(-1, self.d)
+        M = len(Xc)
+        f = np.empty(M)
+        g = np.empty((M, self.d))
+        self._check(self._lib.gpx_kg_grad(self._h, _ptr(A), len(A), _ptr(Xc), M, _ptr(f), _ptr(g)))
+        return f, g
+
     def sample_joint(self, Xc, z, noisy=False, jitter=0.0):
         """Joint draws at the rows of Xc from the standard normals z (S, M): out[s] = mu + R^T z[s] with R^T R = cov + (noisy ? sn2 : 0) I
         + jitter I, factored on the device (gpx_sample_joint); LinAlgError when that matrix is not positive definite."""
@@ -608,7 +632,7 @@ class Engine(object):
         Xc = _f64(Xc)
         Xc = Xc.reshape(-1, self.d) if self.d else np.atleast_2d(Xc)
         M = len(Xc)
-        aid = ACQ[acq] if isinstance(acq, str) else int(acq)
+        aid = acq_id(acq)
         params, nparams = _acq_params(param)
         tv = np.empty(k)
         ti = np.empty(k, dtype=np.int64)
@@ -623,7 +647,7 @@ class Engine(object):
     def sweep_update(self, acq, param, k=0, want_all=True, want_moments=False):
         """Re-score the cached candidate set (option sweep_cache, kept current by append): O(M)."""
         M = self.sweep_cache_size()
-        aid = ACQ[acq] if isinstance(acq, str) else int(acq)
+        aid = acq_id(acq)
         params, nparams = _acq_params(param)
         tv = np.empty(k)
         ti = np.empty(k, dtype=np.int64)
@@ -640,7 +664,7 @@ class Engine(object):
     def sweep_batch(self, kind, param, nb, want_s2_all=False):
         """nb greedy picks on the live sweep cache (gpx_sweep_batch), each conditioned on the earlier ones at their posterior
         mean.  Returns dict(sel_val, sel_idx, sel_s2[, s2_all]); model, cache and a pending announcement are untouched."""
-        aid = ACQ[kind] if isinstance(kind, str) else int(kind)
+        aid = acq_id(kind)
         params, nparams = _acq_params(param)
         n = max(int(nb), 0)
         out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty(n))
@@ -651,7 +675,7 @@ class Engine(object):
         return out
 
     def sweep_dev(self, acq, param, dXc_ptr, M, k, d_acq=None, d_mu=None, d_s2=None):
-        aid = ACQ[acq] if isinstance(acq, str) else int(acq)
+        aid = acq_id(acq)
         params, nparams = _acq_params(param)
         tv = np.empty(k)
         ti = np.empty(k, dtype=np.int64)
@@ -667,7 +691,7 @@ class Engine(object):
         on the device.  `Xc`: host array (M, d) or a DeviceGrid.  Returns dict(top_val, top_idx, acq, mu, s2)."""
         lead = engines[0]
         handles = (_P * len(engines))(*[e._h for e in engines])
-        aid = ACQ[acq] if isinstance(acq, str) else int(acq)
+        aid = acq_id(acq)
         params, nparams = _acq_params(param)
         tv = np.empty(k)
         ti = np.empty(k, dtype=np.int64)
@@ -694,7 +718,7 @@ class Engine(object):
         are left as they were."""
         lead = engines[0]
         handles = (_P * len(engines))(*[e._h for e in engines])
-        aid = ACQ[kind] if isinstance(kind, str) else int(kind)
+        aid = acq_id(kind)
         params, nparams = _acq_params(param)
         n = max(int(nb), 0)
         out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty((len(engines), n)))

@@ -19,6 +19,7 @@ Three paths, chosen by what the policy's index carries:
   * neither (Thompson, or any sampled policy): nb independent policy calls, each one's best grid point; duplicates are allowed.
 `policy='mes'` is refused: its index carries `.acq = ('mes', ystar)` but no `.batch`, and `_score` below raises the ValueError for any kind
 but EI, PI and UCB -- scoring the believer rounds with max-value entropy search is not built (the sampled maxima would have to follow them).
+`policy='kg'` is refused the same way: `.acq = ('kg', support)`, no `.batch` (the support set's means would have to follow the rounds).
 Picks are grid candidates, ranked value descending, then index ascending, NaN last -- the device top-k's order.
 """
 import numpy as np

@@ -14,6 +14,7 @@
 #include "gpx_internal.h"
 #include "gpx_diag.h"
 #include "mes_math.h"
+#include "kg_math.h"
 
 using namespace gpx;
 
@@ -241,7 +242,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // 660: the gate's decision of a selection-only sweep is carried to the next one (prune_hint.h; any gpx_set_option drops it),
 // gpx_prune_report's scalar 19 and gpx_ensemble_prune_report's scalar 10 + n say whether the sweep skipped its gate on it.
 // 670: GPX_ACQ_MES = 16 (max-value entropy search: gpx_sweep*, gpx_sweep_update*, gpx_ensemble_sweep*; params = the sampled maxima).
-extern "C" int gpx_version(void) { return 670; }
+// 680: GPX_ACQ_KG = 32 (knowledge gradient over a support set: gpx_sweep*; params = the support coordinates) and gpx_kg_grad.
+extern "C" int gpx_version(void) { return 680; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -350,7 +352,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -1018,7 +1020,15 @@ struct AcqRule { int id, min_params; bool vec; };
 static const AcqRule ACQ_RULES[] = {
     {GPX_ACQ_EI, 1, false}, {GPX_ACQ_PI, 1, false}, {GPX_ACQ_UCB, 1, false}, {GPX_ACQ_MEAN, 0, false}, {GPX_ACQ_MES, 1, true},
 };
-static int check_acq(gpx_handle* h, const char* what, int acq_id, const double* params, int nparams, int n_members = 0) {
+// GPX_ACQ_KG (params = the support set, (m, d) raw coordinates): only where the entry says it takes it (kg_ok: the cold sweep)
+static int check_acq(gpx_handle* h, const char* what, int acq_id, const double* params, int nparams, int n_members = 0, bool kg_ok = false) {
+    if (acq_id == GPX_ACQ_KG) {
+        if (!kg_ok) return fail(h, GPX_EARG, (std::string(what) + ": KG is not supported").c_str());
+        bool ok = params && h->d > 0 && nparams >= h->d && nparams % h->d == 0 && nparams / h->d <= KG_MAX_M;
+        for (int i = 0; ok && i < nparams; ++i) ok = std::isfinite(params[i]);
+        if (!ok) return fail(h, GPX_EARG, (std::string(what) + ": KG takes m * d finite support coordinates, m in [1, 127]").c_str());
+        return GPX_OK;
+    }
     const AcqRule* rule = nullptr;
     for (const AcqRule& r : ACQ_RULES)
         if (r.id == acq_id) rule = &r;
@@ -1039,6 +1049,7 @@ static int check_acq(gpx_handle* h, const char* what, int acq_id, const double* 
 // the batch entries: the believer rounds are scored by acq_value (kernels_batch.hip), which MES is not part of
 static int check_acq_batch(gpx_handle* h, const char* what, int acq_id) {
     if (acq_id == GPX_ACQ_MES) return fail(h, GPX_EARG, (std::string(what) + ": MES is not supported").c_str());
+    if (acq_id == GPX_ACQ_KG) return fail(h, GPX_EARG, (std::string(what) + ": KG is not supported").c_str());
     return GPX_OK;
 }
 // the maxima of one sweep as k_acq_mes takes them (checked by check_acq)
@@ -1047,6 +1058,55 @@ static MesArg mes_arg(const double* params, int nparams) {
     a.S = nparams;
     for (int i = 0; i < MES_MAX_S; ++i) a.y[i] = i < nparams ? params[i] : 0.0;
     return a;
+}
+
+// The prepared support set of the knowledge gradient (kernels_kg.hip), h->dkg:
+// [A raw 128 d][As scaled 128 d][a_j 128][B Np 128][V_A Np 128][Pp nP 128]; the cross-Gram of the set passes through dKs.
+struct KgBuf { double *A, *As, *al, *B, *V, *Pp; int m; };
+static KgBuf kg_layout(const gpx_handle* h, int m) {
+    KgBuf b;
+    b.A = h->dkg;
+    b.As = b.A + NB * h->d;
+    b.al = b.As + NB * h->d;
+    b.B = b.al + NB;
+    b.V = b.B + h->Np * NB;
+    b.Pp = b.V + h->Np * NB;
+    b.m = m;
+    return b;
+}
+// O(N^2 m), once per support set and model: skipped while the handle holds the bits of this set for this fit (gpx_kg_grad is called
+// many times by one refinement).  Enqueued on the handle's stream; the caller has ensured the inverse.
+static int kg_prepare(gpx_handle* h, const double* A, int m, KgBuf& b) {
+    const int64_t Np = h->Np, d = h->d;
+    const int nP = (int)(Np / NB);
+    const int64_t need = 2 * NB * d + NB + 2 * Np * NB + (int64_t)nP * NB;
+    if (need > h->cap_kg || !h->dkg) h->kg_A.clear();
+    int rc;
+    if ((rc = ensure(h, h->dkg, h->cap_kg, need))) return rc;
+    if ((rc = ensure(h, h->dKs, h->cap_ks, Np * NB))) return rc;
+    b = kg_layout(h, m);
+    const size_t na = (size_t)m * d;
+    if (h->kg_gen == h->gen && h->kg_Np == Np && h->kg_A.size() == na && memcmp(h->kg_A.data(), A, na * 8) == 0) return GPX_OK;
+    h->kg_A.clear();
+    hipStream_t s = h->stream;
+    {
+        Span sp(h, T_COPY);
+        HIPCHK(h, hipMemcpyAsync(b.A, A, na * 8, hipMemcpyHostToDevice, s));
+    }
+    {
+        Span sp(h, T_ACQ);
+        launch_scale_x(s, b.A, m, NB, (int)d, h->dinvell, b.As);
+        launch_cross_gram(s, h->dXs, Np, h->N, (int)d, b.A, 0, m, NB, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
+        launch_cov_trmm(s, h->dU, Np, h->dKs, NB, b.V);
+        launch_cov_mu(s, b.V, Np, NB, h->da, h->bias, b.Pp, b.al);
+        launch_kg_solve(s, h->dU, Np, h->N, m, b.V, b.B);
+        HIPCHK(h, hipGetLastError());
+    }
+    // (A is pageable host memory: the copy above has read it before it returned)
+    h->kg_A.assign(A, A + na);
+    h->kg_gen = h->gen;
+    h->kg_Np = Np;
+    return GPX_OK;
 }
 
 static int check_topk(gpx_handle* h, const char* what, int64_t k, const double* top_val, const int64_t* top_idx) {
@@ -1343,7 +1403,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     if (!h->fitted) return fail(h, GPX_ESTATE, "sweep: model is not fitted");
     if (!dXc || M < 1) return fail(h, GPX_EARG, "sweep: need M >= 1 candidates");
     int rc;
-    if ((rc = check_acq(h, "sweep", acq_id, params, nparams)) || (rc = check_topk(h, "sweep", k, top_val, top_idx))) return rc;
+    if ((rc = check_acq(h, "sweep", acq_id, params, nparams, 0, true)) || (rc = check_topk(h, "sweep", k, top_val, top_idx))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = ensure_inverse(h))) return rc;
     hipStream_t s = h->stream;
@@ -1361,6 +1421,13 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     const bool mes = acq_id == GPX_ACQ_MES;          // its parameters are a vector: k_acq_mes, never pruned
     const MesArg ys = mes_arg(params, mes ? nparams : 0);
     const double p0 = (acq_id == GPX_ACQ_MEAN) ? 0.0 : params[0];
+    // the knowledge gradient: its parameters are the support set, prepared once per sweep; k_kg_cross + k_acq_kg per chunk, never pruned
+    const bool kg = acq_id == GPX_ACQ_KG;
+    KgBuf kb = {};
+    if (kg) {
+        if ((rc = kg_prepare(h, params, nparams / (int)h->d, kb))) return rc;
+        if ((rc = ensure(h, h->dkgw, h->cap_kgw, (int64_t)NB * chunk))) return rc;
+    }
     double* cq = nullptr;
     double* cp = nullptr;
     if (h->cache_on) {
@@ -1403,7 +1470,11 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             h->tacc[T_FLOP] += (double)h->N * (double)h->N * (double)valid;
             {
                 Span sp(h, T_ACQ);
-                if (mes) launch_acq_mes(s, h->dQp, h->dPp, chunk, nP, m0, valid, h->rho, h->bias, ys, out, mu, s2, cq, cp);
+                if (kg) {
+                    launch_kg_cross(s, kb.B, Np, h->dKs, Np, cols, h->dkgw, chunk);
+                    launch_acq_kg(s, h->dQp, h->dPp, chunk, nP, m0, valid, h->rho, h->bias, h->sn2, h->kernel_id, (int)h->d, X, h->dinvell,
+                                  kb.As, kb.m, kb.al, h->dkgw, chunk, out, mu, s2, cq, cp);
+                } else if (mes) launch_acq_mes(s, h->dQp, h->dPp, chunk, nP, m0, valid, h->rho, h->bias, ys, out, mu, s2, cq, cp);
                 else launch_acq(s, h->dQp, h->dPp, chunk, nP, m0, valid, h->rho, h->bias, acq_id, p0, out, mu, s2, cq, cp);
             }
         }
@@ -1757,6 +1828,64 @@ extern "C" int gpx_sample_joint(gpx_handle* h, const double* Xc, int64_t M, cons
         if (S < 1) return fail(h, GPX_EARG, "sample_joint: S must be >= 1");
         if (!(jitter >= 0.0) || !std::isfinite(jitter)) return fail(h, GPX_EARG, "sample_joint: jitter must be finite and >= 0");
         return joint_core(h, "sample_joint", Xc, M, z, S, noisy, jitter, nullptr, nullptr, out);
+    });
+}
+
+// ---- knowledge gradient at a few points: value and gradient (kernels_kg.hip) ---------------------------------------------
+// The L-BFGS refinement's `f(x, grad=True)` for policies.KG.  Per panel of 128 points: Ks_z by the cross-Gram kernel (through dKs),
+// V_z = T Ks_z, W_z = U V_z, the sums over the observed rows, then lines, value and gradient.  One stream, one synchronisation; reads
+// the fit only (the prepared support set is kept in h->dkg for the next call).  Work space (h->dkgw):
+// [Z Mp d][V_z Np 128][W_z Np 128][S 128 (d + 1) 132][L 4 129 128][f Mp][g Mp d]
+extern "C" int gpx_kg_grad(gpx_handle* h, const double* A, int64_t m, const double* Xc, int64_t M, double* f, double* g) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        if (!h->fitted) return fail(h, GPX_ESTATE, "kg_grad: model is not fitted");
+        if (!A || !Xc || !f || !g) return fail(h, GPX_EARG, "kg_grad: NULL A / Xc / f / g");
+        const int64_t d = h->d;
+        bool ok = m >= 1 && m <= KG_MAX_M;
+        for (int64_t i = 0; ok && i < m * d; ++i) ok = std::isfinite(A[i]);
+        if (!ok) return fail(h, GPX_EARG, "kg_grad: KG takes m * d finite support coordinates, m in [1, 127]");
+        if (M < 1 || M > JOINT_MAX_M) return fail(h, GPX_EARG, "kg_grad: M must be in [1, 4096]");
+        HIPCHK(h, hipSetDevice(h->device));
+        int rc;
+        if ((rc = ensure_inverse(h))) return rc;
+        KgBuf kb;
+        if ((rc = kg_prepare(h, A, (int)m, kb))) return rc;
+        hipStream_t s = h->stream;
+        const int64_t Np = h->Np, Mp = (M + TBH - 1) / TBH * TBH;
+        const int64_t nS = (int64_t)NB * (d + 1) * 132, nL = 4 * (int64_t)(KG_MAX_LINES + 1) * NB;
+        if ((rc = ensure(h, h->dkgw, h->cap_kgw, Mp * d + 2 * Np * NB + nS + nL + Mp + Mp * d))) return rc;
+        double* dZ = h->dkgw;
+        double* dVz = dZ + Mp * d;
+        double* dWz = dVz + Np * NB;
+        double* dS = dWz + Np * NB;
+        double* dL = dS + nS;
+        double* df = dL + nL;
+        double* dg = df + Mp;
+        {
+            Span sp(h, T_COPY);
+            HIPCHK(h, hipMemcpyAsync(dZ, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, s));
+        }
+        {
+            Span sp(h, T_ACQ);
+            for (int64_t p0 = 0; p0 < M; p0 += NB) {
+                const int np = (int)std::min<int64_t>(NB, M - p0);
+                launch_cross_gram(s, h->dXs, Np, h->N, (int)d, dZ, p0, M, NB, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
+                launch_cov_trmm(s, h->dU, Np, h->dKs, NB, dVz);
+                launch_kg_solve(s, h->dU, Np, h->N, np, dVz, dWz);
+                launch_kg_point_sums(s, h->dXs, h->N, (int)d, dZ + p0 * d, np, h->dinvell, h->kernel_id, h->rho, kb.B, h->dalpha, dWz, dVz, dS);
+                launch_kg_point_final(s, dS, np, (int)d, dZ + p0 * d, h->dinvell, kb.As, kb.m, kb.al, h->kernel_id, h->rho, h->bias, h->sn2,
+                                      dL, df + p0, dg + p0 * d);
+            }
+            HIPCHK(h, hipGetLastError());
+        }
+        {
+            Span sp(h, T_COPY);
+            HIPCHK(h, hipMemcpyAsync(f, df, (size_t)M * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipMemcpyAsync(g, dg, (size_t)M * d * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(h, hipStreamSynchronize(s));
+        return GPX_OK;
     });
 }
 

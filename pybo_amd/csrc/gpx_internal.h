@@ -234,6 +234,17 @@ struct gpx_handle {
     double* djoint = nullptr;
     int64_t cap_joint = 0;
 
+    // knowledge gradient (GPX_ACQ_KG, gpx_kg_grad; kernels_kg.hip): the prepared support set -- [A raw 128 d][As scaled 128 d][a_j 128]
+    // [B Np 128][V_A Np 128][Pp nP 128], laid out in api.hip (kg_prepare) -- kept while the model (gen) and the set (kg_A) stay what
+    // they were, and work space of a sweep (C: 128 x chunk) or of gpx_kg_grad's point panels
+    double* dkg = nullptr;
+    int64_t cap_kg = 0;
+    double* dkgw = nullptr;
+    int64_t cap_kgw = 0;
+    std::vector<double> kg_A;    // the support set dkg was prepared for (empty: none)
+    uint64_t kg_gen = 0;
+    int64_t kg_Np = 0;
+
     double* dbatch = nullptr;    // gpx_loglik_batch: Gram / factor / scaled inputs / a of the batch (one allocation)
     int64_t cap_batch = 0;
     double* dhyper = nullptr;    // gpx_loglik_grad: the tiles' partial sums [tiles][d + 2], then [L, d + 3 components] (on first use)
@@ -289,6 +300,19 @@ struct MesArg;
 void launch_acq_mes(hipStream_t s, const double* Qp, const double* Pp, int64_t ldp, int nrb, int64_t m0,
                     int64_t cols_valid, double rho, double bias, const MesArg& ys, double* acq_out,
                     double* mu_out, double* s2_out, double* qsum, double* psum);
+// launchers (kernels_kg.hip): W = U V for one k-major panel V [Np][128] (rows >= N, columns >= m: zeros); C[j][c] = sum_n B[n][j] Ks[c's panel][n][c]
+// for the chunk's cols columns; k_acq's moments + the knowledge gradient of candidate m0 + n over the lines of the prepared support
+void launch_kg_solve(hipStream_t s, const double* U, int64_t Np, int64_t N, int m, const double* V, double* W);
+void launch_kg_cross(hipStream_t s, const double* B, int64_t Np, const double* Ks, int64_t ldk, int64_t cols, double* C, int64_t ldc);
+void launch_acq_kg(hipStream_t s, const double* Qp, const double* Pp, int64_t ldp, int nrb, int64_t m0, int64_t cols_valid,
+                   double rho, double bias, double sn2, int kid, int d, const double* X, const double* invell, const double* As, int m,
+                   const double* al, const double* C, int64_t ldc, double* acq_out, double* mu_out, double* s2_out, double* qsum,
+                   double* psum);
+// gpx_kg_grad: the sums of np <= 128 points (S: np (d + 1) 132) and value + gradient from them (L: 4 x 129 x 128 scratch)
+void launch_kg_point_sums(hipStream_t s, const double* Xs, int64_t N, int d, const double* Z, int np, const double* invell, int kid,
+                          double rho, const double* B, const double* alpha, const double* Wz, const double* Vz, double* S);
+void launch_kg_point_final(hipStream_t s, const double* S, int np, int d, const double* Z, const double* invell, const double* As,
+                           int m, const double* al, int kid, double rho, double bias, double sn2, double* L, double* f, double* g);
 // correction of the cached sums after q <= 8 appended observations in one pass (see kernels_sweep.hip)
 void launch_pend_store(hipStream_t s, const double* w, int64_t Nj, int64_t ldw, const double* scal, double* row,
                        double* pscal_j);

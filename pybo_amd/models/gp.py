@@ -502,11 +502,29 @@ class GP(object):
         from ..mes import mes_value_grad
         return mes_value_grad(*self._engine().predict(X, grad=True), ystar)
 
+    def get_knowledge(self, support, X, grad=False):
+        """Knowledge gradient at the rows of X over the support set `support` (m, d), 1 <= m <= 127 (pybo_amd/kg.py): the expected
+        rise of the maximum posterior mean over {x} + support after one noisy observation at x.  Without `grad` a device sweep
+        ('kg': k_kg_cross + k_acq_kg); with it value and gradient from gpx_kg_grad (at most 4096 rows)."""
+        support = np.array(support, dtype=float).reshape(-1, len(self.ell))
+        if not grad:
+            return self._acq('kg', support, X, False)
+        X = np.array(X, ndmin=2, dtype=float)
+        if self.ndata == 0:
+            raise RuntimeError('the model has no data yet')
+        if X.shape[0] == 0:
+            return np.zeros(0), np.zeros((0, X.shape[1]))
+        return self._engine().kg_grad(support, X)
+
     def acq_topk(self, kind, param, xgrid, k):
         """Whole-grid acquisition + top-k on the device: (values (k,), grid indices (k,)).  `xgrid` is a
         host array (uploaded) or a `DeviceGrid` (already in HBM)."""
         if isinstance(xgrid, DeviceGrid) and int(xgrid.device) != int(self._engine().device):
             xgrid = np.asarray(xgrid)                # resident on ANOTHER GPU: through the host, never its pointer
+        if isinstance(xgrid, DeviceGrid) and kind == 'kg':
+            # the knowledge gradient is not a function of a candidate's own moments: always the cold sweep, which leaves a live
+            # cache (another policy's) as it is -- "sweep_cache" stays 0
+            return self._engine().sweep_dev(kind, param, xgrid.ptr, len(xgrid), int(k))
         if isinstance(xgrid, DeviceGrid):
             # Warm BO step: a grid resident in HBM that this device state has swept before is only RE-SCORED --
             # the per-candidate sums were kept current by every add_data since (gpx_append's rank-1 correction),

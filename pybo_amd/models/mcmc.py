@@ -390,6 +390,20 @@ class MCMC(object):
             return np.mean(outs, axis=0)
         return np.mean([o[0] for o in outs], axis=0), np.mean([o[1] for o in outs], axis=0)
 
+    def get_knowledge(self, support, X, grad=False):
+        """Knowledge gradient over the members: every member scores with the shared support set (its own `get_knowledge`: a member
+        sweep, the values copied back), the value is the members' sum in member order divided once.  The device ensemble path is
+        not built (gpx_ensemble_sweep refuses 'kg'), so an index on an ensemble carries no `.topk`."""
+        members = self._need()
+        missing = [type(m).__name__ for m in members if not hasattr(m, 'get_knowledge')]
+        if missing:
+            raise TypeError('get_knowledge: member model %s has no get_knowledge' % missing[0])
+        from ..kg import member_mean
+        outs = [m.get_knowledge(support, X, grad) for m in members]
+        if not grad:
+            return member_mean(outs)
+        return member_mean([o[0] for o in outs]), member_mean([o[1] for o in outs])
+
     def sample_f(self, n, rng=None):
         rng = rstate(rng)
         members = self._need()

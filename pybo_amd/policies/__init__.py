@@ -1,4 +1,4 @@
-"""Acquisition policies; the exported names match pybo.policies (`EI`, `PI`, `UCB`, `Thompson`), plus `MES`."""
-from .simple import EI, PI, UCB, Thompson, MES
+"""Acquisition policies; the exported names match pybo.policies (`EI`, `PI`, `UCB`, `Thompson`), plus `MES` and `KG`."""
+from .simple import EI, PI, UCB, Thompson, MES, KG
 
-__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES']
+__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES', 'KG']

@@ -15,11 +15,11 @@ New: when the model is the device-backed `pybo_amd.models.GP`, the returned inde
 `pybo_amd.solvers.solve_lbfgs` uses instead of `argsort(f(xgrid))` (pybo/solvers/lbfgs.py:50-51).
 Any other model (e.g. a test stub) gets plain closures, exactly as in the reference.  Every EI / PI / UCB index also
 carries `index.acq = (kind, param)` and, for models with `acq_batch`, `index.batch(xgrid, nb)` (pybo_amd/batch.py).
-`MES` (max-value entropy search) is this build's own: the reference has no information-theoretic policy.
+`MES` (max-value entropy search) and `KG` (knowledge gradient over a support set) are this build's own: the reference has neither.
 """
 import numpy as np
 
-__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES']
+__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES', 'KG']
 
 
 def _attach_topk(index, model, kind, param):
@@ -122,6 +122,48 @@ def MES(model, bounds, X, nmax=16, ngrid=10000, xi=0.0, rng=None):
     fast = getattr(model, 'acq_topk', None)
     if fast is not None:
         index.topk = lambda xgrid, k: fast('mes', ystar, xgrid, k)
+        owner = getattr(model, 'topk_engine', None)
+        if owner is not None:
+            index.topk_engine = owner
+    return index
+
+
+def KG(model, bounds, X, nsupport=64, ngrid=10000, support=None, rng=None):
+    """Knowledge gradient (Frazier, Powell & Dayanik 2009) over a finite support set A: the expected rise of the maximum posterior
+    mean over {x} + A after one noisy observation at x (pybo_amd/kg.py) -- the one policy here that uses the correlation between a
+    candidate and the rest of the domain.  Default A: the `nsupport` <= 127 points of `init_uniform(bounds, ngrid, rng)` stacked on X
+    with the highest posterior mean (value descending, then index ascending; one `predict_mean`; an ensemble ranks by its
+    member-averaged mean).  The model needs `get_knowledge(support, X, grad)` (an ensemble: every member).  The index carries
+    `.acq = ('kg', support)` and, for single device GPs, `.topk`; never `.batch` (pybo_amd/batch.py)."""
+    from ..inits import init_uniform
+    from ..kg import KG_MAX_SUPPORT
+    from ..utils import rstate
+    if support is None and not 1 <= int(nsupport) <= KG_MAX_SUPPORT:
+        raise ValueError('KG: nsupport must be in [1, %d], not %r' % (KG_MAX_SUPPORT, nsupport))
+    rng = rstate(rng)
+    model = model.copy()
+    members = getattr(model, 'members', None)
+    lacking = [m for m in ([model] if members is None else [model] + list(members)) if getattr(m, 'get_knowledge', None) is None]
+    if lacking:
+        raise TypeError('KG needs a model with get_knowledge(support, X, grad); %s has none' % type(lacking[0]).__name__)
+    X = np.array(X, ndmin=2, dtype=float)
+    if support is None:
+        pool = np.vstack([init_uniform(bounds, ngrid, rng), X])
+        mean_only = getattr(model, 'predict_mean', None)
+        mu = np.asarray(mean_only(pool) if mean_only is not None else model.predict(pool)[0], dtype=float)
+        v = np.where(np.isnan(mu), -np.inf, mu)
+        support = pool[np.lexsort((np.arange(len(v)), -v))[:int(nsupport)]]
+    support = np.array(support, dtype=float).reshape(-1, X.shape[1])
+    if not 1 <= len(support) <= KG_MAX_SUPPORT:
+        raise ValueError('KG: the support set must have 1 to %d points, not %d' % (KG_MAX_SUPPORT, len(support)))
+
+    def index(X, grad=False):
+        return model.get_knowledge(support, X, grad)
+
+    index.acq = ('kg', support)
+    fast = getattr(model, 'acq_topk', None) if members is None else None
+    if fast is not None:
+        index.topk = lambda xgrid, k: fast('kg', support, xgrid, k)
         owner = getattr(model, 'topk_engine', None)
         if owner is not None:
             index.topk_engine = owner
