@@ -822,12 +822,16 @@ class Engine(object):
         and seed_idx, the bounds and the seed list before the scatter.  nR (block rows of the second bound's prefix, 0: it did not
         run) and nsurv2 (survivors of its cut); with `vectors`, nR > 0 and prune_keep = 1 also ub2, qR (aligned with idx) and idx2 (the
         second-level list).  E: the fp32 kernel's relative margin (NaN where it was not considered).  gate_hint: this sweep skipped its gate
-        on the decision carried from the last one (csrc/prune_hint.h; then done = 0 and gate_s2 is NaN)."""
-        scal = np.full(20, np.nan)
+        on the decision carried from the last one (csrc/prune_hint.h; then done = 0 and gate_s2 is NaN).  bound_fact: the fp32 kernel walked
+        its factorised form (csrc/bound_f32.h; None where that kernel did not run) and bound_tpos, the first 16-row tile of its reordered
+        weights without a positive one (None likewise)."""
+        scal = np.full(22, np.nan)
         self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), None, None, 0, None, None, 0))
         names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'S', 'delta', 'tau', 'gate_s2', 'thr_key', 'kept',
-                 'bound_kernel', 'guard', 'nR', 'nsurv2', 'E', 'gate_hint')
+                 'bound_kernel', 'guard', 'nR', 'nsurv2', 'E', 'gate_hint', 'bound_fact', 'bound_tpos')
         r = dict(zip(names, scal.tolist()))
+        r['bound_fact'] = None if np.isnan(r['bound_fact']) else r['bound_fact'] == 1.0
+        r['bound_tpos'] = None if np.isnan(r['bound_tpos']) else int(r['bound_tpos'])
         r['gate_hint'] = r['gate_hint'] == 1.0
         r['bound_kernel'] = None if np.isnan(r['bound_kernel']) else ('generic', 'mfma', 'mfma32')[int(r['bound_kernel'])]
         for n in ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'kept', 'nR', 'nsurv2'):
@@ -854,10 +858,11 @@ class Engine(object):
     def ensemble_prune_report(engines, vectors=True):
         """Diagnostic (gpx_ensemble_prune_report in csrc/gpx_diag.h): what the last ensemble sweep led by engines[0] decided about pruning.
         dict(path, M, k, G, Gg, done, cap, nsurv, tau, gate, delta (n,), gate_hint: the gate was skipped on the carried decision); with `vectors`, where the bound pass ran, also ub (M,), the ensemble
-        bound as the survivor pass read it, and idx, the survivors in compaction order (empty where it fell back)."""
+        bound as the survivor pass read it, and idx, the survivors in compaction order (empty where it fell back).  bound_fact (n,): 1.0 where a
+        member's dots came from the fp32 kernel's factorised walk, 0.0 from another kernel or form, NaN where the host chose the generic kernel."""
         lead = engines[0]
         handles = (_P * len(engines))(*[e._h for e in engines])
-        scal = np.full(11 + len(engines), np.nan)
+        scal = np.full(11 + 2 * len(engines), np.nan)
         lead._check(lead._lib.gpx_ensemble_prune_report(handles, len(engines), _ptr(scal), len(scal), None, None, 0))
         names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'tau', 'gate')
         r = dict(zip(names, scal[:10].tolist()))
@@ -866,6 +871,7 @@ class Engine(object):
         r['path'] = Engine.PRUNE_PATHS[r['path']]
         r['delta'] = scal[10:10 + len(engines)].copy()
         r['gate_hint'] = scal[10 + len(engines)] == 1.0
+        r['bound_fact'] = scal[11 + len(engines):11 + 2 * len(engines)].copy()
         if vectors and r['path'] in ('pruned', 'fell back'):
             nidx = r['nsurv'] if r['path'] == 'pruned' else 0
             r['ub'] = np.empty(r['M'])

@@ -154,6 +154,7 @@ static const Option kOptions[] = {
     {"prune", SHIP, -1, 1, "prune must be -1 (by size and gate), 0 (never) or 1 (wherever legal)", store<&gpx_handle::prune>},
     {"prune_keep", DIAG, 0, 1, "prune_keep must be 0 or 1", store<&gpx_handle::prune_keep>},
     {"prune_bound", DIAG, -1, 2, "prune_bound must be -1 (by guard), 0 (generic kernel), 1 (matrix-pipe kernel) or 2 (fp32 matrix-pipe kernel)", store<&gpx_handle::prune_bound>},
+    {"bound_fact", DIAG, 0, 1, "bound_fact must be 0 (the fp32 bound kernel never takes its factorised form) or 1 (by its guard)", store<&gpx_handle::bound_fact>},
     {"prune_rows", DIAG, -1, 1000000, "prune_rows must be -1 (by size), 0 (no second bound) or a number of block rows", store<&gpx_handle::prune_rows>},
     {"short_map", DIAG, -1, 1, "short_map must be -1 (by size), 0 (never) or 1 (wherever tile map 3 is in use)", store<&gpx_handle::short_map>},
     {"chol_w", SHIP, 0, 8, "chol_w must be 0 (by size) or in [2, 8]", store<&gpx_handle::chol_w>, [](int64_t v) { return v != 1; }},
@@ -427,7 +428,7 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
             return fail(h, GPX_ESTATE, "prune_report: the last sweep ran without the option prune_keep");
         HIPCHK(h, hipSetDevice(h->device));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        double sc[16];
+        double sc[BM_SC_WORDS];
         int st[4] = {0, 0, 0, 0};
         for (double& v : sc) v = NAN;
         if (bound) {
@@ -436,14 +437,18 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
         }
         // the device chose the bound pass's kernel: sc[8] = guard value, sc[9] = a matrix-pipe kernel ran, sc[12] = the fp32 one, sc[10] = its E
         const bool guarded_bound = bound && r.bound_kernel < 0;
-        double out[20];
+        double out[22];
         report_head(r, out);
         // (slot 11: the gate's mean s2 as it is, not divided by rho)
         const double tail[12] = {sc[0], sc[1], sc[5], r.gate, bound ? (double)st[2] : NAN, r.kept ? 1.0 : 0.0,
                                  bound ? (guarded_bound ? sc[9] + sc[12] : 0.0) : NAN, guarded_bound ? sc[8] : NAN,
                                  (double)r.nR, (double)r.nsurv2, guarded_bound ? sc[10] : NAN, r.hinted ? 1.0 : 0.0};
         std::copy(tail, tail + 12, out + 8);
-        for (int i = 0; i < nscal && i < 20; ++i) scal[i] = out[i];
+        // the fp32 kernel's form (1.0 factorised) and the tile at which its weights change sign; NaN where it did not run
+        const bool f32 = guarded_bound && sc[BM_SC_USE32] == 1.0;
+        out[20] = f32 ? sc[BM_SC_FACT32] : NAN;
+        out[21] = f32 ? sc[BM_SC_TPOS32] : NAN;
+        for (int i = 0; i < nscal && i < 22; ++i) scal[i] = out[i];
         int rc;
         if ((rc = report_vectors(h, r, ub, idx, cap_idx))) return rc;
         if (ub_kept) HIPCHK(h, hipMemcpy(ub_kept, h->dkeep, (size_t)r.M * 8, hipMemcpyDeviceToHost));
@@ -1175,7 +1180,7 @@ static PruneGeom prune_geom(int nP, int64_t k, int64_t M) {
 }
 
 // The pruning workspace, h->dprune:
-// [ub M][vals cap][Xg cap d][idx cap][blk nsel + 1][alpha2 Np][sabs Np][gate s2 Gg][sc 16][extra][hist 2 x 4096 + st 8 (int)]
+// [ub M][vals cap][Xg cap d][idx cap][blk nsel + 1][alpha2 Np][sabs Np][gate s2 Gg][sc BM_SC_WORDS][extra][hist 2 x 4096 + st 8 (int)]
 // [pad to 32 bytes][the matrix-pipe bound kernel's operands]
 // rows (the single model's sweep): [dots M][ub2 cap][qR cap][idx2 cap][Xg2 cap d][blk2 sel_blocks(cap) + 1] -- the second bound's
 struct PruneWs {
@@ -1191,7 +1196,7 @@ struct PruneWs {
 static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t extra, PruneWs& w, bool rows = false) {
     const int64_t Np = h->Np;
     w.nsel = sel_blocks(M);
-    const int64_t words0 = M + cap + cap * h->d + cap + (w.nsel + 1) + 2 * Np + Gg + 16 + extra + (2 * 4096 + 8) / 2;
+    const int64_t words0 = M + cap + cap * h->d + cap + (w.nsel + 1) + 2 * Np + Gg + BM_SC_WORDS + extra + (2 * 4096 + 8) / 2;
     const int64_t words1 = (words0 + 3) / 4 * 4 + bound_mfma_ws_words(Np);
     const int64_t words = words1 + (rows ? M + 3 * cap + cap * h->d + sel_blocks(cap) + 1 : 0);
     if (!h->dprune || words * 8 > h->cap_prune) h->ens_rec = gpx_handle::EnsPruneRecord();   // (its vectors lie in the old allocation)
@@ -1206,7 +1211,7 @@ static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t e
     w.sabs = w.alpha2 + Np;
     w.gs2 = w.sabs + Np;
     w.sc = w.gs2 + Gg;
-    w.extra = w.sc + 16;
+    w.extra = w.sc + BM_SC_WORDS;
     w.hist = reinterpret_cast<int*>(w.extra + extra);
     w.st = w.hist + 2 * 4096;
     w.bws = w.ub + (words0 + 3) / 4 * 4;
@@ -1231,8 +1236,8 @@ static void bound_dots(gpx_handle* h, const double* dXc, int64_t M, const PruneW
     hipStream_t s = h->stream;
     launch_prune_alpha(s, h->dU, h->Np, h->da, h->rho, h->bias, w.alpha2, w.sabs, w.sc);
     if (bound_mfma)
-        launch_bound_mfma(s, h->dXs, h->N, h->Np, (int)h->d, w.alpha2, h->rho, dXc, M, h->dinvell, h->prune_bound, M >= BOUND_F32_MIN_M, w.bws,
-                          w.sc, out);
+        launch_bound_mfma(s, h->dXs, h->N, h->Np, (int)h->d, w.alpha2, h->rho, dXc, M, h->dinvell, h->prune_bound, M >= BOUND_F32_MIN_M, h->bound_fact != 0,
+                          w.bws, w.sc, out);
     launch_sweep_rank1_v(s, h->dXs, h->N, (int)h->d, w.alpha2, h->Np, w.sc + 2, dXc, M, h->dinvell, h->kernel_id, h->rho,
                          nullptr, out, bound_mfma ? w.sc + 9 : nullptr);
 }
@@ -2240,7 +2245,7 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
     hipStream_t s = L->stream;
     gpx_handle::EnsPruneRecord& rec = L->ens_rec;
     rec.n = n;
-    PruneWs w;                   // the lead's: the ensemble bound vector, seeds and survivors; extra = [gate means n][delta n]
+    PruneWs w;                   // the lead's: the ensemble bound vector, seeds and survivors; extra = [gate means n][delta n][bound_fact n]
     SelectOps ops;
     ops.exact = [&](const double* X, int64_t mb, int64_t me, double* o, double* o_mu, double* o_s2) -> int {
         return members(X + mb * d, me - mb, o + mb, o_mu ? o_mu + mb : nullptr, o_s2 ? o_s2 + mb : nullptr, nullptr);
@@ -2271,8 +2276,10 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
             }
             {
                 Span sp(h, T_BOUND);
-                bound_dots(h, dXc, M, wm, h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0, t1);
-                launch_prune_ub_fold(h->stream, t1, ub, M, wm.sc, h->rho, h->bias, params[0], m == 0, delta + m);
+                const bool bound_mfma = h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0;
+                bound_dots(h, dXc, M, wm, bound_mfma, t1);
+                launch_prune_ub_fold(h->stream, t1, ub, M, wm.sc, h->rho, h->bias, params[0], m == 0, delta + m,
+                                     bound_mfma ? 1 : 0, delta + n + m);
             }
             HIPCHK(L, hipStreamSynchronize(h->stream));      // t1 and ub pass to the next member's stream
         }
@@ -2285,7 +2292,7 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
     };
     ops.after_seeds = [&]() -> int { HIPCHK(L, hipStreamSynchronize(s)); return GPX_OK; };      // the members read the seeds from their own streams
     int64_t done = 0;
-    if ((rc = select_topk_pruned(L, members_ok, !d_out && !d_mu && !d_s2, acq_id, n, nPmax, Np_min, dXc, M, k, 2 * n, false, w, L->ens_hint, rec,
+    if ((rc = select_topk_pruned(L, members_ok, !d_out && !d_mu && !d_s2, acq_id, n, nPmax, Np_min, dXc, M, k, 3 * n, false, w, L->ens_hint, rec,
                                  out, ops, &done)))
         return rc;
     if ((rc = plain_rest(ops, dXc, done, sweep_chunk(L, M), M, out, d_mu, d_s2))) return rc;
@@ -2448,15 +2455,16 @@ extern "C" int gpx_ensemble_prune_report(gpx_handle* const* members, int n_membe
         if ((ub || idx) && !bound) return fail(h, GPX_ESTATE, "ensemble_prune_report: the last ensemble sweep did not reach its bound pass");
         HIPCHK(h, hipSetDevice(h->device));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::vector<double> out((size_t)(11 + n_members), NAN);
+        std::vector<double> out((size_t)(11 + 2 * n_members), NAN);      // (behind gate_hint: the members' bound_fact)
         out[10 + n_members] = r.hinted ? 1.0 : 0.0;      // behind the deltas: head[8] is tau, and callers built against 10 + n read on as before
         report_head(r, out.data());
         out[9] = r.gate;
         if (bound) {
             HIPCHK(h, hipMemcpy(&out[8], r.sc + 5, 8, hipMemcpyDeviceToHost));
             HIPCHK(h, hipMemcpy(&out[10], r.delta, (size_t)n_members * 8, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(&out[11 + n_members], r.delta + n_members, (size_t)n_members * 8, hipMemcpyDeviceToHost));
         }
-        for (int i = 0; i < nscal && i < 11 + n_members; ++i) scal[i] = out[i];
+        for (int i = 0; i < nscal && i < 11 + 2 * n_members; ++i) scal[i] = out[i];
         return report_vectors(h, r, ub, idx, cap_idx);
     });
 }

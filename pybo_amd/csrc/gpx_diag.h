@@ -25,6 +25,8 @@
  *                     (SE-ARD, d <= 18), whatever its guard says; 2 the fp32 matrix-pipe kernel, which adds its own error margin to each
  *                     dot (csrc/bound_f32.h), wherever it exists, whatever the guards say; -1 by the guards, the fp32 kernel only from
  *                     131072 candidates on [-1]
+ *   "bound_fact"      0: the fp32 kernel of the bound pass keeps the unfactorised exponent everywhere; 1: it walks the factorised form
+ *                     (csrc/bound_f32.h: norm factors in the weights and once per candidate) wherever that form's guard allows [1]
  *   "prune_rows"      block rows of the row prefix behind a pruned sweep's second bound: 0 never (the
  *                     single bound alone); n > 0: min(n, nP, N / 128) rows wherever the first level pruned; -1 by size: nP / 4 rows where
  *                     M >= 32768, nP >= 32 and more than Gg candidates survived the first bound [-1]
@@ -62,14 +64,15 @@ int64_t gpx_chol_trace(gpx_handle *h, int64_t *out, int64_t n);
 int64_t gpx_chol_tasks2(int nblocks, int chunks, int16_t *out, int64_t cap, int64_t *counts);
 
 /* What the handle's LAST sweep decided about pruning and with what; it only copies what the sweep left behind.
- * scal[0 .. min(nscal, 20)) = { path: 0 plain (not legal or not tried), 1 the gate declined, 2 pruned, 3 the bound pass ran but more than
+ * scal[0 .. min(nscal, 22)) = { path: 0 plain (not legal or not tried), 1 the gate declined, 2 pruned, 3 the bound pass ran but more than
  * cap candidates survived and the plain loop evaluated everything;  M;  k;  G (seeds);  Gg (the gate's generation);  done (leading
  * candidates evaluated before the bound pass);  cap;  nsurv;  S;  delta;  tau (the k-th best seed value);  the gate's mean s2 (NaN: no
  * gate);  the seeds' threshold key;  1 if the kept copies exist;  the bound pass's kernel, 0 generic / 1 matrix pipe / 2 matrix pipe in fp32;  the guard's (d + 4) (R_x + R_z)^2
  * (NaN where the host chose the generic kernel: another covariance, d > 18, prune_bound = 0);  nR, the block rows of the second bound's
  * prefix (0: it did not run);  nsurv2, the survivors of its cut (the candidates evaluated exactly on path 2 where nR > 0);  E, the relative margin of the
  * fp32 kernel (csrc/bound_f32.h; NaN where that kernel was not considered);  1 if this sweep skipped its gate on the decision carried from the last one
- * (csrc/prune_hint.h; then done = 0 and the gate's mean is NaN), else 0 }.  S .. tau, the key, the guard and E are NaN for paths 0 and 1.
+ * (csrc/prune_hint.h; then done = 0 and the gate's mean is NaN), else 0;  1 if the fp32 kernel walked its factorised form, 0 if the unfactorised one;
+ * tpos, the first 16-row tile of that kernel's reordered weights without a positive one (both NaN where it did not run) }.  S .. tau, the key, the guard and E are NaN for paths 0 and 1.
  * ub (optional, M): the bound vector as the survivor pass read it (-inf where a candidate was evaluated as gate or seed);  idx
  * (optional, cap_idx): the first min(nsurv, cap, cap_idx) survivors in the order they were compacted;  ub_kept (optional, M) and
  * seed_idx (optional, cap_seed; G entries): the bound vector and the seed list before the scatter -- only after a sweep that ran with
@@ -91,9 +94,10 @@ int gpx_prune_dots(gpx_handle *h, double *dots);
 int gpx_prune_rows(gpx_handle *h, double *qR, double *ub2, int64_t *idx2, int64_t cap_idx2);
 
 /* What the LAST ensemble sweep led by members[0] decided about pruning; `members`, n as in that call.
- * scal[0 .. min(nscal, 11 + n)) = { path 0 .. 3, M, k, G, Gg, done, cap, nsurv as in gpx_prune_report;  tau (NaN for paths 0 and 1);  the
+ * scal[0 .. min(nscal, 11 + 2 n)) = { path 0 .. 3, M, k, G, Gg, done, cap, nsurv as in gpx_prune_report;  tau (NaN for paths 0 and 1);  the
  * gate's value, the mean over the members of mean(s2_m) / rho_m of its generation (NaN: no gate);  then delta_m of every member (NaN for
- * paths 0 and 1);  then, at 10 + n, 1 if this sweep skipped its gate on the lead's carried decision, else 0 }.  ub (optional, M): the ensemble bound vector -- the members' bounds summed in member order and divided by n -- as the
+ * paths 0 and 1);  then, at 10 + n, 1 if this sweep skipped its gate on the lead's carried decision, else 0;  then per member 1 where its dots came from
+ * the fp32 kernel's factorised walk, 0 from another kernel or form (NaN: the host chose the generic kernel, or paths 0 and 1) }.  ub (optional, M): the ensemble bound vector -- the members' bounds summed in member order and divided by n -- as the
  * survivor pass read it (-inf where a candidate was evaluated as gate or seed);  idx (optional, cap_idx): the first min(nsurv, cap,
  * cap_idx) survivors in the order they were compacted.  GPX_ESTATE: no ensemble sweep of n members since the record was cleared, or a vector
  * was asked for and the path is below 2.  (Every entry into gpx_ensemble_sweep[_dev] clears the lead's record, a refused call included;

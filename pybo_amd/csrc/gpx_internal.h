@@ -192,6 +192,11 @@ struct gpx_handle {
     gpx::PruneHint prune_hint, ens_hint;
     int prune_keep = 0;       // diagnostic option: keep those two device copies
     int prune_bound = -1;     // diagnostic option: the bound pass's kernel (-1 by guard, 0 k_sweep_rankq<1>, 1 k_bound_mfma / 2 k_bound_mfma32 wherever SE-ARD, d <= 18)
+#ifdef GPX_BOUND32_NOFACT
+    int bound_fact = 0;       // (A/B build: sign tiles alone)
+#else
+    int bound_fact = 1;       // diagnostic option: 0 the fp32 bound kernel keeps the unfactorised exponent, 1 the factorised form where its guard allows (bound_f32.h)
+#endif
     int prune_rows = -1;      // diagnostic option: block rows of the second bound's row prefix (-1 by size: nP / 4, 0 never, n > 0: min(n, nP, N / 128) wherever the first level pruned)
     int short_map = -1;       // diagnostic option: the short form of tile map 3 (sweep_map.h) -1 by size (launches that cannot fill the per-XCD patches), 0 never, 1 always
     char* dkeep = nullptr;    // [ub M][seed idx G][dots M]
@@ -341,13 +346,18 @@ void launch_prune_alpha(hipStream_t s, const double* U, int64_t Np, const double
 constexpr int BM_SC_RX2 = 6, BM_SC_RZ2 = 7, BM_SC_GUARD = 8, BM_SC_USE = 9;      // slots of sc[] (0 .. 5: k_prune_delta, gate, tau)
 // the fp32 link (bound_f32.h): E, 1.0 where a weight is outside fp32's normal range, 1.0 where k_bound_mfma32 writes the dots
 // (sc[USE] is 1.0 then as well: the generic kernel skips on it, k_bound_mfma on this one), the margin's factor and flush term
-constexpr int BM_SC_E32 = 10, BM_SC_BADW = 11, BM_SC_USE32 = 12, BM_SC_FAC32 = 13, BM_SC_FLUSH32 = 14;
+// (sc[BADW]: 1.0 a weight w outside the range, 0.5 only a scaled weight w' of the factorised form).
+// TPOS32: the fp32 copies' tiles [0, tpos) hold only w >= 0, the rest only w <= 0 (k_bound_aug); FACT32: 1.0 where the factorised walk runs
+constexpr int BM_SC_E32 = 10, BM_SC_BADW = 11, BM_SC_USE32 = 12, BM_SC_FAC32 = 13, BM_SC_FLUSH32 = 14, BM_SC_TPOS32 = 15, BM_SC_FACT32 = 16;
+constexpr int BM_SC_WORDS = 20;            // the words of sc[] (the last ones spare)
 int bound_mfma_ks(int kernel_id, int d);
 int64_t bound_mfma_ws_words(int64_t Np);
 void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
-                       const double* Z, int64_t M, const double* invell, int force, bool allow32, double* ws, double* sc, double* out);
-// the fp32 link's kernel alone (kernels_bound32.hip; launch_bound_mfma calls it behind its guard): operands as k_bound_aug wrote them
-void launch_bound_mfma32(hipStream_t s, const float* A32, const float* W32, const float* NX32, int KS, bool nc, int ntile, int d,
+                       const double* Z, int64_t M, const double* invell, int force, bool allow32, bool allow_fact, double* ws, double* sc,
+                       double* out);
+// the fp32 link's kernels alone (kernels_bound32.hip; launch_bound_mfma calls it behind its guard): operands as k_bound_aug wrote them,
+// Np + 16 rows in ntile tiles; WF32: the scaled weights of the factorised walk, which runs instead where sc[FACT32] says so
+void launch_bound_mfma32(hipStream_t s, const float* A32, const float* W32, const float* WF32, const float* NX32, int KS, bool nc, int ntile, int d,
                          const double* Z, int64_t M, const double* invell, const double* cen, const double* sc, double* out);
 void launch_prune_ub(hipStream_t s, const double* dots, double* ub, int64_t M, int64_t skip, const double* sc, double rho,
                      double bias, double p0);
@@ -358,7 +368,7 @@ void launch_prune_ub2(hipStream_t s, const double* Qp, int64_t ldp, int nR, int6
 void launch_sel_remap(hipStream_t s, const int64_t* idx, int64_t* idx2, int64_t n);
 // the ensemble's bound: one member's EI bound folded into the running sum (k_ens_accum's addition), then the sum / n (k_ens_finish's)
 void launch_prune_ub_fold(hipStream_t s, const double* dots, double* acc, int64_t M, const double* sc, double rho, double bias,
-                          double p0, int first, double* delta_out);
+                          double p0, int first, double* delta_out, int guarded, double* fact_out);
 void launch_prune_ub_mean(hipStream_t s, double* acc, int64_t M, int64_t skip, double n);
 void launch_prune_mean(hipStream_t s, const double* v, int64_t n, double* out);
 void launch_sel_threshold(hipStream_t s, const double* v, int64_t M, int G, int* hist, int* st);

@@ -874,19 +874,62 @@ __global__ __launch_bounds__(256) void k_bound_centre(const double* __restrict__
 // 16 t + (l & 15) at A[(t KS + ks) 64 + l] -- one coalesced 512-byte read per wave and k-step.  W4[16 t + 4 g + r] = rho alpha2 of row
 // 16 t + g + 4 r: the four weights of a lane's four results (C/D row = (l >> 4) + 4 r) as one 32-byte read.  Rows from N on: zeros.
 // NX4 (non-null: the norms go through the accumulator): -|x~|^2 / 2 in W4's order, and the rows are [x~_1 .. x~_d] alone.
-// A32 (non-null: the fp32 link may run): the same three arrays once more in fp32, at A32, A32 + 4 KS Np and, with NX4, Np behind that --
-// the coordinates and the norm times log2(e), each rounded once from the fp64 value; weights and norms in row order -- and sc[BADW] = 1.0 where a weight is neither 0
-// nor a normal fp32 number.
+// A32 (non-null: the fp32 link may run): the same three arrays once more in fp32, Np + 16 rows in the sign-homogeneous order of
+// bound_f32.h (w > 0, 16 zero rows, w == 0, w < 0; sc[TPOS32] = the first tile without a positive weight): the coordinates at A32, behind
+// them the weights, the factorised walk's weights w r_i and, with NX4, the norms, Np + 16 floats each -- the coordinates and the norm
+// times log2(e), each rounded once from the fp64 value; weights and norms in row order -- and sc[BADW] = 1.0 where a weight is neither 0
+// nor a normal fp32 number, 0.5 where only a weight of the factorised walk is not.
 __global__ __launch_bounds__(256) void k_bound_aug(const double* __restrict__ Xs, int64_t N, int64_t Np, int d, int KS,
                                                    const double* __restrict__ cen, const double* __restrict__ alpha2, double rho,
                                                    double* __restrict__ A, double* __restrict__ W4, double* __restrict__ NX4,
                                                    float* __restrict__ A32, double* __restrict__ sc) {
     __shared__ double red[256];
+    __shared__ int cnt[4], wcnt[4][2];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;       // (Np is a multiple of 128)
+    // The fp32 copies' row of row i (bound_f32.h, sign-homogeneous tiles): every workgroup counts the signs of all weights, and of those
+    // before its own rows, itself (Np / 256 weights a thread) -- no launch and no pass of their own; ranks inside the workgroup by ballot.
+    int64_t i32 = 0, npos = 0;
+    if (A32) {
+        if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
+        __syncthreads();
+        const int64_t i0 = (int64_t)blockIdx.x * 256;
+        int c[4] = {0, 0, 0, 0};      // w > 0 and w == 0 (not < 0, not > 0) among all rows / among the rows before this workgroup's
+        for (int64_t j = threadIdx.x; j < Np; j += 256) {
+            const double wj = (j < N) ? rho * alpha2[j] : 0.0;
+            const int p = wj > 0.0 ? 1 : 0, z = (wj > 0.0 || wj < 0.0) ? 0 : 1;
+            c[0] += p;
+            c[1] += z;
+            c[2] += (j < i0) ? p : 0;
+            c[3] += (j < i0) ? z : 0;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            for (int o = 32; o > 0; o >>= 1) c[q] += __shfl_xor(c[q], o);
+            if ((threadIdx.x & 63) == 0) atomicAdd(&cnt[q], c[q]);
+        }
+        const double wi = (i < N) ? rho * alpha2[i] : 0.0;
+        const bool in = i < Np, p = in && wi > 0.0, z = in && !(wi > 0.0 || wi < 0.0);
+        const unsigned long long bp = __ballot(p), bz = __ballot(z), below = (1ull << (threadIdx.x & 63)) - 1ull;
+        const int wv = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) {
+            wcnt[wv][0] = __popcll(bp);
+            wcnt[wv][1] = __popcll(bz);
+        }
+        __syncthreads();
+        int rp = cnt[2] + __popcll(bp & below), rz = cnt[3] + __popcll(bz & below);
+        for (int q = 0; q < wv; ++q) {
+            rp += wcnt[q][0];
+            rz += wcnt[q][1];
+        }
+        npos = cnt[0];
+        const int64_t rn = i - rp - rz;                               // the rows before i that are neither: w < 0
+        i32 = bound32_row_dest(p ? 1 : (z ? 0 : -1), p ? rp : (z ? rz : rn), npos, cnt[1]);
+        if (i == 0) sc[BM_SC_TPOS32] = (double)bound32_tpos(npos);
+    }
     double n2 = 0.0, badw = 0.0;
     if (i < Np) {
-        const int64_t t = i >> 4;
-        const int row = (int)(i & 15);
+        const int64_t t = i >> 4, t32 = i32 >> 4;
+        const int row = (int)(i & 15), row32 = (int)(i32 & 15);
         double* At = A + t * KS * 64 + row;
         const bool live = i < N;
         for (int k = 0; k < 4 * KS; ++k) {
@@ -898,17 +941,26 @@ __global__ __launch_bounds__(256) void k_bound_aug(const double* __restrict__ Xs
             if (live && !NX4 && k == d) v = -0.5 * n2;
             if (live && !NX4 && k == d + 1) v = 1.0;
             At[(k >> 2) * 64 + (k & 3) * 16] = v;
-            if (A32) A32[t * KS * 64 + row + (k >> 2) * 64 + (k & 3) * 16] = (float)((live && k <= d) ? B32_LOG2E * v : v);
+            if (A32) A32[t32 * KS * 64 + row32 + (k >> 2) * 64 + (k & 3) * 16] = (float)((live && k <= d) ? B32_LOG2E * v : v);
         }
         const int g = row & 3, r = row >> 2;                          // row = g + 4 r
         const double wt = live ? rho * alpha2[i] : 0.0;
         W4[t * 16 + 4 * g + r] = wt;
         if (NX4) NX4[t * 16 + 4 * g + r] = live ? -0.5 * n2 : 0.0;
         if (A32) {
-            float* W32 = A32 + Np * 4 * KS;
-            W32[i] = (float)wt;      // (row order: the fp32 MFMA's C/D row is 4 (l >> 4) + r, a lane's four results are four neighbouring rows)
-            if (NX4) W32[Np + i] = live ? (float)(B32_LOG2E * (-0.5 * n2)) : 0.0f;
-            badw = bound32_bad_weight(wt);
+            const int64_t Np32 = Np + B32_ZROWS;
+            float* W32 = A32 + Np32 * 4 * KS;
+            const double wf = wt * bound32_norm_factor(n2);           // the factorised walk's weight: the row's norm factor goes in before the one rounding
+            W32[i32] = (float)wt;    // (row order: the fp32 MFMA's C/D row is 4 (l >> 4) + r, a lane's four results are four neighbouring rows)
+            W32[Np32 + i32] = (float)wf;
+            if (NX4) W32[2 * Np32 + i32] = live ? (float)(B32_LOG2E * (-0.5 * n2)) : 0.0f;
+            badw = fmax(bound32_bad_weight(wt), 0.5 * bound32_bad_weight_fact(wt, wf));
+            if (i < B32_ZROWS) {                                      // the extra zero tile's rows, behind the positive weights
+                const int64_t e = npos + i;
+                for (int k = 0; k < 4 * KS; ++k) A32[(e >> 4) * KS * 64 + (e & 15) + (k >> 2) * 64 + (k & 3) * 16] = 0.0f;
+                W32[e] = W32[Np32 + e] = 0.0f;
+                if (NX4) W32[2 * Np32 + e] = 0.0f;
+            }
         }
     }
     block_max_nonneg(n2, sc + BM_SC_RX2, red);
@@ -934,22 +986,27 @@ __global__ __launch_bounds__(256) void k_bound_rz(const double* __restrict__ Z, 
 // delta / 2 has room for while that is at most Np u.  force: -1 by guard, 1 the matrix-pipe kernel whatever the guard says.
 // The fp32 link (want32: its operands exist and the host's size rule allows it; force 2: whatever the guards say) runs where the fp64
 // guard passes, E <= 2^-10 and every weight is 0 or a normal fp32 number; sc[E32] is NaN where it was not considered.
-__global__ void k_bound_guard(int d, int64_t Np, int force, int want32, double rho, double* __restrict__ sc) {
+// The factorised walk (allow_fact: option bound_fact) runs where the fp32 kernel does, its own guards hold whatever `force` says, and
+// bound32_fact_ok passes the radii and the weights' sum with no scaled weight outside fp32's normal range.
+__global__ void k_bound_guard(int d, int64_t Np, int force, int want32, int allow_fact, double rho, double* __restrict__ sc) {
     const double R = sqrt(sc[BM_SC_RX2]) + sqrt(sc[BM_SC_RZ2]);
     const double gv = (double)(d + 4) * R * R;
     const bool use64 = force > 0 || gv <= (double)Np;
     sc[BM_SC_GUARD] = gv;
     sc[BM_SC_USE] = use64 ? 1.0 : 0.0;
-    double E = __builtin_nan(""), use32 = 0.0, fac = 0.0, fl = 0.0;
+    double E = __builtin_nan(""), use32 = 0.0, fact = 0.0, fac = 0.0, fl = 0.0;
     if (want32) {
+        const double bw = sc[BM_SC_BADW], sum_w = rho * sc[0] * (1.0 + 0x1p-20);
         E = bound32_E(d, (double)(Np / 16), gv);
-        use32 = (force == 2 || (use64 && E <= B32_E_MAX && sc[BM_SC_BADW] == 0.0)) ? 1.0 : 0.0;
-        fac = bound32_factor(E, sc[BM_SC_BADW]);
-        fl = bound32_flush(rho * sc[0] * (1.0 + 0x1p-20), (double)Np);
+        use32 = (force == 2 || (use64 && E <= B32_E_MAX && bw != 1.0)) ? 1.0 : 0.0;
+        fact = (allow_fact && use32 == 1.0 && E <= B32_E_MAX && bw == 0.0) ? bound32_fact_ok(sc[BM_SC_RX2], sc[BM_SC_RZ2], sum_w) : 0.0;
+        fac = bound32_factor(E, bw == 1.0 ? 1.0 : 0.0);
+        fl = bound32_flush(sum_w, (double)Np);
     }
     sc[BM_SC_E32] = E;
     sc[BM_SC_USE32] = use32;
     sc[BM_SC_FAC32] = fac;
+    sc[BM_SC_FACT32] = fact;
     sc[BM_SC_FLUSH32] = fl;
 }
 
@@ -1059,13 +1116,14 @@ __global__ __launch_bounds__(256, (KS + (NC ? 1 : 0) <= 3) ? 4 : 3) void k_bound
 }
 
 // Prologue, guard and the matrix-pipe kernels on stream s.  ws: [A Np x 4 KS][W4 Np][NX4 Np, where the norms go through the accumulator:
-// KS <= 4 there][cen 4 BM_KS_MAX at its fixed place][the fp32 copies: A Np x 4 KS, W4 Np, NX4 Np floats]; sc: the bound pass's 16 scalars.
-// force: the option prune_bound (-1, 1, 2); allow32: the host's size rule lets the fp32 link run by its guards.
+// KS <= 4 there][cen 4 BM_KS_MAX at its fixed place][the fp32 copies, Np + 16 rows: A x 4 KS, W, W', NX floats]; sc: the bound pass's BM_SC_WORDS scalars.
+// force: the option prune_bound (-1, 1, 2); allow32: the host's size rule lets the fp32 link run by its guards; allow_fact: option bound_fact.
 // The caller launches the generic kernel behind it with sc + BM_SC_USE as its `skip`: exactly one of the three writes `out`.
-int64_t bound_mfma_ws_words(int64_t Np) { return Np * 4 * BM_KS_MAX + Np + 4 * BM_KS_MAX + Np * 2 * BM_KS_MAX + Np; }
+int64_t bound_mfma_ws_words(int64_t Np) { return Np * 4 * BM_KS_MAX + Np + 4 * BM_KS_MAX + (Np + B32_ZROWS) * (2 * BM_KS_MAX + 2); }
 
 void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
-                       const double* Z, int64_t M, const double* invell, int force, bool allow32, double* ws, double* sc, double* out) {
+                       const double* Z, int64_t M, const double* invell, int force, bool allow32, bool allow_fact, double* ws, double* sc,
+                       double* out) {
     const int KS = bound_mfma_steps(d);
     const bool nc = bound_mfma_normc(d);
     double* A = ws;
@@ -1074,12 +1132,14 @@ void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, i
     double* cen = ws + Np * 4 * BM_KS_MAX + Np;
     const bool want32 = force == 2 || (force < 0 && allow32);
     float* A32 = want32 ? reinterpret_cast<float*>(cen + 4 * BM_KS_MAX) : nullptr;
-    const float* W32 = want32 ? A32 + Np * 4 * KS : nullptr;
-    const float* NX32 = (want32 && nc) ? W32 + Np : nullptr;
+    const int64_t Np32 = Np + B32_ZROWS;
+    const float* W32 = want32 ? A32 + Np32 * 4 * KS : nullptr;
+    const float* WF32 = want32 ? W32 + Np32 : nullptr;
+    const float* NX32 = (want32 && nc) ? WF32 + Np32 : nullptr;
     hipLaunchKernelGGL(k_bound_centre, dim3(1), dim3(256), 0, s, Xs, N, d, cen, sc);
     hipLaunchKernelGGL(k_bound_aug, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, Xs, N, Np, d, KS, cen, alpha2, rho, A, W4, NX4, A32, sc);
     hipLaunchKernelGGL(k_bound_rz, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, Z, M, d, invell, cen, sc);
-    hipLaunchKernelGGL(k_bound_guard, dim3(1), dim3(1), 0, s, d, Np, force, want32 ? 1 : 0, rho, sc);
+    hipLaunchKernelGGL(k_bound_guard, dim3(1), dim3(1), 0, s, d, Np, force, want32 ? 1 : 0, allow_fact ? 1 : 0, rho, sc);
     const dim3 grid((unsigned)((M + XN - 1) / XN));
     const int ntile = (int)(Np / 16);
 #define GPX_BM(K, C) hipLaunchKernelGGL((k_bound_mfma<K, C>), grid, dim3(256), 0, s, A, W4, NX4, ntile, d, Z, M, invell, cen, sc, out)
@@ -1096,7 +1156,7 @@ void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, i
     }
 #undef GPX_BM
     if (!want32) return;
-    launch_bound_mfma32(s, A32, W32, NX32, KS, nc, ntile, d, Z, M, invell, cen, sc, out);
+    launch_bound_mfma32(s, A32, W32, WF32, NX32, KS, nc, (int)(Np32 / 16), d, Z, M, invell, cen, sc, out);
 }
 
 // ub[n] <- EI((bias + dots[n]) + delta, s2 = rho), dots[n] = alpha2 . k(X, z_n), by k_acq's own function; -inf for the `skip`
@@ -1160,21 +1220,25 @@ __device__ __forceinline__ double ens_mean(double acc, double n) {
 }
 
 // acc[c] (+)= EI((bias + dots[c]) + delta, s2 = rho): k_prune_ub's value of one member, folded into the running sum in the same
-// pass; delta_out receives the member's delta = sc[1] (for gpx_ensemble_prune_report).
+// pass; delta_out receives the member's delta = sc[1] and fact_out 1.0 where its dots came from the fp32 kernel's factorised walk (guarded:
+// the device chose the kernel; NaN otherwise) (for gpx_ensemble_prune_report).
 __global__ __launch_bounds__(256) void k_prune_ub_fold(const double* __restrict__ dots, double* __restrict__ acc, int64_t M,
                                                        const double* __restrict__ sc, double rho, double bias, double p0, int first,
-                                                       double* __restrict__ delta_out) {
+                                                       double* __restrict__ delta_out, int guarded, double* __restrict__ fact_out) {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= M) return;
     const double ub = acq_value(GPX_ACQ_EI, (bias + dots[n]) + sc[1], rho, p0);
     acc[n] = ens_fold(first, first ? 0.0 : acc[n], ub);
-    if (n == 0) *delta_out = sc[1];
+    if (n == 0) {
+        *delta_out = sc[1];
+        *fact_out = guarded ? ((sc[BM_SC_USE32] == 1.0 && sc[BM_SC_FACT32] == 1.0) ? 1.0 : 0.0) : __builtin_nan("");
+    }
 }
 
 void launch_prune_ub_fold(hipStream_t s, const double* dots, double* acc, int64_t M, const double* sc, double rho, double bias,
-                          double p0, int first, double* delta_out) {
+                          double p0, int first, double* delta_out, int guarded, double* fact_out) {
     hipLaunchKernelGGL(k_prune_ub_fold, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, dots, acc, M, sc, rho, bias, p0, first,
-                       delta_out);
+                       delta_out, guarded, fact_out);
 }
 
 // acc[c] <- acc[c] / n, the ensemble's bound; -inf for the `skip` leading candidates that are exactly evaluated already
