@@ -56,14 +56,14 @@ static int guarded(gpx_handle* h, F&& body) noexcept {
     }
 }
 
-template <typename T>
-static int ensure(gpx_handle* h, T*& p, int64_t& cap, int64_t need) {
-    if (need <= cap && p) return GPX_OK;
-    if (p) HIPCHK(h, hipFree(p));
-    p = nullptr;
-    cap = 0;
-    HIPCHK(h, hipMalloc((void**)&p, (size_t)need * sizeof(T)));
-    cap = need;
+int gpx::ensure_bytes(gpx_handle* h, void** p, int64_t* cap, int64_t need, size_t elem, const char* what) {
+    if (need <= *cap && *p) return GPX_OK;
+    if (*p && what) hipFree(*p);
+    else if (*p) HIPCHK(h, hipFree(*p));
+    *p = nullptr, *cap = 0;
+    if (!what) HIPCHK(h, hipMalloc(p, (size_t)need * elem));
+    else if (hipMalloc(p, (size_t)need * elem) != hipSuccess) return fail(h, GPX_EOOM, (std::string(what) + ": device allocation failed").c_str());
+    *cap = need;
     return GPX_OK;
 }
 
@@ -451,10 +451,10 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
         for (int i = 0; i < nscal && i < 22; ++i) scal[i] = out[i];
         int rc;
         if ((rc = report_vectors(h, r, ub, idx, cap_idx))) return rc;
-        if (ub_kept) HIPCHK(h, hipMemcpy(ub_kept, h->dkeep, (size_t)r.M * 8, hipMemcpyDeviceToHost));
+        const KeepWs kw = keep_ws(WsCarver(h->dkeep), r.M, r.G);
+        if (ub_kept) HIPCHK(h, hipMemcpy(ub_kept, kw.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
         const int64_t nseed = std::min(r.G, cap_seed);
-        if (seed_idx && nseed > 0)
-            HIPCHK(h, hipMemcpy(seed_idx, h->dkeep + r.M * 8, (size_t)nseed * 8, hipMemcpyDeviceToHost));
+        if (seed_idx && nseed > 0) HIPCHK(h, hipMemcpy(seed_idx, kw.seed, (size_t)nseed * 8, hipMemcpyDeviceToHost));
         return GPX_OK;
     });
 }
@@ -483,7 +483,7 @@ extern "C" int gpx_prune_dots(gpx_handle* h, double* dots) {
         if (r.path < 2 || !r.kept) return fail(h, GPX_ESTATE, "prune_dots: the last sweep kept no bound pass (option prune_keep)");
         HIPCHK(h, hipSetDevice(h->device));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(dots, h->dkeep + (r.M + r.G) * 8, (size_t)r.M * 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(dots, keep_ws(WsCarver(h->dkeep), r.M, r.G).dots, (size_t)r.M * 8, hipMemcpyDeviceToHost));
         return GPX_OK;
     });
 }
@@ -764,9 +764,9 @@ static int flush_pending(gpx_handle* h) {
     if (h->npend == 0) return GPX_OK;
     if (h->cache_valid) {
         Span sp(h, T_RANK1);
-        launch_sweep_rankq(h->stream, h->dXs, h->N, (int)h->d, h->dpend, h->pend_ld, h->npend,
-                           h->dpend + (int64_t)PEND_MAX * h->pend_ld, h->dcZ, h->cache_M, h->dinvell, h->kernel_id,
-                           h->rho, h->dcq, h->dcp);
+        const PendWs pw = pend_ws(WsCarver(h->dpend), h->pend_ld);
+        launch_sweep_rankq(h->stream, h->dXs, h->N, (int)h->d, pw.rows, h->pend_ld, h->npend, pw.scal, h->dcZ, h->cache_M, h->dinvell,
+                           h->kernel_id, h->rho, h->dcq, h->dcp);
         HIPCHK(h, hipGetLastError());
     }
     h->npend = 0;
@@ -803,9 +803,7 @@ extern "C" int gpx_append_begin(gpx_handle* h, const double* x) {
         //  announcement's pass on the third stream may still have been reading -- ADVICE round 4)
         if ((rc = grow_factor_if_full(h))) return rc;
         const int64_t d = h->d, M = h->cache_M, ld = h->cap_np;
-        const int64_t xpad = (h->cap_d + 63) / 64 * 64;
-        const int64_t need = 2 * xpad + 5 * ld + 64 + M;
-        if ((rc = ensure(h, h->dspec, h->cap_spec, need))) return rc;
+        if ((rc = ensure(h, h->dspec, h->cap_spec, spec_ws(WsCarver(nullptr), (h->cap_d + 63) / 64 * 64, ld, M).bytes / 8))) return rc;
         h->spec_ld = ld;
         h->spec_M = M;
         const SpecBuf sb = spec_layout(h);
@@ -876,14 +874,13 @@ extern "C" int gpx_append(gpx_handle* h, const double* x, double y) {
                 if (rc2) return rc2;
             }
             if (h->npend == 0 && h->cap_np > h->pend_ld) {
-                if (h->dpend) HIPCHK(h, hipFree(h->dpend));
-                h->dpend = nullptr;
+                int64_t cap = 0;                                  // (the rows' pitch is the capacity the handle keeps)
                 h->pend_ld = 0;
-                HIPCHK(h, hipMalloc((void**)&h->dpend, (size_t)PEND_MAX * (h->cap_np + 2) * 8));
+                if ((rc = ensure(h, h->dpend, cap, pend_ws(WsCarver(nullptr), h->cap_np).bytes / 8))) return rc;
                 h->pend_ld = h->cap_np;
             }
-            launch_pend_store(h->stream, h->app_w, Nold, h->pend_ld, h->dscal, h->dpend + (int64_t)h->npend * h->pend_ld,
-                              h->dpend + (int64_t)PEND_MAX * h->pend_ld + 2 * h->npend);
+            const PendWs pw = pend_ws(WsCarver(h->dpend), h->pend_ld);
+            launch_pend_store(h->stream, h->app_w, Nold, h->pend_ld, h->dscal, pw.rows + (int64_t)h->npend * h->pend_ld, pw.scal + 2 * h->npend);
             HIPCHK(h, hipGetLastError());
             if (++h->npend == PEND_MAX) return flush_pending(h);
         }
@@ -1065,31 +1062,17 @@ static MesArg mes_arg(const double* params, int nparams) {
     return a;
 }
 
-// The prepared support set of the knowledge gradient (kernels_kg.hip), h->dkg:
-// [A raw 128 d][As scaled 128 d][a_j 128][B Np 128][V_A Np 128][Pp nP 128]; the cross-Gram of the set passes through dKs.
-struct KgBuf { double *A, *As, *al, *B, *V, *Pp; int m; };
-static KgBuf kg_layout(const gpx_handle* h, int m) {
-    KgBuf b;
-    b.A = h->dkg;
-    b.As = b.A + NB * h->d;
-    b.al = b.As + NB * h->d;
-    b.B = b.al + NB;
-    b.V = b.B + h->Np * NB;
-    b.Pp = b.V + h->Np * NB;
-    b.m = m;
-    return b;
-}
+// The prepared support set of the knowledge gradient (kernels_kg.hip; h->dkg: kg_ws); its cross-Gram passes through dKs.
 // O(N^2 m), once per support set and model: skipped while the handle holds the bits of this set for this fit (gpx_kg_grad is called
 // many times by one refinement).  Enqueued on the handle's stream; the caller has ensured the inverse.
 static int kg_prepare(gpx_handle* h, const double* A, int m, KgBuf& b) {
     const int64_t Np = h->Np, d = h->d;
-    const int nP = (int)(Np / NB);
-    const int64_t need = 2 * NB * d + NB + 2 * Np * NB + (int64_t)nP * NB;
+    const int64_t need = kg_ws(WsCarver(nullptr), d, Np, m).bytes / 8;
     if (need > h->cap_kg || !h->dkg) h->kg_A.clear();
     int rc;
     if ((rc = ensure(h, h->dkg, h->cap_kg, need))) return rc;
     if ((rc = ensure(h, h->dKs, h->cap_ks, Np * NB))) return rc;
-    b = kg_layout(h, m);
+    b = kg_ws(WsCarver(h->dkg), d, Np, m);
     const size_t na = (size_t)m * d;
     if (h->kg_gen == h->gen && h->kg_Np == Np && h->kg_A.size() == na && memcmp(h->kg_A.data(), A, na * 8) == 0) return GPX_OK;
     h->kg_A.clear();
@@ -1120,7 +1103,7 @@ static int check_topk(gpx_handle* h, const char* what, int64_t k, const double* 
     return GPX_OK;
 }
 
-// The host form of a sweep: stage [Xc (M,d), when given][acq M][mu M][s2 M] in h->dXc, run `core` on the device buffers
+// The host form of a sweep: stage the candidates, when given, and the outputs in h->dXc (staged_ws), run `core` on the device buffers
 // (mu / s2 only where the caller wants them), copy the requested outputs back and synchronise.  `sync_upload`: the core
 // reads the candidates from other streams.
 template <typename Core>
@@ -1129,23 +1112,20 @@ static int staged_sweep(gpx_handle* h, const double* Xc, int64_t M, bool sync_up
     HIPCHK(h, hipSetDevice(h->device));
     const int64_t nx = Xc ? M * h->d : 0;
     int rc;
-    if ((rc = ensure(h, h->dXc, h->cap_xc, nx + 3 * M))) return rc;
-    double* dX = h->dXc;
-    double* dacq = dX + nx;
-    double* dmu = dacq + M;
-    double* ds2 = dmu + M;
+    if ((rc = ensure(h, h->dXc, h->cap_xc, staged_ws(WsCarver(nullptr), nx, M).bytes / 8))) return rc;
+    const StagedWs st = staged_ws(WsCarver(h->dXc), nx, M);
     if (Xc) {
         Span sp(h, T_COPY);
-        HIPCHK(h, hipMemcpyAsync(dX, Xc, (size_t)nx * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st.X, Xc, (size_t)nx * 8, hipMemcpyHostToDevice, h->stream));
     }
     if (sync_upload) HIPCHK(h, hipStreamSynchronize(h->stream));
     // (no staging vector for an output nobody asked for: a sweep that returns only its top-k may then skip candidates)
-    if ((rc = core(dX, acq_all ? dacq : nullptr, mu ? dmu : nullptr, s2 ? ds2 : nullptr))) return rc;
+    if ((rc = core(st.X, acq_all ? st.acq : nullptr, mu ? st.mu : nullptr, s2 ? st.s2 : nullptr))) return rc;
     {
         Span sp(h, T_COPY);
-        if (acq_all) HIPCHK(h, hipMemcpyAsync(acq_all, dacq, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-        if (mu) HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
-        if (s2) HIPCHK(h, hipMemcpyAsync(s2, ds2, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
+        if (acq_all) HIPCHK(h, hipMemcpyAsync(acq_all, st.acq, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
+        if (mu) HIPCHK(h, hipMemcpyAsync(mu, st.mu, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
+        if (s2) HIPCHK(h, hipMemcpyAsync(s2, st.s2, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return GPX_OK;
@@ -1179,51 +1159,12 @@ static PruneGeom prune_geom(int nP, int64_t k, int64_t M) {
     return {G, (int64_t)TBH * gen_tiles, std::max<int64_t>(G, M / PRUNE_MAX_SHARE_DIV)};
 }
 
-// The pruning workspace, h->dprune:
-// [ub M][vals cap][Xg cap d][idx cap][blk nsel + 1][alpha2 Np][sabs Np][gate s2 Gg][sc BM_SC_WORDS][extra][hist 2 x 4096 + st 8 (int)]
-// [pad to 32 bytes][the matrix-pipe bound kernel's operands]
-// rows (the single model's sweep): [dots M][ub2 cap][qR cap][idx2 cap][Xg2 cap d][blk2 sel_blocks(cap) + 1] -- the second bound's
-struct PruneWs {
-    double *ub, *vals, *Xg;
-    int64_t *idx, *blk;
-    double *alpha2, *sabs, *gs2, *sc, *extra;
-    int *hist, *st;
-    double* bws;
-    int64_t nsel;
-    double *dots, *ub2, *qR, *Xg2;
-    int64_t *idx2, *blk2;
-};
+// The pruning workspace of h (h->dprune: prune_ws_layout), grown where it has to
 static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t extra, PruneWs& w, bool rows = false) {
-    const int64_t Np = h->Np;
-    w.nsel = sel_blocks(M);
-    const int64_t words0 = M + cap + cap * h->d + cap + (w.nsel + 1) + 2 * Np + Gg + BM_SC_WORDS + extra + (2 * 4096 + 8) / 2;
-    const int64_t words1 = (words0 + 3) / 4 * 4 + bound_mfma_ws_words(Np);
-    const int64_t words = words1 + (rows ? M + 3 * cap + cap * h->d + sel_blocks(cap) + 1 : 0);
-    if (!h->dprune || words * 8 > h->cap_prune) h->ens_rec = gpx_handle::EnsPruneRecord();   // (its vectors lie in the old allocation)
-    int rc;
-    if ((rc = ensure(h, h->dprune, h->cap_prune, words * 8))) return rc;
-    w.ub = reinterpret_cast<double*>(h->dprune);
-    w.vals = w.ub + M;
-    w.Xg = w.vals + cap;
-    w.idx = reinterpret_cast<int64_t*>(w.Xg + cap * h->d);
-    w.blk = w.idx + cap;
-    w.alpha2 = reinterpret_cast<double*>(w.blk + w.nsel + 1);
-    w.sabs = w.alpha2 + Np;
-    w.gs2 = w.sabs + Np;
-    w.sc = w.gs2 + Gg;
-    w.extra = w.sc + BM_SC_WORDS;
-    w.hist = reinterpret_cast<int*>(w.extra + extra);
-    w.st = w.hist + 2 * 4096;
-    w.bws = w.ub + (words0 + 3) / 4 * 4;
-    w.dots = w.ub2 = w.qR = w.Xg2 = nullptr;
-    w.idx2 = w.blk2 = nullptr;
-    if (!rows) return GPX_OK;
-    w.dots = w.ub + words1;
-    w.ub2 = w.dots + M;
-    w.qR = w.ub2 + cap;
-    w.idx2 = reinterpret_cast<int64_t*>(w.qR + cap);
-    w.Xg2 = reinterpret_cast<double*>(w.idx2 + cap);
-    w.blk2 = reinterpret_cast<int64_t*>(w.Xg2 + cap * h->d);
+    const int64_t need = prune_ws_layout(WsCarver(nullptr), M, cap, h->d, h->Np, Gg, extra, rows).bytes;
+    if (!h->dprune || need > h->cap_prune) h->ens_rec = gpx_handle::EnsPruneRecord();   // (its vectors lie in the old allocation)
+    if (int rc = ensure(h, h->dprune, h->cap_prune, need)) return rc;
+    w = prune_ws_layout(WsCarver(h->dprune), M, cap, h->d, h->Np, Gg, extra, rows);
     return GPX_OK;
 }
 
@@ -1489,6 +1430,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     // ---- selection-only sweep: select_topk_pruned with this model's exact chain, gate, bound and second bound ----
     gpx_handle::PruneRecord& rec = h->prune_rec;
     PruneWs w;
+    KeepWs kw = {};              // (option prune_keep: laid out by the bound pass)
     SelectOps ops;
     ops.exact = run_chunks;
     ops.gate = [&](int64_t Gg, double* value, bool* go) -> int {
@@ -1510,18 +1452,19 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             bound_dots(h, dXc, M, w, bound_mfma, w.dots);      // (kept: the second bound reads the survivors' dots again)
             if (h->prune_keep) {
                 // diagnostic: the dots as the kernel left them (gpx_prune_dots), behind the two copies below
-                if ((rc = ensure(h, h->dkeep, h->cap_keep, (2 * M + rec.G) * 8))) return rc;
-                HIPCHK(h, hipMemcpyAsync(h->dkeep + (M + rec.G) * 8, w.dots, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
+                if ((rc = ensure(h, h->dkeep, h->cap_keep, keep_ws(WsCarver(nullptr), M, rec.G).bytes))) return rc;
+                kw = keep_ws(WsCarver(h->dkeep), M, rec.G);
+                HIPCHK(h, hipMemcpyAsync(kw.dots, w.dots, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
             }
             launch_prune_ub(s, w.dots, ub, M, done, w.sc, h->rho, h->bias, p0);
         }
         rec.bound_kernel = bound_mfma ? -1 : 0, rec.st = w.st, rec.kept = h->prune_keep != 0;
         // diagnostic: the bound vector (and after_seeds: the seed list) as they are before the scatter overwrites them
-        if (rec.kept) HIPCHK(h, hipMemcpyAsync(h->dkeep, ub, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
+        if (rec.kept) HIPCHK(h, hipMemcpyAsync(kw.ub, ub, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
         return GPX_OK;
     };
     ops.after_seeds = [&]() -> int {
-        if (rec.kept) HIPCHK(h, hipMemcpyAsync(h->dkeep + M * 8, w.idx, (size_t)rec.G * 8, hipMemcpyDeviceToDevice, s));
+        if (rec.kept) HIPCHK(h, hipMemcpyAsync(kw.seed, w.idx, (size_t)rec.G * 8, hipMemcpyDeviceToDevice, s));
         return GPX_OK;
     };
     ops.refine = [&](SelectList& list) -> int { return second_bound(h, w, chunk, sweep_order, p0, list); };
@@ -1621,46 +1564,13 @@ extern "C" int gpx_sweep_update(gpx_handle* h, int acq_id, const double* params,
 // Per extra pick: launch_append_prepare (k(X, x), r = T k, w = U r -- its scalars and flag land in this call's own words and are
 // not read: d comes from the CONDITIONED variance), the weight row [w, -1], one rank-1 pass over the cached candidates, one fold +
 // scoring pass.  Everything is enqueued on the handle's stream with ONE synchronisation at the end; the picked index never
-// leaves the device, so no launch depends on it.  Scratch (h->dbsel, doubles), shared by gpx_sweep_batch and, per member, by
-// gpx_ensemble_sweep_batch (whose lead keeps `extra` more words behind V):
-//   [x xpad][xs xpad][ks ld][g ld][r ld][tu ld][row ld][small 384][partv 1024][parti 1024][q' M][s2 M][taken ceil(M / 8)][V nb M][extra]
-//   small: +0 pscal {1/d, 0}  +8 the prepare's scalars (unused)  +24 scal {d, 1/d, 0, d^2}  +40 its flag word  +48 the same-grid
-//          flag word (ensemble lead)  +64 cross (64)  +128 sel_val (64)  +192 sel_s2 (64)  +256 sel_idx (64 int64)
-struct BatchBuf {
-    int64_t ld;
-    double *x, *xs, *ks, *g, *r, *tu, *row, *pscal, *scal_prep, *scal, *cross, *sel_val, *sel_s2, *partv, *qp, *s2, *V, *extra;
-    int *flag, *same;
-    int64_t *sel_idx, *parti;
-    unsigned char* taken;
-    int64_t ntaken;
-};
-static int batch_layout(gpx_handle* h, int64_t M, int64_t nb, int64_t extra, BatchBuf& b) {
+// leaves the device, so no launch depends on it.  Scratch: h->dbsel (batch_ws), shared by gpx_sweep_batch and, per member, by
+// gpx_ensemble_sweep_batch (n_lead > 0: the lead of that many members).
+static int batch_layout(gpx_handle* h, int64_t M, int64_t nb, int64_t n_lead, BatchBuf& b) {
     const int64_t xpad = (h->cap_d + 63) / 64 * 64, ld = h->cap_np + NB;      // N + 1 <= ld whatever the padding holds
-    const int64_t ntaken = (M + 7) / 8;
-    const int64_t need = 2 * xpad + 5 * ld + 384 + 2048 + 2 * M + ntaken + nb * M + extra;
-    if (int rc = ensure(h, h->dbsel, h->cap_bsel, need)) return rc;
-    b.ld = ld;
-    b.x = h->dbsel;
-    b.xs = b.x + xpad;
-    b.ks = b.xs + xpad;
-    b.g = b.ks + ld;
-    b.r = b.g + ld;
-    b.tu = b.r + ld;
-    b.row = b.tu + ld;
-    double* small = b.row + ld;
-    b.pscal = small, b.scal_prep = small + 8, b.scal = small + 24, b.cross = small + 64;
-    b.flag = reinterpret_cast<int*>(small + 40);
-    b.same = reinterpret_cast<int*>(small + 48);
-    b.sel_val = small + 128, b.sel_s2 = small + 192;
-    b.sel_idx = reinterpret_cast<int64_t*>(small + 256);
-    b.partv = small + 384;
-    b.parti = reinterpret_cast<int64_t*>(b.partv + 1024);
-    b.qp = b.partv + 2048;
-    b.s2 = b.qp + M;
-    b.taken = reinterpret_cast<unsigned char*>(b.s2 + M);
-    b.ntaken = ntaken;
-    b.V = b.s2 + M + ntaken;
-    b.extra = b.V + nb * M;
+    const int64_t ndesc = (n_lead * (int64_t)sizeof(EnsBatchMember) + 7) / 8;
+    if (int rc = ensure(h, h->dbsel, h->cap_bsel, batch_ws(WsCarver(nullptr), xpad, ld, M, nb, n_lead, ndesc).bytes / 8)) return rc;
+    b = batch_ws(WsCarver(h->dbsel), xpad, ld, M, nb, n_lead, ndesc);
     return GPX_OK;
 }
 
@@ -1743,7 +1653,7 @@ extern "C" int gpx_predict_mean(gpx_handle* h, const double* Xc, int64_t M, doub
 // mu = bias + V^T a, Kss = k(Z, Z) by the cross-Gram kernel on the scaled points, C = Kss - V^T V; for draws B = C + c I,
 // B = R^T R by launch_cholesky_small under a flag word of its own (dflag[10]), out = mu + z R.  One stream, one synchronisation.
 // Reads the fit only: no flush of queued corrections, the sweep cache, an announcement and their buffers are not touched.
-// Scratch (h->djoint, doubles): [X M d (padded to 32)][Zs Mp d][mu Mp][Pp nP Mp][V Np Mp][Kss Mp Mp][C Mp Mp] + draws: [B Mp Mp][R Mp Mp][z S M][out S M]
+// Scratch: h->djoint (joint_ws).
 static const int64_t JOINT_MAX_M = 4096;
 
 static int joint_core(gpx_handle* h, const char* what, const double* Xc, int64_t M, const double* z, int64_t S, int noisy,
@@ -1760,49 +1670,37 @@ static int joint_core(gpx_handle* h, const char* what, const double* Xc, int64_t
     hipStream_t s = h->stream;
     const int64_t Np = h->Np, d = h->d, Mp = (M + TBH - 1) / TBH * TBH;
     const int nP = (int)(Np / NB);
-    const int64_t nx = (M * d + 31) / 32 * 32;                  // every part below starts on a 256-byte boundary
-    const int64_t need = nx + Mp * d + Mp + nP * Mp + Np * Mp + 2 * Mp * Mp + (draw ? 2 * Mp * Mp + 2 * S * M : 0);
     if ((rc = ensure(h, h->dKs, h->cap_ks, Np * Mp))) return rc;
-    if ((rc = ensure(h, h->djoint, h->cap_joint, need))) return rc;
-    double* dX = h->djoint;
-    double* dZs = dX + nx;
-    double* dmu = dZs + Mp * d;
-    double* dPp = dmu + Mp;
-    double* dV = dPp + nP * Mp;
-    double* dKss = dV + Np * Mp;
-    double* dC = dKss + Mp * Mp;
-    double* dB = dC + Mp * Mp;
-    double* dRj = dB + Mp * Mp;
-    double* dz = dRj + Mp * Mp;
-    double* dout = dz + S * M;
+    if ((rc = ensure(h, h->djoint, h->cap_joint, joint_ws(WsCarver(nullptr), M, Mp, d, nP, Np, draw, S).bytes / 8))) return rc;
+    const JointWs j = joint_ws(WsCarver(h->djoint), M, Mp, d, nP, Np, draw, S);
     int* flag = h->dflag + 10;                // its own word: the fit's flag, the RFF posterior's and an announcement's stay untouched
     {
         Span sp(h, T_COPY);
-        HIPCHK(h, hipMemcpyAsync(dX, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, s));
-        if (draw) HIPCHK(h, hipMemcpyAsync(dz, z, (size_t)S * M * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(j.X, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, s));
+        if (draw) HIPCHK(h, hipMemcpyAsync(j.z, z, (size_t)S * M * 8, hipMemcpyHostToDevice, s));
     }
     {
         Span sp(h, T_JOINT);
-        launch_cross_gram(s, h->dXs, Np, h->N, (int)d, dX, 0, M, Mp, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
-        launch_cov_trmm(s, h->dU, Np, h->dKs, Mp, dV);
-        launch_cov_mu(s, dV, Np, Mp, h->da, h->bias, dPp, dmu);
-        launch_scale_x(s, dX, M, Mp, (int)d, h->dinvell, dZs);
-        launch_cross_gram(s, dZs, Mp, M, (int)d, dX, 0, M, Mp, h->dinvell, h->kernel_id, h->rho, dKss, Mp);
-        launch_cov_syrk(s, dV, Np, dKss, Mp, dC);
+        launch_cross_gram(s, h->dXs, Np, h->N, (int)d, j.X, 0, M, Mp, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
+        launch_cov_trmm(s, h->dU, Np, h->dKs, Mp, j.V);
+        launch_cov_mu(s, j.V, Np, Mp, h->da, h->bias, j.Pp, j.mu);
+        launch_scale_x(s, j.X, M, Mp, (int)d, h->dinvell, j.Zs);
+        launch_cross_gram(s, j.Zs, Mp, M, (int)d, j.X, 0, M, Mp, h->dinvell, h->kernel_id, h->rho, j.Kss, Mp);
+        launch_cov_syrk(s, j.V, Np, j.Kss, Mp, j.C);
         if (draw) {
-            launch_cov_form(s, dC, M, Mp, (noisy ? h->sn2 : 0.0) + jitter, dB);
-            launch_cholesky_small(s, dB, dRj, Mp, flag);
-            launch_cov_draw(s, dRj, Mp, M, dz, S, dmu, flag, dout);
+            launch_cov_form(s, j.C, M, Mp, (noisy ? h->sn2 : 0.0) + jitter, j.B);
+            launch_cholesky_small(s, j.B, j.R, Mp, flag);
+            launch_cov_draw(s, j.R, Mp, M, j.z, S, j.mu, flag, j.out);
         }
         HIPCHK(h, hipGetLastError());
     }
     int fl = 0;
     {
         Span sp(h, T_COPY);
-        if (mu) HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)M * 8, hipMemcpyDeviceToHost, s));
-        if (cov) HIPCHK(h, hipMemcpy2DAsync(cov, (size_t)M * 8, dC, (size_t)Mp * 8, (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost, s));
+        if (mu) HIPCHK(h, hipMemcpyAsync(mu, j.mu, (size_t)M * 8, hipMemcpyDeviceToHost, s));
+        if (cov) HIPCHK(h, hipMemcpy2DAsync(cov, (size_t)M * 8, j.C, (size_t)Mp * 8, (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost, s));
         if (draw) {
-            HIPCHK(h, hipMemcpyAsync(out, dout, (size_t)S * M * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipMemcpyAsync(out, j.out, (size_t)S * M * 8, hipMemcpyDeviceToHost, s));
             HIPCHK(h, hipMemcpyAsync(&fl, flag, sizeof(int), hipMemcpyDeviceToHost, s));
         }
     }
@@ -1839,8 +1737,7 @@ extern "C" int gpx_sample_joint(gpx_handle* h, const double* Xc, int64_t M, cons
 // ---- knowledge gradient at a few points: value and gradient (kernels_kg.hip) ---------------------------------------------
 // The L-BFGS refinement's `f(x, grad=True)` for policies.KG.  Per panel of 128 points: Ks_z by the cross-Gram kernel (through dKs),
 // V_z = T Ks_z, W_z = U V_z, the sums over the observed rows, then lines, value and gradient.  One stream, one synchronisation; reads
-// the fit only (the prepared support set is kept in h->dkg for the next call).  Work space (h->dkgw):
-// [Z Mp d][V_z Np 128][W_z Np 128][S 128 (d + 1) 132][L 4 129 128][f Mp][g Mp d]
+// the fit only (the prepared support set is kept in h->dkg for the next call).  Work space: h->dkgw (kg_point_ws).
 extern "C" int gpx_kg_grad(gpx_handle* h, const double* A, int64_t m, const double* Xc, int64_t M, double* f, double* g) {
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
@@ -1858,36 +1755,29 @@ extern "C" int gpx_kg_grad(gpx_handle* h, const double* A, int64_t m, const doub
         if ((rc = kg_prepare(h, A, (int)m, kb))) return rc;
         hipStream_t s = h->stream;
         const int64_t Np = h->Np, Mp = (M + TBH - 1) / TBH * TBH;
-        const int64_t nS = (int64_t)NB * (d + 1) * 132, nL = 4 * (int64_t)(KG_MAX_LINES + 1) * NB;
-        if ((rc = ensure(h, h->dkgw, h->cap_kgw, Mp * d + 2 * Np * NB + nS + nL + Mp + Mp * d))) return rc;
-        double* dZ = h->dkgw;
-        double* dVz = dZ + Mp * d;
-        double* dWz = dVz + Np * NB;
-        double* dS = dWz + Np * NB;
-        double* dL = dS + nS;
-        double* df = dL + nL;
-        double* dg = df + Mp;
+        if ((rc = ensure(h, h->dkgw, h->cap_kgw, kg_point_ws(WsCarver(nullptr), Mp, d, Np).bytes / 8))) return rc;
+        const KgPointWs pw = kg_point_ws(WsCarver(h->dkgw), Mp, d, Np);
         {
             Span sp(h, T_COPY);
-            HIPCHK(h, hipMemcpyAsync(dZ, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, s));
+            HIPCHK(h, hipMemcpyAsync(pw.Z, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, s));
         }
         {
             Span sp(h, T_ACQ);
             for (int64_t p0 = 0; p0 < M; p0 += NB) {
                 const int np = (int)std::min<int64_t>(NB, M - p0);
-                launch_cross_gram(s, h->dXs, Np, h->N, (int)d, dZ, p0, M, NB, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
-                launch_cov_trmm(s, h->dU, Np, h->dKs, NB, dVz);
-                launch_kg_solve(s, h->dU, Np, h->N, np, dVz, dWz);
-                launch_kg_point_sums(s, h->dXs, h->N, (int)d, dZ + p0 * d, np, h->dinvell, h->kernel_id, h->rho, kb.B, h->dalpha, dWz, dVz, dS);
-                launch_kg_point_final(s, dS, np, (int)d, dZ + p0 * d, h->dinvell, kb.As, kb.m, kb.al, h->kernel_id, h->rho, h->bias, h->sn2,
-                                      dL, df + p0, dg + p0 * d);
+                launch_cross_gram(s, h->dXs, Np, h->N, (int)d, pw.Z, p0, M, NB, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
+                launch_cov_trmm(s, h->dU, Np, h->dKs, NB, pw.Vz);
+                launch_kg_solve(s, h->dU, Np, h->N, np, pw.Vz, pw.Wz);
+                launch_kg_point_sums(s, h->dXs, h->N, (int)d, pw.Z + p0 * d, np, h->dinvell, h->kernel_id, h->rho, kb.B, h->dalpha, pw.Wz, pw.Vz, pw.S);
+                launch_kg_point_final(s, pw.S, np, (int)d, pw.Z + p0 * d, h->dinvell, kb.As, kb.m, kb.al, h->kernel_id, h->rho, h->bias, h->sn2,
+                                      pw.L, pw.f + p0, pw.g + p0 * d);
             }
             HIPCHK(h, hipGetLastError());
         }
         {
             Span sp(h, T_COPY);
-            HIPCHK(h, hipMemcpyAsync(f, df, (size_t)M * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipMemcpyAsync(g, dg, (size_t)M * d * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipMemcpyAsync(f, pw.f, (size_t)M * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipMemcpyAsync(g, pw.g, (size_t)M * d * 8, hipMemcpyDeviceToHost, s));
         }
         HIPCHK(h, hipStreamSynchronize(s));
         return GPX_OK;
@@ -1909,11 +1799,9 @@ static int rff_core(gpx_handle* h, const double* W, const double* b, const doubl
     const int64_t dp = (d + 3) / 4 * 4;
     const int64_t nfb = (n + TBH - 1) / TBH;
     const int64_t nW = S * nfb * dp * TBH, nV = S * nfb * TBH;
-    std::vector<double> stage((size_t)(nW + 2 * nV), 0.0);
+    std::vector<double> stage((size_t)(rff_sweep_ws(WsCarver(nullptr), nW, nV).bytes / 8), 0.0);      // the host image of the device layout
     {
-        double* Wt = stage.data();
-        double* bt = Wt + nW;
-        double* tt = bt + nV;
+        const auto [Wt, bt, tt, nbytes] = rff_sweep_ws(WsCarver(stage.data()), nW, nV);
         for (int64_t q = 0; q < S; ++q)
             for (int64_t j = 0; j < n; ++j) {
                 const int64_t fb = j / TBH, c = j % TBH;
@@ -1923,11 +1811,9 @@ static int rff_core(gpx_handle* h, const double* W, const double* b, const doubl
                 tt[(q * nfb + fb) * TBH + c] = theta[q * n + j];
             }
     }
-    if ((rc = ensure(h, h->drff, h->cap_rff, nW + 2 * nV))) return rc;
-    double* dWt = h->drff;
-    double* dbt = dWt + nW;
-    double* dtt = dbt + nV;
-    HIPCHK(h, hipMemcpyAsync(dWt, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
+    if ((rc = ensure(h, h->drff, h->cap_rff, rff_sweep_ws(WsCarver(nullptr), nW, nV).bytes / 8))) return rc;
+    const RffSweepWs rw = rff_sweep_ws(WsCarver(h->drff), nW, nV);
+    HIPCHK(h, hipMemcpyAsync(rw.Wt, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipStreamSynchronize(s));   // `stage` is a local buffer
     if (!d_vals) {
         if ((rc = ensure(h, h->dout, h->cap_out, S * M))) return rc;
@@ -1936,7 +1822,7 @@ static int rff_core(gpx_handle* h, const double* W, const double* b, const doubl
     {
         Span sp(h, T_RFF);
         Span sp2(h, T_RFFSWEEP);          // the Thompson sweep kernel alone (bench.py: roofline_rff)
-        launch_rff_mfma(s, dWt, dbt, dtt, (int)S, (int)nfb, (int)n, (int)d, (int)dp, bias, dXc, M, d_vals, h->dclk + 2);
+        launch_rff_mfma(s, rw.Wt, rw.bt, rw.tt, (int)S, (int)nfb, (int)n, (int)d, (int)dp, bias, dXc, M, d_vals, h->dclk + 2);
     }
     // algorithmic double-precision lane operations of that launch: per (draw, feature, candidate) d multiply-adds of the
     // projection + 20 instructions of the cosine epilogue (kernels_rff.hip: cos_cw and the weighted sum)
@@ -1947,12 +1833,7 @@ static int rff_core(gpx_handle* h, const double* W, const double* b, const doubl
         const bool rows = k <= TOPK_PASS && S * nblk * k <= ((int64_t)1 << 24) && S <= 65535;
         const int64_t nlist = rows ? S * nblk * k : nblk * k;
         if ((rc = ensure(h, h->dblkv, h->cap_blk, nlist))) return rc;
-        if (!h->dblki || h->cap_blki < nlist) {
-            if (h->dblki) HIPCHK(h, hipFree(h->dblki));
-            h->dblki = nullptr;
-            HIPCHK(h, hipMalloc((void**)&h->dblki, (size_t)nlist * 8));
-            h->cap_blki = nlist;
-        }
+        if ((rc = ensure(h, h->dblki, h->cap_blki, nlist))) return rc;
         if ((rc = ensure(h, h->dtopv, h->cap_top, std::max<int64_t>((int64_t)TOPK_MAX * 2, S * k * 2)))) return rc;
         double* tv = h->dtopv;
         int64_t* ti = reinterpret_cast<int64_t*>(h->dtopv + S * k);
@@ -2034,25 +1915,20 @@ static int rff_gram_batch_dev(gpx_handle* h, const double* W, const double* b, i
             for (int64_t kk = 0; kk < d; ++kk) stage[(size_t)((q * dp + kk) * TBH + j)] = W[(q * n + j) * d + kk];
             stage[(size_t)(nW + q * TBH + j)] = b[q * n + j];
         }
-    // device: [Wt nW][bt nV][A S*n*n][v S*n][extra]
-    const int64_t need = nW + nV + S * n * n + S * n + extra;
-    if ((rc = ensure(h, h->drff, h->cap_rff, need))) return rc;
+    if ((rc = ensure(h, h->drff, h->cap_rff, rff_gram_ws(WsCarver(nullptr), nW, nV, S, n, extra).bytes / 8))) return rc;
     if ((rc = ensure(h, h->drffs, h->cap_rffs, rff_gram_batch_scratch(S, Np)))) return rc;
-    double* dWt = h->drff;
-    double* dbt = dWt + nW;
-    double* dA = dbt + nV;
-    double* dv = dA + S * n * n;
-    HIPCHK(h, hipMemcpyAsync(dWt, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
+    const RffGramWs gw = rff_gram_ws(WsCarver(h->drff), nW, nV, S, n, extra);
+    HIPCHK(h, hipMemcpyAsync(gw.Wt, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipStreamSynchronize(s));   // `stage` is a local buffer
     {
         Span sp(h, T_RFF);
-        launch_rff_gram_batch(s, h->dXraw, N, Np, (int)d, (int)dp, dWt, dbt, (int)S, (int)n, h->dy, h->bias,
-                              h->drffs, dA, dv);
+        launch_rff_gram_batch(s, h->dXraw, N, Np, (int)d, (int)dp, gw.Wt, gw.bt, (int)S, (int)n, h->dy, h->bias,
+                              h->drffs, gw.A, gw.v);
     }
     HIPCHK(h, hipGetLastError());
-    *dA_out = dA;
-    *dv_out = dv;
-    if (dextra) *dextra = dv + S * n;
+    *dA_out = gw.A;
+    *dv_out = gw.v;
+    if (dextra) *dextra = gw.extra;
     return GPX_OK;
 }
 
@@ -2068,22 +1944,16 @@ extern "C" int gpx_rff_gram_batch(gpx_handle* h, const double* W, const double* 
         int rc;
         if (n >= TBH) {
             // wide feature maps: one draw at a time on the generic path
-            // layout: [W n*d][b n][A n*n][v n][Ft n*Np]
-            const int64_t need = n * d + n + n * n + n + n * Np;
-            if ((rc = ensure(h, h->drff, h->cap_rff, need))) return rc;
-            double* dW = h->drff;
-            double* db = dW + n * d;
-            double* dA = db + n;
-            double* dv = dA + n * n;
-            double* dFt = dv + n;
+            if ((rc = ensure(h, h->drff, h->cap_rff, rff_wide_ws(WsCarver(nullptr), n, d, 0, Np, false).bytes / 8))) return rc;
+            const RffWideWs ww = rff_wide_ws(WsCarver(h->drff), n, d, 0, Np, false);
             for (int64_t q = 0; q < S; ++q) {
-                if ((rc = upload_draw(h, W, b, q, n, dW, db))) return rc;
+                if ((rc = upload_draw(h, W, b, q, n, ww.W, ww.b))) return rc;
                 {
                     Span sp(h, T_RFF);
-                    launch_rff_gram(s, h->dXraw, dFt, N, (int)d, dW, db, (int)n, h->dy, h->bias, dA, dv);
+                    launch_rff_gram(s, h->dXraw, ww.Ft, N, (int)d, ww.W, ww.b, (int)n, h->dy, h->bias, ww.A, ww.v);
                 }
-                HIPCHK(h, hipMemcpyAsync(A + q * n * n, dA, (size_t)n * n * 8, hipMemcpyDeviceToHost, s));
-                HIPCHK(h, hipMemcpyAsync(v + q * n, dv, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+                HIPCHK(h, hipMemcpyAsync(A + q * n * n, ww.A, (size_t)n * n * 8, hipMemcpyDeviceToHost, s));
+                HIPCHK(h, hipMemcpyAsync(v + q * n, ww.v, (size_t)n * 8, hipMemcpyDeviceToHost, s));
                 HIPCHK(h, hipStreamSynchronize(s));
             }
             HIPCHK(h, hipGetLastError());
@@ -2115,30 +1985,19 @@ extern "C" int gpx_rff_posterior(gpx_handle* h, const double* W, const double* b
             hipStream_t s = h->stream;
             const int64_t d = h->d, Np = h->Np, N = h->N, np = (n + NB - 1) / NB * NB;
             int rc;
-            // layout: [W n*d][b n][A n*n][v n][z n][work n][theta n][B np*np][R np*np][Ft n*Np]
-            const int64_t need = n * d + 6 * n + n * n + 2 * np * np + n * Np;
-            if ((rc = ensure(h, h->drff, h->cap_rff, need))) return rc;
-            double* dW = h->drff;
-            double* db = dW + n * d;
-            double* dA = db + n;
-            double* dv = dA + n * n;
-            double* dz = dv + n;
-            double* dwork = dz + n;
-            double* dth = dwork + n;
-            double* dB = dth + n;
-            double* dR = dB + np * np;
-            double* dFt = dR + np * np;
+            if ((rc = ensure(h, h->drff, h->cap_rff, rff_wide_ws(WsCarver(nullptr), n, d, np, Np, true).bytes / 8))) return rc;
+            const RffWideWs ww = rff_wide_ws(WsCarver(h->drff), n, d, np, Np, true);
             int* pflag = h->dflag + 8;
             for (int64_t q = 0; q < S; ++q) {
-                if ((rc = upload_draw(h, W, b, q, n, dW, db))) return rc;
-                HIPCHK(h, hipMemcpyAsync(dz, z + q * n, (size_t)n * 8, hipMemcpyHostToDevice, s));
+                if ((rc = upload_draw(h, W, b, q, n, ww.W, ww.b))) return rc;
+                HIPCHK(h, hipMemcpyAsync(ww.z, z + q * n, (size_t)n * 8, hipMemcpyHostToDevice, s));
                 int flag = 0;
                 {
                     Span sp(h, T_RFF);
-                    launch_rff_gram(s, h->dXraw, dFt, N, (int)d, dW, db, (int)n, h->dy, h->bias, dA, dv);
-                    launch_posterior_wide(s, dA, dv, dz, (int)n, np, sc, h->sn2, dB, dR, dwork, pflag, dth);
+                    launch_rff_gram(s, h->dXraw, ww.Ft, N, (int)d, ww.W, ww.b, (int)n, h->dy, h->bias, ww.A, ww.v);
+                    launch_posterior_wide(s, ww.A, ww.v, ww.z, (int)n, np, sc, h->sn2, ww.B, ww.R, ww.work, pflag, ww.th);
                 }
-                HIPCHK(h, hipMemcpyAsync(theta + q * n, dth, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+                HIPCHK(h, hipMemcpyAsync(theta + q * n, ww.th, (size_t)n * 8, hipMemcpyDeviceToHost, s));
                 HIPCHK(h, hipMemcpyAsync(&flag, pflag, sizeof(int), hipMemcpyDeviceToHost, s));
                 HIPCHK(h, hipStreamSynchronize(s));
                 HIPCHK(h, hipGetLastError());
@@ -2200,12 +2059,9 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
     HIPCHK(L, hipSetDevice(L->device));
     // mixture moments for UCB / mean (mu = mean mu_m, s2 = mean(s2_m + mu_m^2) - mu^2), plain mean for EI / PI
     const int mode = (acq_id == GPX_ACQ_UCB || acq_id == GPX_ACQ_MEAN) ? 1 : 0;
-    if ((rc = ensure(L, L->dens, L->cap_ens, 5 * M))) return rc;
-    double* acc0 = L->dens;
-    double* acc1 = acc0 + M;
-    double* t0 = acc1 + M;
-    double* t1 = t0 + M;
-    double* out = d_out ? d_out : t1 + M;
+    if ((rc = ensure(L, L->dens, L->cap_ens, ens_ws(WsCarver(nullptr), M).bytes / 8))) return rc;
+    const EnsWs ew = ens_ws(WsCarver(L->dens), M);
+    double *const acc0 = ew.acc0, *const acc1 = ew.acc1, *const t0 = ew.t0, *const t1 = ew.t1, *const out = d_out ? d_out : ew.out;
     const double beta = (acq_id == GPX_ACQ_UCB) ? params[0] : 0.0;
 
     // The exact ensemble chain for the `cnt` candidates X: every member's sweep in member order, each folded into the running
@@ -2390,13 +2246,12 @@ extern "C" int gpx_ensemble_sweep_batch(gpx_handle* const* members, int n_member
             if (members[m]->cache_M != M) return fail(L, GPX_EARG, "ensemble_sweep_batch: the members' caches differ in size");
         if (nb > M) return fail(L, GPX_EARG, "ensemble_sweep_batch: nb exceeds the number of cached candidates");
         HIPCHK(L, hipSetDevice(L->device));
-        const int64_t desc_words = ((int64_t)n * (int64_t)sizeof(EnsBatchMember) + 7) / 8;
         std::vector<BatchBuf> bufs((size_t)n);
         L->bsel_desc.assign((size_t)n, EnsBatchMember());
         for (int m = 0; m < n; ++m) {
             gpx_handle* h = members[m];
             if ((rc = ensure_inverse(h)) || (rc = flush_pending(h)) ||      // queued appends belong in the sums, on the member's own stream
-                (rc = batch_layout(h, M, nb, m == 0 ? (int64_t)n * nb + desc_words : 0, bufs[m]))) {
+                (rc = batch_layout(h, M, nb, m == 0 ? n : 0, bufs[m]))) {
                 if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
                 return rc;
             }
@@ -2408,8 +2263,8 @@ extern "C" int gpx_ensemble_sweep_batch(gpx_handle* const* members, int n_member
             e.rho = h->rho, e.bias = h->bias, e.sn2 = h->sn2;
         }
         const BatchBuf& lb = bufs[0];
-        double* dsel_s2 = lb.extra;
-        EnsBatchMember* ddesc = reinterpret_cast<EnsBatchMember*>(lb.extra + (int64_t)n * nb);
+        double* dsel_s2 = lb.ens_s2;
+        EnsBatchMember* ddesc = reinterpret_cast<EnsBatchMember*>(lb.desc);
         const double p0 = params[0];
         hipStream_t s = L->stream;
         int differ = 0;

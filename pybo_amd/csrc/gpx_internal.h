@@ -7,17 +7,14 @@
 
 #include "../../include/gpx.h"
 #include "prune_hint.h"
+#include "ws_layout.h"
 
 namespace gpx {
 
-constexpr int NB = 128;       // factorisation block = GEMM tile edge
-constexpr int TBH = 128;      // host-side copy of the GEMM tile edge (gemm_core.h TB)
-constexpr int DMAX = 1024;    // max input dimension (buffer sizing only: the kernels walk coordinates 16 at a time)
 constexpr int DMAX_RFF = DMAX;          // max input dimension of the Thompson / RFF kernels (round 3: the projection walks d in chunks)
 constexpr int DMAX_RFF_RESIDENT = 64;   // up to here the whole k-range of a feature tile [d][144] lives in LDS at once
 constexpr int TOPK_MAX = 4096;   // max k of the device top-k (served TOPK_PASS entries per pass)
 constexpr int TOPK_PASS = 64;
-constexpr int PEND_MAX = 8;   // appended observations per pass of the sweep-cache correction
 
 enum Timer {
     T_GRAM = 0, T_CHOL, T_TRTRI, T_ALPHA, T_XGRAM, T_TRMM, T_ACQ, T_RFF, T_NLAUNCH, T_FLOP, T_COPY, T_APPEND,
@@ -27,7 +24,7 @@ enum Timer {
 struct EventPair { hipEvent_t a, b; int slot; };
 
 // one member of an ensemble batch (gpx_ensemble_sweep_batch) as the kernels of kernels_batch.hip see it: the member's cached sums,
-// its model constants, and where its batch state lies in its own handle's dbsel (batch_layout, api.hip)
+// its model constants, and where its batch state lies in its own handle's dbsel (batch_ws)
 struct EnsBatchMember {
     const double *cq, *cp, *invell;
     double *qp, *V, *cross, *scal, *xs;
@@ -152,12 +149,12 @@ struct gpx_handle {
     int64_t cap_rff = 0;
     double* drffs = nullptr;  // RFF feature-Gram scratch (Phi slabs + split-K partials)
     int64_t cap_rffs = 0;
-    double* dgrad = nullptr;  // predict-with-gradient scratch
+    double* dgrad = nullptr;  // scratch of predict-with-gradients, gpx_append and gpx_rff_grad (grad_ws, append_ws, rff_grad_ws)
     int64_t cap_grad = 0;
-    double* dens = nullptr;   // ensemble sweep: accumulators + member outputs (5 M)
+    double* dens = nullptr;   // ensemble sweep: accumulators + member outputs (ens_ws)
     int64_t cap_ens = 0;
     int prune = -1;           // option: selection-only sweeps skip candidates whose EI bound cannot reach the top-k (-1 by size and gate, 0 never, 1 wherever legal)
-    char* dprune = nullptr;   // their workspace (one allocation, laid out in api.hip: prune_ws)
+    char* dprune = nullptr;   // their workspace (one allocation: prune_ws_layout)
     int64_t cap_prune = 0;    // ... in bytes
     // What the last selection-only sweep decided: the head both records share, filled by select_topk_pruned (api.hip) -- host scalars and
     // where the sweep's vectors lie in the lead's dprune
@@ -199,7 +196,7 @@ struct gpx_handle {
 #endif
     int prune_rows = -1;      // diagnostic option: block rows of the second bound's row prefix (-1 by size: nP / 4, 0 never, n > 0: min(n, nP, N / 128) wherever the first level pruned)
     int short_map = -1;       // diagnostic option: the short form of tile map 3 (sweep_map.h) -1 by size (launches that cannot fill the per-XCD patches), 0 never, 1 always
-    char* dkeep = nullptr;    // [ub M][seed idx G][dots M]
+    char* dkeep = nullptr;    // the diagnostic copies (keep_ws)
     int64_t cap_keep = 0;     // ... in bytes
 
     // sweep cache (warm BO step): candidates and their reduced sums q = colsum(V^2), p = V^T a of the last full
@@ -213,7 +210,7 @@ struct gpx_handle {
     double* dcp = nullptr;
     int64_t cap_cz = 0, cap_cq = 0;
     // appended observations whose cache correction is still due (applied together, at most PEND_MAX per pass)
-    double* dpend = nullptr;     // [PEND_MAX][pend_ld] weight rows, then [PEND_MAX][2] {1/d, a_new}
+    double* dpend = nullptr;     // the queued weight rows of pitch pend_ld and their scalars (pend_ws)
     int64_t pend_ld = 0;
     int npend = 0;
 
@@ -225,23 +222,22 @@ struct gpx_handle {
     bool apply_pending = false;  // ... whose q += v^2, p += v a is still due (applied by flush_pending)
     uint64_t gen = 0, spec_gen = 0;      // model generation (fit / append / grow) now and at the announcement
     std::vector<double> spec_x;  // the announced point (host copy, compared bit for bit)
-    double* dspec = nullptr;     // [x xpad][xs xpad][ks Np][g Np][r Np][tu Np][row ldw][pscal 2 + scal 16][v M]
+    double* dspec = nullptr;     // the announcement's buffers (spec_ws)
     int64_t cap_spec = 0, spec_ld = 0, spec_M = 0;
     hipEvent_t ev_spec_go = nullptr, ev_spec_done = nullptr;
 
-    // batch proposals (gpx_sweep_batch): scratch of its own, laid out in api.hip -- nothing the append / announcement paths own
+    // batch proposals (gpx_sweep_batch): scratch of its own (batch_ws) -- nothing the append / announcement paths own
     double* dbsel = nullptr;
     int64_t cap_bsel = 0;
     std::vector<gpx::EnsBatchMember> bsel_desc;   // host source of the lead's descriptor table (gpx_ensemble_sweep_batch): outlives its copy
 
-    // joint posterior (gpx_predict_cov / gpx_sample_joint): scratch of its own, laid out in api.hip (joint_core); the cross-Gram
-    // of the points goes through dKs like a sweep's
+    // joint posterior (gpx_predict_cov / gpx_sample_joint): scratch of its own (joint_ws); the cross-Gram of the points goes
+    // through dKs like a sweep's
     double* djoint = nullptr;
     int64_t cap_joint = 0;
 
-    // knowledge gradient (GPX_ACQ_KG, gpx_kg_grad; kernels_kg.hip): the prepared support set -- [A raw 128 d][As scaled 128 d][a_j 128]
-    // [B Np 128][V_A Np 128][Pp nP 128], laid out in api.hip (kg_prepare) -- kept while the model (gen) and the set (kg_A) stay what
-    // they were, and work space of a sweep (C: 128 x chunk) or of gpx_kg_grad's point panels
+    // knowledge gradient (GPX_ACQ_KG, gpx_kg_grad; kernels_kg.hip): the prepared support set (kg_ws), kept while the model (gen) and
+    // the set (kg_A) stay what they were, and work space of a sweep (C: 128 x chunk) or of gpx_kg_grad's point panels (kg_point_ws)
     double* dkg = nullptr;
     int64_t cap_kg = 0;
     double* dkgw = nullptr;
@@ -250,9 +246,9 @@ struct gpx_handle {
     uint64_t kg_gen = 0;
     int64_t kg_Np = 0;
 
-    double* dbatch = nullptr;    // gpx_loglik_batch: Gram / factor / scaled inputs / a of the batch (one allocation)
+    double* dbatch = nullptr;    // gpx_loglik_batch: one allocation (loglik_batch_ws)
     int64_t cap_batch = 0;
-    double* dhyper = nullptr;    // gpx_loglik_grad: the tiles' partial sums [tiles][d + 2], then [L, d + 3 components] (on first use)
+    double* dhyper = nullptr;    // gpx_loglik_grad: the tiles' partial sums and the result (hyper_ws; on first use)
     int64_t cap_hyper = 0;
 
     // timers
@@ -262,6 +258,13 @@ struct gpx_handle {
 };
 
 namespace gpx {
+
+// The grow-only allocation behind every workspace (api.hip): on GPX_OK p holds at least `need` elements; a buffer that has to grow is freed
+// first (hipFree waits for the whole device).  `what`: "<what>: device allocation failed" with GPX_EOOM; without it the HIP call and its error.
+int ensure_bytes(gpx_handle* h, void** p, int64_t* cap, int64_t need, size_t elem, const char* what);
+template <typename T> inline int ensure(gpx_handle* h, T*& p, int64_t& cap, int64_t need, const char* what = nullptr) {
+    return ensure_bytes(h, reinterpret_cast<void**>(&p), &cap, need, sizeof(T), what);
+}
 
 // launchers (kernels_fit.hip)
 void launch_scale_x(hipStream_t s, const double* X, int64_t n, int64_t np, int d, const double* invell,
@@ -336,7 +339,6 @@ void launch_topk(hipStream_t s, const double* vals, int64_t M, int k, double* bl
 void launch_topk_merge(hipStream_t s, double* vals, int64_t* idx, int64_t n, int k, double* topv, int64_t* topi);
 void launch_topk_rows(hipStream_t s, const double* vals, int64_t M, int64_t S, int k, double* blkv, int64_t* blki,
                       int64_t nblk, double* topv, int64_t* topi);
-int64_t topk_blocks(int64_t M);
 // selection-only sweeps: weights and error bound of the bound pass, the bound itself, radix select of the G-th largest
 // bound, stable compaction (mode 0: seeds by the selected threshold st[2]; mode 1: survivors of the cut *tau), scatter
 void launch_prune_alpha(hipStream_t s, const double* U, int64_t Np, const double* a, double rho, double bias, double* alpha2,
@@ -349,9 +351,7 @@ constexpr int BM_SC_RX2 = 6, BM_SC_RZ2 = 7, BM_SC_GUARD = 8, BM_SC_USE = 9;     
 // (sc[BADW]: 1.0 a weight w outside the range, 0.5 only a scaled weight w' of the factorised form).
 // TPOS32: the fp32 copies' tiles [0, tpos) hold only w >= 0, the rest only w <= 0 (k_bound_aug); FACT32: 1.0 where the factorised walk runs
 constexpr int BM_SC_E32 = 10, BM_SC_BADW = 11, BM_SC_USE32 = 12, BM_SC_FAC32 = 13, BM_SC_FLUSH32 = 14, BM_SC_TPOS32 = 15, BM_SC_FACT32 = 16;
-constexpr int BM_SC_WORDS = 20;            // the words of sc[] (the last ones spare)
 int bound_mfma_ks(int kernel_id, int d);
-int64_t bound_mfma_ws_words(int64_t Np);
 void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
                        const double* Z, int64_t M, const double* invell, int force, bool allow32, bool allow_fact, double* ws, double* sc,
                        double* out);
@@ -372,7 +372,6 @@ void launch_prune_ub_fold(hipStream_t s, const double* dots, double* acc, int64_
 void launch_prune_ub_mean(hipStream_t s, double* acc, int64_t M, int64_t skip, double n);
 void launch_prune_mean(hipStream_t s, const double* v, int64_t n, double* out);
 void launch_sel_threshold(hipStream_t s, const double* v, int64_t M, int G, int* hist, int* st);
-int64_t sel_blocks(int64_t M);
 void launch_sel_compact(hipStream_t s, const double* v, int64_t M, int mode, const int* st, const double* tau, int64_t* blk,
                         int64_t cap, const double* Xc, int d, int64_t* idx, double* Xg, double* tau_seen = nullptr);
 void launch_sel_scatter(hipStream_t s, const int64_t* idx, const double* vals, int64_t n, double* out, double* mark);
@@ -398,9 +397,8 @@ int append_host(gpx_handle* h, const double* x, double ynew);
 int grow_factor_if_full(gpx_handle* h);
 void launch_append_prepare(gpx_handle* h, hipStream_t s, const double* dx, double* dks, double* dg, double* dr,
                            double* dtu, double resid, double* scal, int* flag);
-// layout of the announcement scratch (pointers into h->dspec)
-struct SpecBuf { double *x, *xs, *ks, *g, *r, *tu, *row, *pscal, *scal, *v; };
-SpecBuf spec_layout(const gpx_handle* h);
+// the announcement's buffers as gpx_append_begin sized them (spec_ld, spec_M)
+inline SpecBuf spec_layout(const gpx_handle* h) { return spec_ws(WsCarver(h->dspec), (h->cap_d + 63) / 64 * 64, h->spec_ld, h->spec_M); }
 int rff_grad_host(gpx_handle* h, const double* W, const double* b, const double* theta, int64_t n, int64_t d,
                   double bias, const double* Xc, int64_t M, double* f, double* g);
 

@@ -1098,27 +1098,10 @@ static int loglik_batch_chunk(gpx_handle* h, int64_t B, const double* hyp, doubl
     }
     if (hipSetDevice(h->device) != hipSuccess) { h->err = "hipSetDevice failed"; return GPX_EHIP; }
     hipStream_t s = h->stream;
-    // one allocation: [S B bs][R B bs][Xs B Np d][a B Np][hyp 3B][invell B DMAX][out B][flag B ints]
-    const int64_t need = 2 * B * bs + B * Np * d + 2 * B * Np + B * (3 + DMAX) + 3 * B + (B + 1) / 2 + 8;
-    if (need > h->cap_batch) {
-        if (h->dbatch) hipFree(h->dbatch);
-        h->dbatch = nullptr;
-        h->cap_batch = 0;
-        if (hipMalloc((void**)&h->dbatch, (size_t)need * 8) != hipSuccess) { h->err = "loglik_batch: device allocation failed"; return GPX_EOOM; }
-        h->cap_batch = need;
-    }
-    double* bS = h->dbatch;
-    double* bR = bS + B * bs;
-    double* bXs = bR + B * bs;
-    double* ba = bXs + B * Np * d;
-    double* bhyp = ba + B * Np;
-    double* binv = bhyp + 3 * B;
-    double* bout = binv + B * DMAX;
-    double* br = bout + B;                     // (large factors) the running right-hand sides, B x Np
-    double* bacc = br + B * Np;                // ... and {a.a, sum log R_ii} per vector
-    int* bflag = reinterpret_cast<int*>(bacc + 2 * B);
-    if (hipMemcpyAsync(bhyp, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemsetAsync(bflag, 0, (size_t)B * sizeof(int), s) != hipSuccess) {
+    if (int rc = ensure(h, h->dbatch, h->cap_batch, loglik_batch_ws(WsCarver(nullptr), B, Np, d).bytes / 8, "loglik_batch")) return rc;
+    const LoglikBatchWs bw = loglik_batch_ws(WsCarver(h->dbatch), B, Np, d);
+    if (hipMemcpyAsync(bw.hyp, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemsetAsync(bw.flag, 0, (size_t)B * sizeof(int), s) != hipSuccess) {
         h->err = "loglik_batch: H2D copy failed";
         return GPX_EHIP;
     }
@@ -1126,10 +1109,10 @@ static int loglik_batch_chunk(gpx_handle* h, int64_t B, const double* hyp, doubl
     {
         const int64_t tot = Np * d;
         hipLaunchKernelGGL(k_scale_x, dim3((unsigned)((tot + 255) / 256), 1, Bz), dim3(256), 0, s, h->dXraw, N, Np,
-                           (int)d, binv, bXs);
+                           (int)d, bw.invell, bw.Xs);
         const unsigned g = (unsigned)(Np / GT);
-        hipLaunchKernelGGL(k_gram_sym, dim3(g, g, Bz), dim3(256), 0, s, bXs, N, Np, (int)d, h->kernel_id, 1.0, 0.0, bS,
-                           (const double*)bhyp);
+        hipLaunchKernelGGL(k_gram_sym, dim3(g, g, Bz), dim3(256), 0, s, bw.Xs, N, Np, (int)d, h->kernel_id, 1.0, 0.0, bw.S,
+                           (const double*)bw.hyp);
     }
     // LARGE factors (round 5; the reference's default model at BASELINE scale, pybo/bayesopt.py:115): the persistent task-graph
     // kernel, vector after vector, on the batch's buffers (the 16 x 16 inverses land in the dead diagonal tiles of the Gram
@@ -1148,9 +1131,9 @@ static int loglik_batch_chunk(gpx_handle* h, int64_t B, const double* hyp, doubl
         if (s_ahead != 0 && h->stream2) (void)hipStreamSynchronize(h->stream2);
         h->want_ahead = false;
         for (int64_t b = 0; b < B && big; ++b) {
-            h->dS = bS + b * bs; h->dR = bR + b * bs; h->dT = nullptr; h->dU = bS + b * bs;
+            h->dS = bw.S + b * bs; h->dR = bw.R + b * bs; h->dT = nullptr; h->dU = bw.S + b * bs;
             const bool ok = launch_cholesky_tg(h);
-            if (ok) (void)hipMemcpyAsync(bflag + b, h->dflag, sizeof(int), hipMemcpyDeviceToDevice, s);
+            if (ok) (void)hipMemcpyAsync(bw.flag + b, h->dflag, sizeof(int), hipMemcpyDeviceToDevice, s);
             if (!ok || hipStreamSynchronize(s) != hipSuccess || tg_abort_code(h) == 2) big = false;
         }
         h->dS = sS; h->dR = sR; h->dT = sT; h->dU = sU;
@@ -1160,21 +1143,21 @@ static int loglik_batch_chunk(gpx_handle* h, int64_t B, const double* hyp, doubl
         (void)hipMemsetAsync(h->dflag, 0, 2 * sizeof(int), s);
         if (!big) {
             (void)hipGetLastError();
-            (void)hipMemsetAsync(bflag, 0, (size_t)B * sizeof(int), s);
+            (void)hipMemsetAsync(bw.flag, 0, (size_t)B * sizeof(int), s);
             const unsigned g = (unsigned)(Np / GT);
-            hipLaunchKernelGGL(k_gram_sym, dim3(g, g, Bz), dim3(256), 0, s, bXs, N, Np, (int)d, h->kernel_id, 1.0, 0.0, bS,
-                               (const double*)bhyp);
+            hipLaunchKernelGGL(k_gram_sym, dim3(g, g, Bz), dim3(256), 0, s, bw.Xs, N, Np, (int)d, h->kernel_id, 1.0, 0.0, bw.S,
+                               (const double*)bw.hyp);
         }
     }
     if (big) {
-        hipLaunchKernelGGL(k_fwd_init, dim3((unsigned)((Np + 255) / 256), Bz), dim3(256), 0, s, h->dy, bhyp, N, Np, br, bacc);
+        hipLaunchKernelGGL(k_fwd_init, dim3((unsigned)((Np + 255) / 256), Bz), dim3(256), 0, s, h->dy, bw.hyp, N, Np, bw.r, bw.acc);
         for (int p = 0; p < nP; ++p) {
-            hipLaunchKernelGGL(k_fwd_diag, dim3(Bz), dim3(128), 0, s, bR, bS, bs, Np, N, p, p == nP - 1 ? 1 : 0, bflag, br, ba,
-                               bacc, bout);
+            hipLaunchKernelGGL(k_fwd_diag, dim3(Bz), dim3(128), 0, s, bw.R, bw.S, bs, Np, N, p, p == nP - 1 ? 1 : 0, bw.flag, bw.r, bw.a,
+                               bw.acc, bw.out);
             if (p + 1 < nP)
-                hipLaunchKernelGGL(k_fwd_update, dim3((unsigned)(nP - 1 - p), Bz), dim3(256), 0, s, bR, bs, Np, p, bflag, ba, br);
+                hipLaunchKernelGGL(k_fwd_update, dim3((unsigned)(nP - 1 - p), Bz), dim3(256), 0, s, bw.R, bs, Np, p, bw.flag, bw.a, bw.r);
         }
-        if (hipMemcpyAsync(out, bout, (size_t)B * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        if (hipMemcpyAsync(out, bw.out, (size_t)B * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
             h->err = "loglik_batch: kernel or D2H copy failed";
             return GPX_EHIP;
@@ -1187,21 +1170,21 @@ static int loglik_batch_chunk(gpx_handle* h, int64_t B, const double* hyp, doubl
         const int P1 = (P0 + CHOL_W < nP) ? P0 + CHOL_W : nP;
         for (int I = P0; I < P1; ++I) {
             if (I > P0)
-                hipLaunchKernelGGL(k_row_update64, dim3((unsigned)(2 * (nP - I)), 2, Bz), dim3(GEMM64_THREADS), 0, s, bR, bS,
+                hipLaunchKernelGGL(k_row_update64, dim3((unsigned)(2 * (nP - I)), 2, Bz), dim3(GEMM64_THREADS), 0, s, bw.R, bw.S,
                                    Np, P0, I, I, bs, nP, 0);
-            hipLaunchKernelGGL(k_potrf16<false>, dim3(1, 1, Bz), dim3(256), 0, s, bS, bR, (double*)nullptr, bS, Np, I,
-                               bflag, (long long*)nullptr, bs);
+            hipLaunchKernelGGL(k_potrf16<false>, dim3(1, 1, Bz), dim3(256), 0, s, bw.S, bw.R, (double*)nullptr, bw.S, Np, I,
+                               bw.flag, (long long*)nullptr, bs);
             const int rem = nP - 1 - I;
             if (rem > 0)
-                hipLaunchKernelGGL(k_panel_solve16, dim3((unsigned)(2 * rem), 1, Bz), dim3(256), 0, s, bS, bS, bR, Np, I,
-                                   bflag, bs);
+                hipLaunchKernelGGL(k_panel_solve16, dim3((unsigned)(2 * rem), 1, Bz), dim3(256), 0, s, bw.S, bw.S, bw.R, Np, I,
+                                   bw.flag, bs);
         }
         if (P1 < nP)
             hipLaunchKernelGGL(k_syrk_update, dim3((unsigned)(nP - P1), (unsigned)(nP - P1), Bz), dim3(GEMM_THREADS), 0, s,
-                               bR, bS, Np, P0, P1, P1, P1, bs);
+                               bw.R, bw.S, Np, P0, P1, P1, P1, bs);
     }
-    hipLaunchKernelGGL(k_loglik_fwd, dim3(Bz), dim3(256), 0, s, bR, bS, bs, Np, N, h->dy, bhyp, bflag, ba, bout);
-    if (hipMemcpyAsync(out, bout, (size_t)B * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+    hipLaunchKernelGGL(k_loglik_fwd, dim3(Bz), dim3(256), 0, s, bw.R, bw.S, bs, Np, N, h->dy, bw.hyp, bw.flag, bw.a, bw.out);
+    if (hipMemcpyAsync(out, bw.out, (size_t)B * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
         h->err = "loglik_batch: kernel or D2H copy failed";
         return GPX_EHIP;

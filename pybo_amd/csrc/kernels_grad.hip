@@ -23,7 +23,6 @@
 
 namespace gpx {
 
-constexpr int GB = 16;  // candidates per pass over T and U (the 10 lock-step L-BFGS seeds of solve_lbfgs fit in one)
 
 // (k and g = dk/dr2: kern_and_grad, gpx_math.h)
 
@@ -498,23 +497,12 @@ static int predict_grad_enqueue(gpx_handle* h, const double* Xc, int mb, bool me
     const int64_t Np = h->Np, N = h->N;
     const int d = (int)h->d;
     const int64_t per = 2 + 2 * d;
-    // scratch: [Xc GB*d][ks][g][V][w] (GB*Np each) [out GB*per] [part nseg*GB*Np]
     const int nseg = rb_nseg(h, N);
     // sized for the factor's CAPACITY, not its current size: when an append adds a 128-block (Np grows inside cap_np) the
     // scratch must not be re-allocated -- hipFree waits for the whole device, i.e. for the announced correction pass on the
     // third stream (measured: the recommender's first call after a growth stalled 7.5 ms)
     const int64_t Ncap = std::max<int64_t>(Np, h->cap_np);
-    const int64_t need = GB * d + 4 * GB * Ncap + GB * per + (int64_t)rb_nseg(h, Ncap) * GB * Ncap;
-    if (need > h->cap_grad) {
-        if (h->dgrad) hipFree(h->dgrad);
-        h->dgrad = nullptr;
-        h->cap_grad = 0;
-        if (hipMalloc((void**)&h->dgrad, (size_t)need * 8) != hipSuccess) {
-            h->err = "predict: device allocation failed";
-            return GPX_EOOM;
-        }
-        h->cap_grad = need;
-    }
+    if (int rc = ensure(h, h->dgrad, h->cap_grad, grad_ws(WsCarver(nullptr), d, Ncap, rb_nseg(h, Ncap)).bytes / 8, "predict")) return rc;
     if (GB * per > h->cap_hpin) {     // pinned: a pageable destination would make the download synchronous
         if (h->hpin) hipHostFree(h->hpin);
         h->hpin = nullptr;
@@ -531,13 +519,7 @@ static int predict_grad_enqueue(gpx_handle* h, const double* Xc, int mb, bool me
         }
         h->hpin_dev = (double*)dp;
     }
-    double* dX = h->dgrad;
-    double* dks = dX + GB * d;
-    double* dg = dks + GB * Np;
-    double* dV = dg + GB * Np;
-    double* dw = dV + GB * Np;
-    double* dout = dw + GB * Np;
-    double* dpart = dout + GB * per;
+    const GradWs gw = grad_ws(WsCarver(h->dgrad), d, Np, nseg);      // (the current size: what the allocation holds beyond it lies idle)
     const unsigned rows4 = (unsigned)((Np + 3) / 4);
     if (one_pass && !mean_only) {
         // [ks] holds the mb (1 + d) right-hand sides, one pass over T, U untouched.  A single point travels in the kernel
@@ -547,16 +529,16 @@ static int predict_grad_enqueue(gpx_handle* h, const double* Xc, int mb, bool me
         XArg xa;
         if (direct) {
             for (int k = 0; k < d; ++k) xa.v[k] = Xc[k];
-        } else if (hipMemcpyAsync(dX, Xc, (size_t)mb * d * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
+        } else if (hipMemcpyAsync(gw.X, Xc, (size_t)mb * d * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
             h->err = "predict: H2D copy failed";
             return GPX_EHIP;
         }
         hipLaunchKernelGGL(k_kstar_d, dim3((unsigned)((Np + 255) / 256), (unsigned)(1 + d), (unsigned)mb), dim3(256), 0, s,
-                           h->dXs, N, Np, d, direct ? (const double*)nullptr : dX, xa, h->dinvell, h->kernel_id, h->rho, dks);
-        launch_tri_matvec_rb(h, s, h->dT, Np, N, dks, nrhs, 0, dpart);
-        hipLaunchKernelGGL(k_grad_reduce_1p, dim3((unsigned)(d + 1), (unsigned)mb), dim3(1024), 0, s, N, Np, d, dks, dpart,
-                           nseg, nrhs, h->da, h->dalpha, h->rho, h->bias, direct ? h->hpin_dev : dout);
-        if (!direct && hipMemcpyAsync(h->hpin, dout, (size_t)mb * per * 8, hipMemcpyDeviceToHost, s) != hipSuccess) {
+                           h->dXs, N, Np, d, direct ? (const double*)nullptr : gw.X, xa, h->dinvell, h->kernel_id, h->rho, gw.ks);
+        launch_tri_matvec_rb(h, s, h->dT, Np, N, gw.ks, nrhs, 0, gw.part);
+        hipLaunchKernelGGL(k_grad_reduce_1p, dim3((unsigned)(d + 1), (unsigned)mb), dim3(1024), 0, s, N, Np, d, gw.ks, gw.part,
+                           nseg, nrhs, h->da, h->dalpha, h->rho, h->bias, direct ? h->hpin_dev : gw.out);
+        if (!direct && hipMemcpyAsync(h->hpin, gw.out, (size_t)mb * per * 8, hipMemcpyDeviceToHost, s) != hipSuccess) {
             h->err = "predict: D2H copy failed";
             return GPX_EHIP;
         }
@@ -569,30 +551,30 @@ static int predict_grad_enqueue(gpx_handle* h, const double* Xc, int mb, bool me
                            h->kernel_id, h->rho, h->dalpha, h->bias, h->hpin_dev);
         return GPX_OK;
     }
-    if (hipMemcpyAsync(dX, Xc, (size_t)mb * d * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
+    if (hipMemcpyAsync(gw.X, Xc, (size_t)mb * d * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
         h->err = "predict: H2D copy failed";
         return GPX_EHIP;
     }
     hipLaunchKernelGGL(k_kstar, dim3((unsigned)((Np + 255) / 256), (unsigned)mb), dim3(256), 0, s, h->dXs,
-                       N, Np, d, dX, h->dinvell, h->kernel_id, h->rho, dks, dg);
+                       N, Np, d, gw.X, h->dinvell, h->kernel_id, h->rho, gw.ks, gw.g);
     if (mean_only) {
         hipLaunchKernelGGL(k_mean_reduce, dim3((unsigned)(d + 1), (unsigned)mb), dim3(256), 0, s, h->dXs, N, Np, d,
-                           dX, h->dinvell, dks, dg, h->dalpha, h->bias, dout);
+                           gw.X, h->dinvell, gw.ks, gw.g, h->dalpha, h->bias, gw.out);
     } else {
         if (h->grad_kernel == 1 || (h->grad_kernel < 0 && rb_call)) {
             const dim3 gs((unsigned)((Np + 255) / 256), (unsigned)mb);
-            launch_tri_matvec_rb(h, s, h->dT, Np, N, dks, mb, 0, dpart);
-            hipLaunchKernelGGL(k_part_sum, gs, dim3(256), 0, s, dpart, Np, mb, nseg, dV);
-            launch_tri_matvec_rb(h, s, h->dU, Np, N, dV, mb, 1, dpart);
-            hipLaunchKernelGGL(k_part_sum, gs, dim3(256), 0, s, dpart, Np, mb, nseg, dw);
+            launch_tri_matvec_rb(h, s, h->dT, Np, N, gw.ks, mb, 0, gw.part);
+            hipLaunchKernelGGL(k_part_sum, gs, dim3(256), 0, s, gw.part, Np, mb, nseg, gw.V);
+            launch_tri_matvec_rb(h, s, h->dU, Np, N, gw.V, mb, 1, gw.part);
+            hipLaunchKernelGGL(k_part_sum, gs, dim3(256), 0, s, gw.part, Np, mb, nseg, gw.w);
         } else {
-            launch_tri_matvec_multi(s, rows4, h->dT, Np, N, dks, mb, 0, dV);
-            launch_tri_matvec_multi(s, rows4, h->dU, Np, N, dV, mb, 1, dw);
+            launch_tri_matvec_multi(s, rows4, h->dT, Np, N, gw.ks, mb, 0, gw.V);
+            launch_tri_matvec_multi(s, rows4, h->dU, Np, N, gw.V, mb, 1, gw.w);
         }
         hipLaunchKernelGGL(k_grad_reduce, dim3((unsigned)(d + 1), (unsigned)mb), dim3(256), 0, s, h->dXs, N, Np,
-                           d, dX, h->dinvell, dg, dV, dw, h->da, h->dalpha, h->rho, h->bias, dout);
+                           d, gw.X, h->dinvell, gw.g, gw.V, gw.w, h->da, h->dalpha, h->rho, h->bias, gw.out);
     }
-    if (hipMemcpyAsync(h->hpin, dout, (size_t)mb * per * 8, hipMemcpyDeviceToHost, s) != hipSuccess) {
+    if (hipMemcpyAsync(h->hpin, gw.out, (size_t)mb * per * 8, hipMemcpyDeviceToHost, s) != hipSuccess) {
         h->err = "predict: D2H copy failed";
         return GPX_EHIP;
     }
@@ -843,22 +825,6 @@ void launch_append_prepare(gpx_handle* h, hipStream_t s, const double* dx, doubl
     launch_tri_matvec_multi(s, rows4, h->dU, Np, N, dr, 1, 1, dtu);
 }
 
-SpecBuf spec_layout(const gpx_handle* h) {
-    const int64_t xpad = (h->cap_d + 63) / 64 * 64, ld = h->spec_ld;
-    SpecBuf b;
-    b.x = h->dspec;
-    b.xs = b.x + xpad;
-    b.ks = b.xs + xpad;
-    b.g = b.ks + ld;
-    b.r = b.g + ld;
-    b.tu = b.r + ld;
-    b.row = b.tu + ld;
-    b.pscal = b.row + ld;
-    b.scal = b.pscal + 2;
-    b.v = b.scal + 16 + 46;          // keeps v 512-byte aligned relative to the base (2 + 16 + 46 = 64 doubles)
-    return b;
-}
-
 int append_host(gpx_handle* h, const double* x, double ynew) {
     if (!h->fitted) { h->err = "append: model is not fitted"; return GPX_ESTATE; }
     if (!x) { h->err = "append: NULL point"; return GPX_EARG; }
@@ -869,24 +835,11 @@ int append_host(gpx_handle* h, const double* x, double ynew) {
     hipStream_t s = h->stream;
     const int64_t Np = h->Np, N = h->N;
     const int d = (int)h->d;
-    // scratch: [x d (padded to a multiple of 64)][ks Np][g Np][r Np][tu Np]
     const int64_t xpad = (d + 63) / 64 * 64;
-    const int64_t need = xpad + 4 * std::max<int64_t>(Np, h->cap_np);      // (capacity: see predict_grad_enqueue)
-    if (need > h->cap_grad) {
-        if (h->dgrad) hipFree(h->dgrad);
-        h->dgrad = nullptr;
-        h->cap_grad = 0;
-        if (hipMalloc((void**)&h->dgrad, (size_t)need * 8) != hipSuccess) {
-            h->err = "append: device allocation failed";
-            return GPX_EOOM;
-        }
-        h->cap_grad = need;
-    }
-    double* dx = h->dgrad;
-    double* dks = dx + xpad;
-    double* dg = dks + Np;
-    double* dr = dg + Np;
-    double* dtu = dr + Np;
+    // (sized for the capacity: see predict_grad_enqueue)
+    if (int rc = ensure(h, h->dgrad, h->cap_grad, append_ws(WsCarver(nullptr), xpad, std::max<int64_t>(Np, h->cap_np)).bytes / 8, "append")) return rc;
+    const AppendWs aw = append_ws(WsCarver(h->dgrad), xpad, Np);
+    double *dx = aw.x, *const dks = aw.ks, *const dg = aw.g, *dr = aw.r, *dtu = aw.tu;
     h->app_w = dtu;                                  // w = U r = K^-1 k(X, x): read by the sweep-cache correction
     if (hipMemsetAsync(h->dflag, 0, sizeof(int), s) != hipSuccess ||
         hipMemcpyAsync(dx, x, (size_t)d * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
@@ -999,31 +952,17 @@ int rff_grad_host(gpx_handle* h, const double* W, const double* b, const double*
     }
     if (hipSetDevice(h->device) != hipSuccess) { h->err = "hipSetDevice failed"; return GPX_EHIP; }
     hipStream_t s = h->stream;
-    const int64_t need = n * d + 2 * n + M * d + M * (d + 1);
-    if (need > h->cap_grad) {
-        if (h->dgrad) hipFree(h->dgrad);
-        h->dgrad = nullptr;
-        h->cap_grad = 0;
-        if (hipMalloc((void**)&h->dgrad, (size_t)need * 8) != hipSuccess) {
-            h->err = "rff_grad: device allocation failed";
-            return GPX_EOOM;
-        }
-        h->cap_grad = need;
-    }
-    double* dW = h->dgrad;
-    double* db = dW + n * d;
-    double* dth = db + n;
-    double* dX = dth + n;
-    double* dout = dX + M * d;
-    bool ok = hipMemcpyAsync(dW, W, (size_t)n * d * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
-              hipMemcpyAsync(db, b, (size_t)n * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
-              hipMemcpyAsync(dth, theta, (size_t)n * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
-              hipMemcpyAsync(dX, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, s) == hipSuccess;
+    if (int rc = ensure(h, h->dgrad, h->cap_grad, rff_grad_ws(WsCarver(nullptr), n, d, M).bytes / 8, "rff_grad")) return rc;
+    const RffGradWs gw = rff_grad_ws(WsCarver(h->dgrad), n, d, M);
+    bool ok = hipMemcpyAsync(gw.W, W, (size_t)n * d * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(gw.b, b, (size_t)n * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(gw.th, theta, (size_t)n * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(gw.X, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, s) == hipSuccess;
     if (!ok) { h->err = "rff_grad: H2D copy failed"; return GPX_EHIP; }
-    hipLaunchKernelGGL(k_rff_grad, dim3((unsigned)M), dim3(256), 0, s, dW, db, dth, (int)n, (int)d, bias, dX,
-                       dout);
+    hipLaunchKernelGGL(k_rff_grad, dim3((unsigned)M), dim3(256), 0, s, gw.W, gw.b, gw.th, (int)n, (int)d, bias, gw.X,
+                       gw.out);
     std::vector<double> host((size_t)M * (d + 1));
-    if (hipMemcpyAsync(host.data(), dout, host.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+    if (hipMemcpyAsync(host.data(), gw.out, host.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
         h->err = "rff_grad: kernel or D2H copy failed";
         return GPX_EHIP;

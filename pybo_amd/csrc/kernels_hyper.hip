@@ -189,28 +189,17 @@ int loglik_grad_host(gpx_handle* h, double* loglik, double* grad) {
     if (int rc0 = ensure_inverse(h)) return rc0;
     const int d = (int)h->d, nP = (int)(h->Np / NB);
     const int64_t ntiles = (int64_t)nP * (nP + 1) / 2;
-    // workspace [tiles][d + 2] slots + [L, d + 3 components], sized for the handle's capacity
-    const int64_t capP = h->cap_np / NB, need = capP * (capP + 1) / 2 * (h->cap_d + 2) + h->cap_d + 4;
-    if (need > h->cap_hyper) {
-        if (h->dhyper) hipFree(h->dhyper);
-        h->dhyper = nullptr;
-        h->cap_hyper = 0;
-        if (hipMalloc((void**)&h->dhyper, (size_t)need * 8) != hipSuccess) {
-            h->err = "loglik_grad: device allocation failed";
-            return GPX_EOOM;
-        }
-        h->cap_hyper = need;
-    }
-    double* part = h->dhyper;
-    double* res = part + ntiles * (d + 2);
+    const int64_t capP = h->cap_np / NB;             // sized for the handle's capacity
+    if (int rc = ensure(h, h->dhyper, h->cap_hyper, hyper_ws(WsCarver(nullptr), capP * (capP + 1) / 2, h->cap_d).bytes / 8, "loglik_grad")) return rc;
+    const HyperWs hw = hyper_ws(WsCarver(h->dhyper), ntiles, d);
     hipStream_t s = h->stream;
     hipLaunchKernelGGL(k_loglik_grad_tiles, dim3((unsigned)ntiles), dim3(GEMM_THREADS), 0, s, h->dT, h->Np, nP, h->N, h->dXs, d,
-                       h->dalpha, h->kernel_id, h->rho, part);
-    hipLaunchKernelGGL(k_loglik_grad_reduce, dim3((unsigned)(d + 3)), dim3(256), 0, s, part, ntiles, d, h->dalpha, h->N, h->rho,
-                       h->dinvell, res);
-    launch_loglik(h, res);
+                       h->dalpha, h->kernel_id, h->rho, hw.part);
+    hipLaunchKernelGGL(k_loglik_grad_reduce, dim3((unsigned)(d + 3)), dim3(256), 0, s, hw.part, ntiles, d, h->dalpha, h->N, h->rho,
+                       h->dinvell, hw.res);
+    launch_loglik(h, hw.res);
     std::vector<double> host((size_t)d + 4);
-    if (hipMemcpyAsync(host.data(), res, host.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+    if (hipMemcpyAsync(host.data(), hw.res, host.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
         h->err = "loglik_grad: kernel or D2H copy failed";
         return GPX_EHIP;

@@ -606,8 +606,6 @@ void launch_sweep_rankq(hipStream_t s, const double* Xs, int64_t Ntot, int d, co
 // ------------------------------------------------------------------------------------------------
 // top-k: value descending, ties -> lower index; NaN ranks below everything.
 // ------------------------------------------------------------------------------------------------
-constexpr int TK_PER_THREAD = 16;
-constexpr int TK_PER_BLOCK = 256 * TK_PER_THREAD;
 #define GPX_NEG_INF (-__builtin_huge_val())
 #define GPX_IDX_NONE ((int64_t)0x7fffffffffffffffLL)
 
@@ -716,7 +714,6 @@ void launch_topk_merge(hipStream_t s, double* vals, int64_t* idx, int64_t n, int
     hipLaunchKernelGGL(k_topk_merge, dim3(1), dim3(256), 0, s, vals, idx, n, k, topv, topi);
 }
 
-int64_t topk_blocks(int64_t M) { return (M + TK_PER_BLOCK - 1) / TK_PER_BLOCK; }
 
 // The k <= TOPK_PASS best of EACH of S value rows (row q at vals + q M) in two launches instead of 2 S (a Thompson sweep of
 // 64 draws ranked its rows one after the other: 128 launches of 5 us).  blkv / blki: S * nblk * k entries; topv / topi: (S, k).
@@ -820,7 +817,6 @@ void launch_prune_alpha(hipStream_t s, const double* U, int64_t Np, const double
 // The inner-product form cancels where the direct differences do not; sc[] carries the radii of the centred data and the
 // guard k_bound_guard derives from them: sc[9] = 1.0 says this kernel runs, 0.0 says k_sweep_rankq<1> does (both read it).
 // ------------------------------------------------------------------------------------------------
-constexpr int BM_KS_MAX = 5;               // d + 2 <= 20: the candidates' fragments stay in registers (8 KS doubles per lane)
 int bound_mfma_ks(int kernel_id, int d) { return (kernel_id == GPX_KERN_SE_ARD && d + 2 <= 4 * BM_KS_MAX) ? (d + 5) / 4 : 0; }
 
 // the norms go through the accumulator where that saves an MFMA per tile; the k-steps of the kernel either way
@@ -1115,34 +1111,27 @@ __global__ __launch_bounds__(256, (KS + (NC ? 1 : 0) <= 3) ? 4 : 3) void k_bound
     }
 }
 
-// Prologue, guard and the matrix-pipe kernels on stream s.  ws: [A Np x 4 KS][W4 Np][NX4 Np, where the norms go through the accumulator:
-// KS <= 4 there][cen 4 BM_KS_MAX at its fixed place][the fp32 copies, Np + 16 rows: A x 4 KS, W, W', NX floats]; sc: the bound pass's BM_SC_WORDS scalars.
+// Prologue, guard and the matrix-pipe kernels on stream s.  ws: the operands' block (bound_ops); sc: the bound pass's BM_SC_WORDS scalars.
 // force: the option prune_bound (-1, 1, 2); allow32: the host's size rule lets the fp32 link run by its guards; allow_fact: option bound_fact.
 // The caller launches the generic kernel behind it with sc + BM_SC_USE as its `skip`: exactly one of the three writes `out`.
-int64_t bound_mfma_ws_words(int64_t Np) { return Np * 4 * BM_KS_MAX + Np + 4 * BM_KS_MAX + (Np + B32_ZROWS) * (2 * BM_KS_MAX + 2); }
-
 void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, int d, const double* alpha2, double rho,
                        const double* Z, int64_t M, const double* invell, int force, bool allow32, bool allow_fact, double* ws, double* sc,
                        double* out) {
     const int KS = bound_mfma_steps(d);
     const bool nc = bound_mfma_normc(d);
-    double* A = ws;
-    double* W4 = A + Np * 4 * KS;
-    double* NX4 = nc ? W4 + Np : nullptr;
-    double* cen = ws + Np * 4 * BM_KS_MAX + Np;
+    WsCarver c(ws);
+    const BoundOps o = bound_ops(c, Np, KS, nc);
     const bool want32 = force == 2 || (force < 0 && allow32);
-    float* A32 = want32 ? reinterpret_cast<float*>(cen + 4 * BM_KS_MAX) : nullptr;
     const int64_t Np32 = Np + B32_ZROWS;
-    const float* W32 = want32 ? A32 + Np32 * 4 * KS : nullptr;
-    const float* WF32 = want32 ? W32 + Np32 : nullptr;
-    const float* NX32 = (want32 && nc) ? WF32 + Np32 : nullptr;
-    hipLaunchKernelGGL(k_bound_centre, dim3(1), dim3(256), 0, s, Xs, N, d, cen, sc);
-    hipLaunchKernelGGL(k_bound_aug, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, Xs, N, Np, d, KS, cen, alpha2, rho, A, W4, NX4, A32, sc);
-    hipLaunchKernelGGL(k_bound_rz, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, Z, M, d, invell, cen, sc);
+    float* const A32 = want32 ? o.A32 : nullptr;
+    const float *const W32 = want32 ? o.W32 : nullptr, *const WF32 = want32 ? o.WF32 : nullptr, *const NX32 = want32 ? o.NX32 : nullptr;
+    hipLaunchKernelGGL(k_bound_centre, dim3(1), dim3(256), 0, s, Xs, N, d, o.cen, sc);
+    hipLaunchKernelGGL(k_bound_aug, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, Xs, N, Np, d, KS, o.cen, alpha2, rho, o.A, o.W4, o.NX4, A32, sc);
+    hipLaunchKernelGGL(k_bound_rz, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, Z, M, d, invell, o.cen, sc);
     hipLaunchKernelGGL(k_bound_guard, dim3(1), dim3(1), 0, s, d, Np, force, want32 ? 1 : 0, allow_fact ? 1 : 0, rho, sc);
     const dim3 grid((unsigned)((M + XN - 1) / XN));
     const int ntile = (int)(Np / 16);
-#define GPX_BM(K, C) hipLaunchKernelGGL((k_bound_mfma<K, C>), grid, dim3(256), 0, s, A, W4, NX4, ntile, d, Z, M, invell, cen, sc, out)
+#define GPX_BM(K, C) hipLaunchKernelGGL((k_bound_mfma<K, C>), grid, dim3(256), 0, s, o.A, o.W4, o.NX4, ntile, d, Z, M, invell, o.cen, sc, out)
     switch (2 * KS + (nc ? 1 : 0)) {
         case 2: GPX_BM(1, false); break;
         case 3: GPX_BM(1, true); break;
@@ -1156,7 +1145,7 @@ void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, i
     }
 #undef GPX_BM
     if (!want32) return;
-    launch_bound_mfma32(s, A32, W32, WF32, NX32, KS, nc, (int)(Np32 / 16), d, Z, M, invell, cen, sc, out);
+    launch_bound_mfma32(s, A32, W32, WF32, NX32, KS, nc, (int)(Np32 / 16), d, Z, M, invell, o.cen, sc, out);
 }
 
 // ub[n] <- EI((bias + dots[n]) + delta, s2 = rho), dots[n] = alpha2 . k(X, z_n), by k_acq's own function; -inf for the `skip`
@@ -1271,9 +1260,6 @@ void launch_prune_mean(hipStream_t s, const double* v, int64_t n, double* out) {
 }
 
 // Order-preserving 24-bit key of a double (sign, exponent, 12 mantissa bits): a <= b implies key(a) <= key(b).
-constexpr int SEL_BINS = 4096;
-constexpr int SEL_PER_THREAD = 16;
-constexpr int SEL_PER_BLOCK = 256 * SEL_PER_THREAD;
 __device__ __forceinline__ unsigned sel_key24(double v) {
     unsigned long long b = (unsigned long long)__double_as_longlong(v);
     b ^= (b >> 63) ? ~0ull : 0x8000000000000000ull;
@@ -1445,7 +1431,6 @@ __global__ __launch_bounds__(256) void k_sel_write(const double* __restrict__ v,
     }
 }
 
-int64_t sel_blocks(int64_t M) { return (M + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK; }
 
 // count only (total -> blk[nblk]) and the offsets the write needs.  tau_seen (optional): the survivor pass leaves the tau it cut
 // with there -- one store by one thread, read only by gpx_prune_report; the shipping path carries it so that the diagnostic adds no

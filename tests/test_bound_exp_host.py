@@ -73,7 +73,7 @@ def test_the_kernel_includes_the_header_the_check_includes():
     """One definition: kernels_sweep.hip and the host program include bound_exp.h; the kernel calls it and not exp_nonpos."""
     ksrc = open(os.path.join(ROOT, 'pybo_amd', 'csrc', 'kernels_sweep.hip')).read()
     assert '#include "bound_exp.h"' in ksrc and 'double bound_exp(' not in ksrc
-    body = ksrc[ksrc.index('void k_bound_mfma('):ksrc.index('int64_t bound_mfma_ws_words(')]
+    body = ksrc[ksrc.index('void k_bound_mfma('):ksrc.index('void launch_bound_mfma(')]
     assert 'bound_exp<false>(' in body and 'exp_nonpos(' not in body
     assert '#include "../../pybo_amd/csrc/bound_exp.h"' in open(SRC).read()
     hdr = open(os.path.join(ROOT, 'pybo_amd', 'csrc', 'bound_exp.h')).read()
