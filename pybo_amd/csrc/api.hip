@@ -13,6 +13,7 @@
 
 #include "gpx_internal.h"
 #include "gpx_diag.h"
+#include "acq_core.h"
 #include "mes_math.h"
 #include "kg_math.h"
 
@@ -984,7 +985,7 @@ extern "C" int gpx_var_at_obs(gpx_handle* h, double* s2_host) {
         // s2_i = sn2 - sn2^2 [K^-1]_ii  (latent variance at observed input i), clipped like the sweep's
         for (int64_t i = 0; i < N; ++i) {
             const double v = h->sn2 * (1.0 - h->sn2 * s2_host[i]);
-            s2_host[i] = v > 1e-100 ? v : 1e-100;
+            s2_host[i] = v > gpx::S2_FLOOR ? v : gpx::S2_FLOOR;
         }
         return GPX_OK;
     });
@@ -1325,7 +1326,7 @@ static int second_bound(gpx_handle* h, const PruneWs& w, int64_t chunk, int swee
             // 4a. rows [0, nR 128) of the survivors' cross-Gram panels and the sweep's tiles of those block rows
             launch_cross_gram(s, h->dXs, (int64_t)nR * NB, h->N, (int)h->d, w.Xg, j0, nsurv, cols, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
             launch_sweep_trmm(s, h->dU, Np, nR, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk, h->short_map);
-            // 4b. ub2 = EI((bias + dot) + delta, fmax(rho - q_R, 1e-100))
+            // 4b. ub2 = EI((bias + dot) + delta, fmax(rho - q_R, S2_FLOOR))
             launch_prune_ub2(s, h->dQp, chunk, nR, j0, valid, w.idx, w.dots, w.sc, h->rho, h->bias, p0, w.ub2, h->prune_keep ? w.qR : nullptr);
         }
     }
@@ -1469,7 +1470,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     };
     ops.refine = [&](SelectList& list) -> int { return second_bound(h, w, chunk, sweep_order, p0, list); };
     int64_t done = 0;
-    const bool legal = !h->cache_on && h->rho >= 1e-100 && h->rho < INFINITY;
+    const bool legal = !h->cache_on && h->rho >= gpx::S2_FLOOR && h->rho < INFINITY;
     if ((rc = select_topk_pruned(h, legal, selection_only, acq_id, 1, nP, Np, dXc, M, k, 0, true, w, h->prune_hint, rec, d_acq, ops, &done)))
         return rc;
     if ((rc = plain_rest(ops, dXc, done, chunk, M, d_acq, d_mu, d_s2))) return rc;
@@ -2095,7 +2096,7 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
     for (int m = 0; m < n; ++m) {
         nPmax = std::max(nPmax, (int)(mem[m]->Np / NB));
         Np_min = std::min(Np_min, mem[m]->Np);
-        members_ok = members_ok && !mem[m]->cache_on && mem[m]->rho >= 1e-100 && mem[m]->rho < INFINITY;
+        members_ok = members_ok && !mem[m]->cache_on && mem[m]->rho >= gpx::S2_FLOOR && mem[m]->rho < INFINITY;
     }
     const int64_t d = L->d;
     hipStream_t s = L->stream;

@@ -15,7 +15,7 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-const-variable $EXTRA"
 SRCS="kernels_fit kernels_chol_tg kernels_sweep kernels_mes kernels_kg kernels_rff kernels_grad kernels_hyper kernels_ens kernels_batch kernels_cov comm api"
-HDRS="bound_exp.h bound_f32.h gemm_core.h sweep_map.h gpx_internal.h ws_layout.h prune_hint.h gpx_diag.h gpx_math.h mes_math.h kg_math.h fit_tiles.h ../../include/gpx.h"
+HDRS="acq_core.h acq_core_dev.h bound_exp.h bound_f32.h gemm_core.h sweep_map.h gpx_internal.h ws_layout.h prune_hint.h gpx_diag.h gpx_math.h mes_math.h kg_math.h fit_tiles.h ../../include/gpx.h"
 FORCE=0
 [ "$1" = "--force" ] && FORCE=1
 pids=()

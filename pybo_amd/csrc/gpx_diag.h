@@ -88,7 +88,7 @@ int gpx_prune_dots(gpx_handle *h, double *dots);
 
 /* The second bound of the last sweep, only after a sweep with the option prune_keep = 1 that ran it (path 2 with nR > 0; GPX_ESTATE
  * otherwise), aligned with the first-level list `idx` of gpx_prune_report: ub2 (optional, nsurv) = EI((bias + dot) + delta,
- * max(rho - qR, 1e-100));  qR (optional, nsurv) = the sum of V^2 over the leading nR block rows, added block by block as the exact
+ * max(rho - qR, S2_FLOOR));  qR (optional, nsurv) = the sum of V^2 over the leading nR block rows, added block by block as the exact
  * chain adds them;  idx2 (optional, cap_idx2): the first min(nsurv2, cap_idx2) candidates that survived the second cut, in order.
  * (An entry point of its own, so that gpx_prune_report keeps the signature its callers were built against.) */
 int gpx_prune_rows(gpx_handle *h, double *qR, double *ub2, int64_t *idx2, int64_t cap_idx2);

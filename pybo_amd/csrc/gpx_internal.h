@@ -361,7 +361,7 @@ void launch_bound_mfma32(hipStream_t s, const float* A32, const float* W32, cons
                          const double* Z, int64_t M, const double* invell, const double* cen, const double* sc, double* out);
 void launch_prune_ub(hipStream_t s, const double* dots, double* ub, int64_t M, int64_t skip, const double* sc, double rho,
                      double bias, double p0);
-// the second bound: ub2[j0 + n] = EI((bias + dots[idx[j0 + n]]) + delta, fmax(rho - sum_{rb < nR} Qp[rb][n], 1e-100)) for the chunk's
+// the second bound: ub2[j0 + n] = EI((bias + dots[idx[j0 + n]]) + delta, fmax(rho - sum_{rb < nR} Qp[rb][n], S2_FLOOR)) for the chunk's
 // cols_valid survivors (qR_out, optional: the sums); idx2[j] <- idx[idx2[j]] after the second cut's compaction of list positions
 void launch_prune_ub2(hipStream_t s, const double* Qp, int64_t ldp, int nR, int64_t j0, int64_t cols_valid, const int64_t* idx,
                       const double* dots, const double* sc, double rho, double bias, double p0, double* ub2, double* qR_out);

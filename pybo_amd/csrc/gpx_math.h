@@ -134,7 +134,7 @@ __device__ __forceinline__ double norm_pdf(double z) {
 }
 
 // The acquisition value from the posterior moments: the ONE place this arithmetic lives.  k_acq calls it with a candidate's
-// exact moments, the bound pass of a selection-only sweep (k_prune_ub) with an upper bound of the mean and s2 = rho.
+// exact moments (acq_core.h: cand_moments), the bound passes of a selection-only sweep through ei_mean_bound below.
 __device__ __forceinline__ double acq_value(int acq_id, double mu, double s2, double p0) {
     switch (acq_id) {
         case GPX_ACQ_EI: {
@@ -152,6 +152,12 @@ __device__ __forceinline__ double acq_value(int acq_id, double mu, double s2, do
         default:
             return mu;
     }
+}
+
+// The EI mean bound of the pruned sweeps (k_prune_ub, k_prune_ub2, k_prune_ub_fold): EI by k_acq's own function at an upper bound of
+// the mean -- dot = alpha2 . k(X, z), delta = the bound pass's margin, added in this order -- and a variance s2 no smaller than the exact one.
+__device__ __forceinline__ double ei_mean_bound(double bias, double dot, double delta, double s2, double p0) {
+    return acq_value(GPX_ACQ_EI, (bias + dot) + delta, s2, p0);
 }
 
 // (the bound pass's matrix-pipe kernels, kernels_sweep.hip and kernels_bound32.hip)

@@ -1,7 +1,7 @@
 // kernels_batch.hip -- batch proposals (gpx_sweep_batch): nb greedy picks on the live sweep cache, each conditioned on the ones
 // before it at their posterior mean (Kriging believer / GP-BUCB hallucination: the mean stays, the variance shrinks).
 //
-// With q' a scratch copy of the cache's q_n = |V(z_n)|^2, round j scores val_n = acq(bias + p_n, max(rho - q'_n, 1e-100)), picks
+// With q' a scratch copy of the cache's q_n = |V(z_n)|^2, round j scores val_n = acq(bias + p_n, max(rho - q'_n, S2_FLOOR)), picks
 // i_j = argmax over the candidates not picked yet (value descending, index ascending, NaN last: the top-k's order) and, unless
 // it was the last pick, conditions on x = z_{i_j}:
 //     c_n = k(x, z_n) - sum_i w_i k(x_i, z_n) - sum_{l<j} v_l[i_j] v_l[n]     w = K^-1 k(X, x)    d^2 = s2_{i_j} + sn2
@@ -13,62 +13,23 @@
 //   k_batch_score  one pass over the candidates: folds the raw row into v_j and q' (round 0: q' <- q), the next round's values,
 //                  and a per-block argmax partial
 // The argmax runs over a total order and every candidate's arithmetic is its own thread's: results do not depend on the grid.
+// The order, the moments, batch_fold, a pick's scalars and the ensemble's fold and finish are acq_core.h's; block_argmax and the
+// front of the pick kernels (merge_pick) acq_core_dev.h's.
 //
 // The ensemble forms (gpx_ensemble_sweep_batch: n members frozen for the batch, every member conditioned on the pick at ITS OWN
 // posterior mean) keep the recurrence per member -- its own w, d, cross terms, 1/ell, V and q' -- and share the pick:
-//   k_ens_batch_score  one pass with all members inside it: per member batch_fold (k_batch_score's statements), its value (EI / PI)
-//                      or moments (UCB), summed in member order with k_ens_accum's statements and divided once with k_ens_finish's
+//   k_ens_batch_score  one pass with all members inside it: per member batch_fold (as k_batch_score), its value (EI / PI) or
+//                      moments (UCB), summed in member order and divided once by k_ens_accum's and k_ens_finish's functions
 //   k_ens_batch_pick   the pick, the raw x once, and per member s2, d, the cross terms, x / ell_m and sel_s2[m][j]
 //   k_ens_same_grid    the members' caches hold the same candidates, bit for bit (one flag word, read at the call's only sync)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "acq_core_dev.h"
 #include "gpx_internal.h"
 #include "gpx_math.h"
 
 namespace gpx {
-
-#define GPX_NEG_INF (-__builtin_huge_val())
-#define GPX_IDX_NONE ((int64_t)0x7fffffffffffffffLL)
-
-__device__ __forceinline__ bool batch_better(double av, int64_t ai, double bv, int64_t bi) {
-    return (av > bv) || (av == bv && ai < bi);
-}
-
-// argmax of (v, i) over a workgroup of four 64-lane waves; the result is broadcast to every thread
-__device__ __forceinline__ void batch_block_argmax(double& v, int64_t& i, double* sv, int64_t* si) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off);
-        const int64_t oi = __shfl_xor((long long)i, off);
-        if (batch_better(ov, oi, v, i)) { v = ov; i = oi; }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) { sv[w] = v; si[w] = i; }
-    __syncthreads();
-    v = sv[0]; i = si[0];
-#pragma unroll
-    for (int ww = 1; ww < 4; ++ww)
-        if (batch_better(sv[ww], si[ww], v, i)) { v = sv[ww]; i = si[ww]; }
-}
-
-// The fold of round j >= 0, shared by both scoring kernels: vraw = V[j][n] as the rank-1 pass left it, qprev = q'_n.  Stores v_j[n],
-// returns the new q'_n.
-__device__ __forceinline__ double batch_fold(int j, int64_t M, int64_t n, double* __restrict__ V, const double* __restrict__ cross,
-                                             double invd, double vraw, double qprev) {
-#pragma clang fp contract(off)
-    double t = 0.0;
-    for (int l = 0; l < j; ++l) {
-        const double prod = cross[l] * V[(int64_t)l * M + n];
-        t = t + prod;
-    }
-    const double td = t * invd;
-    const double v = vraw - td;
-    V[(int64_t)j * M + n] = v;
-    const double vv = v * v;
-    return qprev + vv;
-}
 
 // j < 0: round 0, q' <- q of the cache.  j >= 0: row j of V holds the rank-1 pass's (k(x, z_n) - w . k(X, z_n)) / d; the cross
 // terms are taken off it in pick order, each product rounded before it is added (no contraction), then divided once by d.
@@ -81,8 +42,8 @@ __global__ __launch_bounds__(256) void k_batch_score(int j, int64_t M, const dou
                                                      double* __restrict__ partv, int64_t* __restrict__ parti) {
     __shared__ double sv[4];
     __shared__ int64_t si[4];
-    double bv = GPX_NEG_INF;
-    int64_t bi = GPX_IDX_NONE;
+    double bv = NEG_INF;
+    int64_t bi = IDX_NONE;
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < M; n += stride) {
         double q;
@@ -92,23 +53,21 @@ __global__ __launch_bounds__(256) void k_batch_score(int j, int64_t M, const dou
             q = batch_fold(j, M, n, V, cross, scal[1], V[(int64_t)j * M + n], qp[n]);
         }
         qp[n] = q;
-        const double mu = bias + cp[n];
-        const double s2 = fmax(rho - q, 1e-100);
-        if (s2_out) s2_out[n] = s2;
+        const CandMoments c = moments_of_sums(q, cp[n], rho, bias);
+        if (s2_out) s2_out[n] = c.s2;
         if (!taken[n]) {
-            double val = acq_value(acq_id, mu, s2, p0);
-            if (val != val) val = GPX_NEG_INF;
-            if (batch_better(val, n, bv, bi)) { bv = val; bi = n; }
+            const double val = nan_last(acq_value(acq_id, c.mu, c.s2, p0));
+            if (better(val, n, bv, bi)) { bv = val; bi = n; }
         }
     }
-    batch_block_argmax(bv, bi, sv, si);
+    block_argmax(bv, bi, sv, si);
     if (threadIdx.x == 0) {
         partv[blockIdx.x] = bv;
         parti[blockIdx.x] = bi;
     }
 }
 
-// scal: [0] d  [1] 1/d  [2] 0 (the `a` slot of launch_pend_store: no value exists)  [3] d^2
+// scal: pick_scalars' four words
 __global__ __launch_bounds__(256) void k_batch_pick(int j, int nblk, const double* __restrict__ partv,
                                                     const int64_t* __restrict__ parti, int64_t M, int d,
                                                     const double* __restrict__ Z, const double* __restrict__ invell,
@@ -117,30 +76,12 @@ __global__ __launch_bounds__(256) void k_batch_pick(int j, int nblk, const doubl
                                                     double* __restrict__ scal, double* __restrict__ cross,
                                                     double* __restrict__ sel_val, int64_t* __restrict__ sel_idx,
                                                     double* __restrict__ sel_s2, unsigned char* __restrict__ taken) {
-    __shared__ double sv[4];
-    __shared__ int64_t si[4];
-    double bv = GPX_NEG_INF;
-    int64_t bi = GPX_IDX_NONE;
-    for (int e = threadIdx.x; e < nblk; e += 256) {
-        const int64_t idx = parti[e];
-        if (idx != GPX_IDX_NONE && batch_better(partv[e], idx, bv, bi)) { bv = partv[e]; bi = idx; }
-    }
-    batch_block_argmax(bv, bi, sv, si);
-    const bool none = (bi == GPX_IDX_NONE) || bi < 0 || bi >= M;      // (cannot happen while nb <= M; never index with it)
-    const int64_t row = none ? 0 : bi;
+    const int64_t row = merge_pick(j, nblk, partv, parti, M, sel_val, sel_idx, taken);
     const int t = threadIdx.x;
     if (t == 0) {
-        const double s2 = fmax(rho - qp[row], 1e-100);
-        const double d2 = s2 + sn2;
-        const double dd = sqrt(d2);
-        sel_val[j] = bv;
-        sel_idx[j] = none ? -1 : bi;
+        const double s2 = s2_floored(rho, qp[row]);
         sel_s2[j] = s2;
-        scal[0] = dd;
-        scal[1] = 1.0 / dd;
-        scal[2] = 0.0;
-        scal[3] = d2;
-        if (!none) taken[row] = 1;
+        pick_scalars(s2, sn2, scal);
     }
     if (t < j) cross[t] = V[(int64_t)t * M + row];
     for (int k = t; k < d; k += 256) {
@@ -151,30 +92,6 @@ __global__ __launch_bounds__(256) void k_batch_pick(int j, int nblk, const doubl
 }
 
 // ---- the ensemble forms ---------------------------------------------------------------------------------------------------
-// k_ens_accum's statements on registers (mode 0: t0 = the member's value; mode 1: t0 = mu_m, t1 = s2_m) ...
-__device__ __forceinline__ void ens_fold(int mode, bool first, double t0, double t1, double& acc0, double& acc1) {
-#pragma clang fp contract(off)
-    if (mode == 0) {
-        acc0 = first ? t0 : acc0 + t0;
-    } else {
-        const double m2 = t0 * t0;
-        const double q = t1 + m2;
-        acc0 = first ? t0 : acc0 + t0;
-        acc1 = first ? q : acc1 + q;
-    }
-}
-
-// ... and k_ens_finish's
-__device__ __forceinline__ double ens_value(int mode, double acc0, double acc1, double n, double beta) {
-#pragma clang fp contract(off)
-    const double mu = acc0 / n;
-    if (mode == 0) return mu;
-    const double mu2 = mu * mu;
-    double s2 = acc1 / n - mu2;
-    s2 = fmax(s2, 0.0);
-    return mu + sqrt(beta * s2);
-}
-
 // One thread per candidate, the members in order inside it.  HBM-bound, n (j + 4) 8 M bytes per round: member m + 1's three
 // streaming loads (q', p, the raw row) are issued before member m's arithmetic, its cross-term rows follow as that retires.
 __global__ __launch_bounds__(256) void k_ens_batch_score(int j, int nmem, int64_t M, const EnsBatchMember* __restrict__ mem,
@@ -182,8 +99,8 @@ __global__ __launch_bounds__(256) void k_ens_batch_score(int j, int nmem, int64_
                                                          double* __restrict__ partv, int64_t* __restrict__ parti) {
     __shared__ double sv[4];
     __shared__ int64_t si[4];
-    double bv = GPX_NEG_INF;
-    int64_t bi = GPX_IDX_NONE;
+    double bv = NEG_INF;
+    int64_t bi = IDX_NONE;
     const int mode = (acq_id == GPX_ACQ_UCB) ? 1 : 0;
     const double nd = (double)nmem;
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -203,20 +120,18 @@ __global__ __launch_bounds__(256) void k_ens_batch_score(int j, int nmem, int64_
             }
             const double q = (j < 0) ? qprev : batch_fold(j, M, n, e.V, e.cross, e.scal[1], vraw, qprev);
             e.qp[n] = q;
-            const double mu = e.bias + p;
-            const double s2 = fmax(e.rho - q, 1e-100);
+            const CandMoments c = moments_of_sums(q, p, e.rho, e.bias);
             if (mode == 0)
-                ens_fold(0, m == 0, acq_value(acq_id, mu, s2, p0), 0.0, acc0, acc1);
+                ens_fold(0, m == 0, acq_value(acq_id, c.mu, c.s2, p0), 0.0, acc0, acc1);
             else
-                ens_fold(1, m == 0, mu, s2, acc0, acc1);
+                ens_fold(1, m == 0, c.mu, c.s2, acc0, acc1);
         }
         if (!taken[n]) {
-            double val = ens_value(mode, acc0, acc1, nd, p0);
-            if (val != val) val = GPX_NEG_INF;
-            if (batch_better(val, n, bv, bi)) { bv = val; bi = n; }
+            const double val = nan_last(ens_value(mode, acc0, acc1, nd, p0));
+            if (better(val, n, bv, bi)) { bv = val; bi = n; }
         }
     }
-    batch_block_argmax(bv, bi, sv, si);
+    block_argmax(bv, bi, sv, si);
     if (threadIdx.x == 0) {
         partv[blockIdx.x] = bv;
         parti[blockIdx.x] = bi;
@@ -230,33 +145,13 @@ __global__ __launch_bounds__(256) void k_ens_batch_pick(int j, int nblk, const d
                                                         const EnsBatchMember* __restrict__ mem, double* __restrict__ x,
                                                         double* __restrict__ sel_val, int64_t* __restrict__ sel_idx,
                                                         double* __restrict__ sel_s2, unsigned char* __restrict__ taken) {
-    __shared__ double sv[4];
-    __shared__ int64_t si[4];
-    double bv = GPX_NEG_INF;
-    int64_t bi = GPX_IDX_NONE;
-    for (int e = threadIdx.x; e < nblk; e += 256) {
-        const int64_t idx = parti[e];
-        if (idx != GPX_IDX_NONE && batch_better(partv[e], idx, bv, bi)) { bv = partv[e]; bi = idx; }
-    }
-    batch_block_argmax(bv, bi, sv, si);
-    const bool none = (bi == GPX_IDX_NONE) || bi < 0 || bi >= M;      // (cannot happen while nb <= M; never index with it)
-    const int64_t row = none ? 0 : bi;
+    const int64_t row = merge_pick(j, nblk, partv, parti, M, sel_val, sel_idx, taken);
     const int t = threadIdx.x;
-    if (t == 0) {
-        sel_val[j] = bv;
-        sel_idx[j] = none ? -1 : bi;
-        if (!none) taken[row] = 1;
-    }
     for (int m = t; m < nmem; m += 256) {
         const EnsBatchMember& e = mem[m];
-        const double s2 = fmax(e.rho - e.qp[row], 1e-100);
-        const double d2 = s2 + e.sn2;
-        const double dd = sqrt(d2);
+        const double s2 = s2_floored(e.rho, e.qp[row]);
         sel_s2[(int64_t)m * nb + j] = s2;
-        e.scal[0] = dd;
-        e.scal[1] = 1.0 / dd;
-        e.scal[2] = 0.0;
-        e.scal[3] = d2;
+        pick_scalars(s2, e.sn2, e.scal);
     }
     for (int c = t; c < nmem * j; c += 256) {
         const int m = c / j, l = c - m * j;

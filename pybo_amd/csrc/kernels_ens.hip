@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "gpx_internal.h"
+#include "acq_core.h"
 
 // Results here are compared bit-for-bit with host arithmetic (numpy): no mul+add contraction into FMA
 // (the default is -ffp-contract=fast; HIP's __dmul_rn / __dadd_rn are header functions compiled under that
@@ -19,9 +20,9 @@
 namespace gpx {
 
 // ---------------------------------------------------------------------------------------------------
-// ensemble accumulate / finish.  Order of the additions = member order, then ONE division by n: the same
-// association as numpy's mean over axis 0, so the result does not depend on launch geometry.
-//   mode 0 (EI / PI / mean):  acc0 += t0
+// ensemble accumulate / finish: ens_fold and ens_mean / ens_mix_s2 / ens_ucb of acq_core.h over arrays (the batch scoring and the
+// pruned sweep's bound call the same functions on registers).  The result does not depend on launch geometry.
+//   mode 0 (EI / PI / mean):  acc0 += t0                                          acc1 is neither read nor written
 //   mode 1 (UCB, mixture moments):  acc0 += mu_m ;  acc1 += s2_m + mu_m^2
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ens_accum(double* __restrict__ acc0, double* __restrict__ acc1,
@@ -30,15 +31,10 @@ __global__ __launch_bounds__(256) void k_ens_accum(double* __restrict__ acc0, do
                                                    int first) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
-        const double m = t0[i];
-        if (mode == 0) {
-            acc0[i] = first ? m : acc0[i] + m;
-        } else {
-            const double m2 = m * m;
-            const double q = t1[i] + m2;
-            acc0[i] = first ? m : acc0[i] + m;
-            acc1[i] = first ? q : acc1[i] + q;
-        }
+        double a0 = first ? 0.0 : acc0[i], a1 = (first || mode == 0) ? 0.0 : acc1[i];
+        ens_fold(mode, first, t0[i], mode == 0 ? 0.0 : t1[i], a0, a1);
+        acc0[i] = a0;
+        if (mode != 0) acc1[i] = a1;
     }
 }
 
@@ -49,16 +45,14 @@ __global__ __launch_bounds__(256) void k_ens_finish(const double* __restrict__ a
                                                     double* __restrict__ s2_out) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
-        const double mu = acc0[i] / n;
+        const double mu = ens_mean(acc0[i], n);
         if (mode == 0) {
             out[i] = mu;
         } else {
-            const double mu2 = mu * mu;
-            double s2 = acc1[i] / n - mu2;
-            s2 = fmax(s2, 0.0);
+            const double s2 = ens_mix_s2(mu, acc1[i], n);
             if (mu_out) mu_out[i] = mu;
             if (s2_out) s2_out[i] = s2;
-            if (out) out[i] = mu + sqrt(beta * s2);
+            if (out) out[i] = ens_ucb(mu, s2, beta);
         }
     }
 }

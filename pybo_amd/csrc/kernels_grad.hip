@@ -20,6 +20,7 @@
 
 #include "gpx_internal.h"
 #include "gpx_math.h"
+#include "acq_core.h"
 
 namespace gpx {
 
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(const double* __restrict__ 
         q = block_sum(q, sh);
         if (threadIdx.x == 0) {
             o[0] = bias + p;
-            o[1] = fmax(rho - q, 1e-100);
+            o[1] = s2_floored(rho, q);
         }
         return;
     }
@@ -435,7 +436,7 @@ __global__ __launch_bounds__(1024) void k_grad_reduce_1p(int64_t N, int64_t Np, 
         q = block_sum16(q, sh);
         if (threadIdx.x == 0) {
             o[0] = bias + p;
-            o[1] = fmax(rho - q, 1e-100);
+            o[1] = s2_floored(rho, q);
         }
         return;
     }

@@ -15,6 +15,7 @@
 #include "gemm_core.h"
 #include "gpx_internal.h"
 #include "gpx_math.h"
+#include "acq_core.h"
 #include "kg_math.h"
 
 namespace gpx {
@@ -92,8 +93,8 @@ struct KgLdsLines {
     __device__ __forceinline__ double b(int i) const { return i == 0 ? b0 : be[(i - 1) * KG_CB]; }
 };
 
-// k_acq (kernels_sweep.hip) with another last part: q, p, mu = bias + p and s2 = fmax(rho - q, 1e-100) by the same statements in the
-// same order, so the moments -- and the sums a sweep cache is seeded with -- are the bits every other acquisition returns.
+// k_acq (kernels_sweep.hip) with another last part and another workgroup shape: the sums and moments are cand_moments' (acq_core.h), so
+// they -- and the sums a sweep cache is seeded with -- are the bits every other acquisition returns.
 // Workgroup: KG_CB candidates x KG_WAYS waves; wave t forms the slopes of the support points t, t + 4, .. and the partial sum of the
 // lines t, t + 4, .. (kg_partial); wave 0 combines.  Every wave forms the moments (a few loads), wave 0 stores them.  A candidate's
 // value depends on its coordinates and the support set alone: nothing here reads the chunk, the panel or the lane but to find the
@@ -112,21 +113,12 @@ __global__ __launch_bounds__(KG_CB* KG_WAYS) void k_acq_kg(const double* __restr
     const bool live = n < cols_valid;
     KgLdsLines ln = {0.0, 0.0, al, be + c};
     if (live) {
-        double q = 0.0, p = 0.0;
-        if (nrb == 0) {
-            q = Qp[n];
-            p = Pp[n];
-        }
-        for (int rb = 0; rb < nrb; ++rb) {
-            q += Qp[(int64_t)rb * ldp + n];
-            p += Pp[(int64_t)rb * ldp + n];
-        }
+        const CandMoments cm = cand_moments(Qp, Pp, ldp, nrb, n, rho, bias);
+        const double mu = cm.mu, s2 = cm.s2;
         if (qsum && t == 0) {
-            qsum[m0 + n] = q;
-            psum[m0 + n] = p;
+            qsum[m0 + n] = cm.q;
+            psum[m0 + n] = cm.p;
         }
-        const double mu = bias + p;
-        const double s2 = fmax(rho - q, 1e-100);
         if (t == 0) {
             if (mu_out) mu_out[m0 + n] = mu;
             if (s2_out) s2_out[m0 + n] = s2;
@@ -242,7 +234,7 @@ __global__ __launch_bounds__(KG_CB* KG_WAYS) void k_kg_point_final(const double*
     if (live) {
         const double* Sv = Sp + (int64_t)d * KG_EC;
         const double mu = bias + Sv[KG_PANEL];
-        s2 = fmax(rho - Sv[KG_PANEL + 2], 1e-100);
+        s2 = s2_floored(rho, Sv[KG_PANEL + 2]);
         D = sqrt(s2 + sn2);
         if (t == 0) {
             misc[0] = mu;

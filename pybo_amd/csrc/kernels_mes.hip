@@ -1,6 +1,8 @@
 // kernels_mes.hip -- the acquisition line of the sweep for max-value entropy search (GPX_ACQ_MES).
-// A translation unit of its own: kernels_sweep.hip, acq_value's switch and k_acq stay textually what they were, so the code the
-// compiler makes of them -- what tests/golden/kernel_digests.json and the bit-identity tests pin -- cannot move.
+// A translation unit of its own only so that mes_math.h is compiled where it is used: k_acq_mes is k_acq's frame (acq_frame,
+// acq_core_dev.h) with the MES value as its scoring step, so its moments -- and the sums a sweep cache is seeded with -- are the bits
+// every other acquisition returns, by construction.
+#include "acq_core_dev.h"
 #include "gpx_internal.h"
 #include "mes_math.h"
 
@@ -22,45 +24,30 @@ __device__ __forceinline__ double mes_div(double a, double b) {
     return a / b;
 }
 
-// k_acq (kernels_sweep.hip) with another last line: q, p, mu = bias + p and s2 = fmax(rho - q, 1e-100) by the same statements in the
-// same order, for the partials form (nrb > 0) and the cache form (nrb = 0) alike, so the moments -- and the sums a sweep cache is
-// seeded with -- are the bits every other acquisition returns.  One thread per candidate.  The maxima arrive by value (MesArg): the
-// index s is wave-uniform, the compiler reads y[s] on the scalar path.
+// The scoring step.  The maxima arrive by value (MesArg, a kernel argument): the index s is wave-uniform, the compiler reads y[s] on
+// the scalar path.
 // value = (g(c_0) + g(c_1) + ... + g(c_{S-1})) / S, c_s = (y*_s - mu) / sqrt(s2): summed in s ascending from g(c_0) with the roundings
 // carried (mes_add), ONE division, no contraction -- equal samples sum exactly and a power-of-two S divides exactly
 // (tests/test_gpu_mes.py).  An infinite term (c = -inf) makes the carried part NaN: the sum itself is returned then.
+struct MesScore {
+    const MesArg& ys;
+    __device__ __forceinline__ double operator()(double mu, double s2) const {
+        const double s = sqrt(s2);
+        double acc = mes_g((ys.y[0] - mu) / s), lost = 0.0;
+        for (int i = 1; i < ys.S; ++i) acc = mes_add(acc, mes_g((ys.y[i] - mu) / s), lost);
+        double unused = 0.0;
+        const double tot = mes_add(acc, lost, unused);
+        return mes_div((tot == tot) ? tot : acc, (double)ys.S);
+    }
+};
+
 __global__ __launch_bounds__(256) void k_acq_mes(const double* __restrict__ Qp, const double* __restrict__ Pp,
                                                  int64_t ldp, int nrb, int64_t m0, int64_t cols_valid,
                                                  double rho, double bias, const MesArg ys,
                                                  double* __restrict__ acq_out, double* __restrict__ mu_out,
                                                  double* __restrict__ s2_out, double* __restrict__ qsum,
                                                  double* __restrict__ psum) {
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (n >= cols_valid) return;
-    double q = 0.0, p = 0.0;
-    if (nrb == 0) {
-        q = Qp[n];
-        p = Pp[n];
-    }
-    for (int rb = 0; rb < nrb; ++rb) {
-        q += Qp[(int64_t)rb * ldp + n];
-        p += Pp[(int64_t)rb * ldp + n];
-    }
-    if (qsum) {
-        qsum[m0 + n] = q;
-        psum[m0 + n] = p;
-    }
-    const double mu = bias + p;
-    const double s2 = fmax(rho - q, 1e-100);
-    const double s = sqrt(s2);
-    double acc = mes_g((ys.y[0] - mu) / s), lost = 0.0;
-    for (int i = 1; i < ys.S; ++i) acc = mes_add(acc, mes_g((ys.y[i] - mu) / s), lost);
-    double unused = 0.0;
-    const double tot = mes_add(acc, lost, unused);
-    const double val = mes_div((tot == tot) ? tot : acc, (double)ys.S);
-    acq_out[m0 + n] = val;
-    if (mu_out) mu_out[m0 + n] = mu;
-    if (s2_out) s2_out[m0 + n] = s2;
+    acq_frame(Qp, Pp, ldp, nrb, m0, cols_valid, rho, bias, MesScore{ys}, acq_out, mu_out, s2_out, qsum, psum);
 }
 
 void launch_acq_mes(hipStream_t s, const double* Qp, const double* Pp, int64_t ldp, int nrb, int64_t m0,

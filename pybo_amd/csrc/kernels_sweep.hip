@@ -12,8 +12,9 @@
 //                     reduces colsum(V^2) and V^T a per 128-row block into Qp/Pp[mt][n]   (default: k_sweep_trmm_l -- operands by
 //                     LDS-DMA, the zero rows of T's diagonal block skipped; the other schedules are bit-identical witnesses)
 //   3. k_acq          q = sum_mt Qp, p = sum_mt Pp (fixed order -> deterministic),
-//                     mu = bias + p, s2 = max(rho - q, 1e-100), acquisition value
+//                     mu = bias + p, s2 = max(rho - q, S2_FLOOR), acquisition value   (cand_moments, acq_core.h)
 // then one block-local + one merge top-k pass over all M values.
+#include "acq_core_dev.h"
 #include "gemm_core.h"
 #include "gpx_internal.h"
 #include "gpx_math.h"
@@ -358,37 +359,18 @@ void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const
 // ------------------------------------------------------------------------------------------------
 // (norm_cdf, norm_pdf and acq_value, the ONE place the acquisition arithmetic lives: gpx_math.h -- kernels_batch.hip scores with them too)
 
-// nrb > 0: Qp/Pp are per-row-block partials (nrb, ldp) of this chunk, reduced here in block order.
+// nrb > 0: Qp/Pp are per-row-block partials (nrb, ldp) of this chunk, reduced in block order.
 // nrb = 0: Qp/Pp are the already reduced per-candidate sums of the whole grid (the sweep cache), m0 = 0.
-// qsum/psum (optional): the reduced sums are stored per candidate -- the state gpx_append's rank-1 correction
-// keeps current (warm BO step).
+// qsum/psum (optional): the reduced sums are stored per candidate (warm BO step).  acq_frame (acq_core_dev.h) with acq_value as its
+// scoring step; k_acq_mes (kernels_mes.hip) is the same frame with another one.
 __global__ __launch_bounds__(256) void k_acq(const double* __restrict__ Qp, const double* __restrict__ Pp,
                                              int64_t ldp, int nrb, int64_t m0, int64_t cols_valid,
                                              double rho, double bias, int acq_id, double p0,
                                              double* __restrict__ acq_out, double* __restrict__ mu_out,
                                              double* __restrict__ s2_out, double* __restrict__ qsum,
                                              double* __restrict__ psum) {
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (n >= cols_valid) return;
-    double q = 0.0, p = 0.0;
-    if (nrb == 0) {
-        q = Qp[n];
-        p = Pp[n];
-    }
-    for (int rb = 0; rb < nrb; ++rb) {
-        q += Qp[(int64_t)rb * ldp + n];
-        p += Pp[(int64_t)rb * ldp + n];
-    }
-    if (qsum) {
-        qsum[m0 + n] = q;
-        psum[m0 + n] = p;
-    }
-    const double mu = bias + p;
-    const double s2 = fmax(rho - q, 1e-100);
-    const double val = acq_value(acq_id, mu, s2, p0);
-    acq_out[m0 + n] = val;
-    if (mu_out) mu_out[m0 + n] = mu;
-    if (s2_out) s2_out[m0 + n] = s2;
+    acq_frame(Qp, Pp, ldp, nrb, m0, cols_valid, rho, bias, [=](double mu, double s2) { return acq_value(acq_id, mu, s2, p0); }, acq_out,
+              mu_out, s2_out, qsum, psum);
 }
 
 void launch_acq(hipStream_t s, const double* Qp, const double* Pp, int64_t ldp, int nrb, int64_t m0,
@@ -604,32 +586,8 @@ void launch_sweep_rankq(hipStream_t s, const double* Xs, int64_t Ntot, int d, co
 }
 
 // ------------------------------------------------------------------------------------------------
-// top-k: value descending, ties -> lower index; NaN ranks below everything.
+// top-k: value descending, ties -> lower index; NaN ranks below everything (the order and its block_argmax: acq_core.h, acq_core_dev.h)
 // ------------------------------------------------------------------------------------------------
-#define GPX_NEG_INF (-__builtin_huge_val())
-#define GPX_IDX_NONE ((int64_t)0x7fffffffffffffffLL)
-
-__device__ __forceinline__ bool better(double av, int64_t ai, double bv, int64_t bi) {
-    return (av > bv) || (av == bv && ai < bi);
-}
-
-// block-wide argmax of (v, i); result broadcast to all threads
-__device__ __forceinline__ void block_argmax(double& v, int64_t& i, double* sv, int64_t* si) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off);
-        const int64_t oi = __shfl_xor((long long)i, off);
-        if (better(ov, oi, v, i)) { v = ov; i = oi; }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) { sv[w] = v; si[w] = i; }
-    __syncthreads();
-    v = sv[0]; i = si[0];
-#pragma unroll
-    for (int ww = 1; ww < 4; ++ww)
-        if (better(sv[ww], si[ww], v, i)) { v = sv[ww]; i = si[ww]; }
-}
 
 // cutv / cuti (optional, device): only candidates that rank strictly AFTER the pair (*cutv, *cuti) take part -- the
 // k-th best of an earlier pass: requests beyond TOPK_PASS entries are served TOPK_PASS at a time (launch_topk).
@@ -652,9 +610,7 @@ __global__ __launch_bounds__(256) void k_topk_block(const double* __restrict__ v
 #pragma unroll
     for (int e = 0; e < TK_PER_THREAD; ++e) {
         const int64_t idx = base + e * 256 + threadIdx.x;
-        double x = (idx < M) ? vals[idx] : GPX_NEG_INF;
-        if (x != x) x = GPX_NEG_INF;
-        v[e] = x;
+        v[e] = nan_last((idx < M) ? vals[idx] : NEG_INF);
     }
     unsigned used = 0;  // bit e set: element e already emitted (or ranked at / before the cut)
     if (cut) {
@@ -666,15 +622,15 @@ __global__ __launch_bounds__(256) void k_topk_block(const double* __restrict__ v
         }
     }
     for (int it = 0; it < k; ++it) {
-        double bv = GPX_NEG_INF;
-        int64_t bi = GPX_IDX_NONE;
+        double bv = NEG_INF;
+        int64_t bi = IDX_NONE;
 #pragma unroll
         for (int e = 0; e < TK_PER_THREAD; ++e) {
             const int64_t idx = base + e * 256 + threadIdx.x;
             if (!((used >> e) & 1u) && idx < M && better(v[e], idx, bv, bi)) { bv = v[e]; bi = idx; }
         }
         block_argmax(bv, bi, sv, si);
-        if (bi != GPX_IDX_NONE) {
+        if (bi != IDX_NONE) {
             const int64_t off = bi - base;
             if ((int)(off & 255) == (int)threadIdx.x) used |= 1u << (unsigned)(off >> 8);
         }
@@ -695,17 +651,17 @@ __global__ __launch_bounds__(256) void k_topk_merge(double* __restrict__ blkv, i
     topv += (int64_t)blockIdx.x * k;
     topi += (int64_t)blockIdx.x * k;
     for (int it = 0; it < k; ++it) {
-        double bv = GPX_NEG_INF;
-        int64_t bi = GPX_IDX_NONE;
+        double bv = NEG_INF;
+        int64_t bi = IDX_NONE;
         int64_t bpos = -1;
         for (int64_t e = threadIdx.x; e < n; e += 256) {
             const int64_t idx = blki[e];
-            if (idx != GPX_IDX_NONE && better(blkv[e], idx, bv, bi)) { bv = blkv[e]; bi = idx; bpos = e; }
+            if (idx != IDX_NONE && better(blkv[e], idx, bv, bi)) { bv = blkv[e]; bi = idx; bpos = e; }
         }
         const int64_t mine = bi;
         block_argmax(bv, bi, sv, si);
-        if (bi != GPX_IDX_NONE && mine == bi && bpos >= 0) blki[bpos] = GPX_IDX_NONE;  // consume
-        if (threadIdx.x == 0) { topv[it] = bv; topi[it] = (bi == GPX_IDX_NONE) ? -1 : bi; }
+        if (bi != IDX_NONE && mine == bi && bpos >= 0) blki[bpos] = IDX_NONE;  // consume
+        if (threadIdx.x == 0) { topv[it] = bv; topi[it] = (bi == IDX_NONE) ? -1 : bi; }
         __syncthreads();
     }
 }
@@ -1148,13 +1104,13 @@ void launch_bound_mfma(hipStream_t s, const double* Xs, int64_t N, int64_t Np, i
     launch_bound_mfma32(s, A32, W32, WF32, NX32, KS, nc, (int)(Np32 / 16), d, Z, M, invell, o.cen, sc, out);
 }
 
-// ub[n] <- EI((bias + dots[n]) + delta, s2 = rho), dots[n] = alpha2 . k(X, z_n), by k_acq's own function; -inf for the `skip`
+// ub[n] <- EI((bias + dots[n]) + delta, s2 = rho), dots[n] = alpha2 . k(X, z_n) (ei_mean_bound, gpx_math.h); -inf for the `skip`
 // leading candidates that are exactly evaluated already.  The dots stay where they are: the second bound reads them again.
 __global__ __launch_bounds__(256) void k_prune_ub(const double* __restrict__ dots, double* __restrict__ ub, int64_t M, int64_t skip,
                                                   const double* __restrict__ sc, double rho, double bias, double p0) {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= M) return;
-    ub[n] = (n < skip) ? GPX_NEG_INF : acq_value(GPX_ACQ_EI, (bias + dots[n]) + sc[1], rho, p0);
+    ub[n] = (n < skip) ? NEG_INF : ei_mean_bound(bias, dots[n], sc[1], rho, p0);
 }
 
 void launch_prune_ub(hipStream_t s, const double* dots, double* ub, int64_t M, int64_t skip, const double* sc, double rho,
@@ -1163,8 +1119,8 @@ void launch_prune_ub(hipStream_t s, const double* dots, double* ub, int64_t M, i
 }
 
 // The second bound of a selection-only sweep, for survivor j of the chunk at j0: qR = the sum of the
-// row-prefix launch's Qp[rb][j], rb < nR, in k_acq's order from 0.0 -- every term a sum of squares, so no larger than k_acq's q,
-// bit for bit -- s2R = fmax(rho - qR, 1e-100) >= s2 and ub2 = EI((bias + dot) + delta, s2R) with k_prune_ub's mean bound.
+// row-prefix launch's Qp[rb][j], rb < nR, by the loop k_acq sums its q with (add_rowblocks) -- every term a sum of squares, so no
+// larger than k_acq's q, bit for bit -- s2R = s2_floored(rho, qR) >= s2 and ub2 = EI((bias + dot) + delta, s2R) with k_prune_ub's mean bound.
 // qR_out (optional) keeps the sums for gpx_prune_rows.
 __global__ __launch_bounds__(256) void k_prune_ub2(const double* __restrict__ Qp, int64_t ldp, int nR, int64_t j0, int64_t cols_valid,
                                                    const int64_t* __restrict__ idx, const double* __restrict__ dots,
@@ -1172,10 +1128,9 @@ __global__ __launch_bounds__(256) void k_prune_ub2(const double* __restrict__ Qp
                                                    double* __restrict__ ub2, double* __restrict__ qR_out) {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= cols_valid) return;
-    double q = 0.0;
-    for (int rb = 0; rb < nR; ++rb) q += Qp[(int64_t)rb * ldp + n];
-    const double s2R = fmax(rho - q, 1e-100);
-    ub2[j0 + n] = acq_value(GPX_ACQ_EI, (bias + dots[idx[j0 + n]]) + sc[1], s2R, p0);
+    double q = 0.0, unused = 0.0;
+    add_rowblocks<false>(Qp, nullptr, ldp, nR, n, q, unused);
+    ub2[j0 + n] = ei_mean_bound(bias, dots[idx[j0 + n]], sc[1], s2_floored(rho, q), p0);
     if (qR_out) qR_out[j0 + n] = q;
 }
 
@@ -1196,17 +1151,9 @@ void launch_sel_remap(hipStream_t s, const int64_t* idx, int64_t* idx2, int64_t 
     hipLaunchKernelGGL(k_sel_remap, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, idx, idx2, n);
 }
 
-// The ensemble's bound.  The sum of the members' bounds and its division are the arithmetic of k_ens_accum /
-// k_ens_finish (kernels_ens.hip) literally: one addition per member in member order, one division -- never contracted with
+// The ensemble's bound.  The sum of the members' bounds and its division are k_ens_accum's and k_ens_finish's own
+// (ens_fold in mode 0, ens_mean: acq_core.h): one addition per member in member order, one division -- never contracted with
 // the last multiply of acq_value -- so that ub_m >= v_m for every member gives a result >= the exact chain's, bit for bit.
-__device__ __forceinline__ double ens_fold(int first, double acc, double ub) {
-#pragma clang fp contract(off)
-    return first ? ub : acc + ub;
-}
-__device__ __forceinline__ double ens_mean(double acc, double n) {
-#pragma clang fp contract(off)
-    return acc / n;
-}
 
 // acc[c] (+)= EI((bias + dots[c]) + delta, s2 = rho): k_prune_ub's value of one member, folded into the running sum in the same
 // pass; delta_out receives the member's delta = sc[1] and fact_out 1.0 where its dots came from the fp32 kernel's factorised walk (guarded:
@@ -1216,8 +1163,9 @@ __global__ __launch_bounds__(256) void k_prune_ub_fold(const double* __restrict_
                                                        double* __restrict__ delta_out, int guarded, double* __restrict__ fact_out) {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= M) return;
-    const double ub = acq_value(GPX_ACQ_EI, (bias + dots[n]) + sc[1], rho, p0);
-    acc[n] = ens_fold(first, first ? 0.0 : acc[n], ub);
+    double a0 = first ? 0.0 : acc[n], unused = 0.0;
+    ens_fold(0, first, ei_mean_bound(bias, dots[n], sc[1], rho, p0), 0.0, a0, unused);
+    acc[n] = a0;
     if (n == 0) {
         *delta_out = sc[1];
         *fact_out = guarded ? ((sc[BM_SC_USE32] == 1.0 && sc[BM_SC_FACT32] == 1.0) ? 1.0 : 0.0) : __builtin_nan("");
@@ -1234,7 +1182,7 @@ void launch_prune_ub_fold(hipStream_t s, const double* dots, double* acc, int64_
 __global__ __launch_bounds__(256) void k_prune_ub_mean(double* __restrict__ acc, int64_t M, int64_t skip, double n) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= M) return;
-    acc[c] = (c < skip) ? GPX_NEG_INF : ens_mean(acc[c], n);
+    acc[c] = (c < skip) ? NEG_INF : ens_mean(acc[c], n);
 }
 
 void launch_prune_ub_mean(hipStream_t s, double* acc, int64_t M, int64_t skip, double n) {
@@ -1340,7 +1288,7 @@ __device__ __forceinline__ long long sel_class(int mode, double v, unsigned thr,
 __device__ __forceinline__ double sel_cut(int mode, const double* tau) {
     if (mode == 0) return 0.0;
     const double t = *tau;
-    return (t >= PRUNE_TAU_MIN) ? t * (1.0 - PRUNE_SLACK) : GPX_NEG_INF;
+    return (t >= PRUNE_TAU_MIN) ? t * (1.0 - PRUNE_SLACK) : NEG_INF;
 }
 
 __global__ __launch_bounds__(256) void k_sel_count(const double* __restrict__ v, int64_t M, int mode, const int* __restrict__ st,
@@ -1450,7 +1398,7 @@ __global__ __launch_bounds__(256) void k_sel_scatter(const int64_t* __restrict__
     if (j >= n) return;
     const int64_t i = idx[j];
     out[i] = vals[j];
-    if (mark) mark[i] = GPX_NEG_INF;
+    if (mark) mark[i] = NEG_INF;
 }
 
 void launch_sel_scatter(hipStream_t s, const int64_t* idx, const double* vals, int64_t n, double* out, double* mark) {
@@ -1460,7 +1408,7 @@ void launch_sel_scatter(hipStream_t s, const int64_t* idx, const double* vals, i
 
 __global__ __launch_bounds__(256) void k_fill_neg_inf(double* __restrict__ out, int64_t from, int64_t M) {
     const int64_t n = from + (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (n < M) out[n] = GPX_NEG_INF;
+    if (n < M) out[n] = NEG_INF;
 }
 
 void launch_fill_neg_inf(hipStream_t s, double* out, int64_t from, int64_t M) {
