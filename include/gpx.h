@@ -75,7 +75,7 @@ int gpx_version(void);
  *                    k-step 32, two workgroups per CU, the all-zero quarter-rows of T's diagonal block skipped; 3 = the same without the skip; 1 =
  *                    barrier-free, every wave fetching its own operand halves; 7 = k-step 16, three workgroups per CU; 6 / 5 / 2 = the register-staged loops
  *                    of rounds 5 / 2 / 1: independently scheduled witnesses) [-1 = by size: 7 below 32 block rows, else 19]
- *   "super_m"        rows of the XCD super-tile of 64 workgroups: 1, 2, 4, 8, 16 [8 -> 8 x 8]
+ *   "super_m"        rows of the XCD super-tile of 64 workgroups: 1, 2, 4, 8, 16 [8];  "sweep_cols": candidates per tile of k-loop 4: 128, 64, 32 [-1: by size]
  *   "sweep_cache"    1: full sweeps keep candidates and reduced sums for gpx_sweep_update; 0: leave a live cache alone; -1: drop it [0]
  *   "prune"          EI sweeps for ONLY the top-k (ensembles: members[0]'s value) skip what a bound rules out: -1 by size and gate, 0 never, 1 where legal [-1]
  *                    (-1: a sweep whose pruning paid lets the next of the same shape skip the gate: kept across fits / appends, dropped by ANY gpx_set_option)

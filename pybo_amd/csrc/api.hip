@@ -157,6 +157,9 @@ static const Option kOptions[] = {
     {"prune_bound", DIAG, -1, 2, "prune_bound must be -1 (by guard), 0 (generic kernel), 1 (matrix-pipe kernel) or 2 (fp32 matrix-pipe kernel)", store<&gpx_handle::prune_bound>},
     {"bound_fact", DIAG, 0, 1, "bound_fact must be 0 (the fp32 bound kernel never takes its factorised form) or 1 (by its guard)", store<&gpx_handle::bound_fact>},
     {"prune_rows", DIAG, -1, 1000000, "prune_rows must be -1 (by size), 0 (no second bound) or a number of block rows", store<&gpx_handle::prune_rows>},
+    {"sweep_cols", SHIP, -1, 128, "sweep_cols must be -1 (by size), 128, 64 or 32", store<&gpx_handle::sweep_cols>,
+     [](int64_t v) { return v == -1 || v == 128 || v == 64 || v == 32; }},
+    {"prune_seeds", DIAG, 0, 1000000, "prune_seeds must be 0 (by the rule) or a number of seeds", store<&gpx_handle::prune_seeds>},
     {"short_map", DIAG, -1, 1, "short_map must be -1 (by size), 0 (never) or 1 (wherever tile map 3 is in use)", store<&gpx_handle::short_map>},
     {"chol_w", SHIP, 0, 8, "chol_w must be 0 (by size) or in [2, 8]", store<&gpx_handle::chol_w>, [](int64_t v) { return v != 1; }},
     {"chol_tg", SHIP, -1, 1000000000, TG, store<&gpx_handle::chol_tg>, [](int64_t v) { return v == 0 || v == 1; }, "chol_tg must be 0 or 1"},
@@ -1140,20 +1143,35 @@ static const int64_t PRUNE_MIN_M = 32768, PRUNE_MIN_NP = 1024, PRUNE_MAX_SHARE_D
 static const double PRUNE_GATE_S2 = 1.0 / 64.0;
 // The second bound (option "prune_rows" = -1): the variance bound from the leading nP / 4 block rows
 // (measured on the headline workload against nP / 16 and nP / 8: profiles/prune_rows_ab.md),
-// tried where the first level left more than one generation of survivors -- an exact launch costs a whole generation however few
-// candidates it has, so at or below Gg survivors there is nothing to save -- of at least PRUNE_MIN_M candidates over at least 32
+// tried where the first level left more than one generation of survivors -- an exact launch on wide tiles costs a whole generation
+// however few candidates it has, so at or below Gg survivors there is nothing to save (the rule was measured with wide tiles and is
+// left as it is: the narrow tiles of sweep_cols_of shorten launches of up to 1024 candidates) -- of at least PRUNE_MIN_M candidates over at least 32
 // block rows: below those the prefix pass's launch chain and its sync are no small part of what it saves (the reasoning of
 // PRUNE_MIN_M / PRUNE_MIN_NP).  These conditions leave the single-bound accounting untouched at every shape
 // tests/test_gpu_prune_bound.py pins (prune = 1: M <= 13288 wherever nP >= 32; its larger M run at nP <= 20).
 static const int PRUNE_ROWS_MIN_NP = 32, PRUNE_ROWS_DIV = 4;
+// Seeds sized to the chip: where the seeds' exact launch can run on narrow tiles (kernels_sweep.hip, sweep_cols_of:
+// the default schedule, option sweep_cols not 128) over at least 48 block rows and M >= PRUNE_MIN_M, G is the column count at which
+// the narrowest tile gives every compute unit one workgroup, not a wide generation.  The lower edge is 48 block rows, not the 32 from
+// which the default schedule runs: tests/test_gpu_prune_rows.py pins G, the seed list, tau and the launch accounting at N = 4096,
+// M = 65536 and at every smaller shape, so the gain at 32 - 47 block rows is left on the table, deliberately.
+static const int PRUNE_SEEDS_MIN_NP = SWEEP_NARROW_MIN_NP;
+static bool seeds_narrow(const gpx_handle* h) {
+    return h->Np / NB >= PRUNE_SEEDS_MIN_NP && (h->tile_order < 0 || h->tile_order == 19) && h->sweep_cols != 128;
+}
 
 // Geometry of a selection-only sweep of M candidates for the k best over a factor of nP block rows.
 // G: the candidates of one generation of sweep workgroups (512 resident, each a pair of tiles; at most 4096: short
 // factors would ask for tens of thousands), at least k.
+// narrow: the seeds' launch runs on narrow tiles (seeds_narrow, every member's): G0 = the candidates of 256 workgroups, one per compute
+// unit, each a pair of 32-column tiles -- 256 at nP = 64 (profiles/narrow_seeds_ab.md: 0.54 ms against the wide generation's 1.96).
+// Gg, cap and the form of the conditions on M do not change.  seeds > 0 (diagnostic option prune_seeds): G0 = that many.
 struct PruneGeom { int64_t G, Gg, cap; };
-static PruneGeom prune_geom(int nP, int64_t k, int64_t M) {
+static PruneGeom prune_geom(int nP, int64_t k, int64_t M, bool narrow = false, int64_t seeds = 0) {
     const int64_t gen_tiles = std::max<int64_t>(1, 512 / ((nP + 1) / 2));       // candidate tiles of 512 workgroups
-    const int64_t G0 = (int64_t)TBH * std::min<int64_t>(32, gen_tiles);
+    int64_t G0 = (int64_t)TBH * std::min<int64_t>(32, gen_tiles);
+    if (narrow && M >= PRUNE_MIN_M) G0 = 32 * std::max<int64_t>(1, 256 / ((nP + 1) / 2));
+    if (seeds > 0) G0 = (seeds + 31) / 32 * 32;
     const int64_t G = std::max<int64_t>(G0, (k + TBH - 1) / TBH * TBH);
     // cap: survivors beyond this: the plain loop is the better path
     // the gate's generation is a FULL one (a launch that fills half the chip takes as long as one that fills it: config B)
@@ -1212,10 +1230,10 @@ struct SelectOps {
 // over the rest (plain_rest).  `rec` arrives as its owner started it (the fields behind the common head); the head is filled here.
 // `w`: the lead's workspace, laid out here before any callback runs.  `hint`: read, reset and re-armed by "prune" = -1 sweeps only.
 template <typename Rec>
-static int select_topk_pruned(gpx_handle* L, bool legal, bool selection_only, int acq_id, int n, int nP, int64_t Np_min, const double* dXc,
-                              int64_t M, int64_t k, int64_t ws_extra, bool ws_rows, PruneWs& w, PruneHint& hint, Rec& rec, double* out,
-                              const SelectOps& ops, int64_t* done) {
-    const PruneGeom geom = prune_geom(nP, k, M);
+static int select_topk_pruned(gpx_handle* L, bool legal, bool selection_only, int acq_id, int n, int nP, int64_t Np_min, bool narrow,
+                              const double* dXc, int64_t M, int64_t k, int64_t ws_extra, bool ws_rows, PruneWs& w, PruneHint& hint, Rec& rec,
+                              double* out, const SelectOps& ops, int64_t* done) {
+    const PruneGeom geom = prune_geom(nP, k, M, narrow, L->prune_seeds);
     const int64_t G = geom.G, Gg = geom.Gg, cap = geom.cap;
     const Rec fresh = rec;
     auto start_rec = [&]() {
@@ -1325,7 +1343,7 @@ static int second_bound(gpx_handle* h, const PruneWs& w, int64_t chunk, int swee
             const int64_t cols = (valid + TBH - 1) / TBH * TBH;
             // 4a. rows [0, nR 128) of the survivors' cross-Gram panels and the sweep's tiles of those block rows
             launch_cross_gram(s, h->dXs, (int64_t)nR * NB, h->N, (int)h->d, w.Xg, j0, nsurv, cols, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
-            launch_sweep_trmm(s, h->dU, Np, nR, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk, h->short_map);
+            launch_sweep_trmm(s, h->dU, Np, nR, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk, h->short_map);      // (wide tiles)
             // 4b. ub2 = EI((bias + dot) + delta, fmax(rho - q_R, S2_FLOOR))
             launch_prune_ub2(s, h->dQp, chunk, nR, j0, valid, w.idx, w.dots, w.sc, h->rho, h->bias, p0, w.ub2, h->prune_keep ? w.qR : nullptr);
         }
@@ -1408,7 +1426,8 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             }
             {
                 Span sp(h, T_TRMM);
-                launch_sweep_trmm(s, h->dU, Np, nP, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk, h->short_map);
+                launch_sweep_trmm(s, h->dU, Np, nP, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk, h->short_map,
+                                  valid, h->sweep_cols);
             }
             h->tacc[T_NLAUNCH] += 1.0;
             // ALGORITHMIC work of this launch: N^2 flop per candidate (N^2/2 multiply-adds of the
@@ -1471,7 +1490,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     ops.refine = [&](SelectList& list) -> int { return second_bound(h, w, chunk, sweep_order, p0, list); };
     int64_t done = 0;
     const bool legal = !h->cache_on && h->rho >= gpx::S2_FLOOR && h->rho < INFINITY;
-    if ((rc = select_topk_pruned(h, legal, selection_only, acq_id, 1, nP, Np, dXc, M, k, 0, true, w, h->prune_hint, rec, d_acq, ops, &done)))
+    if ((rc = select_topk_pruned(h, legal, selection_only, acq_id, 1, nP, Np, seeds_narrow(h), dXc, M, k, 0, true, w, h->prune_hint, rec, d_acq, ops, &done)))
         return rc;
     if ((rc = plain_rest(ops, dXc, done, chunk, M, d_acq, d_mu, d_s2))) return rc;
     if (h->cache_on) {
@@ -2148,8 +2167,11 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
         return GPX_OK;
     };
     ops.after_seeds = [&]() -> int { HIPCHK(L, hipStreamSynchronize(s)); return GPX_OK; };      // the members read the seeds from their own streams
+    // (narrow = false: the ensemble keeps the wide generation of seeds.  It has no second bound, so every member evaluates the whole
+    //  first-level list, and the list that 256 seeds leave is longer by more than the seeds save: 153.5 against 150.5 ms per step of
+    //  bench.py --ensemble 10, profiles/narrow_seeds_ab.md section 2.  The members' short launches are narrow all the same.)
     int64_t done = 0;
-    if ((rc = select_topk_pruned(L, members_ok, !d_out && !d_mu && !d_s2, acq_id, n, nPmax, Np_min, dXc, M, k, 3 * n, false, w, L->ens_hint, rec,
+    if ((rc = select_topk_pruned(L, members_ok, !d_out && !d_mu && !d_s2, acq_id, n, nPmax, Np_min, false, dXc, M, k, 3 * n, false, w, L->ens_hint, rec,
                                  out, ops, &done)))
         return rc;
     if ((rc = plain_rest(ops, dXc, done, sweep_chunk(L, M), M, out, d_mu, d_s2))) return rc;

@@ -42,11 +42,12 @@ constexpr int GEMM_THREADS = 256;
 constexpr int GEMM_LDS_F64 = 2 * 2 * BK * LDT;        // [buf][A|B][BK][LDT]
 constexpr int GEMM_LDS_BYTES = GEMM_LDS_F64 * 8;      // 73,728 B -> 2 workgroups per CU
 
-__device__ __forceinline__ void acc_zero(d4 (&acc)[4][4]) {
+template <int NJ>
+__device__ __forceinline__ void acc_zero(d4 (&acc)[4][NJ]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+        for (int j = 0; j < NJ; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
 }
 
 // The sustained shader clock of a launch (the power-bound sweeps: k_sweep_trmm*, k_rff_mfma5): every workgroup stamps both
@@ -459,10 +460,16 @@ constexpr int gemm_l_lds_f64() { return 2 * BKL * LDT; }
 // NEGA: acc += -(A) B through the MFMA's own negation of its A operand (neg:[1,0,0]): the same bits as negating A on its way
 //      into LDS (the register-staged loops), which a DMA cannot do.  AUX: cache policy of the operand loads (see gemm_tile_128_d).
 // REV: the 32-row k-steps in DESCENDING order (see gemm_tile_128_g).
-template <int BKL, int PRIO = 1, int NSET = 2, bool ILV = false, bool TRI = false, bool NEGA = false, int AUX = 0, bool REV = false>
-__device__ __forceinline__ void gemm_tile_128_l(d4 (&acc)[4][4], const double* __restrict__ A, int64_t lda,
+// NJ (deduced from acc): the 16-column groups a wave owns.  NJ = 4 is the 128 x 128 tile.  NJ = 2, 1: a NARROW tile of 128 rows x
+//      32 NJ columns that starts at column bcol (a multiple of 32 NJ) of the 128-column B image: wave (wm, wn) keeps its rows and
+//      owns columns bcol + 16 NJ wn + 16 j.  The images, the DMA and the k-steps are those of the wide tile; only the fragment
+//      reads and MFMAs of the other columns are left out.  An MFMA's result column depends on its own column of the B fragment
+//      alone, so acc[i][j] of a narrow tile sees the operands and the order its column group sees in the wide tile: the same bits.
+template <int BKL, int PRIO = 1, int NSET = 2, bool ILV = false, bool TRI = false, bool NEGA = false, int AUX = 0, bool REV = false, int NJ = 4>
+__device__ __forceinline__ void gemm_tile_128_l(d4 (&acc)[4][NJ], const double* __restrict__ A, int64_t lda,
                                                 const double* __restrict__ B, int64_t ldb, int k_lo, int k_hi,
-                                                double* smem) {
+                                                double* smem, int bcol = 0) {
+    static_assert(NJ == 4 || NJ == 2 || NJ == 1, "a wave owns 4, 2 or 1 column groups");
     static_assert(!TRI || ILV, "TRI needs the interleaved row blocks");
     static_assert(!REV || BKL == 32, "REV is the order of the 32-row steps: gemm_rev32 for other step sizes");
     constexpr int G = BKL / 4;         // MFMA groups per step
@@ -492,7 +499,7 @@ __device__ __forceinline__ void gemm_tile_128_l(d4 (&acc)[4][4], const double* _
     const int fr = lane & 15, fk = lane >> 4;
     constexpr int IST = ILV ? 32 : 16;                                  // row-block stride of a wave's A fragments
     const double* as = As + (ILV ? wm * 16 : wm * 64) + fr + fk * LDT;
-    const double* bs = Bs + wn * 64 + fr + fk * LDT;
+    const double* bs = Bs + bcol + wn * (16 * NJ) + fr + fk * LDT;
     // one k-step; I0: row blocks i < I0 are skipped (TRI); more: there is a next step whose loads go out at the end
     auto step = [&](auto i0c, bool more) {
         constexpr int I0 = decltype(i0c)::value;
@@ -500,12 +507,12 @@ __device__ __forceinline__ void gemm_tile_128_l(d4 (&acc)[4][4], const double* _
         __builtin_amdgcn_s_barrier();                  // every wave's rows of this step are in LDS
         asm volatile("" ::: "memory");
         if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
-        double a[NSET][4], b[NSET][4];
+        double a[NSET][4], b[NSET][NJ];
         auto frag = [&](int set, int g) {
 #pragma unroll
             for (int i = I0; i < 4; ++i) a[set][i] = as[g * 4 * LDT + i * IST];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) b[set][j] = bs[g * 4 * LDT + j * 16];
+            for (int j = 0; j < NJ; ++j) b[set][j] = bs[g * 4 * LDT + j * 16];
         };
         frag(0, 0);
 #pragma unroll
@@ -513,14 +520,14 @@ __device__ __forceinline__ void gemm_tile_128_l(d4 (&acc)[4][4], const double* _
             if (PRIO && kk == G / 2) __builtin_amdgcn_s_setprio(PRIO + 1);
             if (NSET == 2 && kk + 1 < G) {
                 frag((kk + 1) & 1, kk + 1);
-                __builtin_amdgcn_sched_group_barrier(0x100, 8 - I0, 0);      // the LDS reads of group kk + 1 first,
+                __builtin_amdgcn_sched_group_barrier(0x100, 4 + NJ - I0, 0); // the LDS reads of group kk + 1 first,
             }
 #pragma unroll
             for (int i = I0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
+                for (int j = 0; j < NJ; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk % NSET][i], b[kk % NSET][j], acc[i][j], 0, 0, NEGA ? 1 : 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 4 * (4 - I0), 0);    // then the MFMAs of group kk
+            __builtin_amdgcn_sched_group_barrier(0x008, NJ * (4 - I0), 0);   // then the MFMAs of group kk
             if (NSET == 1 && kk + 1 < G) frag(0, kk + 1);
         }
         if (PRIO) __builtin_amdgcn_s_setprio(0);

@@ -33,6 +33,8 @@
  *   "short_map"       the short form of tile map 3 (csrc/sweep_map.h: an XCD owns a slice of the candidate tiles AND a slice of the pair rows):
  *                     0 never; 1 wherever map 3 is in use; -1 by size: launches whose ceil(NT / 8) tiles per XCD are fewer than a
  *                     super-tile's RES / super_m -- the results are the same bits under every value [-1]
+ *   "prune_seeds"     the seed count G of a pruned sweep: 0 by the rule (prune_geom); n > 0: n rounded up
+ *                     to a multiple of 32, and to at least k -- the top-k stays what it is, the lists and the launches change [0]
  */
 #ifndef GPX_DIAG_H
 #define GPX_DIAG_H

@@ -158,19 +158,21 @@ void launch_cross_gram(hipStream_t s, const double* Xs, int64_t rows, int64_t N,
 __device__ __forceinline__ bool sweep_tile_rev(int mt, int nP) { return nP >= 32 && 2 * mt < nP - 1; }
 
 // epilogue of a tile: column sums of V^2 and V*a over its 128 rows -> Qp / Pp[mt][n0 ..] (red: 512 doubles of LDS, free)
-template <bool ILV = false>
-__device__ __forceinline__ void sweep_epilogue(const d4 (&acc)[4][4], const double* __restrict__ avec, int64_t m0,
+// NJ < 4: a narrow tile (gemm_tile_128_l): 32 NJ columns, wave (wm, wn) holds columns 16 NJ wn + 16 j.  A column's sums are formed
+// from its own accumulator column by its own two waves in the wide tile's order, so they are the wide tile's bits.
+template <bool ILV = false, int NJ = 4>
+__device__ __forceinline__ void sweep_epilogue(const d4 (&acc)[4][NJ], const double* __restrict__ avec, int64_t m0,
                                                double* __restrict__ Qrow, double* __restrict__ Prow, double* red) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int wm = w >> 1, wn = w & 1;
-    double qs[4] = {0.0, 0.0, 0.0, 0.0}, ps[4] = {0.0, 0.0, 0.0, 0.0};
+    double qs[NJ] = {}, ps[NJ] = {};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         double av[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) av[r] = avec[m0 + (ILV ? (2 * i + wm) * 16 : wm * 64 + i * 16) + (lane >> 4) + 4 * r];
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const double v = acc[i][j][r];
@@ -179,7 +181,7 @@ __device__ __forceinline__ void sweep_epilogue(const d4 (&acc)[4][4], const doub
             }
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < NJ; ++j) {
         double q = qs[j], p = ps[j];
         q += __shfl_xor(q, 16);
         p += __shfl_xor(p, 16);
@@ -190,14 +192,14 @@ __device__ __forceinline__ void sweep_epilogue(const d4 (&acc)[4][4], const doub
     }
     if (lane < 16) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int c = wn * 64 + j * 16 + lane;
+        for (int j = 0; j < NJ; ++j) {
+            const int c = wn * (16 * NJ) + j * 16 + lane;
             red[(wm * TB + c) * 2 + 0] = qs[j];
             red[(wm * TB + c) * 2 + 1] = ps[j];
         }
     }
     __syncthreads();
-    if (threadIdx.x < TB) {
+    if (threadIdx.x < 32 * NJ) {
         const int c = threadIdx.x;
         Qrow[c] = red[c * 2] + red[(TB + c) * 2];
         Prow[c] = red[c * 2 + 1] + red[(TB + c) * 2 + 1];
@@ -210,7 +212,11 @@ __device__ __forceinline__ void sweep_epilogue(const d4 (&acc)[4][4], const doub
 // Np is the leading dimension of U, the panel pitch of Ks and, as nP, the factor's block rows of the up/down rule; nR <= nP is the
 // number of block rows the map covers.  A tile's arithmetic depends on its rows of U, its panel, its K-extent and the rule -- not
 // on nR: a row-prefix launch (nR < nP) writes into Qp / Pp[mt < nR] the very bits the full launch (nR = nP) writes there.
-template <int RES, class Loop>
+// NJ < 4: NARROW tiles of 128 rows x W = 32 NJ candidates (the default schedule only): NT counts narrow tiles, tile nt is columns
+// [nt W, nt W + W) of panel nt W / 128 and writes the Qp / Pp entries of those columns.  Per wave the rows (ILV), the k-step order,
+// the TRI skip, the up/down rule and the sequence of MFMAs along k of every accumulator block are those of the wide tile, and no
+// column of a tile enters another column's sums (gemm_tile_128_l, sweep_epilogue): a launch writes the same bits at every width.
+template <int RES, int NJ = 4, class Loop>
 __device__ __forceinline__ void sweep_tiles(int b, const double* __restrict__ U, int64_t Np, const double* __restrict__ Ks, int NT,
                                             int nR, const double* __restrict__ avec, double* __restrict__ Qp, double* __restrict__ Pp,
                                             int64_t ldp, int order, int sm, unsigned long long* clk, double* smem, Loop loop) {
@@ -225,12 +231,12 @@ __device__ __forceinline__ void sweep_tiles(int b, const double* __restrict__ U,
             mt = mt2;
             __syncthreads();               // the epilogue's LDS reads are done before the next tile stages
         }
-        const int64_t m0 = (int64_t)mt * TB, n0 = (int64_t)nt * TB;
-        d4 acc[4][4];
+        const int64_t m0 = (int64_t)mt * TB, n0 = (int64_t)nt * (32 * NJ);
+        d4 acc[4][NJ];
         acc_zero(acc);
-        loop(acc, U + m0, Ks + (int64_t)nt * Np * TB, (mt + 1) * TB, sweep_tile_rev(mt, nP));
+        loop(acc, U + m0, Ks + (n0 / TB) * Np * TB, (mt + 1) * TB, sweep_tile_rev(mt, nP), (int)(n0 % TB));
         // the k-loop ended on a barrier, LDS is free
-        sweep_epilogue<true>(acc, avec, m0, Qp + (int64_t)mt * ldp + n0, Pp + (int64_t)mt * ldp + n0, smem);
+        sweep_epilogue<true, NJ>(acc, avec, m0, Qp + (int64_t)mt * ldp + n0, Pp + (int64_t)mt * ldp + n0, smem);
     }
     lc.add(clk);
 }
@@ -246,7 +252,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm(const double* __
                                                                 int order, int sm, unsigned long long* clk) {
     __shared__ __attribute__((aligned(16))) double smem[GEMM_LDS_F64];
     sweep_tiles<64>(blockIdx.x, U, Np, Ks, NT, nR, avec, Qp, Pp, ldp, order, sm, clk, smem,
-                    [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev) {
+                    [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev, int) {
         if (!rev) {
             if (VAR == 2) gemm_tile_128_b<true, true>(acc, At, Np, Bt, TB, 0, kend, smem);
             else if (VAR == 5) gemm_tile_128_g<1, false, true>(acc, At, Np, Bt, TB, 0, kend, smem);
@@ -262,7 +268,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm(const double* __
 // The same tiles through the register-free k-loop (gemm_tile_128_l): WGS workgroups per compute unit.
 // TRI: the all-zero quarter-rows of T's diagonal block are skipped (1.5 of 4 k-steps of every tile).
 // DOWN = false: every tile upwards (probe builds only: the A/B of the order rule -- NOT bit-identical with the shipped schedules)
-template <int BKL, int WGS, int PRIO, int NSET, bool TRI, int AUX = 0, bool DOWN = true>
+// NJ = 2, 1: narrow tiles of 64 / 32 candidates (sweep_tiles), for launches of few candidates over long factors: a workgroup's k-chain
+// is as long as the wide tile's but a k-step holds a half / a quarter of its MFMAs, and the launch has 2 / 4 times the workgroups.
+template <int BKL, int WGS, int PRIO, int NSET, bool TRI, int AUX = 0, bool DOWN = true, int NJ = 4>
 __global__ __launch_bounds__(GEMM_THREADS, WGS) void k_sweep_trmm_l(const double* __restrict__ U, int64_t Np,
                                                                     const double* __restrict__ Ks, int64_t ldk, int NT, int nR,
                                                                     const double* __restrict__ avec,
@@ -270,10 +278,11 @@ __global__ __launch_bounds__(GEMM_THREADS, WGS) void k_sweep_trmm_l(const double
                                                                     int64_t ldp, int order, int sm,
                                                                     unsigned long long* clk, int b0) {
     __shared__ __attribute__((aligned(16))) double smem[gemm_l_lds_f64<BKL>()];
-    sweep_tiles<32 * WGS>((int)blockIdx.x + b0, U, Np, Ks, NT, nR, avec, Qp, Pp, ldp, order, sm, clk, smem,
-                          [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev) {
-        if (!(DOWN && rev)) gemm_tile_128_l<BKL, PRIO, NSET, true, TRI, false, AUX>(acc, At, Np, Bt, TB, 0, kend, smem);
-        else if constexpr (BKL == 32) gemm_tile_128_l<32, PRIO, NSET, true, TRI, false, AUX, true>(acc, At, Np, Bt, TB, 0, kend, smem);
+    static_assert(NJ == 4 || BKL == 32, "narrow tiles: the 32-row k-step only");
+    sweep_tiles<32 * WGS, NJ>((int)blockIdx.x + b0, U, Np, Ks, NT, nR, avec, Qp, Pp, ldp, order, sm, clk, smem,
+                              [&](d4 (&acc)[4][NJ], const double* At, const double* Bt, int kend, bool rev, int bcol) {
+        if (!(DOWN && rev)) gemm_tile_128_l<BKL, PRIO, NSET, true, TRI, false, AUX>(acc, At, Np, Bt, TB, 0, kend, smem, bcol);
+        else if constexpr (BKL == 32) gemm_tile_128_l<32, PRIO, NSET, true, TRI, false, AUX, true>(acc, At, Np, Bt, TB, 0, kend, smem, bcol);
         else gemm_rev32(0, kend, [&](int k0, int k1) { gemm_tile_128_l<BKL, PRIO, NSET, true, false, false, AUX>(acc, At, Np, Bt, TB, k0, k1, smem); });
     });
 }
@@ -287,7 +296,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm_w(const double* 
                                                                   unsigned long long* clk) {
     __shared__ __attribute__((aligned(16))) double smem[4 * GEMM_W_IMG_F64];
     sweep_tiles<64>(blockIdx.x, U, Np, Ks, NT, nR, avec, Qp, Pp, ldp, order, sm, clk, smem,
-                    [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev) {
+                    [&](d4 (&acc)[4][4], const double* At, const double* Bt, int kend, bool rev, int) {
         if (!rev) gemm_tile_128_w<1, 1, false, true, 0, true>(acc, At, Np, Bt, TB, 0, kend, smem);
         else gemm_rev32(0, kend, [&](int k0, int k1) { gemm_tile_128_w<1, 1, false, true, 0, false>(acc, At, Np, Bt, TB, k0, k1, smem); });
     });
@@ -301,12 +310,24 @@ static int sweep_order_of(int order, int short_map, int sm, int NT) {
     return short_map == 2 ? SWEEP_ORDER_SHORT_STRIDED : SWEEP_ORDER_SHORT;
 }
 
+// The width of a launch's tiles (gpx_internal.h).  By size: narrow where a launch of the default schedule over a long factor (at least
+// SWEEP_NARROW_MIN_NP block rows, all of them: not a row-prefix launch) has so few candidates that wide tiles leave compute units
+// without a workgroup; the thresholds are the measured crossovers of profiles/narrow_seeds_ab.md, section 1 (N = 8192).
+static const int64_t SWEEP_COLS32_MAX = 512, SWEEP_COLS64_MAX = 1024;
+int sweep_cols_of(int sweep_cols, int tile_order, int nP, int nR, int64_t valid) {
+    if (tile_order < 0 || ((tile_order >> 2) & 7) != 4 || (tile_order >> 5) != 0) return TB;      // narrow instances: the default k-loop only
+    if (sweep_cols > 0) return sweep_cols;
+    if (nP < SWEEP_NARROW_MIN_NP || nR != nP || (tile_order & 3) != 3) return TB;
+    return valid <= SWEEP_COLS32_MAX ? 32 : valid <= SWEEP_COLS64_MAX ? 64 : TB;
+}
+
 // nR: the block rows [0, nR) the launch covers -- the factor's Np / 128 for the sweep itself, fewer for the row-prefix pass of a
 // selection-only sweep (api.hip: second_bound, step 4a), which needs rows [0, nR 128) of every Ks panel only.
 void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const double* Ks, int64_t ldk,
                        int64_t cols, const double* a, double* Qp, double* Pp, int64_t ldp,
-                       int tile_order, int super_m, unsigned long long* clk, int short_map) {
+                       int tile_order, int super_m, unsigned long long* clk, int short_map, int64_t valid, int sweep_cols) {
     const int NT = (int)(cols / TB);
+    if (valid < 0 || valid > cols) valid = cols;
     // bits 0-1: tile map, bits 2-4: k-loop (4 = default: operands by LDS-DMA, k-step 32, two workgroups per CU, the zero rows of
     // T's diagonal block skipped; 3: the same without the skip; 1: the barrier-free wave-private loop; 7: k-step 16, three workgroups per CU; 6, 5, 2: the
     // register-staged schedules of rounds 5, 2, 1 -- all kept as independently scheduled witnesses of the bit-identity test)
@@ -323,6 +344,15 @@ void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const
         const int order = sweep_order_of<64>(order0, short_map, super_m, NT);
         const unsigned nblk = sweep_grid<64>(order, super_m, NT, nR);
         GPX_SW(k_sweep_trmm_w);
+    } else if (const int W = sweep_cols_of(sweep_cols, tile_order, (int)(Np / TB), nR, valid); W < TB) {
+        // the default schedule on narrow tiles: the same maps over NTn tiles of W columns
+        const int NTn = (int)((valid + W - 1) / W);
+        const int order = sweep_order_of<64>(order0, short_map, super_m, NTn);
+        const unsigned nblk = sweep_grid<64>(order, super_m, NTn, nR);
+#define GPX_SWN(K) hipLaunchKernelGGL(K, dim3(nblk), dim3(GEMM_THREADS), 0, s, U, Np, Ks, ldk, NTn, nR, a, Qp, Pp, ldp, order, super_m, clk, 0)
+        if (W == 64) GPX_SWN((k_sweep_trmm_l<32, 2, 1, 2, true, 0, true, 2>));
+        else GPX_SWN((k_sweep_trmm_l<32, 2, 1, 2, true, 0, true, 1>));
+#undef GPX_SWN
     } else if (var == 4 || var == 3) {   // two workgroups per CU, k-step 32; 4: with the diagonal block's zero rows skipped
         const int order = sweep_order_of<64>(order0, short_map, super_m, NT);
         const unsigned nblk = sweep_grid<64>(order, super_m, NT, nR);

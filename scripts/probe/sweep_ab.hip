@@ -6,8 +6,9 @@
 //   workgroup per CU on gemm_tile_128_d / _ld / _w<2> (the factorisation's worker loops); 2000 / 2001: the wave-private loop with /
 //   without the diagonal-block skip, every tile upwards.  bash scripts/probe/pmc_fetch.sh adds the L2 -> fabric read bytes.
 //   Suffixes of a variant, in this order: "/S" the launch's short_map (sweep_map.h: 0 never, 1 the short form of map 3, 2 its strided form;
-//   default -1, by size as the library); "c" COLD: a pass over a 1 GiB buffer (larger than the 256 MiB MALL and every L2) before each
-//   timed launch, so that the launch finds neither U nor Ks in a cache (profiles/short_launch_map_ab.md).  Example: 19:8/0c
+//   default -1, by size as the library); "wW" the width of the default schedule's tiles, W = 128 (default), 64 or 32 candidates (narrow tiles:
+//   kernels_sweep.hip, sweep_tiles; the checksum must not change with W: profiles/narrow_seeds_ab.md); "c" COLD: a pass over a 1 GiB buffer (larger than the 256 MiB MALL and every L2) before each
+//   timed launch, so that the launch finds neither U nor Ks in a cache (profiles/short_launch_map_ab.md).  Examples: 19:8/0c  19w32
 #include "../../pybo_amd/csrc/kernels_sweep.hip"
 #include <stdio.h>
 #include <stdlib.h>
@@ -104,6 +105,9 @@ int main(int argc, char** argv) {
         if (const char* c = strchr(argv[v], ':')) sm = atoi(c + 1);
         int short_map = -1;
         if (const char* c = strchr(argv[v], '/')) short_map = atoi(c + 1);
+        int width = 128;
+        if (const char* c = strchr(argv[v], 'w')) width = atoi(c + 1);
+        if (width != 128 && width != 64 && width != 32) { fprintf(stderr, "width must be 128, 64 or 32\n"); return 1; }
         const bool cold = argv[v][strlen(argv[v]) - 1] == 'c';
         if (cold && !flush) CK(hipMalloc(&flush, nflush * 8));
         std::vector<float> ms_all;
@@ -128,7 +132,7 @@ int main(int argc, char** argv) {
                 else { CK(hipFuncSetAttribute((const void*)k_lone<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
                     hipLaunchKernelGGL(k_lone<2>, dim3(nblk), dim3(GEMM_THREADS), lb, 0, U, Np, Ks, (int)(cols / TB), a, Qp, Pp, cols, sm); }
             } else
-            launch_sweep_trmm(0, U, Np, nP, Ks, Np, cols, a, Qp, Pp, cols, to, sm, clk, short_map);
+            launch_sweep_trmm(0, U, Np, nP, Ks, Np, cols, a, Qp, Pp, cols, to, sm, clk, short_map, cols, width);
             hipEventRecord(e1);
             CK(hipEventSynchronize(e1));
             CK(hipGetLastError());
@@ -150,8 +154,8 @@ int main(int argc, char** argv) {
             dq = std::max(dq, fabs(hq[i] - rq[i])); sq = std::max(sq, fabs(rq[i]));
             dp = std::max(dp, fabs(hp[i] - rp[i])); sp = std::max(sp, fabs(rp[i]));
         }
-        printf("RESULT tile_order %d super_m %d short_map %d %s N %lld cols %lld: min %.3f median %.3f ms  %.2f TFLOP/s  frac %.4f  sclk %.0f MHz  checksum %016llx  maxdiff/scale q %.2e p %.2e\n",
-               to, sm, short_map, cold ? "cold" : "warm", (long long)N, (long long)cols, ms_all[0], med, (double)N * N * cols / med / 1e9, (double)N * N * cols / med / 1e9 / 78.6, mhz, x, dq / sq, dp / sp);
+        printf("RESULT tile_order %d super_m %d short_map %d width %d %s N %lld cols %lld: min %.3f median %.3f ms  %.2f TFLOP/s  frac %.4f  sclk %.0f MHz  checksum %016llx  maxdiff/scale q %.2e p %.2e\n",
+               to, sm, short_map, width, cold ? "cold" : "warm", (long long)N, (long long)cols, ms_all[0], med, (double)N * N * cols / med / 1e9, (double)N * N * cols / med / 1e9 / 78.6, mhz, x, dq / sq, dp / sp);
         fflush(stdout);
     }
     return 0;
