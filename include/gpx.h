@@ -1,10 +1,8 @@
 /*
  * gpx.h -- C-ABI of libgpx.so: the MI355X (gfx950) GP-posterior + acquisition engine.
  *
- * The reference (mwhoffman/pybo) has NO native boundary: its GP arithmetic is a set of Python
- * method calls on a duck-typed `model` object (the un-vendored `reggie` package).  Each entry point
- * below therefore cites the *call site in pybo* whose work it performs; the Python model/policy/
- * solver plugins in pybo_amd/ bind these through ctypes.
+ * The reference (mwhoffman/pybo) has NO native boundary: its GP arithmetic is a set of Python method calls on a duck-typed `model` object (the un-vendored
+ * `reggie` package).  Each entry point below therefore cites the *call site in pybo* whose work it performs; pybo_amd/ binds these by ctypes.
  *
  * Conventions
  *   - every function returns an int status: 0 = GPX_OK, negative = error class;
@@ -103,11 +101,10 @@ int gpx_version(void);
 int gpx_set_option(gpx_handle *h, const char *name, int64_t value);
 
 /* ---- GP fit = model.add_data(X, Y)            [pybo/bayesopt.py:114,258,269] ------------- */
-/* Limits: 1 <= d <= 1024 for every entry point (the Thompson / RFF kernels keep a whole feature tile in LDS up to
- * d = 64 and walk the coordinates 32 at a time beyond); top-k requests k <= 4096 (64 per pass over the values).
- * Gram build K = k(X,X) + sn2 I and Cholesky K = R^T R.  The triangular inverse T = R^-T, a = T (y - bias)
- * and alpha follow on FIRST USE (sweep, predict, mean_at_obs, loglik, append, introspection): the Thompson
- * entry points never read them.  X is (N,d), y is (N,), ell is (d,) on the HOST in both variants. */
+/* Limits: 1 <= d <= 1024 for every entry point (the Thompson / RFF kernels keep a whole feature tile in LDS up to d = 64 and walk the coordinates 32 at a
+ * time beyond); top-k requests k <= 4096 (64 per pass over the values).  Gram build K = k(X,X) + sn2 I and Cholesky K = R^T R.  The triangular inverse
+ * T = R^-T, a = T (y - bias) and alpha follow on FIRST USE (sweep, predict, mean_at_obs, loglik, append, introspection): the Thompson entry points never
+ * read them.  X is (N,d), y is (N,), ell is (d,) on the HOST in both variants. */
 int gpx_fit(gpx_handle *h, const double *X, int64_t N, int64_t d, const double *y, int kernel_id, const double *ell, double rho, double sn2, double bias);
 int gpx_fit_dev(gpx_handle *h, const double *dX, int64_t N, int64_t d, const double *dy, int kernel_id, const double *ell, double rho, double sn2, double bias);
 /* log marginal likelihood of the fit, -1/2 a.a - sum log R_ii - N/2 log 2pi: what reggie.MCMC [pybo/bayesopt.py:115] evaluates once per proposal */
@@ -209,13 +206,11 @@ int gpx_rff_grad(gpx_handle *h, const double *W, const double *b, const double *
 int gpx_rff_gram(gpx_handle *h, const double *W, const double *b, int64_t n, double *A, double *v);
 /* the same for S draws in one call: W (S,n,d), b (S,n) -> A (S,n,n), v (S,n) */
 int gpx_rff_gram_batch(gpx_handle *h, const double *W, const double *b, int64_t S, int64_t n, double *A, double *v);
-/* the weight posterior of S draws WITHOUT leaving the device (the n x n solve inside sample_f,
- * pybo/policies/simple.py:48): feature Grams as above, then per draw
- *     B = sc^2 A + sn2 I = L L^T,    theta = sc ( B^-1 (sc v) + sqrt(sn2) L^-T z )
- * with z (S,n) the caller's standard-normal draws, sc = sqrt(2 rho / n) and sn2 the fitted noise variance (> 0);
- * theta (S,n) comes back ready for gpx_rff_sweep* / gpx_rff_grad.  n <= 127: all S draws in one launch chain (the n x n
- * posterior of a draw lives in LDS); 128 <= n <= 4096: per draw the blocked Cholesky kernels of the fit + two vector
- * substitutions (`n` is a free keyword of the reference's sample_f, pybo/policies/simple.py:44).  GPX_ENOTPD if a B is not PD. */
+/* the weight posterior of S draws WITHOUT leaving the device (the n x n solve inside sample_f, pybo/policies/simple.py:48): feature Grams as above, then per
+ * draw  B = sc^2 A + sn2 I = L L^T,  theta = sc ( B^-1 (sc v) + sqrt(sn2) L^-T z )  with z (S,n) the caller's standard-normal draws, sc = sqrt(2 rho / n) and
+ * sn2 the fitted noise variance (> 0); theta (S,n) comes back ready for gpx_rff_sweep* / gpx_rff_grad.  n <= 127: all S draws in one launch chain (the n x n
+ * posterior of a draw lives in LDS); 128 <= n <= 4096: per draw the blocked Cholesky kernels of the fit + two vector substitutions (`n` is a free keyword
+ * of the reference's sample_f, pybo/policies/simple.py:44).  GPX_ENOTPD if a B is not PD. */
 int gpx_rff_posterior(gpx_handle *h, const double *W, const double *b, const double *z, int64_t S, int64_t n, double sc, double *theta);
 
 /* ---- hyper-parameter ensemble = pybo's DEFAULT model, reggie.MCMC(gp, n=10) [pybo/bayesopt.py:115]: every index is the average over the n member
@@ -237,17 +232,25 @@ int gpx_ensemble_sweep_batch(gpx_handle *const *members, int n_members, int acq_
  * latency-bound kernels run concurrently on their own streams (one call instead of n_members gpx_predict calls) and the caller forms the average it
  * needs (mixture moments for UCB / mean, the mean of the members' EI / PI and their gradients). */
 int gpx_ensemble_predict(gpx_handle *const *members, int n_members, const double *Xc, int64_t M, double *mu, double *s2, double *dmu, double *ds2);
+/* ---- constrained optimisation: cEI(x) = acq_f(x) * prod_j Pr(c_j(x) >= thr[j]) (Gardner et al. 2014; Gelbart et al. 2014): one fitted handle for the
+ *      objective and one per black-box constraint, 1 <= nc <= 16, each with its own hyper-parameters, on ONE device with the same d, every handle once (else
+ *      GPX_EARG; unfitted: GPX_ESTATE).  With obj, acq_id is GPX_ACQ_EI or GPX_ACQ_PI (non-negative values; others GPX_EARG); obj = NULL (no feasible
+ *      incumbent yet): the value is the probability of feasibility alone, acq_id / params are not read.  The lead (obj, else cons[0]) owns the scratch and
+ *      the error text.  thr (nc,) finite.  Per candidate v_0 = acq, v_j = v_{j-1} * min(P_j, 1) in the caller's order, P_j the bits of gpx_sweep(GPX_ACQ_PI,
+ *      {thr[j]}) on cons[j]; pof_all (optional, (M,)): the same product started at 1; acq_all optional; top-k and `_dev` as gpx_sweep*.  An EI call for the
+ *      top-k alone skips what the OBJECTIVE's bound rules out ("prune" of obj; never with a "sweep_cache" on): constraints sweep seeds and survivors only. */
+int gpx_constrained_sweep(gpx_handle *obj, gpx_handle *const *cons, int nc, const double *thr, int acq_id, const double *params, int nparams,
+                          const double *Xc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *acq_all, double *pof_all);
+int gpx_constrained_sweep_dev(gpx_handle *obj, gpx_handle *const *cons, int nc, const double *thr, int acq_id, const double *params, int nparams,
+                              const double *dXc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *d_acq_all, double *d_pof_all);
 
-/* ---- candidate grid generated and kept in HBM = the solver's grid
- *      xgrid = init_uniform(bounds, ngrid, rng)   [pybo/solvers/lbfgs.py:45; pybo/inits/methods.py:24-38]
- *      or a Sobol' grid                            [pybo/inits/methods.py:62-77]
- *      without the host array and its PCIe upload; pass gpx_grid_data() to the *_dev sweeps.
- * GPX_GRID_UNIFORM: counter-based Philox4x32-10, key = seed, counter = element-pair index; element 2c, 2c+1
- *      of the row-major (first+M,d) array = the two 53-bit uniforms of output c; x = lo + u*(hi-lo); rows
- *      first .. first+M-1 of that array are generated (a shard of a grid holds the numbers the whole grid holds).
- * GPX_GRID_SOBOL: unscrambled Sobol' points first .. first+M-1 in Gray-code order (the order of
- *      scipy.stats.qmc.Sobol), from caller-supplied direction numbers sv (d, bits) uint32, 1 <= bits <= 32.
- * bounds (d,2) row-major [lo, hi].  Errors of the grid calls are read with gpx_last_error(NULL). */
+/* ---- candidate grid generated and kept in HBM = the solver's grid xgrid = init_uniform(bounds, ngrid, rng) [pybo/solvers/lbfgs.py:45;
+ *      pybo/inits/methods.py:24-38] or a Sobol' grid [pybo/inits/methods.py:62-77] without the host array and its PCIe upload; pass gpx_grid_data() to
+ *      the *_dev sweeps.
+ * GPX_GRID_UNIFORM: counter-based Philox4x32-10, key = seed, counter = element-pair index; element 2c, 2c+1 of the row-major (first+M,d) array = the two
+ *      53-bit uniforms of output c; x = lo + u*(hi-lo); rows first .. first+M-1 of that array are generated (a shard holds the numbers the whole grid holds).
+ * GPX_GRID_SOBOL: unscrambled Sobol' points first .. first+M-1 in Gray-code order (the order of scipy.stats.qmc.Sobol), from caller-supplied direction
+ *      numbers sv (d, bits) uint32, 1 <= bits <= 32.  bounds (d,2) row-major [lo, hi].  Errors of the grid calls are read with gpx_last_error(NULL). */
 typedef struct gpx_grid gpx_grid;
 enum { GPX_GRID_UNIFORM = 0, GPX_GRID_SOBOL = 1 };
 int gpx_grid_create(int device, int kind, const double *bounds, int64_t M, int64_t d, uint64_t seed,
@@ -257,11 +260,10 @@ const double *gpx_grid_data(const gpx_grid *g);     /* device pointer, (M,d) row
 int gpx_grid_rows(gpx_grid *g, const int64_t *idx, int64_t k, double *out);
 int gpx_grid_destroy(gpx_grid *g);
 
-/* ---- multi-GPU exchange: the one collective of the sharded sweep.  The reference is single-process (its only hint at
- *      parallelism is the comment pybo/solvers/lbfgs.py:60); layout per SURVEY.md 8(e): one process per GPU, candidates sharded
- *      contiguously, every rank fits redundantly (bitwise-identical factor), each rank's best (value, GLOBAL index) pairs
- *      all-gathered over RCCL/xGMI and merged "value descending, then index ascending".  RCCL is bound at run time (dlopen of
- *      librccl, override with $GPX_RCCL_LIB): single-GPU use never loads it.  Errors: gpx_comm_last_error() (thread-local). */
+/* ---- multi-GPU exchange: the one collective of the sharded sweep.  The reference is single-process (its only hint at parallelism is the comment
+ *      pybo/solvers/lbfgs.py:60); layout per SURVEY.md 8(e): one process per GPU, candidates sharded contiguously, every rank fits redundantly
+ *      (bitwise-identical factor), each rank's best (value, GLOBAL index) pairs all-gathered over RCCL/xGMI and merged "value descending, then index
+ *      ascending".  RCCL is bound at run time (dlopen of librccl, override with $GPX_RCCL_LIB): single-GPU use never loads it.  Errors: gpx_comm_last_error */
 typedef struct gpx_comm gpx_comm;
 #define GPX_COMM_ID_BYTES 128
 /* rank 0 generates the id (ncclGetUniqueId) and hands its 128 bytes to every rank over any side channel */
@@ -271,13 +273,11 @@ int gpx_comm_init(gpx_handle *h, int rank, int nranks, const unsigned char *id, 
 int gpx_comm_destroy(gpx_comm *c);
 int gpx_comm_size(const gpx_comm *c, int *rank, int *nranks);
 const char *gpx_comm_last_error(void);
-/* All-gather of the n (value, index) pairs the handle's LAST sweep left in HBM (n = its k for gpx_sweep* /
- * gpx_ensemble_sweep*, S*k for gpx_rff_sweep*), taken straight from the device, `index_offset` (this rank's
- * shard origin) added to every valid index.
- *   k > 0: every rank receives the same merged k best in out_val[k], out_idx[k]
- *          = the global argsort(finit)[::-1][:k] of pybo/solvers/lbfgs.py:51 over the sharded grid.
- *   k = 0: no merge; out_val / out_idx receive all nranks*n pairs in rank order (batch-BO: one recommendation
- *          per Thompson draw, draws sharded over ranks). */
+/* All-gather of the n (value, index) pairs the handle's LAST sweep left in HBM (n = its k for gpx_sweep* / gpx_ensemble_sweep* / gpx_constrained_sweep*
+ * (the lead), S*k for gpx_rff_sweep*), taken straight from the device, `index_offset` (this rank's shard origin) added to every valid index.
+ *   k > 0: every rank receives the same merged k best in out_val[k], out_idx[k] = the global argsort(finit)[::-1][:k] of pybo/solvers/lbfgs.py:51 over
+ *          the sharded grid.
+ *   k = 0: no merge; out_val / out_idx receive all nranks*n pairs in rank order (batch-BO: one recommendation per Thompson draw, draws sharded over ranks). */
 int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, double *out_val, int64_t *out_idx);
 
 /* ---- measurement ------------------------------------------------------------------------ */

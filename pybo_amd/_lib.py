@@ -51,6 +51,7 @@ DIAG_SYMBOLS = {
     'gpx_prune_dots': (C.c_int, [_P, _P]),
     'gpx_prune_rows': (C.c_int, [_P, _P, _P, _P, _i64]),
     'gpx_ensemble_prune_report': (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _i64]),
+    'gpx_constrained_prune_report': (C.c_int, [_P, _P, C.c_int, _P, _P, _i64]),
 }
 SYMBOLS = {
     'gpx_create': (C.c_int, [C.c_int, _P, C.POINTER(_P)]),
@@ -93,6 +94,8 @@ SYMBOLS = {
     'gpx_ensemble_sweep_dev': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P, _P]),
     'gpx_ensemble_sweep_batch': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _i64, _P, _P, _P]),
     'gpx_ensemble_predict': (C.c_int, [_P, C.c_int, _P, _i64, _P, _P, _P, _P]),
+    'gpx_constrained_sweep': (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P]),
+    'gpx_constrained_sweep_dev': (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P]),
     'gpx_grid_create': (C.c_int, [C.c_int, C.c_int, _P, _i64, _i64, C.c_uint64, _i64, _P, C.c_int, C.POINTER(_P)]),
     'gpx_grid_data': (_P, [_P]),
     'gpx_grid_rows': (C.c_int, [_P, _P, _i64, _P]),
@@ -738,6 +741,54 @@ class Engine(object):
         dmu, ds2 = np.empty((n, M, d)), np.empty((n, M, d))
         lead._check(lead._lib.gpx_ensemble_predict(handles, n, _ptr(Xc), M, _ptr(mu), _ptr(s2), _ptr(dmu), _ptr(ds2)))
         return mu, s2, dmu, ds2
+
+    @staticmethod
+    def constrained_sweep(obj, cons, thr, acq, param, Xc, k=0, want_all=True, want_pof=False, d_acq=None, d_pof=None):
+        """Constrained sweep (gpx_constrained_sweep[_dev]): EI / PI of the engine `obj` times the probability that every constraint engine
+        of `cons` exceeds its threshold `thr[j]`; obj = None: the probability of feasibility alone (acq / param unread).  `Xc`: host
+        array (M, d) or a DeviceGrid (then d_acq / d_pof: optional device pointers of (M,) vectors).  Returns dict(top_val, top_idx, acq,
+        pof); the lead (obj, else cons[0]) raises the errors."""
+        cons = list(cons)
+        lead = obj if obj is not None else cons[0]
+        handles = (_P * len(cons))(*[e._h for e in cons])
+        thr = _f64(thr).reshape(-1)
+        if len(thr) != len(cons):
+            raise ValueError('one threshold per constraint')
+        aid = acq_id(acq) if obj is not None else 0
+        params, nparams = _acq_params(param)
+        tv = np.empty(k)
+        ti = np.empty(k, dtype=np.int64)
+        oh = obj._h if obj is not None else None
+        if isinstance(Xc, DeviceGrid):
+            lead._check(lead._lib.gpx_constrained_sweep_dev(oh, handles, len(cons), _ptr(thr), aid, _ptr(params), nparams, Xc.ptr, len(Xc), k,
+                                                            _ptr(tv) if k else None, _ptr(ti) if k else None,
+                                                            _P(d_acq) if d_acq else None, _P(d_pof) if d_pof else None))
+            return dict(top_val=tv, top_idx=ti, acq=None, pof=None)
+        Xc = _f64(Xc).reshape(-1, lead.d)
+        M = len(Xc)
+        out = np.empty(M) if want_all else None
+        pof = np.empty(M) if want_pof else None
+        lead._check(lead._lib.gpx_constrained_sweep(oh, handles, len(cons), _ptr(thr), aid, _ptr(params), nparams, _ptr(Xc), M, k,
+                                                    _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out), _ptr(pof)))
+        return dict(top_val=tv, top_idx=ti, acq=out, pof=pof)
+
+    def constrained_prune_report(self, vectors=True):
+        """Diagnostic (gpx_constrained_prune_report in csrc/gpx_diag.h): what the last constrained sweep led by this engine decided about
+        pruning.  dict(path, M, k, G, Gg, done, cap, nsurv, tau, gate, delta); with `vectors`, where the bound pass ran, also ub (M,), the
+        objective's EI bound as the survivor pass read it, and idx, the survivors in compaction order (empty where it fell back)."""
+        scal = np.full(11, np.nan)
+        self._check(self._lib.gpx_constrained_prune_report(self._h, _ptr(scal), len(scal), None, None, 0))
+        names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'tau', 'gate', 'delta')
+        r = dict(zip(names, scal.tolist()))
+        for n in names[:8]:
+            r[n] = int(r[n])
+        r['path'] = Engine.PRUNE_PATHS[r['path']]
+        if vectors and r['path'] in ('pruned', 'fell back'):
+            nidx = r['nsurv'] if r['path'] == 'pruned' else 0
+            r['ub'] = np.empty(r['M'])
+            r['idx'] = np.empty(nidx, dtype=np.int64)
+            self._check(self._lib.gpx_constrained_prune_report(self._h, _ptr(scal), len(scal), _ptr(r['ub']), _ptr(r['idx']), nidx))
+        return r
 
     # -- Thompson --------------------------------------------------------------------------------
     def rff_gram(self, W, b):

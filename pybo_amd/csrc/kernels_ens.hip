@@ -1,6 +1,7 @@
 // kernels_ens.hip -- (1) the hyper-parameter ENSEMBLE sweep: pybo's default model is reggie.MCMC(gp, n=10)
 // (/root/reference/pybo/bayesopt.py:115), whose acquisition is the average over the member GPs; the
 // member sweeps stay on the device and only the k winners of the averaged index come back.
+// (1b) the constraint fold of the constrained sweep (gpx_constrained_sweep: EI / PI times the probability of feasibility).
 // (2) candidate grids generated in HBM: the solver's grid
 // (/root/reference/pybo/solvers/lbfgs.py:45 `init_uniform`, pybo/inits/methods.py:24-38,62-77) never crosses
 // PCIe and stays resident for the whole BO run.
@@ -57,9 +58,28 @@ __global__ __launch_bounds__(256) void k_ens_finish(const double* __restrict__ a
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// constrained index (gpx_constrained_sweep): one constraint's probability of feasibility p folded into the running product(s),
+// con_fold of acq_core.h over arrays.  v (optional): v *= min(p, 1), whatever value the objective left there.  w (optional): the
+// probability of feasibility alone, started at 1.0 by the `first` constraint whatever w held.  Independent of launch geometry.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_con_fold(double* __restrict__ v, double* __restrict__ w, const double* __restrict__ p,
+                                                  int64_t M, int first) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
+        const double pi = p[i];
+        if (v) v[i] = con_fold(v[i], pi);
+        if (w) w[i] = con_fold(first ? 1.0 : w[i], pi);
+    }
+}
+
 static inline int ew_blocks(int64_t M) {
     int64_t b = (M + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
+}
+
+void launch_con_fold(hipStream_t s, double* v, double* w, const double* p, int64_t M, int first) {
+    hipLaunchKernelGGL(k_con_fold, dim3(ew_blocks(M)), dim3(256), 0, s, v, w, p, M, first);
 }
 
 void launch_ens_accum(hipStream_t s, double* acc0, double* acc1, const double* t0, const double* t1, int64_t M,

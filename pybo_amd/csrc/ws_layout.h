@@ -60,6 +60,13 @@ inline EnsWs ens_ws(WsCarver c, int64_t M) {
     return {c.take<double>(M, "acc0"), c.take<double>(M, "acc1"), c.take<double>(M, "t0"), c.take<double>(M, "t1"), c.take<double>(M, "out"), c.bytes()};
 }
 
+// the constrained sweep's scratch (h->dcon): one constraint's probabilities of feasibility, and the running product where the caller
+// gave no vector for it
+struct ConWs { double *t0, *out; int64_t bytes; };
+inline ConWs con_ws(WsCarver c, int64_t M) {
+    return {c.take<double>(M, "t0"), c.take<double>(M, "out"), c.bytes()};
+}
+
 // The matrix-pipe bound kernels' operands (kernels_sweep.hip: launch_bound_mfma), every one on a 32-byte boundary: the augmented rows
 // in KS k-steps, the weights, the norms where they go through the accumulator (nc; KS <= 4 there), the centre at its fixed place, then
 // the fp32 copies over Np + B32_ZROWS rows (W': the factorised walk's scaled weights).  Sized with KS = BM_KS_MAX, nc = false.

@@ -1,4 +1,4 @@
-"""Acquisition policies; the exported names match pybo.policies (`EI`, `PI`, `UCB`, `Thompson`), plus `MES` and `KG`."""
-from .simple import EI, PI, UCB, Thompson, MES, KG
+"""Acquisition policies; the exported names match pybo.policies (`EI`, `PI`, `UCB`, `Thompson`), plus `MES`, `KG` and `CEI`."""
+from .simple import EI, PI, UCB, Thompson, MES, KG, CEI
 
-__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES', 'KG']
+__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES', 'KG', 'CEI']

@@ -15,11 +15,12 @@ New: when the model is the device-backed `pybo_amd.models.GP`, the returned inde
 `pybo_amd.solvers.solve_lbfgs` uses instead of `argsort(f(xgrid))` (pybo/solvers/lbfgs.py:50-51).
 Any other model (e.g. a test stub) gets plain closures, exactly as in the reference.  Every EI / PI / UCB index also
 carries `index.acq = (kind, param)` and, for models with `acq_batch`, `index.batch(xgrid, nb)` (pybo_amd/batch.py).
-`MES` (max-value entropy search) and `KG` (knowledge gradient over a support set) are this build's own: the reference has neither.
+`MES` (max-value entropy search), `KG` (knowledge gradient over a support set) and `CEI` (constrained expected improvement on a
+`models.Constrained`) are this build's own: the reference has none of them.
 """
 import numpy as np
 
-__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES', 'KG']
+__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES', 'KG', 'CEI']
 
 
 def _attach_topk(index, model, kind, param):
@@ -164,6 +165,35 @@ def KG(model, bounds, X, nsupport=64, ngrid=10000, support=None, rng=None):
     fast = getattr(model, 'acq_topk', None) if members is None else None
     if fast is not None:
         index.topk = lambda xgrid, k: fast('kg', support, xgrid, k)
+        owner = getattr(model, 'topk_engine', None)
+        if owner is not None:
+            index.topk_engine = owner
+    return index
+
+
+def CEI(model, _, X, xi=0.0, pmin=0.5):
+    """Constrained expected improvement (Gardner et al. 2014; Gelbart et al. 2014) on a `models.Constrained`: EI of the objective
+    times the probability that every constraint holds.  The target is the highest objective posterior mean among the observed X
+    whose `feasibility` is at least `pmin`, plus xi; while no observation qualifies the index is the probability of feasibility
+    alone (target None).  The index carries `.acq = ('cei', target)` and, for models with `acq_topk`, `.topk`; never `.batch`."""
+    model = model.copy()
+    lacking = [n for n in ('feasibility', 'get_constrained') if getattr(model, n, None) is None]
+    if lacking:
+        raise TypeError('CEI needs a model with feasibility(X) and get_constrained(target, X, grad); %s has none' % type(model).__name__)
+    X = np.array(X, ndmin=2, dtype=float)
+    target = None
+    if len(X):
+        ok = np.asarray(model.feasibility(X)) >= pmin
+        if ok.any():
+            target = float(np.asarray(model.predict_mean(X))[ok].max() + xi)
+
+    def index(X, grad=False):
+        return model.get_constrained(target, X, grad)
+
+    index.acq = ('cei', target)
+    fast = getattr(model, 'acq_topk', None)
+    if fast is not None and getattr(model, '_device_members', lambda: True)():
+        index.topk = lambda xgrid, k: fast('cei', target, xgrid, k)
         owner = getattr(model, 'topk_engine', None)
         if owner is not None:
             index.topk_engine = owner

@@ -1,13 +1,14 @@
 """
 Recommenders (/root/reference/pybo/recommenders.py:14-35): where to point the user after each step.
 `best_latent` maximises the posterior mean starting from the observed points (through solve_lbfgs with
-`xgrid=X`), `best_incumbent` returns the observed point with the highest posterior mean.
+`xgrid=X`), `best_incumbent` returns the observed point with the highest posterior mean.  `best_feasible` (this build's own,
+for `models.Constrained`) returns the best observed point that is probably feasible.
 """
 import numpy as np
 
 from . import solvers
 
-__all__ = ['best_latent', 'best_incumbent']
+__all__ = ['best_latent', 'best_incumbent', 'best_feasible']
 
 
 def best_latent(model, bounds, X):
@@ -32,3 +33,16 @@ def best_incumbent(model, _, X):
     mean_only = getattr(model, 'predict_mean', None)
     mu = mean_only(X) if mean_only is not None else model.predict(X)[0]
     return np.asarray(X)[int(np.argmax(mu))]
+
+
+def best_feasible(model, _, X, pmin=0.5):
+    """For a `models.Constrained`: the observed point of highest objective posterior mean among those whose probability of
+    feasibility is at least `pmin`; where none qualifies, the observed point of highest feasibility."""
+    X = np.array(X, ndmin=2, dtype=float)
+    pof = np.asarray(model.feasibility(X), dtype=float)
+    ok = pof >= pmin
+    if not ok.any():
+        return X[int(np.argmax(np.where(np.isnan(pof), -np.inf, pof)))]
+    mean_only = getattr(model, 'predict_mean', None)
+    mu = np.asarray(mean_only(X) if mean_only is not None else model.predict(X)[0], dtype=float)
+    return X[int(np.argmax(np.where(ok & ~np.isnan(mu), mu, -np.inf)))]
