@@ -5,13 +5,11 @@
  * `reggie` package).  Each entry point below therefore cites the *call site in pybo* whose work it performs; pybo_amd/ binds these by ctypes.
  *
  * Conventions
- *   - every function returns an int status: 0 = GPX_OK, negative = error class;
- *     gpx_last_error(h) returns a NUL-terminated description (handle-local; NULL handle ->
- *     thread-local string of the last failed gpx_create).
+ *   - every function returns an int status: 0 = GPX_OK, negative = error class; gpx_last_error(h) returns a NUL-terminated description (handle-local; NULL
+ *     handle -> thread-local string of the last failed gpx_create).
  *   - caller owns every host buffer; arrays are row-major C-contiguous float64 / int64.
- *   - `_dev` variants take DEVICE pointers (e.g. torch.Tensor.data_ptr()) valid on the handle's
- *     device; they enqueue on the handle's stream and are synchronous on return only where an
- *     output lands in a host buffer (top-k, status).
+ *   - `_dev` variants take DEVICE pointers (e.g. torch.Tensor.data_ptr()) valid on the handle's device; they enqueue on the handle's stream and are synchronous
+ *     on return only where an output lands in a host buffer (top-k, status).
  *   - a handle is not re-entrant; distinct handles may be driven from distinct threads.
  *   - a handle owns up to four HIP streams (its own or the caller's + three side streams created on first need); a process
  *     that keeps several handles alive should export GPU_MAX_HW_QUEUES=8 BEFORE its first HIP call, or work meant to overlap
@@ -25,7 +23,6 @@
 extern "C" {
 #endif
 typedef struct gpx_handle gpx_handle;
-
 enum gpx_status {
     GPX_OK = 0,
     GPX_EARG = -1,    /* bad argument */
@@ -35,7 +32,6 @@ enum gpx_status {
     GPX_ESTATE = -5,  /* call order error (e.g. sweep before fit) */
     GPX_ERCCL = -6    /* RCCL could not be loaded, or a collective failed; see gpx_comm_last_error */
 };
-
 /* covariance functions; parametrisation (sn2, rho, ell[d], bias) = the arguments of
  * reggie.make_gp(sn2, rho, ell, bias)                       [pybo/bayesopt.py:98-105] */
 enum gpx_kernel {
@@ -44,7 +40,6 @@ enum gpx_kernel {
     GPX_KERN_MATERN32 = 2, /* rho * (1 + sqrt3 r) exp(-sqrt3 r) */
     GPX_KERN_MATERN12 = 3  /* rho * exp(-r) */
 };
-
 /* acquisition functions evaluated by the sweep */
 enum gpx_acq {
     GPX_ACQ_EI = 0,   /* model.get_improvement(target, X)  [pybo/policies/simple.py:25]  params = {target} */
@@ -85,19 +80,17 @@ int gpx_version(void);
  *   "grad_form"      gpx_predict WITH gradients: 0 auto (one point: one pass over T with 1 + d right-hand sides; batches: two
  *                    passes), 1 always two passes, 2 always one; the forms agree to rounding [0]
  *   "grad_kernel"    triangular matvec of the two-pass form: -1 auto, 0 one wave per row, 1 register-blocked [-1]
- *   "chol_tg"        1: the factorisation is ONE persistent task-graph kernel for fits of "chol_tg_min" (2) .. "chol_tg_max" (160)
- *                    128-blocks; 0: the stream schedule (~250 launches over four streams) [1].  "chol_tg_db" -1 / 0 / 1: one workgroup per
- *                    CU with two k-step images of LDS up to "chol_tg_db_max" (112) blocks / never / always [-1]; "chol_tg_fuse" 1: a
- *                    column's solve and the final chunk of the tile below it are one task [1]; "chol_tg_tmo_ms": bound of every spin
- *                    -- on expiry the fit re-runs on the stream schedule and says so on stderr [2000]
+ *   "chol_tg"        1: the factorisation is ONE persistent task-graph kernel for fits of "chol_tg_min" (2) .. "chol_tg_max" (160) 128-blocks; 0: the stream
+ *                    schedule (~250 launches over four streams) [1].  "chol_tg_db" -1 / 0 / 1: one workgroup per CU with two k-step images of LDS up to
+ *                    "chol_tg_db_max" (112) blocks / never / always [-1]; "chol_tg_fuse" 1: a column's solve and the final chunk of the tile below it are one
+ *                    task [1]; "chol_tg_tmo_ms": bound of every spin -- on expiry the fit re-runs on the stream schedule and says so on stderr [2000]
  *   "chol_w", "chol_rl", "chol_merge", "chol_fuse", "chol_graph"   the stream schedule: outer panel width in blocks (2..8, 0 = by
  *                    size), right- / left-looking in-panel updates [1], far updates of two panels in one pass [1], diagonal block
  *                    factored inside the panel solve [0], replay from a captured hipGraph [0]
- * Diagnostic knobs ("chol_tg_chunks", "chol_tg_nap", "chol_tg_grid", "chol_tg_isolate", "chol_tg_trace", "grad_rb_cs", "x_rff",
- * "x_bg*", "x_skip" -- the last one leaves parts of the factorisation OUT) exist only in a library built with -DGPX_DIAGNOSTICS
- * (pybo_amd/csrc/libgpx_diag.so; pybo_amd/csrc/gpx_diag.h); the shipping library answers them with GPX_EARG.
- * Environment: GPX_OPTIONS="name=value,name=value" applies options to every handle at creation (A/B runs through a plug-in layer
- * whose handles the caller never sees); a bad entry fails gpx_create with GPX_EARG. */
+ * Diagnostic knobs ("chol_tg_chunks", "chol_tg_nap", "chol_tg_grid", "chol_tg_isolate", "chol_tg_trace", "grad_rb_cs", "x_rff", "x_bg*", "x_skip" -- the last
+ * one leaves parts of the factorisation OUT) exist only in a library built with -DGPX_DIAGNOSTICS (pybo_amd/csrc/libgpx_diag.so; pybo_amd/csrc/gpx_diag.h); the
+ * shipping library answers them with GPX_EARG. Environment: GPX_OPTIONS="name=value,name=value" applies options to every handle at creation (A/B runs through a
+ * plug-in layer whose handles the caller never sees); a bad entry fails gpx_create with GPX_EARG. */
 int gpx_set_option(gpx_handle *h, const char *name, int64_t value);
 
 /* ---- GP fit = model.add_data(X, Y)            [pybo/bayesopt.py:114,258,269] ------------- */
@@ -109,30 +102,26 @@ int gpx_fit(gpx_handle *h, const double *X, int64_t N, int64_t d, const double *
 int gpx_fit_dev(gpx_handle *h, const double *dX, int64_t N, int64_t d, const double *dy, int kernel_id, const double *ell, double rho, double sn2, double bias);
 /* log marginal likelihood of the fit, -1/2 a.a - sum log R_ii - N/2 log 2pi: what reggie.MCMC [pybo/bayesopt.py:115] evaluates once per proposal */
 int gpx_loglik(gpx_handle *h, double *out);
-/* The same for B hyper-parameter vectors at once on the handle's RESIDENT data, without touching the handle's own fit: hypers
- * (B, d + 3) row-major [sn2, rho, ell_1..d, bias] (the argument order of reggie.make_gp, pybo/bayesopt.py:105), out (B,); -inf
- * where K + sn2 I is not positive definite.  One batched launch chain and one host synchronisation per 64 vectors: what
- * reggie.MCMC(model, n=10, burn=100) [pybo/bayesopt.py:115] repeats per proposal. */
+/* The same for B hyper-parameter vectors at once on the handle's RESIDENT data, without touching the handle's own fit: hypers (B, d + 3) row-major [sn2, rho,
+ * ell_1..d, bias] (the argument order of reggie.make_gp, pybo/bayesopt.py:105), out (B,); -inf where K + sn2 I is not positive definite.  One batched launch
+ * chain and one host synchronisation per 64 vectors: what reggie.MCMC(model, n=10, burn=100) [pybo/bayesopt.py:115] repeats per proposal. */
 int gpx_loglik_batch(gpx_handle *h, int64_t B, const double *hypers, double *out);
 /* L = gpx_loglik (loglik may be NULL) and its gradient, grad (d + 3), in the order [sn2, rho, ell_1..d, bias] of gpx_loglik_batch's rows
  * (natural parameters): what maximum-likelihood / MAP fitting of the hyper-parameters asks for.  From the fitted handle's T, alpha and
  * scaled inputs: N^3/3 multiply-adds on the tile engine, one host synchronisation, no atomics (same fit, same bits); fit and sweep cache untouched. */
 int gpx_loglik_grad(gpx_handle *h, double *loglik, double *grad);
-/* Incremental fit: absorb ONE more observation x (d,), y into the current factorisation in O(N^2) (two memory-bound passes over
- * T and U) instead of refitting -- the per-iteration `model.add_data(x, y)` of the BO loop [pybo/bayesopt.py:269].  A full
- * 128-block is extended inside buffers allocated with head-room (device copy, no refit).  GPX_ENOTPD like gpx_fit.  A live sweep
- * cache (below) is corrected for the new observation in the same call (one N*M pass). */
+/* Incremental fit: absorb ONE more observation x (d,), y into the current factorisation in O(N^2) (two memory-bound passes over T and U) instead of refitting
+ * -- the per-iteration `model.add_data(x, y)` of the BO loop [pybo/bayesopt.py:269].  A full 128-block is extended inside buffers allocated with head-room
+ * (device copy, no refit).  GPX_ENOTPD like gpx_fit.  A live sweep cache (below) is corrected for the new observation in the same call (one N*M pass). */
 int gpx_append(gpx_handle *h, const double *x, double y);
-/* ANNOUNCE the next observation's location before its value exists (between `x, _ = solver(index, bounds)` and
- * `y = objective(x)`, pybo/bayesopt.py:265-268: the time the reference spends idle): everything of the coming gpx_append(h, x, y)
- * that does not depend on y is enqueued now without a host synchronisation -- k(X, x), the two triangular passes and, on a side
- * stream, the N*M covariance evaluations of the sweep-cache correction.  A following gpx_append with the bit-identical x then costs
- * O(N + M); any other x, or a model change, and the announcement is ignored.  Results bit-identical to an unannounced append.
+/* ANNOUNCE the next observation's location before its value exists (between `x, _ = solver(index, bounds)` and `y = objective(x)`, pybo/bayesopt.py:265-268:
+ * the time the reference spends idle): everything of the coming gpx_append(h, x, y) that does not depend on y is enqueued now without a host synchronisation --
+ * k(X, x), the two triangular passes and, on a side stream, the N*M covariance evaluations of the sweep-cache correction.  A following gpx_append with the
+ * bit-identical x then costs O(N + M); any other x, or a model change, and the announcement is ignored.  Results bit-identical to an unannounced append.
  * GPX_ESTATE (nothing started, not an error) without a live sweep cache or when the next append has to add a 128-block first. */
 int gpx_append_begin(gpx_handle *h, const double *x);
 /* 0-based index of the failing pivot of the last GPX_ENOTPD fit, else -1. */
 int64_t gpx_fail_pivot(const gpx_handle *h);
-
 /* introspection for parity tests (host outputs): which = 0: L (N,N) lower Cholesky factor, row-major (K + sn2 I = L L^T);
  * 1: T = L^-1 (N,N) lower; 2: K + sn2 I, upper triangle (only after gpx_fit_stage(.., 1): the factorisation consumes it) */
 int gpx_get_matrix(gpx_handle *h, int which, double *out);
@@ -140,7 +129,6 @@ int gpx_get_matrix(gpx_handle *h, int which, double *out);
 int gpx_get_vectors(gpx_handle *h, double *a, double *alpha);
 int gpx_fit_stage(gpx_handle *h, const double *X, int64_t N, int64_t d, const double *y,
                   int kernel_id, const double *ell, double rho, double sn2, double bias, int stage);
-
 /* posterior (latent) mean at the N observed points, closed form y - sn2*alpha = model.predict(X_obs)[0] [pybo/policies/simple.py:21,35] */
 int gpx_mean_at_obs(gpx_handle *h, double *mu_host, double *mu_max);
 /* posterior (latent) variance at the N observed points, closed form sn2 - sn2^2 [K^-1]_ii with [K^-1]_ii = sum_m U[i][m]^2 (one HBM-read pass over
@@ -148,7 +136,6 @@ int gpx_mean_at_obs(gpx_handle *h, double *mu_host, double *mu_max);
 int gpx_var_at_obs(gpx_handle *h, double *s2_host);
 /* rows (a multiple of 128) the factor buffers are allocated for: 4 matrices of capacity^2 doubles stay on the device until gpx_destroy (size pools by it) */
 int64_t gpx_capacity(const gpx_handle *h);
-
 /* ---- posterior moments = model.predict(X, grad) [pybo/policies/simple.py:64] ------------- */
 /* Xc (M,d) -> mu (M,), s2 (M,) latent variance; dmu, ds2 (M,d) optional (NULL to skip).  With gradients a single point
  * (M = 1) is answered in the one-pass form, batches in the two-pass form: option "grad_form" above. */
@@ -243,6 +230,20 @@ int gpx_constrained_sweep(gpx_handle *obj, gpx_handle *const *cons, int nc, cons
                           const double *Xc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *acq_all, double *pof_all);
 int gpx_constrained_sweep_dev(gpx_handle *obj, gpx_handle *const *cons, int nc, const double *thr, int acq_id, const double *params, int nparams,
                               const double *dXc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *d_acq_all, double *d_pof_all);
+/* ---- two objectives, maximised: expected hypervolume improvement (Emmerich et al. 2011; Yang et al. 2019) of independent posteriors over the front of the raw
+ *      points P (np, 2), 0 <= np <= 4096, above the reference point ref (2); P, ref finite, on the HOST in every variant.  Points not strictly above ref,
+ *      weakly dominated ones and duplicates are dropped; at most 1024 may remain (else GPX_EARG); np = 0: an empty front.  With the n survivors by f1
+ *      ascending, a_0 = ref[0], a_i = f1_i, b_i = f2_{i+1}, b_n = ref[1]: value = sum_{i=0..n} max(EI_1(a_i) - EI_1(a_{i+1}), 0) EI_2(b_i), EI_1(a_{n+1}) := 0,
+ *      EI_j(t) the bits of gpx_sweep(GPX_ACQ_EI, {t}) on f_j; from +0.0, in strip order, every product rounded.  f1 != f2 fitted (GPX_ESTATE) on ONE device,
+ *      same d; f1 (the lead) owns scratch, error text and top-k pairs.  Never pruned; a member's live sweep cache: as gpx_sweep_dev of it.  acq_all optional;
+ *      d_mom (optional, (4, M) device): mu1, s2_1, mu2, s2_2 as the fold read them.  gpx_ehvi_fold_dev: the fold + top-k alone on the caller's moments (e.g.
+ *      of two gpx_sweep_update_dev), on lead's stream. */
+int gpx_ehvi_sweep(gpx_handle *f1, gpx_handle *f2, const double *P, int np, const double *ref, const double *Xc, int64_t M, int64_t k,
+                   double *top_val, int64_t *top_idx, double *acq_all);
+int gpx_ehvi_sweep_dev(gpx_handle *f1, gpx_handle *f2, const double *P, int np, const double *ref, const double *dXc, int64_t M, int64_t k,
+                       double *top_val, int64_t *top_idx, double *d_acq_all, double *d_mom);
+int gpx_ehvi_fold_dev(gpx_handle *lead, const double *d_mom, int64_t M, const double *P, int np, const double *ref, int64_t k,
+                      double *top_val, int64_t *top_idx, double *d_acq_all);
 
 /* ---- candidate grid generated and kept in HBM = the solver's grid xgrid = init_uniform(bounds, ngrid, rng) [pybo/solvers/lbfgs.py:45;
  *      pybo/inits/methods.py:24-38] or a Sobol' grid [pybo/inits/methods.py:62-77] without the host array and its PCIe upload; pass gpx_grid_data() to
@@ -273,21 +274,20 @@ int gpx_comm_init(gpx_handle *h, int rank, int nranks, const unsigned char *id, 
 int gpx_comm_destroy(gpx_comm *c);
 int gpx_comm_size(const gpx_comm *c, int *rank, int *nranks);
 const char *gpx_comm_last_error(void);
-/* All-gather of the n (value, index) pairs the handle's LAST sweep left in HBM (n = its k for gpx_sweep* / gpx_ensemble_sweep* / gpx_constrained_sweep*
- * (the lead), S*k for gpx_rff_sweep*), taken straight from the device, `index_offset` (this rank's shard origin) added to every valid index.
+/* All-gather of the n (value, index) pairs the handle's LAST sweep left in HBM (n = its k for gpx_sweep* / gpx_ensemble_sweep* / gpx_constrained_sweep* /
+ * gpx_ehvi_* (the lead), S*k for gpx_rff_sweep*), taken straight from the device, `index_offset` (this rank's shard origin) added to every valid index.
  *   k > 0: every rank receives the same merged k best in out_val[k], out_idx[k] = the global argsort(finit)[::-1][:k] of pybo/solvers/lbfgs.py:51 over
  *          the sharded grid.
  *   k = 0: no merge; out_val / out_idx receive all nranks*n pairs in rank order (batch-BO: one recommendation per Thompson draw, draws sharded over ranks). */
 int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, double *out_val, int64_t *out_idx);
 
 /* ---- measurement ------------------------------------------------------------------------ */
-/* Stage timers in milliseconds accumulated since the last reset (HIP events on the handle's stream): [0] gram [1] cholesky
- * [2] trtri [3] alpha [4] cross_gram [5] sweep_trmm [6] acq_topk [7] rff [8] sweep_trmm launches [9] sweep_trmm algorithmic flop
- * [10] h2d/d2h copies [11] append [12] correction passes over the sweep cache [13] the Thompson sweep kernel alone (part of [7])
- * [14] its algorithmic fp64 lane operations, S n (d + 20) M per launch [15] fits whose task-graph factorisation gave up and re-ran on
- * the stream schedule [16] the shader clock in MHz the sweep_trmm launches sustained (their workgroups' s_memtime over s_memrealtime
- * ticks) [17] the same for the Thompson sweep kernel [18] inversions whose leading part ran behind the factorisation ("trtri_ahead":
- * for those [2] holds only what was left after the factor was done) [19] bound pass of selection-only sweeps [20] batch selection
+/* Stage timers in milliseconds accumulated since the last reset (HIP events on the handle's stream): [0] gram [1] cholesky [2] trtri [3] alpha [4] cross_gram
+ * [5] sweep_trmm [6] acq_topk [7] rff [8] sweep_trmm launches [9] sweep_trmm algorithmic flop [10] h2d/d2h copies [11] append [12] correction passes over the
+ * sweep cache [13] the Thompson sweep kernel alone (part of [7]) [14] its algorithmic fp64 lane operations, S n (d + 20) M per launch [15] fits whose
+ * task-graph factorisation gave up and re-ran on the stream schedule [16] the shader clock in MHz the sweep_trmm launches sustained (their workgroups'
+ * s_memtime over s_memrealtime ticks) [17] the same for the Thompson sweep kernel [18] inversions whose leading part ran behind the factorisation
+ * ("trtri_ahead": for those [2] holds only what was left after the factor was done) [19] bound pass of selection-only sweeps [20] batch selection
  * (gpx_[ensemble_]sweep_batch) [21] joint posterior (gpx_predict_cov / gpx_sample_joint: all between their copies).  Synchronises; returns slots written. */
 int gpx_timers(gpx_handle *h, double *out, int n, int reset);
 /* 1 when the library was built with -DGPX_DIAGNOSTICS (the diagnostic options above are accepted), else 0 */

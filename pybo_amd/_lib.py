@@ -96,6 +96,9 @@ SYMBOLS = {
     'gpx_ensemble_predict': (C.c_int, [_P, C.c_int, _P, _i64, _P, _P, _P, _P]),
     'gpx_constrained_sweep': (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P]),
     'gpx_constrained_sweep_dev': (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P]),
+    'gpx_ehvi_sweep': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _i64, _i64, _P, _P, _P]),
+    'gpx_ehvi_sweep_dev': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _i64, _i64, _P, _P, _P, _P]),
+    'gpx_ehvi_fold_dev': (C.c_int, [_P, _P, _i64, _P, C.c_int, _P, _i64, _P, _P, _P]),
     'gpx_grid_create': (C.c_int, [C.c_int, C.c_int, _P, _i64, _i64, C.c_uint64, _i64, _P, C.c_int, C.POINTER(_P)]),
     'gpx_grid_data': (_P, [_P]),
     'gpx_grid_rows': (C.c_int, [_P, _P, _i64, _P]),
@@ -771,6 +774,45 @@ class Engine(object):
         lead._check(lead._lib.gpx_constrained_sweep(oh, handles, len(cons), _ptr(thr), aid, _ptr(params), nparams, _ptr(Xc), M, k,
                                                     _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out), _ptr(pof)))
         return dict(top_val=tv, top_idx=ti, acq=out, pof=pof)
+
+    @staticmethod
+    def _front_args(front, ref):
+        front = np.ascontiguousarray(_f64(front if front is not None else np.empty((0, 2))).reshape(-1, 2))
+        ref = np.ascontiguousarray(_f64(ref).reshape(-1))
+        if len(ref) != 2:
+            raise ValueError('the reference point has two coordinates')
+        return front, ref
+
+    @staticmethod
+    def ehvi_sweep(f1, f2, front, ref, Xc, k=0, want_all=True, d_acq=None, d_mom=None):
+        """Two-objective sweep (gpx_ehvi_sweep[_dev]): the expected hypervolume improvement of the engines `f1`, `f2` over the raw points
+        `front` (np, 2) above `ref` (2), both host arrays.  `Xc`: host array (M, d) or a DeviceGrid (then d_acq / d_mom: optional device
+        pointers of an (M,) and a (4, M) array: mu1, s2_1, mu2, s2_2).  Returns dict(top_val, top_idx, acq); f1 (the lead) raises the errors."""
+        front, ref = Engine._front_args(front, ref)
+        tv = np.empty(k)
+        ti = np.empty(k, dtype=np.int64)
+        fp = _ptr(front) if len(front) else None
+        if isinstance(Xc, DeviceGrid):
+            f1._check(f1._lib.gpx_ehvi_sweep_dev(f1._h, f2._h, fp, len(front), _ptr(ref), Xc.ptr, len(Xc), k, _ptr(tv) if k else None,
+                                                 _ptr(ti) if k else None, _P(d_acq) if d_acq else None, _P(d_mom) if d_mom else None))
+            return dict(top_val=tv, top_idx=ti, acq=None)
+        Xc = _f64(Xc).reshape(-1, f1.d)
+        M = len(Xc)
+        out = np.empty(M) if want_all else None
+        f1._check(f1._lib.gpx_ehvi_sweep(f1._h, f2._h, fp, len(front), _ptr(ref), _ptr(Xc), M, k, _ptr(tv) if k else None,
+                                         _ptr(ti) if k else None, _ptr(out)))
+        return dict(top_val=tv, top_idx=ti, acq=out)
+
+    def ehvi_fold(self, d_mom, M, front, ref, k=0, d_acq=None):
+        """The fold and the top-k of a two-objective sweep alone (gpx_ehvi_fold_dev) on this engine's stream: `d_mom` the device pointer of
+        a (4, M) array mu1, s2_1, mu2, s2_2 (e.g. of two `sweep_update` calls), `d_acq` an optional device pointer of (M,) values.
+        Returns dict(top_val, top_idx)."""
+        front, ref = Engine._front_args(front, ref)
+        tv = np.empty(k)
+        ti = np.empty(k, dtype=np.int64)
+        self._check(self._lib.gpx_ehvi_fold_dev(self._h, _P(d_mom), int(M), _ptr(front) if len(front) else None, len(front), _ptr(ref), k,
+                                                _ptr(tv) if k else None, _ptr(ti) if k else None, _P(d_acq) if d_acq else None))
+        return dict(top_val=tv, top_idx=ti)
 
     def constrained_prune_report(self, vectors=True):
         """Diagnostic (gpx_constrained_prune_report in csrc/gpx_diag.h): what the last constrained sweep led by this engine decided about

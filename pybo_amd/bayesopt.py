@@ -306,7 +306,7 @@ def array2str(a):
 
 
 def _report(i, x, y, xbest):
-    if np.ndim(y) > 0:                   # a constrained objective returns (f, c_1 .. c_J): the line shows f
+    if np.ndim(y) > 0:                   # a constrained objective returns (f, c_1 .. c_J), a two-objective one (f1, f2): the line shows the first
         y = np.ravel(y)[0]
     print('i={:s}, x={:s}, y={:s}, xbest={:s}'.format(int2str(i), array2str(x), float2str(y),
                                                      array2str(xbest)))

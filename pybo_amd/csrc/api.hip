@@ -15,6 +15,7 @@
 #include "gpx_internal.h"
 #include "gpx_diag.h"
 #include "acq_core.h"
+#include "ehvi_math.h"
 #include "mes_math.h"
 #include "kg_math.h"
 
@@ -250,7 +251,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // 670: GPX_ACQ_MES = 16 (max-value entropy search: gpx_sweep*, gpx_sweep_update*, gpx_ensemble_sweep*; params = the sampled maxima).
 // 680: GPX_ACQ_KG = 32 (knowledge gradient over a support set: gpx_sweep*; params = the support coordinates) and gpx_kg_grad.
 // 690: gpx_constrained_sweep[_dev] (EI / PI times the probability of feasibility of up to 16 constraint models), gpx_constrained_prune_report.
-extern "C" int gpx_version(void) { return 690; }
+// 700: gpx_ehvi_sweep[_dev], gpx_ehvi_fold_dev (expected hypervolume improvement of two objectives over a Pareto front).
+extern "C" int gpx_version(void) { return 700; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -359,7 +361,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dcon, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dcon, h->dehvi, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -2420,6 +2422,132 @@ extern "C" int gpx_constrained_prune_report(gpx_handle* lead, double* scal, int 
         }
         for (int i = 0; i < nscal && i < 11; ++i) scal[i] = out[i];
         return report_vectors(h, r, ub, idx, cap_idx);
+    });
+}
+
+// ---- two-objective sweep: expected hypervolume improvement over a Pareto front ----
+// The front's part of every refusal, and the strips (ehvi_math.h: a then b, n + 2 doubles each) the fold reads.  Touches no handle but
+// the lead's error text.
+static int ehvi_front(gpx_handle* L, const char* what, const double* P, int np, const double* ref, std::vector<double>& strips, int& n) {
+    const std::string w(what);
+    if (!ref || !std::isfinite(ref[0]) || !std::isfinite(ref[1])) return fail(L, GPX_EARG, (w + ": the reference point must be two finite doubles").c_str());
+    if (np < 0 || np > EHVI_MAX_RAW) return fail(L, GPX_EARG, (w + ": takes 0 to 4096 raw front points").c_str());
+    if (np > 0 && !P) return fail(L, GPX_EARG, (w + ": NULL front").c_str());
+    for (int i = 0; i < 2 * np; ++i)
+        if (!std::isfinite(P[i])) return fail(L, GPX_EARG, (w + ": the front must be finite").c_str());
+    std::vector<double> a((size_t)np + 2), b((size_t)np + 2, 0.0);
+    n = ehvi_strips(P, np, ref, a.data(), b.data());
+    if (n > EHVI_MAX_FRONT) return fail(L, GPX_EARG, (w + ": more than 1024 non-dominated points above the reference point").c_str());
+    strips.assign((size_t)2 * (n + 2), 0.0);
+    std::copy(a.begin(), a.begin() + n + 2, strips.begin());
+    std::copy(b.begin(), b.begin() + n + 1, strips.begin() + n + 2);
+    return GPX_OK;
+}
+
+// every refusal of gpx_ehvi_sweep[_dev], before anything touches a handle's fit, cache or queue (f1 is not NULL)
+static int ehvi_check(gpx_handle* f1, gpx_handle* f2, const double* P, int np, const double* ref, const double* Xc, int64_t M, int64_t k,
+                      const double* top_val, const int64_t* top_idx, std::vector<double>& strips, int& n) {
+    if (!f2) return fail(f1, GPX_EARG, "ehvi_sweep: NULL handle");
+    if (f1 == f2) return fail(f1, GPX_EARG, "ehvi_sweep: the two objectives need a handle each");
+    int rc;
+    if ((rc = ehvi_front(f1, "ehvi_sweep", P, np, ref, strips, n))) return rc;
+    if (!Xc || M < 1) return fail(f1, GPX_EARG, "ehvi_sweep: need M >= 1 candidates");
+    if ((rc = check_topk(f1, "ehvi_sweep", k, top_val, top_idx))) return rc;
+    if (!f1->fitted || !f2->fitted) return fail(f1, GPX_ESTATE, "ehvi_sweep: an objective's model is not fitted");
+    if (f1->device != f2->device || f1->d != f2->d) return fail(f1, GPX_EARG, "ehvi_sweep: the handles must share the device and the input dimension");
+    return GPX_OK;
+}
+
+// the lead's workspace for M candidates and a front of n points
+static int ehvi_layout(gpx_handle* L, int64_t M, int n, EhviWs& w) {
+    if (int rc = ensure(L, L->dehvi, L->cap_ehvi, ehvi_ws(WsCarver(nullptr), M, n).bytes / 8)) return rc;
+    w = ehvi_ws(WsCarver(L->dehvi), M, n);
+    return GPX_OK;
+}
+
+// The fold and the top-k on the lead's stream: mom (4, M) device moments, strips as ehvi_front left them.  Synchronises.
+static int ehvi_fold_core(gpx_handle* L, const EhviWs& w, const double* d_mom, int64_t M, const std::vector<double>& strips, int n, int64_t k,
+                          double* top_val, int64_t* top_idx, double* d_out) {
+    hipStream_t s = L->stream;
+    double* const out = d_out ? d_out : w.out;
+    {
+        Span sp(L, T_COPY);
+        // (pageable host memory: the copy has read it before it returns; a and b are adjacent in the walk)
+        HIPCHK(L, hipMemcpyAsync(w.a, strips.data(), strips.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    {
+        Span sp(L, T_ACQ);
+        launch_ehvi_fold(s, d_mom, M, w.a, n, out);
+    }
+    if (k > 0) {
+        if (int rc = topk_core(L, out, M, k, top_val, top_idx)) return rc;
+    } else {
+        HIPCHK(L, hipStreamSynchronize(s));
+    }
+    HIPCHK(L, hipGetLastError());
+    return GPX_OK;
+}
+
+// (arguments checked by ehvi_check)  Each member's plain sweep leaves its moments in HBM -- a live sweep cache is re-seeded exactly as
+// gpx_sweep_dev of that member would -- then the fold.  Never pruned: the caller of sweep_core reads mu and s2.
+static int ehvi_core(gpx_handle* f1, gpx_handle* f2, const std::vector<double>& strips, int n, const double* dXc, int64_t M, int64_t k,
+                     double* top_val, int64_t* top_idx, double* d_out, double* d_mom) {
+    gpx_handle* L = f1;
+    int rc;
+    HIPCHK(L, hipSetDevice(L->device));
+    EhviWs w;
+    if ((rc = ehvi_layout(L, M, n, w))) return rc;
+    double* const mom = d_mom ? d_mom : w.mom;
+    gpx_handle* const hs[2] = {f1, f2};
+    for (int j = 0; j < 2; ++j) {
+        gpx_handle* h = hs[j];
+        if ((rc = sweep_core(h, GPX_ACQ_MEAN, nullptr, 0, dXc, M, 0, nullptr, nullptr, nullptr, mom + (2 * j) * M, mom + (2 * j + 1) * M))) {
+            if (h != L) L->err = "objective 2: " + h->err;
+            return rc;
+        }
+        HIPCHK(L, hipStreamSynchronize(h->stream));      // the fold runs on the lead's stream
+    }
+    return ehvi_fold_core(L, w, mom, M, strips, n, k, top_val, top_idx, d_out);
+}
+
+extern "C" int gpx_ehvi_sweep_dev(gpx_handle* f1, gpx_handle* f2, const double* P, int np, const double* ref, const double* dXc, int64_t M,
+                                  int64_t k, double* top_val, int64_t* top_idx, double* d_acq_all, double* d_mom) {
+    if (!f1) return GPX_EARG;
+    return guarded(f1, [&]() -> int {
+        std::vector<double> strips;
+        int n = 0;
+        if (int rc = ehvi_check(f1, f2, P, np, ref, dXc, M, k, top_val, top_idx, strips, n)) return rc;
+        return ehvi_core(f1, f2, strips, n, dXc, M, k, top_val, top_idx, d_acq_all, d_mom);
+    });
+}
+
+extern "C" int gpx_ehvi_sweep(gpx_handle* f1, gpx_handle* f2, const double* P, int np, const double* ref, const double* Xc, int64_t M, int64_t k,
+                              double* top_val, int64_t* top_idx, double* acq_all) {
+    if (!f1) return GPX_EARG;
+    return guarded(f1, [&]() -> int {
+        std::vector<double> strips;
+        int n = 0;
+        if (int rc = ehvi_check(f1, f2, P, np, ref, Xc, M, k, top_val, top_idx, strips, n)) return rc;
+        // (true: the second objective reads the candidates from its own stream)
+        return staged_sweep(f1, Xc, M, true, acq_all, nullptr, nullptr, [&](double* dX, double* dacq, double*, double*) {
+            return ehvi_core(f1, f2, strips, n, dX, M, k, top_val, top_idx, dacq, nullptr);
+        });
+    });
+}
+
+extern "C" int gpx_ehvi_fold_dev(gpx_handle* lead, const double* d_mom, int64_t M, const double* P, int np, const double* ref, int64_t k,
+                                 double* top_val, int64_t* top_idx, double* d_acq_all) {
+    if (!lead) return GPX_EARG;
+    return guarded(lead, [&]() -> int {
+        std::vector<double> strips;
+        int n = 0, rc;
+        if ((rc = ehvi_front(lead, "ehvi_fold", P, np, ref, strips, n))) return rc;
+        if (!d_mom || M < 1) return fail(lead, GPX_EARG, "ehvi_fold: need the moments of M >= 1 candidates");
+        if ((rc = check_topk(lead, "ehvi_fold", k, top_val, top_idx))) return rc;
+        HIPCHK(lead, hipSetDevice(lead->device));
+        EhviWs w;
+        if ((rc = ehvi_layout(lead, M, n, w))) return rc;
+        return ehvi_fold_core(lead, w, d_mom, M, strips, n, k, top_val, top_idx, d_acq_all);
     });
 }
 

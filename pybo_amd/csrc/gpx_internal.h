@@ -155,6 +155,8 @@ struct gpx_handle {
     int64_t cap_ens = 0;
     double* dcon = nullptr;   // constrained sweep: one constraint's probabilities + the running product (con_ws)
     int64_t cap_con = 0;
+    double* dehvi = nullptr;  // two-objective sweep: the members' four moment vectors, the values, the front's strips (ehvi_ws)
+    int64_t cap_ehvi = 0;
     int prune = -1;          // option: selection-only sweeps skip candidates whose EI bound cannot reach the top-k (-1 by size and gate, 0 never, 1 wherever legal)
     char* dprune = nullptr;   // their workspace (one allocation: prune_ws_layout)
     int64_t cap_prune = 0;    // ... in bytes
@@ -466,6 +468,8 @@ void launch_ens_accum(hipStream_t s, double* acc0, double* acc1, const double* t
 void launch_ens_finish(hipStream_t s, const double* acc0, const double* acc1, int64_t M, int mode, double n,
                        double beta, double* out, double* mu_out, double* s2_out);
 void launch_con_fold(hipStream_t s, double* v, double* w, const double* p, int64_t M, int first);
+// (kernels_ehvi.hip) mom (4, M): mu1, s2_1, mu2, s2_2; strips: a then b, n + 2 doubles each, n <= EHVI_MAX_FRONT
+void launch_ehvi_fold(hipStream_t s, const double* mom, int64_t M, const double* strips, int n, double* out);
 void launch_grid_sobol(hipStream_t s, const uint32_t* sv, int bits, int64_t first, int64_t M, int d,
                        const double* bounds, double* X);
 void launch_grid_uniform(hipStream_t s, uint64_t seed, int64_t first, int64_t M, int d, const double* bounds,

@@ -67,6 +67,15 @@ inline ConWs con_ws(WsCarver c, int64_t M) {
     return {c.take<double>(M, "t0"), c.take<double>(M, "out"), c.bytes()};
 }
 
+// the two-objective sweep's scratch (h->dehvi): the members' moments as k_ehvi_fold reads them ((4, M): mu1, s2_1, mu2, s2_2), the values
+// where the caller gave no vector for them, and the strips of a front of n points (a_0 .. a_{n+1}, then b_0 .. b_n and one word of padding)
+struct EhviWs { double *mom, *out, *a, *b; int64_t bytes; };
+inline EhviWs ehvi_ws(WsCarver c, int64_t M, int64_t n) {
+    double* const mom = c.take<double>(M, "mu1");
+    c.take<double>(M, "s2_1"), c.take<double>(M, "mu2"), c.take<double>(M, "s2_2");
+    return {mom, c.take<double>(M, "out"), c.take<double>(n + 2, "a"), c.take<double>(n + 2, "b"), c.bytes()};
+}
+
 // The matrix-pipe bound kernels' operands (kernels_sweep.hip: launch_bound_mfma), every one on a 32-byte boundary: the augmented rows
 // in KS k-steps, the weights, the norms where they go through the accumulator (nc; KS <= 4 there), the centre at its fixed place, then
 // the fp32 copies over Np + B32_ZROWS rows (W': the factorised walk's scaled weights).  Sized with KS = BM_KS_MAX, nc = false.

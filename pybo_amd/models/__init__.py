@@ -4,5 +4,6 @@ from .mcmc import MCMC                            # noqa: F401
 from .sharded import ShardedGP                    # noqa: F401
 from .optimize import optimize                    # noqa: F401
 from .constrained import Constrained              # noqa: F401
+from .multiobjective import MultiObjective        # noqa: F401
 
-__all__ = ['GP', 'make_gp', 'MCMC', 'ShardedGP', 'optimize', 'Constrained']
+__all__ = ['GP', 'make_gp', 'MCMC', 'ShardedGP', 'optimize', 'Constrained', 'MultiObjective']

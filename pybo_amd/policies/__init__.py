@@ -1,4 +1,4 @@
-"""Acquisition policies; the exported names match pybo.policies (`EI`, `PI`, `UCB`, `Thompson`), plus `MES`, `KG` and `CEI`."""
-from .simple import EI, PI, UCB, Thompson, MES, KG, CEI
+"""Acquisition policies; the exported names match pybo.policies (`EI`, `PI`, `UCB`, `Thompson`), plus `MES`, `KG`, `CEI` and `EHVI`."""
+from .simple import EI, PI, UCB, Thompson, MES, KG, CEI, EHVI
 
-__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES', 'KG', 'CEI']
+__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES', 'KG', 'CEI', 'EHVI']

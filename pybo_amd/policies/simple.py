@@ -15,12 +15,13 @@ New: when the model is the device-backed `pybo_amd.models.GP`, the returned inde
 `pybo_amd.solvers.solve_lbfgs` uses instead of `argsort(f(xgrid))` (pybo/solvers/lbfgs.py:50-51).
 Any other model (e.g. a test stub) gets plain closures, exactly as in the reference.  Every EI / PI / UCB index also
 carries `index.acq = (kind, param)` and, for models with `acq_batch`, `index.batch(xgrid, nb)` (pybo_amd/batch.py).
-`MES` (max-value entropy search), `KG` (knowledge gradient over a support set) and `CEI` (constrained expected improvement on a
-`models.Constrained`) are this build's own: the reference has none of them.
+`MES` (max-value entropy search), `KG` (knowledge gradient over a support set), `CEI` (constrained expected improvement on a
+`models.Constrained`) and `EHVI` (expected hypervolume improvement on a `models.MultiObjective`) are this build's own: the reference
+has none of them.
 """
 import numpy as np
 
-__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES', 'KG', 'CEI']
+__all__ = ['EI', 'PI', 'UCB', 'Thompson', 'MES', 'KG', 'CEI', 'EHVI']
 
 
 def _attach_topk(index, model, kind, param):
@@ -194,6 +195,33 @@ def CEI(model, _, X, xi=0.0, pmin=0.5):
     fast = getattr(model, 'acq_topk', None)
     if fast is not None and getattr(model, '_device_members', lambda: True)():
         index.topk = lambda xgrid, k: fast('cei', target, xgrid, k)
+        owner = getattr(model, 'topk_engine', None)
+        if owner is not None:
+            index.topk_engine = owner
+    return index
+
+
+def EHVI(model, bounds, X, ref=None):
+    """Expected hypervolume improvement (Emmerich et al. 2011) on a `models.MultiObjective`, both objectives maximised.  The front is
+    the posterior means of both objectives at the observed X; `ref` (2,) defaults to `F.min(0) - 0.1 span` with span = F.max(0) - F.min(0)
+    (1 where that is 0).  The index carries `.acq = ('ehvi', (front, ref))` and, for models with `acq_topk`, `.topk`; never `.batch`."""
+    from .. import pareto
+    model = model.copy()
+    if getattr(model, 'get_ehvi', None) is None:
+        raise TypeError('EHVI needs a model with get_ehvi(front, ref, X, grad); %s has none' % type(model).__name__)
+    X = np.array(X, ndmin=2, dtype=float)
+    front = np.asarray(model.predict_mean(X), dtype=float).reshape(-1, 2) if len(X) else np.empty((0, 2))
+    if ref is None:
+        ref = pareto.default_ref(front) if len(front) else np.zeros(2)
+    ref = np.array(ref, dtype=float).reshape(2)
+
+    def index(X, grad=False):
+        return model.get_ehvi(front, ref, X, grad)
+
+    index.acq = ('ehvi', (front, ref))
+    fast = getattr(model, 'acq_topk', None)
+    if fast is not None and getattr(model, '_device_members', lambda: True)():
+        index.topk = lambda xgrid, k: fast('ehvi', (front, ref), xgrid, k)
         owner = getattr(model, 'topk_engine', None)
         if owner is not None:
             index.topk_engine = owner

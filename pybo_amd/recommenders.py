@@ -2,13 +2,14 @@
 Recommenders (/root/reference/pybo/recommenders.py:14-35): where to point the user after each step.
 `best_latent` maximises the posterior mean starting from the observed points (through solve_lbfgs with
 `xgrid=X`), `best_incumbent` returns the observed point with the highest posterior mean.  `best_feasible` (this build's own,
-for `models.Constrained`) returns the best observed point that is probably feasible.
+for `models.Constrained`) returns the best observed point that is probably feasible; `best_pareto` (for `models.MultiObjective`) the
+observed point whose posterior mean contributes most to the hypervolume.
 """
 import numpy as np
 
 from . import solvers
 
-__all__ = ['best_latent', 'best_incumbent', 'best_feasible']
+__all__ = ['best_latent', 'best_incumbent', 'best_feasible', 'best_pareto']
 
 
 def best_latent(model, bounds, X):
@@ -46,3 +47,16 @@ def best_feasible(model, _, X, pmin=0.5):
     mean_only = getattr(model, 'predict_mean', None)
     mu = np.asarray(mean_only(X) if mean_only is not None else model.predict(X)[0], dtype=float)
     return X[int(np.argmax(np.where(ok & ~np.isnan(mu), mu, -np.inf)))]
+
+
+def best_pareto(model, _, X, ref=None):
+    """For a `models.MultiObjective`: the observed point whose posterior mean (both objectives) has the largest hypervolume
+    contribution over `ref` (default: the EHVI policy's, `pareto.default_ref` of the means); ties go to the lowest index.  The whole
+    non-dominated set is `model.pareto_set(X)`."""
+    from . import pareto
+    X = np.array(X, ndmin=2, dtype=float)
+    F = np.asarray(model.predict_mean(X), dtype=float).reshape(-1, 2)
+    if ref is None:
+        ref = pareto.default_ref(F)
+    contrib = pareto.hv_contributions(F, ref)
+    return X[int(np.argmax(np.where(np.isnan(contrib), -np.inf, contrib)))]
