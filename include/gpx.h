@@ -60,8 +60,7 @@ int gpx_create(int device, void *stream, gpx_handle **out);
 int gpx_destroy(gpx_handle *h);
 const char *gpx_last_error(const gpx_handle *h);
 int gpx_version(void);
-/* Options (int64 values).  Every option below selects among schedules that give BIT-IDENTICAL results unless it says
- * otherwise; defaults in brackets.  The measurements behind the defaults: DESIGN.md section 4.
+/* Options (int64 values), defaults in brackets: schedules that give BIT-IDENTICAL results unless an option says otherwise.  Measurements: DESIGN.md section 4.
  *   "chunk"          candidate columns per sweep chunk, a multiple of 128 [by size: 65536; 131072 up to N = 4096]
  *   "tile_order"     sweep-kernel schedule: bits 0-1 blockIdx->tile map (0 linear heavy-first, 1 per-XCD candidate slices, 2 per-XCD 8x8 super-tiles, 3 the
  *                    same with every workgroup computing the PAIR of tiles (nP-1-i, nt), (i, nt): equal work), bits 2-4 k-loop (4 = operands by LDS-DMA,
@@ -69,6 +68,7 @@ int gpx_version(void);
  *                    barrier-free, every wave fetching its own operand halves; 7 = k-step 16, three workgroups per CU; 6 / 5 / 2 = the register-staged loops
  *                    of rounds 5 / 2 / 1: independently scheduled witnesses) [-1 = by size: 7 below 32 block rows, else 19]
  *   "super_m"        rows of the XCD super-tile of 64 workgroups: 1, 2, 4, 8, 16 [8];  "sweep_cols": candidates per tile of k-loop 4: 128, 64, 32 [-1: by size]
+ *   "sweep_images"   LDS images of k-loop 4: 1 (two workgroups per CU), 2 (one per CU, the next k-step loads meanwhile) [-1: 2 where no CU would hold two]
  *   "sweep_cache"    1: full sweeps keep candidates and reduced sums for gpx_sweep_update; 0: leave a live cache alone; -1: drop it [0]
  *   "prune"          EI sweeps for ONLY the top-k (ensembles: members[0]'s value) skip what a bound rules out: -1 by size and gate, 0 never, 1 where legal [-1]
  *                    (-1: a sweep whose pruning paid lets the next of the same shape skip the gate: kept across fits / appends, dropped by ANY gpx_set_option)

@@ -161,6 +161,7 @@ static const Option kOptions[] = {
     {"prune_rows", DIAG, -1, 1000000, "prune_rows must be -1 (by size), 0 (no second bound) or a number of block rows", store<&gpx_handle::prune_rows>},
     {"sweep_cols", SHIP, -1, 128, "sweep_cols must be -1 (by size), 128, 64 or 32", store<&gpx_handle::sweep_cols>,
      [](int64_t v) { return v == -1 || v == 128 || v == 64 || v == 32; }},
+    {"sweep_images", SHIP, -1, 2, "sweep_images must be -1 (by size), 1 or 2", store<&gpx_handle::sweep_images>, [](int64_t v) { return v != 0; }},
     {"prune_seeds", DIAG, 0, 1000000, "prune_seeds must be 0 (by the rule) or a number of seeds", store<&gpx_handle::prune_seeds>},
     {"short_map", DIAG, -1, 1, "short_map must be -1 (by size), 0 (never) or 1 (wherever tile map 3 is in use)", store<&gpx_handle::short_map>},
     {"chol_w", SHIP, 0, 8, "chol_w must be 0 (by size) or in [2, 8]", store<&gpx_handle::chol_w>, [](int64_t v) { return v != 1; }},
@@ -1149,12 +1150,12 @@ static const double PRUNE_GATE_S2 = 1.0 / 64.0;
 // (measured on the headline workload against nP / 16 and nP / 8: profiles/prune_rows_ab.md),
 // tried where the first level left more than one generation of survivors -- an exact launch on wide tiles costs a whole generation
 // however few candidates it has, so at or below Gg survivors there is nothing to save (the rule was measured with wide tiles and is
-// left as it is: the narrow tiles of sweep_cols_of shorten launches of up to 1024 candidates) -- of at least PRUNE_MIN_M candidates over at least 32
+// left as it is: the narrow tiles of sweep_shape_of (sweep_map.h) shorten launches of up to 1024 candidates) -- of at least PRUNE_MIN_M candidates over at least 32
 // block rows: below those the prefix pass's launch chain and its sync are no small part of what it saves (the reasoning of
 // PRUNE_MIN_M / PRUNE_MIN_NP).  These conditions leave the single-bound accounting untouched at every shape
 // tests/test_gpu_prune_bound.py pins (prune = 1: M <= 13288 wherever nP >= 32; its larger M run at nP <= 20).
 static const int PRUNE_ROWS_MIN_NP = 32, PRUNE_ROWS_DIV = 4;
-// Seeds sized to the chip: where the seeds' exact launch can run on narrow tiles (kernels_sweep.hip, sweep_cols_of:
+// Seeds sized to the chip: where the seeds' exact launch can run on narrow tiles (sweep_map.h, sweep_shape_of:
 // the default schedule, option sweep_cols not 128) over at least 48 block rows and M >= PRUNE_MIN_M, G is the column count at which
 // the narrowest tile gives every compute unit one workgroup, not a wide generation.  The lower edge is 48 block rows, not the 32 from
 // which the default schedule runs: tests/test_gpu_prune_rows.py pins G, the seed list, tau and the launch accounting at N = 4096,
@@ -1351,7 +1352,8 @@ static int second_bound(gpx_handle* h, const PruneWs& w, int64_t chunk, int swee
             const int64_t cols = (valid + TBH - 1) / TBH * TBH;
             // 4a. rows [0, nR 128) of the survivors' cross-Gram panels and the sweep's tiles of those block rows
             launch_cross_gram(s, h->dXs, (int64_t)nR * NB, h->N, (int)h->d, w.Xg, j0, nsurv, cols, h->dinvell, h->kernel_id, h->rho, h->dKs, Np);
-            launch_sweep_trmm(s, h->dU, Np, nR, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk, h->short_map);      // (wide tiles)
+            launch_sweep_trmm(s, h->dU, Np, nR, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk, h->short_map,
+                              valid, h->sweep_cols, h->sweep_images);
             // 4b. ub2 = EI((bias + dot) + delta, fmax(rho - q_R, S2_FLOOR))
             launch_prune_ub2(s, h->dQp, chunk, nR, j0, valid, w.idx, w.dots, w.sc, h->rho, h->bias, p0, w.ub2, h->prune_keep ? w.qR : nullptr);
         }
@@ -1435,7 +1437,7 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
             {
                 Span sp(h, T_TRMM);
                 launch_sweep_trmm(s, h->dU, Np, nP, h->dKs, chunk, cols, h->da, h->dQp, h->dPp, chunk, sweep_order, h->super_m, h->dclk, h->short_map,
-                                  valid, h->sweep_cols);
+                                  valid, h->sweep_cols, h->sweep_images);
             }
             h->tacc[T_NLAUNCH] += 1.0;
             // ALGORITHMIC work of this launch: N^2 flop per candidate (N^2/2 multiply-adds of the

@@ -19,6 +19,7 @@
 //     gemm_tile_128_l   k-step 32 (or 16) through ONE LDS image: the sweep (two workgroups per CU), the triangular inverse, the
 //                       factorisation's workers at two workgroups per CU; optional skip of a triangular last k-block (TRI)
 //     gemm_tile_128_ld  two images, the next step's loads behind the first four MFMA groups: a workgroup alone on its CU
+//     gemm_tile_128_l2  gemm_tile_128_l<32> on two images (skip, order, narrow tiles and all): the sweep's short launches, one workgroup per CU
 //     gemm_tile_128_w   every WAVE keeps its own operand halves: no barrier at all (a witness of the sweep: it moves twice the bytes)
 //   operands through registers (rounds 1-5; kept as independently scheduled witnesses and for the Gram / RFF products):
 //     gemm_tile_128_s   k-step 32, buffer loads, banded priority, second fragment set (round 5's sweep)
@@ -651,6 +652,131 @@ __device__ __forceinline__ void gemm_tile_128_ld(d4 (&acc)[4][4], const double* 
     for (; kt + 1 < nk; ++kt) step(kt, std::true_type{});
     step(kt, std::false_type{});
     if (PRIO) __builtin_amdgcn_s_setprio(PRIO - 1);
+    __builtin_amdgcn_s_barrier();                                       // the caller may reuse LDS
+}
+
+// The SWEEP's loop for a workgroup that has its compute unit to itself: gemm_tile_128_l<32> with the two images and the one barrier
+// per step of gemm_tile_128_ld.  A short exact launch (at most one working workgroup per compute unit) has no partner workgroup to
+// cover the load-to-barrier latency the single-image loop leaves standing in every step; here the DMA of step t + 1 fills image
+// (t + 1) & 1 while step t is multiplied out of image t & 1.  The loads go out behind the step's first FG MFMA groups, 16 / FG
+// instructions at a time: FG = 4 as in gemm_tile_128_ld, but all 16 behind the first group of the narrowest tile, whose step is
+// so short that its loads must leave at once to have the rest of it to land (256 columns at N = 8192, 32 wide: 0.414 ms against
+// 0.444 / 0.428 with FG = 2 / 4; 64 wide: 0.531 with FG = 4 against 0.578 with 2 -- profiles/exact_launch_images_ab.md).  The
+// barrier that ends step t: every wave has finished reading image t & 1 (lgkmcnt) and its own rows of step t + 1 have landed (vmcnt).
+// ILV, TRI (the sequence I0 = 0, .., 0, 1, 2, 3; 3, 2, 1, 0, .. under REV), NEGA, AUX, REV, NJ and bcol as in gemm_tile_128_l: per
+// accumulator block the same MFMAs on the same operands in the same order along k -- the same bits.  Ends on a barrier with no LDS
+// read pending: the caller may reuse LDS.  smem: 2 x gemm_l_lds_f64<32>() doubles (147,456 B: one workgroup per CU).
+template <int PRIO = 1, int NSET = 2, bool ILV = false, bool TRI = false, bool NEGA = false, int AUX = 0, bool REV = false, int NJ = 4, int FG = (NJ == 1 ? 1 : 4)>
+__device__ __forceinline__ void gemm_tile_128_l2(d4 (&acc)[4][NJ], const double* __restrict__ A, int64_t lda,
+                                                 const double* __restrict__ B, int64_t ldb, int k_lo, int k_hi,
+                                                 double* smem, int bcol = 0) {
+    static_assert(NJ == 4 || NJ == 2 || NJ == 1, "a wave owns 4, 2 or 1 column groups");
+    static_assert(!TRI || ILV, "TRI needs the interleaved row blocks");
+    static_assert(FG == 1 || FG == 2 || FG == 4 || FG == 8, "the step's 16 DMA instructions in FG equal pieces");
+    constexpr int G = BK32 / 4;        // MFMA groups per step
+    constexpr int IMG = gemm_l_lds_f64<BK32>();
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = w >> 1, wn = w & 1;
+    const int nk = (k_hi - k_lo) / BK32;
+    if (nk <= 0) return;
+    const char* Abase = reinterpret_cast<const char*>(A + (int64_t)(REV ? k_hi - BK32 : k_lo) * lda);
+    const char* Bbase = reinterpret_cast<const char*>(B + (int64_t)(REV ? k_hi - BK32 : k_lo) * ldb);
+    const int64_t stepA = (REV ? -1 : 1) * (int64_t)BK32 * lda * 8, stepB = (REV ? -1 : 1) * (int64_t)BK32 * ldb * 8;
+    const int voA = (int)(((int64_t)w * lda + 2 * lane) * 8), voB = (int)(((int64_t)w * ldb + 2 * lane) * 8);
+    const int soA = (int)(4 * lda * 8), soB = (int)(4 * ldb * 8);      // four rows on: the SGPR offset of load p is p * so
+    // rows w + 4 p, p = p0 .. p1 - 1, of the step at Abase / Bbase into image img
+    auto issue = [&](int img, int p0, int p1) {
+        double* As = smem + img * IMG;
+        double* Bs = As + BK32 * LDT;
+        __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Abase, 0, -1, 0x00020000);
+        __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bbase, 0, -1, 0x00020000);
+#pragma unroll
+        for (int p = p0; p < p1; ++p) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (gemm_lds_ptr)(As + (w + 4 * p) * LDT), 16, voA, p * soA, 0, AUX);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (gemm_lds_ptr)(Bs + (w + 4 * p) * LDT), 16, voB, p * soB, 0, AUX);
+        }
+    };
+    auto bump = [&]() {
+        Abase += stepA;
+        Bbase += stepB;
+    };
+    const int fr = lane & 15, fk = lane >> 4;
+    constexpr int IST = ILV ? 32 : 16;                                  // row-block stride of a wave's A fragments
+    const int aoff = (ILV ? wm * 16 : wm * 64) + fr + fk * LDT;
+    const int boff = BK32 * LDT + bcol + wn * (16 * NJ) + fr + fk * LDT;
+    issue(0, 0, G);
+    bump();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                       // every wave's rows of the first step are in image 0
+    if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
+    int kt = 0;
+    // one k-step; I0: row blocks i < I0 are skipped (TRI); FILL: there is a next step, fetched meanwhile into the other image
+    auto step = [&](auto i0c, auto fillc) {
+        constexpr int I0 = decltype(i0c)::value;
+        constexpr bool FILL = decltype(fillc)::value;
+        const double* as = smem + (kt & 1) * IMG + aoff;
+        const double* bs = smem + (kt & 1) * IMG + boff;
+        const int img = (kt + 1) & 1;
+        asm volatile("" ::: "memory");
+        double a[NSET][4], b[NSET][NJ];
+        auto frag = [&](int set, int g) {
+#pragma unroll
+            for (int i = I0; i < 4; ++i) a[set][i] = as[g * 4 * LDT + i * IST];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) b[set][j] = bs[g * 4 * LDT + j * 16];
+        };
+        frag(0, 0);
+#pragma unroll
+        for (int kk = 0; kk < G; ++kk) {
+            if (NSET == 2 && kk + 1 < G) {
+                frag((kk + 1) & 1, kk + 1);
+                __builtin_amdgcn_sched_group_barrier(0x100, 4 + NJ - I0, 0); // the LDS reads of group kk + 1 first,
+            }
+#pragma unroll
+            for (int i = I0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk % NSET][i], b[kk % NSET][j], acc[i][j], 0, 0, NEGA ? 1 : 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, NJ * (4 - I0), 0);   // then the MFMAs of group kk,
+            if (FILL && kk < FG) {                                           // then its piece of the next step's loads
+                issue(img, kk * (G / FG), (kk + 1) * (G / FG));
+                __builtin_amdgcn_sched_group_barrier(0x020, 2 * (G / FG), 0);
+            }
+            if (NSET == 1 && kk + 1 < G) frag(0, kk + 1);
+        }
+        asm volatile("" ::: "memory");
+        if (FILL) {
+            bump();
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's rows of the next step; its LDS reads of this one
+            __builtin_amdgcn_s_barrier();                               // image kt & 1 is read, the other image is complete
+        }
+        ++kt;
+    };
+    using T_ = std::true_type;
+    using F_ = std::false_type;
+    using I0_ = std::integral_constant<int, 0>;
+    if (!TRI) {
+        for (int t = 0; t + 1 < nk; ++t) step(I0_{}, T_{});
+        step(I0_{}, F_{});
+    } else {
+        // the triangular block's quarters: its first (lowest k) is full
+        const int nd = nk - 3;                          // steps that multiply all four row blocks (nk >= 4: the block itself)
+        if (!REV) {
+            for (int t = 0; t < nd; ++t) step(I0_{}, T_{});
+            step(std::integral_constant<int, 1>{}, T_{});
+            step(std::integral_constant<int, 2>{}, T_{});
+            step(std::integral_constant<int, 3>{}, F_{});
+        } else {
+            step(std::integral_constant<int, 3>{}, T_{});
+            step(std::integral_constant<int, 2>{}, T_{});
+            step(std::integral_constant<int, 1>{}, T_{});
+            for (int t = 0; t + 1 < nd; ++t) step(I0_{}, T_{});
+            step(I0_{}, F_{});
+        }
+    }
+    if (PRIO) __builtin_amdgcn_s_setprio(PRIO - 1);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                                       // the caller may reuse LDS
 }
 

@@ -7,6 +7,7 @@
 
 #include "../../include/gpx.h"
 #include "prune_hint.h"
+#include "sweep_map.h"
 #include "ws_layout.h"
 
 namespace gpx {
@@ -203,7 +204,8 @@ struct gpx_handle {
     int bound_fact = 1;       // diagnostic option: 0 the fp32 bound kernel keeps the unfactorised exponent, 1 the factorised form where its guard allows (bound_f32.h)
 #endif
     int prune_rows = -1;      // diagnostic option: block rows of the second bound's row prefix (-1 by size: nP / 4, 0 never, n > 0: min(n, nP, N / 128) wherever the first level pruned)
-    int sweep_cols = -1;      // option: candidate columns of a sweep workgroup's tile (sweep_cols_of): -1 by size, 128 / 64 / 32 forced
+    int sweep_cols = -1;      // option: candidate columns of a sweep workgroup's tile (sweep_shape_of): -1 by size, 128 / 64 / 32 forced
+    int sweep_images = -1;    // option: LDS images of the default sweep schedule's k-loop (sweep_shape_of): -1 by size, 1 / 2 forced
     int prune_seeds = 0;      // diagnostic option: the seed count G of a pruned sweep (0: by the rule, api.hip: prune_geom)
     int short_map = -1;       // diagnostic option: the short form of tile map 3 (sweep_map.h) -1 by size (launches that cannot fill the per-XCD patches), 0 never, 1 always
     char* dkeep = nullptr;    // the diagnostic copies (keep_ws)
@@ -307,13 +309,12 @@ void launch_cross_gram(hipStream_t s, const double* Xs, int64_t rows, int64_t N,
 // nR: the block rows [0, nR) the launch covers (Np / 128: the sweep; fewer: a row-prefix launch, whose Qp / Pp[mt < nR] are the full launch's bits)
 void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const double* Ks, int64_t ldk,
                        int64_t cols, const double* a, double* Qp, double* Pp, int64_t ldp,
-                       int tile_order, int super_m, unsigned long long* clk, int short_map = -1, int64_t valid = -1, int sweep_cols = 128);
-// The candidate columns of a workgroup's tile in that launch: 128, or 64 / 32 (narrow tiles: kernels_sweep.hip, sweep_tiles) -- the
-// same bits at every width.  sweep_cols: the option (-1: by size; 128 / 64 / 32: that width wherever narrow instances exist, i.e. on the
-// default k-loop).  valid <= cols: the columns that hold candidates; the columns of narrow tiles past them are not computed.
-int sweep_cols_of(int sweep_cols, int tile_order, int nP, int nR, int64_t valid);
-// By size, launches are narrow from this many block rows on only (api.hip, PRUNE_SEEDS_MIN_NP: why)
-constexpr int SWEEP_NARROW_MIN_NP = 48;
+                       int tile_order, int super_m, unsigned long long* clk, int short_map = -1, int64_t valid = -1, int sweep_cols = 128,
+                       int sweep_images = 1);
+// The shape of that launch's tiles (sweep_map.h: sweep_shape_of; SWEEP_NARROW_MIN_NP lives there too): 128, or 64 / 32 candidate
+// columns (narrow tiles: kernels_sweep.hip, sweep_tiles) on one LDS image or two -- the same bits in every shape.  sweep_cols,
+// sweep_images: the options (-1: by size; else that value wherever instances exist, i.e. on the default k-loop).  valid <= cols: the
+// columns that hold candidates; the columns of narrow tiles past them are not computed.
 // reduce partials, form mu/s2/acq for columns [0,cols) of this chunk -> global candidate m0+..
 // nrb = 0: Qp/Pp are reduced per-candidate sums (the sweep cache); qsum/psum (optional) receive the reduced sums
 void launch_acq(hipStream_t s, const double* Qp, const double* Pp, int64_t ldp, int nrb, int64_t m0,

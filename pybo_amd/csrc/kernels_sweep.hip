@@ -287,6 +287,30 @@ __global__ __launch_bounds__(GEMM_THREADS, WGS) void k_sweep_trmm_l(const double
     });
 }
 
+// The default schedule for a launch with at most one working workgroup per compute unit (sweep_shape_of: images = 2): the same tiles,
+// wide or narrow, through gemm_tile_128_l2 -- two k-step images, the next step's DMA behind this step's MFMAs, one barrier per step.
+// ONE workgroup per CU (2 x 73,728 B of dynamic LDS), so the map's RES is 32.  FG: gemm_tile_128_l2 (probe builds vary it).
+// (launch bounds of TWO workgroups per CU although LDS admits one: with one the compiler keeps the accumulators in AGPRs and copies
+//  all of them to VGPRs and back around every k-step; the register budget of two keeps them in VGPRs as in k_sweep_trmm_l.)
+template <int NSET, int NJ, int FG = (NJ == 1 ? 1 : 4)>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm_l2(const double* __restrict__ U, int64_t Np,
+                                                                   const double* __restrict__ Ks, int64_t ldk, int NT, int nR,
+                                                                   const double* __restrict__ avec,
+                                                                   double* __restrict__ Qp, double* __restrict__ Pp,
+                                                                   int64_t ldp, int order, int sm,
+                                                                   unsigned long long* clk, int b0) {
+    extern __shared__ __attribute__((aligned(16))) double sweep_l2_smem[];
+    sweep_tiles<32, NJ>((int)blockIdx.x + b0, U, Np, Ks, NT, nR, avec, Qp, Pp, ldp, order, sm, clk, sweep_l2_smem,
+                        [&](d4 (&acc)[4][NJ], const double* At, const double* Bt, int kend, bool rev, int bcol) {
+        if (!rev) gemm_tile_128_l2<1, NSET, true, true, false, 0, false, NJ, FG>(acc, At, Np, Bt, TB, 0, kend, sweep_l2_smem, bcol);
+        else gemm_tile_128_l2<1, NSET, true, true, false, 0, true, NJ, FG>(acc, At, Np, Bt, TB, 0, kend, sweep_l2_smem, bcol);
+    });
+}
+constexpr int SWEEP_L2_LDS_BYTES = 2 * gemm_l_lds_f64<32>() * 8;
+#ifdef GPX_SWEEP_PROBES
+static int g_sweep_probe_fg = 0;   // 0: the library's FG
+#endif
+
 // The same tiles on the barrier-free loop (gemm_tile_128_w: every wave fetches its own operand halves, one 16-row image per
 // wave, two workgroups per CU), with the diagonal block's zero rows skipped.  Twice the L2 -> LDS bytes of k_sweep_trmm_l.
 __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm_w(const double* __restrict__ U, int64_t Np,
@@ -302,32 +326,31 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_trmm_w(const double* 
     });
 }
 
-// the map of a launch: order 3 in its short form where the option short_map and the launch's size say so
-template <int RES>
-static int sweep_order_of(int order, int short_map, int sm, int NT) {
-    if (order != 3 || short_map == 0) return order;
-    if (short_map < 0 && !sweep_map_is_short<RES>(sm, NT)) return order;
-    return short_map == 2 ? SWEEP_ORDER_SHORT_STRIDED : SWEEP_ORDER_SHORT;
-}
+// The map of a launch (sweep_order_of) and the shape of its tiles (sweep_shape_of: width and LDS images of the default schedule, by
+// the options or by size): sweep_map.h.
 
-// The width of a launch's tiles (gpx_internal.h).  By size: narrow where a launch of the default schedule over a long factor (at least
-// SWEEP_NARROW_MIN_NP block rows, all of them: not a row-prefix launch) has so few candidates that wide tiles leave compute units
-// without a workgroup; the thresholds are the measured crossovers of profiles/narrow_seeds_ab.md, section 1 (N = 8192).
-static const int64_t SWEEP_COLS32_MAX = 512, SWEEP_COLS64_MAX = 1024;
-int sweep_cols_of(int sweep_cols, int tile_order, int nP, int nR, int64_t valid) {
-    if (tile_order < 0 || ((tile_order >> 2) & 7) != 4 || (tile_order >> 5) != 0) return TB;      // narrow instances: the default k-loop only
-    if (sweep_cols > 0) return sweep_cols;
-    if (nP < SWEEP_NARROW_MIN_NP || nR != nP || (tile_order & 3) != 3) return TB;
-    return valid <= SWEEP_COLS32_MAX ? 32 : valid <= SWEEP_COLS64_MAX ? 64 : TB;
+// the compute units of the current device (the by-size rule of sweep_shape_of), asked for once per device
+static int device_cus() {
+    static int cus[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (!cus[dev]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 0;
+        cus[dev] = n;
+    }
+    return cus[dev];
 }
 
 // nR: the block rows [0, nR) the launch covers -- the factor's Np / 128 for the sweep itself, fewer for the row-prefix pass of a
 // selection-only sweep (api.hip: second_bound, step 4a), which needs rows [0, nR 128) of every Ks panel only.
 void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const double* Ks, int64_t ldk,
                        int64_t cols, const double* a, double* Qp, double* Pp, int64_t ldp,
-                       int tile_order, int super_m, unsigned long long* clk, int short_map, int64_t valid, int sweep_cols) {
+                       int tile_order, int super_m, unsigned long long* clk, int short_map, int64_t valid, int sweep_cols, int sweep_images) {
     const int NT = (int)(cols / TB);
     if (valid < 0 || valid > cols) valid = cols;
+    const SweepShape shape = sweep_shape_of(tile_order, (int)(Np / TB), nR, valid, sweep_images < 0 ? device_cus() : 0, sweep_cols, sweep_images,
+                                            super_m, short_map);
     // bits 0-1: tile map, bits 2-4: k-loop (4 = default: operands by LDS-DMA, k-step 32, two workgroups per CU, the zero rows of
     // T's diagonal block skipped; 3: the same without the skip; 1: the barrier-free wave-private loop; 7: k-step 16, three workgroups per CU; 6, 5, 2: the
     // register-staged schedules of rounds 5, 2, 1 -- all kept as independently scheduled witnesses of the bit-identity test)
@@ -344,7 +367,31 @@ void launch_sweep_trmm(hipStream_t s, const double* U, int64_t Np, int nR, const
         const int order = sweep_order_of<64>(order0, short_map, super_m, NT);
         const unsigned nblk = sweep_grid<64>(order, super_m, NT, nR);
         GPX_SW(k_sweep_trmm_w);
-    } else if (const int W = sweep_cols_of(sweep_cols, tile_order, (int)(Np / TB), nR, valid); W < TB) {
+    } else if (shape.images == 2) {
+        // the default schedule, one workgroup per CU on two LDS images: the same maps (32 workgroups resident per XCD) over NTn tiles of W columns
+        const int W = shape.width;
+        const int NTn = (int)((valid + W - 1) / W);
+        const int order = sweep_order_of<32>(order0, short_map, super_m, NTn);
+        const unsigned nblk = sweep_grid<32>(order, super_m, NTn, nR);
+#define GPX_SW2(K)                                                                                                        \
+    do {                                                                                                                  \
+        hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEP_L2_LDS_BYTES);              \
+        hipLaunchKernelGGL(K, dim3(nblk), dim3(GEMM_THREADS), SWEEP_L2_LDS_BYTES, s, U, Np, Ks, ldk, NTn, nR, a, Qp, Pp, ldp, order, super_m, clk, 0); \
+    } while (0)
+#ifdef GPX_SWEEP_PROBES          // scripts/probe/sweep_ab.hip only: the pieces the next step's DMA goes out in (gemm_tile_128_l2: FG)
+        const int fg = (int)g_sweep_probe_fg;
+        if (W == 32 && fg == 2) GPX_SW2((k_sweep_trmm_l2<2, 1, 2>));
+        else if (W == 32 && fg == 4) GPX_SW2((k_sweep_trmm_l2<2, 1, 4>));
+        else if (W == 64 && fg == 2) GPX_SW2((k_sweep_trmm_l2<2, 2, 2>));
+        else if (W == 64 && fg == 1) GPX_SW2((k_sweep_trmm_l2<2, 2, 1>));
+        else if (W == 128 && fg == 1) GPX_SW2((k_sweep_trmm_l2<2, 4, 1>));
+        else
+#endif
+        if (W == 32) GPX_SW2((k_sweep_trmm_l2<2, 1>));
+        else if (W == 64) GPX_SW2((k_sweep_trmm_l2<2, 2>));
+        else GPX_SW2((k_sweep_trmm_l2<2, 4>));
+#undef GPX_SW2
+    } else if (const int W = shape.width; W < TB) {
         // the default schedule on narrow tiles: the same maps over NTn tiles of W columns
         const int NTn = (int)((valid + W - 1) / W);
         const int order = sweep_order_of<64>(order0, short_map, super_m, NTn);

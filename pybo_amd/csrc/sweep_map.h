@@ -1,6 +1,7 @@
-// sweep_map.h -- block -> tile maps of the dominant sweep kernel (kernels_sweep.hip: sweep_tiles) and the grid of a launch.
-// Plain C++ without HIP types: the device code and the host launch share it, and tests/c/sweep_map_check.cpp compiles it into a
-// host-only program that walks every grid and proves each map total and exact before a launch relies on it.
+// sweep_map.h -- block -> tile maps of the dominant sweep kernel (kernels_sweep.hip: sweep_tiles), the grid of a launch, and the shape
+// of a launch's tiles (sweep_shape_of: width and LDS images).  Plain C++ without HIP types: the device code and the host launch share
+// it, and tests/c/sweep_map_check.cpp and tests/c/sweep_shape_check.cpp compile it into host-only programs that walk every grid and
+// every shape and prove each map total and exact, and the rule what it says, before a launch relies on them.
 //
 // A map turns a block index b into a tile (mt, nt) of the nR x NT tiles of a launch (mt: 128 observed rows, nt: 128 candidates) and,
 // in the paired maps, a second tile (mt2, nt) the workgroup computes afterwards.  A tile's bits do not depend on the block that
@@ -158,6 +159,93 @@ GPX_MAP_FN unsigned sweep_grid(int order, int super_m, int NT, int nP) {
         return dmax ? (unsigned)(8 * (dmax - 1) + xlast + 1) : 0u;
     }
     return (unsigned)(NT * nP);
+}
+
+// the map of a launch: order 3 in its short form where the option short_map and the launch's size say so
+// (short_map: -1 where the launch cannot fill the per-XCD patches, 0 never, 1 always, 2 the strided short form)
+template <int RES>
+GPX_MAP_FN int sweep_order_of(int order, int short_map, int sm, int NT) {
+    if (order != 3 || short_map == 0) return order;
+    if (short_map < 0 && !sweep_map_is_short<RES>(sm, NT)) return order;
+    return short_map == 2 ? SWEEP_ORDER_SHORT_STRIDED : SWEEP_ORDER_SHORT;
+}
+
+// ---- the shape of a launch of the default schedule: tile width and LDS images ------------------------------------------------
+// Width W = 128, 64 or 32 candidates per tile (narrow tiles: kernels_sweep.hip, sweep_tiles), images = 1 (gemm_tile_128_l, two
+// workgroups per CU) or 2 (gemm_tile_128_l2, one per CU).  Every shape writes the same bits; the choice is about time alone.
+// By size, launches leave the wide single-image tile from this many block rows of the factor on only (api.hip, PRUNE_SEEDS_MIN_NP: why)
+constexpr int SWEEP_NARROW_MIN_NP = 48;
+constexpr long long SWEEP_COLS32_MAX = 512, SWEEP_COLS64_MAX = 1024;     // full launches: profiles/narrow_seeds_ab.md, section 1
+constexpr int SWEEP_PREFIX_MIN_W = 32;                                  // the narrowest tile a row-prefix launch takes by size
+struct SweepShape { int width, images; };
+
+// working workgroups of a launch of NT tiles over nR block rows: one per tile, in the paired maps one per pair or lone middle tile
+GPX_MAP_FN long long sweep_working(int order, int NT, int nR) { return (long long)NT * (order == 3 ? (nR + 1) / 2 : nR); }
+
+// The most working workgroups any XCD holds in a launch of map 3 (in the form sweep_order_of<RES> picks) of NT tiles over nR block rows
+template <int RES>
+GPX_MAP_FN long long sweep_xcd_load(int short_map, int sm, int NT, int nR) {
+    const int P = (nR + 1) / 2;
+    const int order = sweep_order_of<RES>(3, short_map, sm, NT);
+    long long worst = 0;
+    for (int x = 0; x < 8; ++x) {
+        long long wx;
+        if (order == 3) {
+            const int per = (NT + 7) / 8;                  // the XCD's slice of candidate tiles, all pair rows
+            const int t0 = x * per;
+            wx = (long long)P * (t0 >= NT ? 0 : (NT - t0 < per ? NT - t0 : per));
+        } else {
+            int p0, pstep, R, t0, W;
+            wx = sweep_short_share<RES>(x, order == SWEEP_ORDER_SHORT_STRIDED, sm, NT, nR, p0, pstep, R, t0, W) ? (long long)R * W : 0;
+        }
+        if (wx > worst) worst = wx;
+    }
+    return worst;
+}
+
+// Row-prefix launches (nR < nP, single image, 64 workgroups resident per XCD): the width whose workgroups fill whole generations
+// best.  A launch takes as long as its fullest XCD.  Its cost in units of 1 / 2000 of a wide generation: per full generation of 64
+// workgroups 20, for a last one of up to 32 (one per CU: nobody shares the matrix pipe) 12, times W / 32, times what a narrow
+// tile's shorter k-steps lose at two workgroups per CU (100 / 105 / 115 at W = 128 / 64 / 32).  The figures are the prefix table
+// of profiles/exact_launch_images_ab.md (nR = 16, 2048 .. 16384 columns).
+GPX_MAP_FN long long sweep_prefix_cost(int short_map, int sm, int nR, long long valid, int W) {
+    const long long load = sweep_xcd_load<64>(short_map, sm, (int)((valid + W - 1) / W), nR);
+    const long long rem = load % 64;
+    const long long units = load / 64 * 20 + (rem == 0 ? 0 : rem <= 32 ? 12 : 20);
+    return units * (W / 32) * (W == 128 ? 100 : W == 64 ? 105 : 115);
+}
+// The wide tile unless a narrower one costs at least 5 % less than the best wider one (ties and near-ties: the wide tile).
+GPX_MAP_FN int sweep_prefix_width(int short_map, int sm, int nR, long long valid) {
+    int best = 128;
+    long long best_cost = sweep_prefix_cost(short_map, sm, nR, valid, 128);
+    for (int W = 64; W >= SWEEP_PREFIX_MIN_W; W /= 2) {
+        const long long cost = sweep_prefix_cost(short_map, sm, nR, valid, W);
+        if (cost * 100 < best_cost * 95) best = W, best_cost = cost;
+    }
+    return best;
+}
+
+// tile_order: the launch's (bits 0-1 map, bits 2-4 k-loop, above: probe builds' cache policy); nP: the factor's block rows; nR <= nP: the
+// block rows the launch covers; valid: its candidate columns; cus: the device's compute units; sweep_cols, sweep_images: the options
+// (-1: by size; else forced wherever instances exist, i.e. on the default k-loop); sm, short_map: the launch's super_m and short_map.
+// By size (map 3 over at least SWEEP_NARROW_MIN_NP block rows; wide, one image everywhere else):
+//   width   full launches: 32 up to 512 columns, 64 up to 1024, 128 beyond; row-prefix launches: sweep_prefix_width
+//   images  2 exactly where the launch's working workgroups number at most the compute units, and no XCD's share of them (block b
+//           runs on XCD b % 8) more than its eighth of the units: no workgroup would have a partner on its CU, none waits for a slot
+GPX_MAP_FN SweepShape sweep_shape_of(int tile_order, int nP, int nR, long long valid, int cus, int sweep_cols, int sweep_images, int sm,
+                                     int short_map) {
+    SweepShape s = {128, 1};
+    if (tile_order < 0 || ((tile_order >> 2) & 7) != 4 || (tile_order >> 5) != 0) return s;       // instances: the default k-loop only
+    const int order0 = tile_order & 3;
+    const bool by_size = nP >= SWEEP_NARROW_MIN_NP && order0 == 3;
+    if (sweep_cols > 0) s.width = sweep_cols;
+    else if (by_size) s.width = nR != nP ? sweep_prefix_width(short_map, sm, nR, valid) : valid <= SWEEP_COLS32_MAX ? 32 : valid <= SWEEP_COLS64_MAX ? 64 : 128;
+    if (sweep_images > 0) s.images = sweep_images;
+    else if (by_size) {
+        const int NT = (int)((valid + s.width - 1) / s.width);
+        if (sweep_working(order0, NT, nR) <= cus && 8 * sweep_xcd_load<32>(short_map, sm, NT, nR) <= cus) s.images = 2;
+    }
+    return s;
 }
 
 }  // namespace gpx

@@ -8,7 +8,11 @@
 //   Suffixes of a variant, in this order: "/S" the launch's short_map (sweep_map.h: 0 never, 1 the short form of map 3, 2 its strided form;
 //   default -1, by size as the library); "wW" the width of the default schedule's tiles, W = 128 (default), 64 or 32 candidates (narrow tiles:
 //   kernels_sweep.hip, sweep_tiles; the checksum must not change with W: profiles/narrow_seeds_ab.md); "c" COLD: a pass over a 1 GiB buffer (larger than the 256 MiB MALL and every L2) before each
-//   timed launch, so that the launch finds neither U nor Ks in a cache (profiles/short_launch_map_ab.md).  Examples: 19:8/0c  19w32
+//   timed launch, so that the launch finds neither U nor Ks in a cache (profiles/short_launch_map_ab.md); "iI" the LDS images of the default
+//   schedule's k-loop, I = 1 (default) or 2 (gemm_tile_128_l2, one workgroup per CU: profiles/exact_launch_images_ab.md); "fF" (with i2) the
+//   pieces the next step's DMA goes out in, F = 1, 2 or 4 where they are not the library's (gemm_tile_128_l2: 1 at 32 columns, else 4).  Examples: 19:8/0c  19w32  19w32i2
+//   Row-prefix mode: N given as N:nR launches the leading nR block rows only (api.hip: second_bound).  cols need not be a multiple of 128:
+//   the panels are padded, the launch is told the valid columns, and the checksum covers rows < nR and the valid columns alone.
 #include "../../pybo_amd/csrc/kernels_sweep.hip"
 #include <stdio.h>
 #include <stdlib.h>
@@ -79,10 +83,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_sweep_w(const double* __res
 
 int main(int argc, char** argv) {
     if (argc < 5) { fprintf(stderr, "usage: N cols reps tile_order[:super_m] ...\n"); return 1; }
-    const int64_t N = atoll(argv[1]), cols = atoll(argv[2]);
+    const int64_t N = atoll(argv[1]), valid = atoll(argv[2]);
+    const int64_t cols = (valid + 127) / 128 * 128;
     const int reps = atoi(argv[3]);
     const int64_t Np = (N + 127) / 128 * 128;
     const int nP = (int)(Np / 128);
+    int nR = nP;
+    if (const char* c = strchr(argv[1], ':')) nR = atoi(c + 1);
+    if (N < 1 || valid < 1 || reps < 1 || nR < 1 || nR > nP) { fprintf(stderr, "need N, cols, reps >= 1 and 1 <= nR <= N / 128\n"); return 1; }
     double *U, *Ks, *a, *Qp, *Pp;
     unsigned long long* clk;
     CK(hipMalloc(&U, Np * Np * 8));
@@ -108,6 +116,12 @@ int main(int argc, char** argv) {
         int width = 128;
         if (const char* c = strchr(argv[v], 'w')) width = atoi(c + 1);
         if (width != 128 && width != 64 && width != 32) { fprintf(stderr, "width must be 128, 64 or 32\n"); return 1; }
+        int images = 1, fg = 0;
+        if (const char* c = strchr(argv[v], 'i')) images = atoi(c + 1);
+        if (const char* c = strchr(argv[v], 'f')) fg = atoi(c + 1);
+        if (images != 1 && images != 2) { fprintf(stderr, "images must be 1 or 2\n"); return 1; }
+        if ((to >= 1000 || (to & 3) != 3) && nR != nP) { fprintf(stderr, "row-prefix mode: the library's schedules on map 3 only\n"); return 1; }
+        g_sweep_probe_fg = fg;
         const bool cold = argv[v][strlen(argv[v]) - 1] == 'c';
         if (cold && !flush) CK(hipMalloc(&flush, nflush * 8));
         std::vector<float> ms_all;
@@ -132,7 +146,7 @@ int main(int argc, char** argv) {
                 else { CK(hipFuncSetAttribute((const void*)k_lone<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
                     hipLaunchKernelGGL(k_lone<2>, dim3(nblk), dim3(GEMM_THREADS), lb, 0, U, Np, Ks, (int)(cols / TB), a, Qp, Pp, cols, sm); }
             } else
-            launch_sweep_trmm(0, U, Np, nP, Ks, Np, cols, a, Qp, Pp, cols, to, sm, clk, short_map, cols, width);
+            launch_sweep_trmm(0, U, Np, nR, Ks, Np, cols, a, Qp, Pp, cols, to, sm, clk, short_map, valid, width, images);
             hipEventRecord(e1);
             CK(hipEventSynchronize(e1));
             CK(hipGetLastError());
@@ -147,15 +161,19 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(hq.data(), Qp, hq.size() * 8, hipMemcpyDeviceToHost));
         CK(hipMemcpy(hp.data(), Pp, hp.size() * 8, hipMemcpyDeviceToHost));
         unsigned long long x = 0;
-        for (size_t i = 0; i < hq.size(); ++i) { unsigned long long b; memcpy(&b, &hq[i], 8); x = x * 1099511628211ull ^ b; memcpy(&b, &hp[i], 8); x = x * 1099511628211ull ^ b; }
         double dq = 0, dp = 0, sq = 0, sp = 0;
         if (rq.empty()) { rq = hq; rp = hp; }
-        for (size_t i = 0; i < hq.size(); ++i) {
-            dq = std::max(dq, fabs(hq[i] - rq[i])); sq = std::max(sq, fabs(rq[i]));
-            dp = std::max(dp, fabs(hp[i] - rp[i])); sp = std::max(sp, fabs(rp[i]));
-        }
-        printf("RESULT tile_order %d super_m %d short_map %d width %d %s N %lld cols %lld: min %.3f median %.3f ms  %.2f TFLOP/s  frac %.4f  sclk %.0f MHz  checksum %016llx  maxdiff/scale q %.2e p %.2e\n",
-               to, sm, short_map, width, cold ? "cold" : "warm", (long long)N, (long long)cols, ms_all[0], med, (double)N * N * cols / med / 1e9, (double)N * N * cols / med / 1e9 / 78.6, mhz, x, dq / sq, dp / sp);
+        for (int mt = 0; mt < nR; ++mt)
+            for (int64_t c = 0; c < valid; ++c) {
+                const size_t i = (size_t)mt * cols + c;
+                unsigned long long b; memcpy(&b, &hq[i], 8); x = x * 1099511628211ull ^ b; memcpy(&b, &hp[i], 8); x = x * 1099511628211ull ^ b;
+                dq = std::max(dq, fabs(hq[i] - rq[i])); sq = std::max(sq, fabs(rq[i]));
+                dp = std::max(dp, fabs(hp[i] - rp[i])); sp = std::max(sp, fabs(rp[i]));
+            }
+        // us per k-step: the median over the (nR + 1) 128 / 32 steps of a pair of tiles -- a workgroup's chain where the launch is one generation
+        printf("RESULT tile_order %d super_m %d short_map %d width %d images %d fg %d %s N %lld nR %d cols %lld: min %.3f median %.3f ms  %.2f us/step  %.2f TFLOP/s  frac %.4f  sclk %.0f MHz  checksum %016llx  maxdiff/scale q %.2e p %.2e\n",
+               to, sm, short_map, width, images, fg, cold ? "cold" : "warm", (long long)N, nR, (long long)valid, ms_all[0], med, med * 1e3 / ((nR + 1) * 4.0),
+               (double)N * N * valid / med / 1e9, (double)N * N * valid / med / 1e9 / 78.6, mhz, x, dq / sq, dp / sp);
         fflush(stdout);
     }
     return 0;
