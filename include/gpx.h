@@ -32,8 +32,7 @@ enum gpx_status {
     GPX_ESTATE = -5,  /* call order error (e.g. sweep before fit) */
     GPX_ERCCL = -6    /* RCCL could not be loaded, or a collective failed; see gpx_comm_last_error */
 };
-/* covariance functions; parametrisation (sn2, rho, ell[d], bias) = the arguments of
- * reggie.make_gp(sn2, rho, ell, bias)                       [pybo/bayesopt.py:98-105] */
+/* covariance functions; parametrisation (sn2, rho, ell[d], bias) = the arguments of reggie.make_gp(sn2, rho, ell, bias) [pybo/bayesopt.py:98-105] */
 enum gpx_kernel {
     GPX_KERN_SE_ARD = 0,   /* rho * exp(-r2/2),                      r2 = sum_k ((x_k-z_k)/ell_k)^2 */
     GPX_KERN_MATERN52 = 1, /* rho * (1 + sqrt5 r + 5 r2/3) exp(-sqrt5 r) */
@@ -53,7 +52,6 @@ enum gpx_acq {
                        * b_0 = s2 / D, b_j = Sigma(a_j, z) / D, D = sqrt(s2 + sn2).  params = A, raw coordinates (m, d) row-major on the HOST, nparams = m d,
                        * 1 <= m <= 127, finite (else GPX_EARG).  Taken by gpx_sweep* ONLY (every output, cache seeding); never pruned.  Ids 17 .. 31: refused */
 };
-
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* `stream` is a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) or NULL for a library-owned stream. */
 int gpx_create(int device, void *stream, gpx_handle **out);
@@ -92,7 +90,6 @@ int gpx_version(void);
  * shipping library answers them with GPX_EARG. Environment: GPX_OPTIONS="name=value,name=value" applies options to every handle at creation (A/B runs through a
  * plug-in layer whose handles the caller never sees); a bad entry fails gpx_create with GPX_EARG. */
 int gpx_set_option(gpx_handle *h, const char *name, int64_t value);
-
 /* ---- GP fit = model.add_data(X, Y)            [pybo/bayesopt.py:114,258,269] ------------- */
 /* Limits: 1 <= d <= 1024 for every entry point (the Thompson / RFF kernels keep a whole feature tile in LDS up to d = 64 and walk the coordinates 32 at a
  * time beyond); top-k requests k <= 4096 (64 per pass over the values).  Gram build K = k(X,X) + sn2 I and Cholesky K = R^T R.  The triangular inverse
@@ -120,8 +117,7 @@ int gpx_append(gpx_handle *h, const double *x, double y);
  * bit-identical x then costs O(N + M); any other x, or a model change, and the announcement is ignored.  Results bit-identical to an unannounced append.
  * GPX_ESTATE (nothing started, not an error) without a live sweep cache or when the next append has to add a 128-block first. */
 int gpx_append_begin(gpx_handle *h, const double *x);
-/* 0-based index of the failing pivot of the last GPX_ENOTPD fit, else -1. */
-int64_t gpx_fail_pivot(const gpx_handle *h);
+int64_t gpx_fail_pivot(const gpx_handle *h);     /* 0-based index of the failing pivot of the last GPX_ENOTPD fit, else -1. */
 /* introspection for parity tests (host outputs): which = 0: L (N,N) lower Cholesky factor, row-major (K + sn2 I = L L^T);
  * 1: T = L^-1 (N,N) lower; 2: K + sn2 I, upper triangle (only after gpx_fit_stage(.., 1): the factorisation consumes it) */
 int gpx_get_matrix(gpx_handle *h, int which, double *out);
@@ -150,7 +146,6 @@ int gpx_predict_cov(gpx_handle *h, const double *Xc, int64_t M, double *mu, doub
 /* S joint draws from the caller's standard normals z (S,M): out (S,M), out[s] = mu + R^T z[s], R^T R = cov + (noisy ? sn2 : 0) I + jitter I (R upper;
  * jitter finite, >= 0).  A draw's bits do not depend on S.  GPX_ENOTPD (out undefined): gpx_last_error names the pivot; gpx_fail_pivot still describes fits. */
 int gpx_sample_joint(gpx_handle *h, const double *Xc, int64_t M, const double *z, int64_t S, int noisy, double jitter, double *out);
-
 /* ---- acquisition sweep + top-k = the solver's batched index call and argsort: finit = f(xgrid); idx = argsort(finit)[::-1] [pybo/solvers/lbfgs.py:50-51] */
 /* Evaluates acq over M candidates, returns the k best (value desc, then index asc) in host buffers top_val[k], top_idx[k] (indices are LOCAL to Xc;
  * add your shard offset).  acq_all, mu, s2 (each (M,), host in gpx_sweep / device in gpx_sweep_dev) are optional (NULL to skip). */
@@ -158,7 +153,6 @@ int gpx_sweep(gpx_handle *h, int acq_id, const double *params, int nparams, cons
               double *top_val, int64_t *top_idx, double *acq_all, double *mu, double *s2);
 int gpx_sweep_dev(gpx_handle *h, int acq_id, const double *params, int nparams, const double *dXc, int64_t M, int64_t k,
                   double *top_val, int64_t *top_idx, double *d_acq_all, double *d_mu, double *d_s2);
-
 /* ---- warm BO step: the NEXT iteration's `index(xgrid)` over the SAME grid with the SAME hyper-parameters
  *      [pybo/bayesopt.py:262-269 with a fixed `xgrid=` in pybo/solvers/lbfgs.py:42-50].  The reference pays a full refit and a full
  *      solve again; with option "sweep_cache" = 1 a full gpx_sweep* keeps the candidates and their reduced sums q = colsum(V^2),
@@ -176,9 +170,7 @@ int gpx_sweep_batch(gpx_handle *h, int acq_id, const double *params, int nparams
 /* Knowledge gradient (GPX_ACQ_KG) and its gradient at M <= 4096 points, host buffers: A (m, d) the support set as for the sweep, f (M,), g (M, d) -- the
  * `f(x, grad=True)` of the L-BFGS refinement.  f agrees with the sweep's value to rounding.  One host synchronisation; fit, sweep cache and queue untouched. */
 int gpx_kg_grad(gpx_handle *h, const double *A, int64_t m, const double *Xc, int64_t M, double *f, double *g);
-/* number of candidates in the live sweep cache (0: none) */
-int64_t gpx_sweep_cache_size(const gpx_handle *h);
-
+int64_t gpx_sweep_cache_size(const gpx_handle *h);     /* number of candidates in the live sweep cache (0: none) */
 /* ---- Thompson sampling = model.sample_f(n, rng).get(X)   [pybo/policies/simple.py:44-48] -- */
 /* S random-Fourier-feature posterior draws f_s(x) = bias + sum_j theta[s][j] cos(W[s][j].x + b[s][j]) (the sqrt(2 rho/n) factor is folded into theta by the
  * caller).  W (S,n,d), b (S,n), theta (S,n) on the host.  Per draw returns the k best candidates: top_val (S,k), top_idx (S,k).  vals_all (S,M) optional. */
@@ -199,7 +191,22 @@ int gpx_rff_gram_batch(gpx_handle *h, const double *W, const double *b, int64_t 
  * posterior of a draw lives in LDS); 128 <= n <= 4096: per draw the blocked Cholesky kernels of the fit + two vector substitutions (`n` is a free keyword
  * of the reference's sample_f, pybo/policies/simple.py:44).  GPX_ENOTPD if a B is not PD. */
 int gpx_rff_posterior(gpx_handle *h, const double *W, const double *b, const double *z, int64_t S, int64_t n, double sc, double *theta);
-
+/* ---- pathwise Thompson draws (Matheron's rule; Wilson et al. 2020): f_s(x) = bias + sum_j theta_sj cos(W_sj.x + b_sj) + sum_{i<nv} v_si k(x, X_i): the RFF
+ *      draw is the PRIOR, corrected exactly by the factorisation.  FITTED handle (else GPX_ESTATE); W, b as gpx_rff_*; d the handle's, 1 <= n <= 4096.
+ * gpx_path_weights: theta (S,n) = sc*w; v (S,N) = (K + sn2 I)^-1 ((y - bias) - Phi_s(X) theta_s - sqrt(sn2) eps_s); w (S,n), eps (S,N) the caller's standard
+ *      normals (eps == NULL: zeros); host buffers.  Forms the inverse on first use.  One host synchronisation; the fit, a live sweep cache, queued
+ *      corrections and a pending gpx_append_begin are left as they are.
+ * gpx_path_sweep*: f_s over M candidates + per-draw top-k, outputs exactly as gpx_rff_sweep*, time in slot [7]; v (S,nv), 1 <= nv <= N: conditioned on the
+ *      handle's LEADING nv observations (a handle appended to since still evaluates the same function; the hyper-parameters are the caller's to keep fixed).
+ * gpx_path_grad: value f (M,) and gradient g (M,d) of ONE draw at M <= 4096 points, host buffers; f agrees with the sweep's value to rounding. */
+int gpx_path_weights(gpx_handle *h, const double *W, const double *b, const double *w, const double *eps, int64_t S, int64_t n, double sc,
+                     double *theta, double *v);
+int gpx_path_sweep(gpx_handle *h, const double *W, const double *b, const double *theta, const double *v, int64_t nv, int64_t S, int64_t n, int64_t d,
+                   double bias, const double *Xc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *vals_all);
+int gpx_path_sweep_dev(gpx_handle *h, const double *W, const double *b, const double *theta, const double *v, int64_t nv, int64_t S, int64_t n, int64_t d,
+                       double bias, const double *dXc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *d_vals_all);
+int gpx_path_grad(gpx_handle *h, const double *W, const double *b, const double *theta, const double *v, int64_t nv, int64_t n, int64_t d, double bias,
+                  const double *Xc, int64_t M, double *f, double *g);
 /* ---- hyper-parameter ensemble = pybo's DEFAULT model, reggie.MCMC(gp, n=10) [pybo/bayesopt.py:115]: every index is the average over the n member
  *      GPs.  `members` are fitted handles on ONE device with the same input dimension (members[0] owns the scratch and the error text).
  *      EI / PI: value = mean_m acq_m(x).  UCB / MEAN: mixture moments mu = mean_m mu_m, s2 = mean_m(s2_m + mu_m^2) - mu^2, value = mu + sqrt(params[0] * s2)
@@ -244,7 +251,6 @@ int gpx_ehvi_sweep_dev(gpx_handle *f1, gpx_handle *f2, const double *P, int np, 
                        double *top_val, int64_t *top_idx, double *d_acq_all, double *d_mom);
 int gpx_ehvi_fold_dev(gpx_handle *lead, const double *d_mom, int64_t M, const double *P, int np, const double *ref, int64_t k,
                       double *top_val, int64_t *top_idx, double *d_acq_all);
-
 /* ---- candidate grid generated and kept in HBM = the solver's grid xgrid = init_uniform(bounds, ngrid, rng) [pybo/solvers/lbfgs.py:45;
  *      pybo/inits/methods.py:24-38] or a Sobol' grid [pybo/inits/methods.py:62-77] without the host array and its PCIe upload; pass gpx_grid_data() to
  *      the *_dev sweeps.
@@ -257,30 +263,26 @@ enum { GPX_GRID_UNIFORM = 0, GPX_GRID_SOBOL = 1 };
 int gpx_grid_create(int device, int kind, const double *bounds, int64_t M, int64_t d, uint64_t seed,
                     int64_t first, const uint32_t *sv, int bits, gpx_grid **out);
 const double *gpx_grid_data(const gpx_grid *g);     /* device pointer, (M,d) row-major */
-/* rows idx[0..k) -> out (k,d) host; idx == NULL: the whole grid (M,d) */
-int gpx_grid_rows(gpx_grid *g, const int64_t *idx, int64_t k, double *out);
+int gpx_grid_rows(gpx_grid *g, const int64_t *idx, int64_t k, double *out);     /* rows idx[0..k) -> out (k,d) host; idx == NULL: the whole grid (M,d) */
 int gpx_grid_destroy(gpx_grid *g);
-
 /* ---- multi-GPU exchange: the one collective of the sharded sweep.  The reference is single-process (its only hint at parallelism is the comment
  *      pybo/solvers/lbfgs.py:60); layout per SURVEY.md 8(e): one process per GPU, candidates sharded contiguously, every rank fits redundantly
  *      (bitwise-identical factor), each rank's best (value, GLOBAL index) pairs all-gathered over RCCL/xGMI and merged "value descending, then index
  *      ascending".  RCCL is bound at run time (dlopen of librccl, override with $GPX_RCCL_LIB): single-GPU use never loads it.  Errors: gpx_comm_last_error */
 typedef struct gpx_comm gpx_comm;
 #define GPX_COMM_ID_BYTES 128
-/* rank 0 generates the id (ncclGetUniqueId) and hands its 128 bytes to every rank over any side channel */
-int gpx_comm_unique_id(unsigned char *id);
+int gpx_comm_unique_id(unsigned char *id);     /* rank 0 generates the id (ncclGetUniqueId) and hands its 128 bytes to every rank over any side channel */
 /* collective over all ranks: binds the communicator to the handle's device and stream */
 int gpx_comm_init(gpx_handle *h, int rank, int nranks, const unsigned char *id, gpx_comm **out);
 int gpx_comm_destroy(gpx_comm *c);
 int gpx_comm_size(const gpx_comm *c, int *rank, int *nranks);
 const char *gpx_comm_last_error(void);
 /* All-gather of the n (value, index) pairs the handle's LAST sweep left in HBM (n = its k for gpx_sweep* / gpx_ensemble_sweep* / gpx_constrained_sweep* /
- * gpx_ehvi_* (the lead), S*k for gpx_rff_sweep*), taken straight from the device, `index_offset` (this rank's shard origin) added to every valid index.
+ * gpx_ehvi_* (the lead), S*k for gpx_rff/path_sweep*), taken straight from the device, `index_offset` (this rank's shard origin) added to every valid index.
  *   k > 0: every rank receives the same merged k best in out_val[k], out_idx[k] = the global argsort(finit)[::-1][:k] of pybo/solvers/lbfgs.py:51 over
  *          the sharded grid.
  *   k = 0: no merge; out_val / out_idx receive all nranks*n pairs in rank order (batch-BO: one recommendation per Thompson draw, draws sharded over ranks). */
 int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, double *out_val, int64_t *out_idx);
-
 /* ---- measurement ------------------------------------------------------------------------ */
 /* Stage timers in milliseconds accumulated since the last reset (HIP events on the handle's stream): [0] gram [1] cholesky [2] trtri [3] alpha [4] cross_gram
  * [5] sweep_trmm [6] acq_topk [7] rff [8] sweep_trmm launches [9] sweep_trmm algorithmic flop [10] h2d/d2h copies [11] append [12] correction passes over the
@@ -290,10 +292,8 @@ int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, 
  * ("trtri_ahead": for those [2] holds only what was left after the factor was done) [19] bound pass of selection-only sweeps [20] batch selection
  * (gpx_[ensemble_]sweep_batch) [21] joint posterior (gpx_predict_cov / gpx_sample_joint: all between their copies).  Synchronises; returns slots written. */
 int gpx_timers(gpx_handle *h, double *out, int n, int reset);
-/* 1 when the library was built with -DGPX_DIAGNOSTICS (the diagnostic options above are accepted), else 0 */
-int gpx_diagnostics(void);
+int gpx_diagnostics(void);     /* 1 when the library was built with -DGPX_DIAGNOSTICS (the diagnostic options above are accepted), else 0 */
 int gpx_sync(gpx_handle *h);
-
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,10 @@ SYMBOLS = {
     'gpx_rff_gram': (C.c_int, [_P, _P, _P, _i64, _P, _P]),
     'gpx_rff_gram_batch': (C.c_int, [_P, _P, _P, _i64, _i64, _P, _P]),
     'gpx_rff_posterior': (C.c_int, [_P, _P, _P, _P, _i64, _i64, _dbl, _P]),
+    'gpx_path_weights': (C.c_int, [_P, _P, _P, _P, _P, _i64, _i64, _dbl, _P, _P]),
+    'gpx_path_sweep': (C.c_int, [_P, _P, _P, _P, _P, _i64, _i64, _i64, _i64, _dbl, _P, _i64, _i64, _P, _P, _P]),
+    'gpx_path_sweep_dev': (C.c_int, [_P, _P, _P, _P, _P, _i64, _i64, _i64, _i64, _dbl, _P, _i64, _i64, _P, _P, _P]),
+    'gpx_path_grad': (C.c_int, [_P, _P, _P, _P, _P, _i64, _i64, _i64, _dbl, _P, _i64, _P, _P]),
     'gpx_ensemble_sweep': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P, _P]),
     'gpx_ensemble_sweep_dev': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P, _P]),
     'gpx_ensemble_sweep_batch': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _i64, _P, _P, _P]),
@@ -898,6 +902,64 @@ class Engine(object):
         self._check(self._lib.gpx_rff_sweep_dev(self._h, _ptr(W), _ptr(b), _ptr(theta), S, n, d, bias,
                                                 _P(dXc_ptr), M, k, _ptr(tv), _ptr(ti), None))
         return tv, ti
+
+    # -- pathwise Thompson draws (the RFF draw as the prior, corrected exactly by the factorisation) -----
+    def path_weights(self, W, b, w, eps, sc):
+        """theta (S, n) = sc * w and v (S, N) = (K + sn2 I)^-1 ((y - bias) - Phi_s(X) theta_s - sqrt(sn2) eps_s) of S draws;
+        w (S, n), eps (S, N) the caller's standard normals (eps None: zeros)."""
+        W = _f64(W)
+        S, n, d = W.shape
+        b = _f64(b).reshape(S, n)
+        w = _f64(w).reshape(S, n)
+        N = self.N
+        if eps is not None:
+            eps = _f64(eps).reshape(S, N)
+        theta = np.empty((S, n))
+        v = np.empty((S, N))
+        self._check(self._lib.gpx_path_weights(self._h, _ptr(W), _ptr(b), _ptr(w), _ptr(eps), S, n, float(sc), _ptr(theta), _ptr(v)))
+        return theta, v
+
+    def path_sweep(self, W, b, theta, v, bias, Xc, k=0, want_all=True):
+        W = _f64(W)
+        S, n, d = W.shape
+        b = _f64(b).reshape(S, n)
+        theta = _f64(theta).reshape(S, n)
+        v = _f64(v).reshape(S, -1)
+        Xc = _f64(Xc).reshape(-1, d)
+        M = len(Xc)
+        tv = np.empty((S, k))
+        ti = np.empty((S, k), dtype=np.int64)
+        out = np.empty((S, M)) if want_all else None
+        self._check(self._lib.gpx_path_sweep(self._h, _ptr(W), _ptr(b), _ptr(theta), _ptr(v), v.shape[1], S, n, d, bias, _ptr(Xc), M,
+                                             k, _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out)))
+        return dict(top_val=tv, top_idx=ti, vals=out)
+
+    def path_sweep_dev(self, W, b, theta, v, bias, dXc_ptr, M, k, d_vals=None):
+        W = _f64(W)
+        S, n, d = W.shape
+        b = _f64(b).reshape(S, n)
+        theta = _f64(theta).reshape(S, n)
+        v = _f64(v).reshape(S, -1)
+        tv = np.empty((S, k))
+        ti = np.empty((S, k), dtype=np.int64)
+        self._check(self._lib.gpx_path_sweep_dev(self._h, _ptr(W), _ptr(b), _ptr(theta), _ptr(v), v.shape[1], S, n, d, bias,
+                                                 _P(dXc_ptr), M, k, _ptr(tv) if k else None, _ptr(ti) if k else None,
+                                                 _P(d_vals) if d_vals else None))
+        return tv, ti
+
+    def path_eval_grad(self, W, b, theta, v, bias, Xc):
+        W = _f64(W)
+        n, d = W.shape
+        b = _f64(b)
+        theta = _f64(theta)
+        v = _f64(v).ravel()
+        Xc = _f64(Xc).reshape(-1, d)
+        M = len(Xc)
+        f = np.empty(M)
+        g = np.empty((M, d))
+        self._check(self._lib.gpx_path_grad(self._h, _ptr(W), _ptr(b), _ptr(theta), _ptr(v), len(v), n, d, bias, _ptr(Xc), M,
+                                            _ptr(f), _ptr(g)))
+        return f, g
 
     # -- measurement -----------------------------------------------------------------------------
     def timers(self, reset=False):

@@ -362,7 +362,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dcon, h->dehvi, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dcon, h->dehvi, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw, h->dpath};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -1815,9 +1815,28 @@ extern "C" int gpx_kg_grad(gpx_handle* h, const double* A, int64_t m, const doub
 }
 
 // ---- Thompson / RFF ---------------------------------------------------------------------------
+// the host image of the MFMA kernels' draw parameters (rff_sweep_ws): features padded to 128 per tile, k-major tiles
+static void rff_retile(const double* W, const double* b, const double* theta, int64_t S, int64_t n, int64_t d, int64_t dp, int64_t nfb,
+                       std::vector<double>& stage) {
+    const int64_t nW = S * nfb * dp * TBH, nV = S * nfb * TBH;
+    stage.assign((size_t)(rff_sweep_ws(WsCarver(nullptr), nW, nV).bytes / 8), 0.0);
+    const auto [Wt, bt, tt, nbytes] = rff_sweep_ws(WsCarver(stage.data()), nW, nV);
+    for (int64_t q = 0; q < S; ++q)
+        for (int64_t j = 0; j < n; ++j) {
+            const int64_t fb = j / TBH, c = j % TBH;
+            for (int64_t kk = 0; kk < d; ++kk)
+                Wt[((q * nfb + fb) * dp + kk) * TBH + c] = W[(q * n + j) * d + kk];
+            bt[(q * nfb + fb) * TBH + c] = b[q * n + j];
+            tt[(q * nfb + fb) * TBH + c] = theta[q * n + j];
+        }
+}
+
+// path (gpx_path_sweep*): the weights (S, nv) of the update term that k_path_update adds to the feature part before the top-k
+struct PathArg { const double* v; int64_t nv; };
+
 static int rff_core(gpx_handle* h, const double* W, const double* b, const double* theta, int64_t S,
                     int64_t n, int64_t d, double bias, const double* dXc, int64_t M, int64_t k,
-                    double* top_val, int64_t* top_idx, double* d_vals) {
+                    double* top_val, int64_t* top_idx, double* d_vals, const PathArg* path = nullptr) {
     if (!W || !b || !theta || !dXc) return fail(h, GPX_EARG, "rff_sweep: NULL pointer");
     if (S < 1 || n < 1 || d < 1 || M < 1) return fail(h, GPX_EARG, "rff_sweep: bad sizes");
     if (d > DMAX_RFF) return fail(h, GPX_EARG, "rff_sweep: d must be <= 1024");
@@ -1829,18 +1848,8 @@ static int rff_core(gpx_handle* h, const double* W, const double* b, const doubl
     const int64_t dp = (d + 3) / 4 * 4;
     const int64_t nfb = (n + TBH - 1) / TBH;
     const int64_t nW = S * nfb * dp * TBH, nV = S * nfb * TBH;
-    std::vector<double> stage((size_t)(rff_sweep_ws(WsCarver(nullptr), nW, nV).bytes / 8), 0.0);      // the host image of the device layout
-    {
-        const auto [Wt, bt, tt, nbytes] = rff_sweep_ws(WsCarver(stage.data()), nW, nV);
-        for (int64_t q = 0; q < S; ++q)
-            for (int64_t j = 0; j < n; ++j) {
-                const int64_t fb = j / TBH, c = j % TBH;
-                for (int64_t kk = 0; kk < d; ++kk)
-                    Wt[((q * nfb + fb) * dp + kk) * TBH + c] = W[(q * n + j) * d + kk];
-                bt[(q * nfb + fb) * TBH + c] = b[q * n + j];
-                tt[(q * nfb + fb) * TBH + c] = theta[q * n + j];
-            }
-    }
+    std::vector<double> stage;      // the host image of the device layout
+    rff_retile(W, b, theta, S, n, d, dp, nfb, stage);
     if ((rc = ensure(h, h->drff, h->cap_rff, rff_sweep_ws(WsCarver(nullptr), nW, nV).bytes / 8))) return rc;
     const RffSweepWs rw = rff_sweep_ws(WsCarver(h->drff), nW, nV);
     HIPCHK(h, hipMemcpyAsync(rw.Wt, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
@@ -1853,6 +1862,15 @@ static int rff_core(gpx_handle* h, const double* W, const double* b, const doubl
         Span sp(h, T_RFF);
         Span sp2(h, T_RFFSWEEP);          // the Thompson sweep kernel alone (bench.py: roofline_rff)
         launch_rff_mfma(s, rw.Wt, rw.bt, rw.tt, (int)S, (int)nfb, (int)n, (int)d, (int)dp, bias, dXc, M, d_vals, h->dclk + 2);
+    }
+    if (path) {
+        // (bias + feature sum) + update: the second term on top of what the kernel above left in d_vals
+        const int64_t nv = path->nv;
+        if ((rc = ensure(h, h->dpath, h->cap_path, path_sweep_ws(WsCarver(nullptr), S, nv).bytes / 8))) return rc;
+        const PathSweepWs pw = path_sweep_ws(WsCarver(h->dpath), S, nv);
+        HIPCHK(h, hipMemcpyAsync(pw.v, path->v, (size_t)S * nv * 8, hipMemcpyHostToDevice, s));      // (the caller's buffer: it outlives the call's last wait)
+        Span sp(h, T_RFF);
+        launch_path_update(s, h->dXs, (int)d, pw.v, nv, S, pw.frag, dXc, M, h->dinvell, h->kernel_id, h->rho, d_vals);
     }
     // algorithmic double-precision lane operations of that launch: per (draw, feature, candidate) d multiply-adds of the
     // projection + 20 instructions of the cosine epilogue (kernels_rff.hip: cos_cw and the weighted sum)
@@ -1919,6 +1937,117 @@ extern "C" int gpx_rff_grad(gpx_handle* h, const double* W, const double* b, con
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
         return gpx::rff_grad_host(h, W, b, theta, n, d, bias, Xc, M, f, g);
+    });
+}
+
+// ---- pathwise Thompson draws (kernels_path.hip) --------------------------------------------------------------------------
+static int path_check(gpx_handle* h, const char* what, const void* v, int64_t nv, int64_t S, int64_t n, int64_t d) {
+    char msg[160];
+    if (!h->fitted) {
+        snprintf(msg, sizeof msg, "%s: model is not fitted", what);
+        return fail(h, GPX_ESTATE, msg);
+    }
+    const char* bad = !v ? "NULL weights" : d != h->d ? "d must equal the fitted model's" : (nv < 1 || nv > h->N) ? "nv must be in [1, N]"
+                      : S < 1 ? "S must be >= 1" : (n < 1 || n > 4096) ? "n must be in [1, 4096]" : nullptr;
+    if (!bad) return GPX_OK;
+    snprintf(msg, sizeof msg, "%s: %s", what, bad);
+    return fail(h, GPX_EARG, msg);
+}
+
+extern "C" int gpx_path_sweep_dev(gpx_handle* h, const double* W, const double* b, const double* theta, const double* v, int64_t nv,
+                                  int64_t S, int64_t n, int64_t d, double bias, const double* dXc, int64_t M, int64_t k,
+                                  double* top_val, int64_t* top_idx, double* d_vals_all) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        if (int rc = path_check(h, "path_sweep", v, nv, S, n, d)) return rc;
+        const PathArg pa = {v, nv};
+        return rff_core(h, W, b, theta, S, n, d, bias, dXc, M, k, top_val, top_idx, d_vals_all, &pa);
+    });
+}
+
+extern "C" int gpx_path_sweep(gpx_handle* h, const double* W, const double* b, const double* theta, const double* v, int64_t nv,
+                              int64_t S, int64_t n, int64_t d, double bias, const double* Xc, int64_t M, int64_t k,
+                              double* top_val, int64_t* top_idx, double* vals_all) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        if (int rc0 = path_check(h, "path_sweep", v, nv, S, n, d)) return rc0;
+        if (!Xc || M < 1) return fail(h, GPX_EARG, "path_sweep: bad candidates");
+        if (k < 0 || k > TOPK_MAX) return fail(h, GPX_EARG, "path_sweep: k must be in [0, 4096]");
+        HIPCHK(h, hipSetDevice(h->device));
+        int rc;
+        if ((rc = ensure(h, h->dXc, h->cap_xc, M * d))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->dXc, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, h->stream));
+        if ((rc = ensure(h, h->dout, h->cap_out, S * M))) return rc;
+        const PathArg pa = {v, nv};
+        rc = rff_core(h, W, b, theta, S, n, d, bias, h->dXc, M, k, top_val, top_idx, h->dout, &pa);
+        if (rc) return rc;
+        if (vals_all) {
+            HIPCHK(h, hipMemcpyAsync(vals_all, h->dout, (size_t)S * M * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+        return GPX_OK;
+    });
+}
+
+extern "C" int gpx_path_grad(gpx_handle* h, const double* W, const double* b, const double* theta, const double* v, int64_t nv,
+                             int64_t n, int64_t d, double bias, const double* Xc, int64_t M, double* f, double* g) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        if (int rc = path_check(h, "path_grad", v, nv, 1, n, d)) return rc;
+        if (!W || !b || !theta || !Xc || !f || !g) return fail(h, GPX_EARG, "path_grad: NULL pointer");
+        if (M < 1 || M > JOINT_MAX_M) return fail(h, GPX_EARG, "path_grad: M must be in [1, 4096]");
+        return gpx::path_grad_host(h, W, b, theta, v, nv, n, d, bias, Xc, M, f, g);
+    });
+}
+
+// The weights of S draws.  The prior at the observations is the Thompson sweep kernel's feature sum over the handle's own inputs
+// (bias 0), r the right-hand sides as panels of 128 draws, v = U (T r) by the panel products of the joint posterior (k_cov_trmm) and
+// the knowledge gradient (k_kg_solve).  Forms the inverse on first use; reads the fit only: no flush of queued corrections, the sweep
+// cache, an announcement and their buffers are not touched.  One stream, one synchronisation (the staged host images live until it).
+extern "C" int gpx_path_weights(gpx_handle* h, const double* W, const double* b, const double* w, const double* eps, int64_t S,
+                                int64_t n, double sc, double* theta, double* v) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        if (int rc0 = path_check(h, "path_weights", v, 1, S, n, h->d)) return rc0;
+        if (!W || !b || !w || !theta) return fail(h, GPX_EARG, "path_weights: NULL pointer");
+        if (!std::isfinite(sc)) return fail(h, GPX_EARG, "path_weights: sc must be finite");
+        const int64_t d = h->d;
+        if (d > DMAX_RFF) return fail(h, GPX_EARG, "path_weights: d must be <= 1024");
+        HIPCHK(h, hipSetDevice(h->device));
+        int rc;
+        if ((rc = ensure_inverse(h))) return rc;
+        hipStream_t s = h->stream;
+        const int64_t N = h->N, Np = h->Np, Sp = (S + TBH - 1) / TBH * TBH;
+        for (int64_t e = 0; e < S * n; ++e) theta[e] = sc * w[e];
+        const int64_t dp = (d + 3) / 4 * 4, nfb = (n + TBH - 1) / TBH;
+        const int64_t nW = S * nfb * dp * TBH, nV = S * nfb * TBH;
+        std::vector<double> stage;
+        rff_retile(W, b, theta, S, n, d, dp, nfb, stage);
+        if ((rc = ensure(h, h->drff, h->cap_rff, rff_sweep_ws(WsCarver(nullptr), nW, nV).bytes / 8))) return rc;
+        if ((rc = ensure(h, h->dpath, h->cap_path, path_weights_ws(WsCarver(nullptr), S, N, Np, Sp, eps != nullptr).bytes / 8))) return rc;
+        const RffSweepWs rw = rff_sweep_ws(WsCarver(h->drff), nW, nV);
+        const PathWeightsWs pw = path_weights_ws(WsCarver(h->dpath), S, N, Np, Sp, eps != nullptr);
+        {
+            Span sp(h, T_COPY);
+            HIPCHK(h, hipMemcpyAsync(rw.Wt, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
+            if (eps) HIPCHK(h, hipMemcpyAsync(pw.eps, eps, (size_t)S * N * 8, hipMemcpyHostToDevice, s));
+        }
+        {
+            Span sp(h, T_RFF);
+            launch_rff_mfma(s, rw.Wt, rw.bt, rw.tt, (int)S, (int)nfb, (int)n, (int)d, (int)dp, 0.0, h->dXraw, N, pw.prior, nullptr);
+            launch_path_resid(s, h->dy, h->bias, pw.prior, pw.eps, sqrt(h->sn2), S, N, Np, Sp, pw.R);
+            launch_cov_trmm(s, h->dU, Np, pw.R, Sp, pw.V);
+            for (int64_t p = 0; p < Sp / TBH; ++p)
+                launch_kg_solve(s, h->dU, Np, N, (int)std::min<int64_t>(TBH, S - p * TBH), pw.V + p * Np * TBH, pw.W + p * Np * TBH);
+            launch_path_gather(s, pw.W, S, N, Np, pw.v);
+            HIPCHK(h, hipGetLastError());
+        }
+        {
+            Span sp(h, T_COPY);
+            HIPCHK(h, hipMemcpyAsync(v, pw.v, (size_t)S * N * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(h, hipStreamSynchronize(s));
+        return GPX_OK;
     });
 }
 

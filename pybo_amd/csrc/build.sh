@@ -2,7 +2,7 @@
 # Build libgpx.so and libgpx_diag.so for gfx950 in-tree (the .so files are git-ignored).
 #   build.sh          compile the objects that are older than their inputs (incremental: development)
 #   build.sh --force  compile EVERY object from source (what __graft_entry__.build() runs: the driver's build check must
-#                     compile all sixteen translation units, also on a snapshot that shipped up-to-date .o files)
+#                     compile all seventeen translation units, also on a snapshot that shipped up-to-date .o files)
 # The two libraries link the same objects but one: diag_flag.cpp, compiled twice (diag_flag.o, and diag_flag_diag.o with
 # -DGPX_DIAGNOSTICS), decides whether gpx_set_option accepts the diagnostic knobs of gpx_diag.h.  The test-suite drives
 # libgpx_diag.so (tests/conftest.py: GPX_DIAGNOSTICS=1); everything else loads libgpx.so.
@@ -14,8 +14,8 @@ set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-const-variable $EXTRA"
-SRCS="kernels_fit kernels_chol_tg kernels_sweep kernels_mes kernels_kg kernels_rff kernels_grad kernels_hyper kernels_ens kernels_ehvi kernels_batch kernels_cov comm api"
-HDRS="acq_core.h acq_core_dev.h ehvi_math.h bound_exp.h bound_f32.h gemm_core.h sweep_map.h gpx_internal.h ws_layout.h prune_hint.h gpx_diag.h gpx_math.h mes_math.h kg_math.h fit_tiles.h ../../include/gpx.h"
+SRCS="kernels_fit kernels_chol_tg kernels_sweep kernels_mes kernels_kg kernels_rff kernels_path kernels_grad kernels_hyper kernels_ens kernels_ehvi kernels_batch kernels_cov comm api"
+HDRS="xgram_core.h acq_core.h acq_core_dev.h ehvi_math.h bound_exp.h bound_f32.h gemm_core.h sweep_map.h gpx_internal.h ws_layout.h prune_hint.h gpx_diag.h gpx_math.h mes_math.h kg_math.h fit_tiles.h ../../include/gpx.h"
 FORCE=0
 [ "$1" = "--force" ] && FORCE=1
 pids=()

@@ -258,6 +258,11 @@ struct gpx_handle {
     uint64_t kg_gen = 0;
     int64_t kg_Np = 0;
 
+    // pathwise Thompson draws (gpx_path_weights / gpx_path_sweep / gpx_path_grad; kernels_path.hip): scratch of its own
+    // (path_weights_ws, path_sweep_ws, path_grad_ws)
+    double* dpath = nullptr;
+    int64_t cap_path = 0;
+
     double* dbatch = nullptr;    // gpx_loglik_batch: one allocation (loglik_batch_ws)
     int64_t cap_batch = 0;
     double* dhyper = nullptr;    // gpx_loglik_grad: the tiles' partial sums and the result (hyper_ws; on first use)
@@ -462,6 +467,18 @@ void launch_rff_gram_batch(hipStream_t s, const double* Xraw, int64_t N, int64_t
 void launch_rff_gram(hipStream_t s, const double* Xraw, const double* Ft_scratch, int64_t N, int d,
                      const double* W, const double* b, int n, const double* y, double bias, double* A,
                      double* v);
+
+// launchers (kernels_path.hip): the update term of S pathwise draws added to vals (S, M), which holds the feature part (v: the device
+// copy of the weights (S, nv), frag: path_frag_words(S, nv) doubles); the right-hand sides of the weights as panels of 128 draws, and
+// the panels of U T r back to (S, N)
+void launch_path_update(hipStream_t s, const double* Xs, int d, const double* v, int64_t nv, int64_t S, double* frag,
+                        const double* Xc, int64_t M, const double* invell, int kernel_id, double rho, double* vals);
+void launch_path_resid(hipStream_t s, const double* y, double bias, const double* prior, const double* eps, double sn, int64_t S,
+                       int64_t N, int64_t Np, int64_t Sp, double* R);
+void launch_path_gather(hipStream_t s, const double* Wp, int64_t S, int64_t N, int64_t Np, double* v);
+// (kernels_grad.hip) value and gradient of one pathwise draw at M points
+int path_grad_host(gpx_handle* h, const double* W, const double* b, const double* theta, const double* v, int64_t nv, int64_t n,
+                   int64_t d, double bias, const double* Xc, int64_t M, double* f, double* g);
 
 // launchers (kernels_ens.hip)
 void launch_ens_accum(hipStream_t s, double* acc0, double* acc1, const double* t0, const double* t1, int64_t M,

@@ -975,4 +975,53 @@ int rff_grad_host(gpx_handle* h, const double* W, const double* b, const double*
     return GPX_OK;
 }
 
+// ---- pathwise draw: value + gradient at M points ------------------------------------------------
+// f = (bias + feature sum) + sum_{i < nv} v_i k(x, X_i) and its gradient: k_rff_grad's part, then per pass of GB points the mean's
+// own kernels (k_kstar, k_mean_reduce) over the leading nv observations with v in alpha's place and no bias, added by k_path_grad_add.
+// out per point: [f, df/dx]; part: k_mean_reduce's layout (value at 0, gradient at 2 ..)
+__global__ __launch_bounds__(256) void k_path_grad_add(const double* __restrict__ part, int mb, int d, double* __restrict__ out) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= mb * (d + 1)) return;
+    const int m = e / (d + 1), c = e - m * (d + 1);
+    out[e] = out[e] + part[(int64_t)m * (2 + 2 * d) + (c == 0 ? 0 : 1 + c)];
+}
+
+// One stream, one synchronisation; reads the fit's resident inputs and hyper-parameters only (no inverse, no cache, no announcement).
+int path_grad_host(gpx_handle* h, const double* W, const double* b, const double* theta, const double* v, int64_t nv, int64_t n,
+                   int64_t d, double bias, const double* Xc, int64_t M, double* f, double* g) {
+    if (hipSetDevice(h->device) != hipSuccess) { h->err = "hipSetDevice failed"; return GPX_EHIP; }
+    hipStream_t s = h->stream;
+    const int64_t Np = h->Np;
+    if (int rc = ensure(h, h->dpath, h->cap_path, path_grad_ws(WsCarver(nullptr), n, d, nv, Np, M).bytes / 8, "path_grad")) return rc;
+    const PathGradWs gw = path_grad_ws(WsCarver(h->dpath), n, d, nv, Np, M);
+    bool ok = hipMemcpyAsync(gw.W, W, (size_t)n * d * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(gw.b, b, (size_t)n * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(gw.th, theta, (size_t)n * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(gw.v, v, (size_t)nv * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(gw.X, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, s) == hipSuccess;
+    if (!ok) { h->err = "path_grad: H2D copy failed"; return GPX_EHIP; }
+    hipLaunchKernelGGL(k_rff_grad, dim3((unsigned)M), dim3(256), 0, s, gw.W, gw.b, gw.th, (int)n, (int)d, bias, gw.X, gw.out);
+    for (int64_t m0 = 0; m0 < M; m0 += GB) {
+        const int mb = (int)std::min<int64_t>(GB, M - m0);
+        const double* X = gw.X + m0 * d;
+        hipLaunchKernelGGL(k_kstar, dim3((unsigned)((Np + 255) / 256), (unsigned)mb), dim3(256), 0, s, h->dXs, nv, Np, (int)d, X,
+                           h->dinvell, h->kernel_id, h->rho, gw.ks, gw.g);
+        hipLaunchKernelGGL(k_mean_reduce, dim3((unsigned)(d + 1), (unsigned)mb), dim3(256), 0, s, h->dXs, nv, Np, (int)d, X, h->dinvell,
+                           gw.ks, gw.g, gw.v, 0.0, gw.part);
+        hipLaunchKernelGGL(k_path_grad_add, dim3((unsigned)((mb * (d + 1) + 255) / 256)), dim3(256), 0, s, gw.part, mb, (int)d,
+                           gw.out + m0 * (d + 1));
+    }
+    std::vector<double> host((size_t)M * (d + 1));
+    if (hipMemcpyAsync(host.data(), gw.out, host.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+        h->err = "path_grad: kernel or D2H copy failed";
+        return GPX_EHIP;
+    }
+    for (int64_t m = 0; m < M; ++m) {
+        f[m] = host[(size_t)m * (d + 1)];
+        for (int64_t k = 0; k < d; ++k) g[m * d + k] = host[(size_t)m * (d + 1) + 1 + k];
+    }
+    return GPX_OK;
+}
+
 }  // namespace gpx

@@ -21,35 +21,14 @@
 #include "bound_exp.h"
 #include "bound_f32.h"
 #include "sweep_map.h"
+#include "xgram_core.h"
 
 namespace gpx {
 
 // ------------------------------------------------------------------------------------------------
 // cross-Gram: tile 64 observed rows x 128 candidate columns, 8x4 outputs per thread
 // ------------------------------------------------------------------------------------------------
-constexpr int XK = 64, XN = 128, XDC = 16;
-
-// Staging of a (rows x kc) block of row-major coordinates into LDS as [k][row] WITHOUT index divisions: a thread owns
-// one row and every STRIDE-th coordinate of it (counters: the e / kc, e % kc form cost ~13 of 50-58 VALU instructions
-// per covariance evaluation at d = 8 -- these kernels are VALU-issue-bound).
-// Squared scaled distances of an 8 x 4 block per thread, one dimension at a time; the first dimension starts the sums
-// (df * df == fma(df, df, +0): same bits as a zero-initialised accumulator).
-template <bool FIRST>
-__device__ __forceinline__ void dist_step(const double (*xo)[XK], const double (*xc)[XN], int k, int ty, int tx,
-                                          double (&r2)[8][4]) {
-    double a8[8], b4[4];
-#pragma unroll
-    for (int a = 0; a < 8; ++a) a8[a] = xo[k][ty * 8 + a];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) b4[b] = xc[k][tx * 4 + b];
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const double df = a8[a] - b4[b];
-            r2[a][b] = FIRST ? df * df : fma(df, df, r2[a][b]);
-        }
-}
+// (the tile's shape XK x XN, the coordinate chunk XDC and the distance arithmetic itself: xgram_core.h, shared with kernels_path.hip)
 
 // One workgroup: 128 candidates x xrt consecutive 64-row tiles (the candidates' coordinates are staged once when
 // d <= XDC).  grid (ceil(Np / 64 / xrt), cols / 128): consecutive workgroups write consecutive runs of Ks.
@@ -63,38 +42,14 @@ __global__ __launch_bounds__(256, 3) void k_cross_gram(const double* __restrict_
     __shared__ double xo[XDC][XK];
     __shared__ double xc[XDC][XN];
     const int t = threadIdx.x, tx = t & 31, ty = t >> 5;
-    const int crow = t & (XN - 1), ckq = t >> 7;      // staging of candidates: row, first coordinate (stride 2)
-    const int orow = t & (XK - 1), okq = t >> 6;      // staging of observed rows: row, first coordinate (stride 4)
     const int64_t n0 = (int64_t)blockIdx.y * XN;      // chunk-local candidate origin
-    const int64_t gmc = m0 + n0 + crow;
     const bool onepass = (d <= XDC);
-    if (onepass)
-        for (int k = ckq; k < d; k += 2) xc[k][crow] = (gmc < M) ? Xc[gmc * d + k] * invell[k] : 0.0;
+    if (onepass) xgram_stage_cand(xc, Xc, m0 + n0 + (t & (XN - 1)), M, d, invell, 0, d);
     for (int rt = 0; rt < xrt; ++rt) {
         const int64_t k0 = ((int64_t)blockIdx.x * xrt + rt) * XK;   // observed row origin
         if (k0 >= Np) break;
         double r2[8][4];
-        auto stage = [&](int c0, int kc) {
-            __syncthreads();
-            for (int k = okq; k < kc; k += 4) xo[k][orow] = Xs[(k0 + orow) * d + c0 + k];
-            if (!onepass)
-                for (int k = ckq; k < kc; k += 2)
-                    xc[k][crow] = (gmc < M) ? Xc[gmc * d + c0 + k] * invell[c0 + k] : 0.0;
-            __syncthreads();
-        };
-        {
-            const int kc = min(XDC, d);
-            stage(0, kc);
-            dist_step<true>(xo, xc, 0, ty, tx, r2);
-#pragma unroll 1
-            for (int k = 1; k < kc; ++k) dist_step<false>(xo, xc, k, ty, tx, r2);
-        }
-        for (int c0 = XDC; c0 < d; c0 += XDC) {
-            const int kc = min(XDC, d - c0);
-            stage(c0, kc);
-#pragma unroll 1
-            for (int k = 0; k < kc; ++k) dist_step<false>(xo, xc, k, ty, tx, r2);
-        }
+        xgram_tile_r2(xo, xc, Xs, k0, d, Xc, m0 + n0, M, invell, onepass, r2);
         // a tile without padding rows / columns (every tile of the north-star launch) needs no selects: two of the 58 VALU
         // instructions per entry of a kernel that is bound by their issue (workgroup-uniform branch)
         const bool full = (k0 + XK <= N) && (m0 + n0 + XN <= M);

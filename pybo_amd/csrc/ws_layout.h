@@ -7,6 +7,7 @@
 #pragma once
 #include <assert.h>
 #include <stdint.h>
+#include <algorithm>
 #include <vector>
 
 #include "bound_f32.h"
@@ -238,6 +239,41 @@ inline RffWideWs rff_wide_ws(WsCarver c, int64_t n, int64_t d, int64_t np, int64
     if (p) c.skip<double>(n);        // slack the allocation has always had
     w.bytes = c.bytes();
     return w;
+}
+
+// Pathwise Thompson draws (h->dpath; kernels_path.hip).  The weight panel of a sweep in the fragment order of v_mfma_f64_16x16x4:
+// per group of at most PATH_GROUP draws, per 64-row tile of the leading nv observations, per k-step of 4 rows, one 64-lane fragment
+// for each block of 16 draws the group holds (rows >= nv and draws >= S: zeros).
+constexpr int PATH_GROUP = 64, PATH_ROWS = 64;
+inline int64_t path_tiles(int64_t nv) { return (nv + PATH_ROWS - 1) / PATH_ROWS; }
+inline int path_group_blocks(int64_t S, int64_t g) { return (int)((std::min<int64_t>(PATH_GROUP, S - g * PATH_GROUP) + 15) / 16); }
+inline int64_t path_group_offset(int64_t nv, int64_t g) { return g * path_tiles(nv) * (PATH_ROWS / 4) * (PATH_GROUP / 16) * 64; }      // (every earlier group is full)
+inline int64_t path_frag_words(int64_t S, int64_t nv) {
+    const int64_t G = (S + PATH_GROUP - 1) / PATH_GROUP;
+    return path_group_offset(nv, G - 1) + path_tiles(nv) * (PATH_ROWS / 4) * path_group_blocks(S, G - 1) * 64;
+}
+// gpx_path_sweep: the caller's weights (S, nv) as uploaded, then the panel on a 512-byte boundary
+struct PathSweepWs { double *v, *frag; int64_t bytes; };
+inline PathSweepWs path_sweep_ws(WsCarver c, int64_t S, int64_t nv) {
+    double* const v = c.take<double>(S * nv, "v");
+    c.align_to(512);
+    return {v, c.take<double>(path_frag_words(S, nv), "frag"), c.bytes()};
+}
+// gpx_path_weights: the prior draws at the N observations (S, N), the caller's noise normals, the right-hand sides, T r and U T r as
+// k-major panels of 128 draws [Sp / 128][Np][128] (every panel on a 512-byte boundary: Np 128 doubles each), the weights (S, N)
+struct PathWeightsWs { double *prior, *eps, *R, *V, *W, *v; int64_t bytes; };
+inline PathWeightsWs path_weights_ws(WsCarver c, int64_t S, int64_t N, int64_t Np, int64_t Sp, bool eps) {
+    double* const prior = c.take<double>(S * N, "prior");
+    double* const e = eps ? c.take<double>(S * N, "eps") : nullptr;
+    c.align_to(512);
+    return {prior, e, c.take<double>(Np * Sp, "R"), c.take<double>(Np * Sp, "V"), c.take<double>(Np * Sp, "W"), c.take<double>(S * N, "v"), c.bytes()};
+}
+// gpx_path_grad (h->dpath): one draw's parameters and leading weights, the M points, per pass of GB points k* and dk/dr2 over Np rows
+// and k_mean_reduce's 2 + 2 d outputs per point, then [f, df/dx] per point
+struct PathGradWs { double *W, *b, *th, *v, *X, *ks, *g, *part, *out; int64_t bytes; };
+inline PathGradWs path_grad_ws(WsCarver c, int64_t n, int64_t d, int64_t nv, int64_t Np, int64_t M) {
+    return {c.take<double>(n * d, "W"), c.take<double>(n, "b"), c.take<double>(n, "th"), c.take<double>(nv, "v"), c.take<double>(M * d, "X"),
+            c.take<double>(GB * Np, "ks"), c.take<double>(GB * Np, "g"), c.take<double>(GB * (2 + 2 * d), "part"), c.take<double>(M * (d + 1), "out"), c.bytes()};
 }
 
 // gpx_loglik_batch (h->dbatch), B vectors at once: Gram, factor, scaled inputs, a, {rho, sn2, bias}, 1 / ell, the results, and for

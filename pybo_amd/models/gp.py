@@ -153,6 +153,47 @@ class RFFSampleDevice(object):
     __call__ = get
 
 
+class PathSampleDevice(object):
+    """One PATHWISE posterior function sample (Matheron's rule; Wilson et al. 2020): the RFF draw is the prior sample, corrected
+    exactly with the model's factorisation -- f(x) = bias + theta . cos(W x + b) + v . k(X[:nv], x).  `.get(X, grad=False)` and
+    `.topk(xgrid, k)` evaluate on the device.  The sample is a FIXED function of the hyper-parameters and the nv observations it was
+    conditioned on: it stays valid while the model is only appended to, and raises RuntimeError -- rather than silently becoming
+    another function -- once the hyper-parameters or those leading rows differ.  It refers to the model itself, never to a copy: a
+    shared device state would turn every later `add_data` from an append into a refit."""
+
+    def __init__(self, model, W, b, theta, v):
+        self._model, self.W, self.b, self.theta, self.v, self.bias = model, W, b, theta, v, float(model.bias)
+        self._key, self.nv = model._hyper_key(), len(v)
+        self._X = model._X                           # (replaced by add_data, never mutated in place)
+
+    def _eng(self):
+        m = self._model
+        if m._hyper_key() != self._key:
+            raise RuntimeError('the pathwise sample was drawn under other hyper-parameters than the model now carries')
+        if m.ndata < self.nv or not (m._X is self._X or np.array_equal(m._X[:self.nv], self._X[:self.nv])):
+            raise RuntimeError('the model no longer begins with the %d observations the pathwise sample was conditioned on' % self.nv)
+        return m._engine()
+
+    def get(self, X, grad=False):
+        X = np.array(X, ndmin=2, dtype=float)
+        eng = self._eng()
+        if grad:
+            return eng.path_eval_grad(self.W, self.b, self.theta, self.v, self.bias, X)
+        return eng.path_sweep(self.W[None], self.b[None], self.theta[None], self.v[None], self.bias, X, k=0)['vals'][0]
+
+    def topk(self, xgrid, k):
+        eng = self._eng()
+        if isinstance(xgrid, DeviceGrid) and int(xgrid.device) != int(eng.device):
+            xgrid = np.asarray(xgrid)                # resident on ANOTHER GPU: its pointer means nothing here
+        if isinstance(xgrid, DeviceGrid):            # grid already resident in HBM
+            tv, ti = eng.path_sweep_dev(self.W[None], self.b[None], self.theta[None], self.v[None], self.bias, xgrid.ptr, len(xgrid), int(k))
+            return tv[0], ti[0]
+        out = eng.path_sweep(self.W[None], self.b[None], self.theta[None], self.v[None], self.bias, xgrid, k=int(k), want_all=False)
+        return out['top_val'][0], out['top_idx'][0]
+
+    __call__ = get
+
+
 class GP(object):
     APPEND_MAX = 16     # add_data with at most this many new rows extends the factorisation in place
     MEAN_DIRECT_ROWS = 256      # predict_mean of at most this many points: k(x, X).alpha, 16 points per device call
@@ -577,10 +618,15 @@ class GP(object):
         """The device handle whose HBM holds the (value, index) pairs of the last `acq_topk`."""
         return self._engine()
 
-    def sample_f(self, n, rng=None):
+    def sample_f(self, n, rng=None, method='rff'):
         """RFF posterior function sample.  Host draws (order fixed: randn(n,d), [chisquare], rand(n),
         randn(n)); the O(N n^2) feature Gram and the n x n weight posterior run on the device (n <= 4096 features; a
-        noise-free model solves on the host)."""
+        noise-free model solves on the host).
+        method='pathwise': the same draws give the PRIOR sample (same W, b, w for the same seed), then randn(N) the noise of
+        Matheron's update; the weights v = (K + sn2 I)^-1 (y - prior(X) - sqrt(sn2) eps) come from the device
+        (gpx_path_weights) and the result is a `PathSampleDevice`, which passes through the data up to the noise."""
+        if method not in ('rff', 'pathwise'):
+            raise ValueError("sample_f: method must be 'rff' or 'pathwise', not %r" % (method,))
         rng = rstate(rng)
         d = len(self.ell)
         W = rng.randn(n, d)
@@ -594,6 +640,10 @@ class GP(object):
         sc = np.sqrt(2.0 * self.rho / n)
         if self.ndata == 0:
             return RFFSampleDevice(self, W, b, sc * z)
+        if method == 'pathwise':
+            eps = rng.randn(self.ndata)
+            theta, v = self._engine().path_weights(W[None], b[None], z[None], eps[None], sc)
+            return PathSampleDevice(self, W, b, theta[0], v[0])
         if n <= 4096 and self.sn2 > 0.0:    # feature Gram AND the n x n weight posterior on the device (gpx_rff_posterior)
             theta = self._engine().rff_posterior(W[None], b[None], z[None], sc)[0]
             return RFFSampleDevice(self, W, b, theta)

@@ -404,10 +404,11 @@ class MCMC(object):
             return member_mean(outs)
         return member_mean([o[0] for o in outs]), member_mean([o[1] for o in outs])
 
-    def sample_f(self, n, rng=None):
+    def sample_f(self, n, rng=None, method='rff'):
         rng = rstate(rng)
         members = self._need()
-        return members[rng.randint(len(members))].sample_f(n, rng)
+        member = members[rng.randint(len(members))]
+        return member.sample_f(n, rng) if method == 'rff' else member.sample_f(n, rng, method=method)
 
     def sample(self, X, size=None, latent=True, rng=None, jitter=None):
         """Joint draws at the rows of X from the MIXTURE: every draw comes from a member chosen uniformly by `rng` (as `sample_f`

@@ -232,9 +232,11 @@ class ShardedGP(object):
         return _sharded_topk([lambda g, kk, r=r: r.acq_topk(kind, param, g, kk) for r in self._reps], xgrid, k,
                              self.devices)
 
-    def sample_f(self, n, rng=None):
+    def sample_f(self, n, rng=None, method='rff'):
         """ONE posterior function sample (the host draws and the weight posterior come from replica 0), evaluated by
-        every replica on its shard of the grid."""
+        every replica on its shard of the grid.  Pathwise draws (models/gp.py) are not sharded yet."""
+        if method != 'rff':
+            raise NotImplementedError("ShardedGP.sample_f: only method='rff' is sharded (got %r)" % (method,))
         first = self._reps[0].sample_f(n, rstate(rng))
         rest = [RFFSampleDevice(r, first.W, first.b, first.theta) for r in self._reps[1:]]
         for s in rest:

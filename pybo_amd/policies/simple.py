@@ -66,9 +66,10 @@ def PI(model, _, X, xi=0.05):
     return _attach_topk(index, model, 'pi', target)
 
 
-def Thompson(model, _, __, n=100, rng=None):
-    """Thompson sampling: the index is one posterior function sample built from n random features."""
-    sample = model.sample_f(n, rng)
+def Thompson(model, _, __, n=100, rng=None, method='rff'):
+    """Thompson sampling: the index is one posterior function sample built from n random features.  method='pathwise' (device
+    models): the feature draw is only the prior, conditioned exactly on the data by the model's factorisation (Matheron's rule)."""
+    sample = model.sample_f(n, rng) if method == 'rff' else model.sample_f(n, rng, method=method)
     fast = getattr(sample, 'topk', None)
     if fast is None:
         return sample.get
