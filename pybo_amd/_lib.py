@@ -190,6 +190,49 @@ def _f64(a, shape=None):
     return a
 
 
+def _dptr(p):
+    """A device pointer given as an integer (0 / None: NULL)."""
+    return _P(p) if p else None
+
+
+def _handles(engines):
+    return (_P * len(engines))(*[e._h for e in engines])
+
+
+def _topk_out(k, S=None):
+    """The top-k buffers of a sweep entry ((S, k) for S draws) and the pointers it takes for them: NULL for k = 0."""
+    shape = k if S is None else (S, k)
+    tv, ti = np.empty(shape), np.empty(shape, dtype=np.int64)
+    return tv, ti, _ptr(tv) if k else None, _ptr(ti) if k else None
+
+
+def _candidates(Xc, d, **want):
+    """(dev, pointer, M, outputs) of the candidates of a sweep entry with a host and a _dev form: a DeviceGrid gives its device pointer
+    and no host output; anything else is a host array (M, d) and gives an (M,) buffer for every name of `want` that is true."""
+    if isinstance(Xc, DeviceGrid):
+        return True, Xc.ptr, len(Xc), dict.fromkeys(want)
+    Xc = _f64(Xc).reshape(-1, d)      # (the pointer keeps the array alive)
+    return False, _ptr(Xc), len(Xc), {name: np.empty(len(Xc)) if on else None for name, on in want.items()}
+
+
+def _report_head(scal):
+    """The eight scalars every prune report starts with."""
+    r = {name: int(v) for name, v in zip(('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv'), scal[:8])}
+    r['path'] = Engine.PRUNE_PATHS[r['path']]
+    return r
+
+
+def _report_vectors(r, vectors, fetch):
+    """The second call of a prune report, where the bound pass ran: r['ub'] (M,) and r['idx'] (the survivors; empty where it fell back),
+    filled by fetch(ub pointer, idx pointer, nidx)."""
+    if vectors and r['path'] in ('pruned', 'fell back'):
+        nidx = r['nsurv'] if r['path'] == 'pruned' else 0
+        r['ub'] = np.empty(r['M'])
+        r['idx'] = np.empty(nidx, dtype=np.int64)
+        fetch(_ptr(r['ub']), _ptr(r['idx']), nidx)
+    return r
+
+
 def _acq_params(param):
     """The (params, nparams) pair of a sweep entry from an acquisition parameter: a scalar (EI / PI target, UCB beta) or None (the
     mean) is one double; an array (the maximum samples of 'mes', (S,) or member-major (n, S)) passes through flattened, untouched."""
@@ -642,30 +685,23 @@ class Engine(object):
         Xc = _f64(Xc)
         Xc = Xc.reshape(-1, self.d) if self.d else np.atleast_2d(Xc)
         M = len(Xc)
-        aid = acq_id(acq)
         params, nparams = _acq_params(param)
-        tv = np.empty(k)
-        ti = np.empty(k, dtype=np.int64)
+        tv, ti, ptv, pti = _topk_out(k)
         out = np.empty(M) if want_all else None
         mu = np.empty(M) if want_moments else None
         s2 = np.empty(M) if want_moments else None
-        self._check(self._lib.gpx_sweep(self._h, aid, _ptr(params), nparams, _ptr(Xc), M, k,
-                                        _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out),
-                                        _ptr(mu), _ptr(s2)))
+        self._check(self._lib.gpx_sweep(self._h, acq_id(acq), _ptr(params), nparams, _ptr(Xc), M, k, ptv, pti, _ptr(out), _ptr(mu), _ptr(s2)))
         return dict(top_val=tv, top_idx=ti, acq=out, mu=mu, s2=s2)
 
     def sweep_update(self, acq, param, k=0, want_all=True, want_moments=False):
         """Re-score the cached candidate set (option sweep_cache, kept current by append): O(M)."""
         M = self.sweep_cache_size()
-        aid = acq_id(acq)
         params, nparams = _acq_params(param)
-        tv = np.empty(k)
-        ti = np.empty(k, dtype=np.int64)
+        tv, ti, ptv, pti = _topk_out(k)
         out = np.empty(M) if want_all else None
         mu = np.empty(M) if want_moments else None
         s2 = np.empty(M) if want_moments else None
-        self._check(self._lib.gpx_sweep_update(self._h, aid, _ptr(params), nparams, k, _ptr(tv) if k else None,
-                                               _ptr(ti) if k else None, _ptr(out), _ptr(mu), _ptr(s2)))
+        self._check(self._lib.gpx_sweep_update(self._h, acq_id(acq), _ptr(params), nparams, k, ptv, pti, _ptr(out), _ptr(mu), _ptr(s2)))
         return dict(top_val=tv, top_idx=ti, acq=out, mu=mu, s2=s2)
 
     def sweep_cache_size(self):
@@ -685,14 +721,10 @@ class Engine(object):
         return out
 
     def sweep_dev(self, acq, param, dXc_ptr, M, k, d_acq=None, d_mu=None, d_s2=None):
-        aid = acq_id(acq)
         params, nparams = _acq_params(param)
-        tv = np.empty(k)
-        ti = np.empty(k, dtype=np.int64)
-        self._check(self._lib.gpx_sweep_dev(self._h, aid, _ptr(params), nparams, _P(dXc_ptr), M, k,
-                                            _ptr(tv) if k else None, _ptr(ti) if k else None,
-                                            _P(d_acq) if d_acq else None, _P(d_mu) if d_mu else None,
-                                            _P(d_s2) if d_s2 else None))
+        tv, ti, ptv, pti = _topk_out(k)
+        self._check(self._lib.gpx_sweep_dev(self._h, acq_id(acq), _ptr(params), nparams, _P(dXc_ptr), M, k, ptv, pti, _dptr(d_acq), _dptr(d_mu),
+                                            _dptr(d_s2)))
         return tv, ti
 
     @staticmethod
@@ -700,26 +732,13 @@ class Engine(object):
         """Hyper-parameter ensemble sweep (gpx_ensemble_sweep[_dev]): the member sweeps and their average stay
         on the device.  `Xc`: host array (M, d) or a DeviceGrid.  Returns dict(top_val, top_idx, acq, mu, s2)."""
         lead = engines[0]
-        handles = (_P * len(engines))(*[e._h for e in engines])
-        aid = acq_id(acq)
         params, nparams = _acq_params(param)
-        tv = np.empty(k)
-        ti = np.empty(k, dtype=np.int64)
-        if isinstance(Xc, DeviceGrid):
-            M = len(Xc)
-            lead._check(lead._lib.gpx_ensemble_sweep_dev(handles, len(engines), aid, _ptr(params), nparams, Xc.ptr, M,
-                                                         k, _ptr(tv) if k else None, _ptr(ti) if k else None,
-                                                         None, None, None))
-            return dict(top_val=tv, top_idx=ti, acq=None, mu=None, s2=None)
-        Xc = _f64(Xc).reshape(-1, lead.d)
-        M = len(Xc)
-        out = np.empty(M) if want_all else None
-        mu = np.empty(M) if want_moments else None
-        s2 = np.empty(M) if want_moments else None
-        lead._check(lead._lib.gpx_ensemble_sweep(handles, len(engines), aid, _ptr(params), nparams, _ptr(Xc), M, k,
-                                                 _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out),
-                                                 _ptr(mu), _ptr(s2)))
-        return dict(top_val=tv, top_idx=ti, acq=out, mu=mu, s2=s2)
+        tv, ti, ptv, pti = _topk_out(k)
+        dev, X, M, o = _candidates(Xc, lead.d, acq=want_all, mu=want_moments, s2=want_moments)
+        fn = lead._lib.gpx_ensemble_sweep_dev if dev else lead._lib.gpx_ensemble_sweep
+        lead._check(fn(_handles(engines), len(engines), acq_id(acq), _ptr(params), nparams, X, M, k, ptv, pti, _ptr(o['acq']), _ptr(o['mu']),
+                       _ptr(o['s2'])))
+        return dict(top_val=tv, top_idx=ti, **o)
 
     @staticmethod
     def ensemble_batch(engines, kind, param, nb):
@@ -727,13 +746,11 @@ class Engine(object):
         conditioned on a pick at its own posterior mean.  Returns dict(sel_val (nb,), sel_idx (nb,), sel_s2 (n, nb)); the members
         are left as they were."""
         lead = engines[0]
-        handles = (_P * len(engines))(*[e._h for e in engines])
-        aid = acq_id(kind)
         params, nparams = _acq_params(param)
         n = max(int(nb), 0)
         out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty((len(engines), n)))
-        lead._check(lead._lib.gpx_ensemble_sweep_batch(handles, len(engines), aid, _ptr(params), nparams, int(nb), _ptr(out['sel_val']),
-                                                       _ptr(out['sel_idx']), _ptr(out['sel_s2'])))
+        lead._check(lead._lib.gpx_ensemble_sweep_batch(_handles(engines), len(engines), acq_id(kind), _ptr(params), nparams, int(nb),
+                                                       _ptr(out['sel_val']), _ptr(out['sel_idx']), _ptr(out['sel_s2'])))
         return out
 
     @staticmethod
@@ -741,12 +758,11 @@ class Engine(object):
         """Per-member moments and gradients at the rows of Xc in ONE call (gpx_ensemble_predict):
         mu, s2 (n, M); dmu, ds2 (n, M, d)."""
         lead = engines[0]
-        handles = (_P * len(engines))(*[e._h for e in engines])
         Xc = _f64(Xc).reshape(-1, lead.d)
         n, M, d = len(engines), len(Xc), lead.d
         mu, s2 = np.empty((n, M)), np.empty((n, M))
         dmu, ds2 = np.empty((n, M, d)), np.empty((n, M, d))
-        lead._check(lead._lib.gpx_ensemble_predict(handles, n, _ptr(Xc), M, _ptr(mu), _ptr(s2), _ptr(dmu), _ptr(ds2)))
+        lead._check(lead._lib.gpx_ensemble_predict(_handles(engines), n, _ptr(Xc), M, _ptr(mu), _ptr(s2), _ptr(dmu), _ptr(ds2)))
         return mu, s2, dmu, ds2
 
     @staticmethod
@@ -757,27 +773,18 @@ class Engine(object):
         pof); the lead (obj, else cons[0]) raises the errors."""
         cons = list(cons)
         lead = obj if obj is not None else cons[0]
-        handles = (_P * len(cons))(*[e._h for e in cons])
         thr = _f64(thr).reshape(-1)
         if len(thr) != len(cons):
             raise ValueError('one threshold per constraint')
         aid = acq_id(acq) if obj is not None else 0
         params, nparams = _acq_params(param)
-        tv = np.empty(k)
-        ti = np.empty(k, dtype=np.int64)
-        oh = obj._h if obj is not None else None
-        if isinstance(Xc, DeviceGrid):
-            lead._check(lead._lib.gpx_constrained_sweep_dev(oh, handles, len(cons), _ptr(thr), aid, _ptr(params), nparams, Xc.ptr, len(Xc), k,
-                                                            _ptr(tv) if k else None, _ptr(ti) if k else None,
-                                                            _P(d_acq) if d_acq else None, _P(d_pof) if d_pof else None))
-            return dict(top_val=tv, top_idx=ti, acq=None, pof=None)
-        Xc = _f64(Xc).reshape(-1, lead.d)
-        M = len(Xc)
-        out = np.empty(M) if want_all else None
-        pof = np.empty(M) if want_pof else None
-        lead._check(lead._lib.gpx_constrained_sweep(oh, handles, len(cons), _ptr(thr), aid, _ptr(params), nparams, _ptr(Xc), M, k,
-                                                    _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out), _ptr(pof)))
-        return dict(top_val=tv, top_idx=ti, acq=out, pof=pof)
+        tv, ti, ptv, pti = _topk_out(k)
+        dev, X, M, o = _candidates(Xc, lead.d, acq=want_all, pof=want_pof)
+        fn = lead._lib.gpx_constrained_sweep_dev if dev else lead._lib.gpx_constrained_sweep
+        outs = (_dptr(d_acq), _dptr(d_pof)) if dev else (_ptr(o['acq']), _ptr(o['pof']))
+        lead._check(fn(obj._h if obj is not None else None, _handles(cons), len(cons), _ptr(thr), aid, _ptr(params), nparams, X, M, k, ptv, pti,
+                       *outs))
+        return dict(top_val=tv, top_idx=ti, **o)
 
     @staticmethod
     def _front_args(front, ref):
@@ -793,29 +800,20 @@ class Engine(object):
         `front` (np, 2) above `ref` (2), both host arrays.  `Xc`: host array (M, d) or a DeviceGrid (then d_acq / d_mom: optional device
         pointers of an (M,) and a (4, M) array: mu1, s2_1, mu2, s2_2).  Returns dict(top_val, top_idx, acq); f1 (the lead) raises the errors."""
         front, ref = Engine._front_args(front, ref)
-        tv = np.empty(k)
-        ti = np.empty(k, dtype=np.int64)
-        fp = _ptr(front) if len(front) else None
-        if isinstance(Xc, DeviceGrid):
-            f1._check(f1._lib.gpx_ehvi_sweep_dev(f1._h, f2._h, fp, len(front), _ptr(ref), Xc.ptr, len(Xc), k, _ptr(tv) if k else None,
-                                                 _ptr(ti) if k else None, _P(d_acq) if d_acq else None, _P(d_mom) if d_mom else None))
-            return dict(top_val=tv, top_idx=ti, acq=None)
-        Xc = _f64(Xc).reshape(-1, f1.d)
-        M = len(Xc)
-        out = np.empty(M) if want_all else None
-        f1._check(f1._lib.gpx_ehvi_sweep(f1._h, f2._h, fp, len(front), _ptr(ref), _ptr(Xc), M, k, _ptr(tv) if k else None,
-                                         _ptr(ti) if k else None, _ptr(out)))
-        return dict(top_val=tv, top_idx=ti, acq=out)
+        tv, ti, ptv, pti = _topk_out(k)
+        dev, X, M, o = _candidates(Xc, f1.d, acq=want_all)
+        args = (f1._h, f2._h, _ptr(front) if len(front) else None, len(front), _ptr(ref), X, M, k, ptv, pti)
+        f1._check(f1._lib.gpx_ehvi_sweep_dev(*args, _dptr(d_acq), _dptr(d_mom)) if dev else f1._lib.gpx_ehvi_sweep(*args, _ptr(o['acq'])))
+        return dict(top_val=tv, top_idx=ti, **o)
 
     def ehvi_fold(self, d_mom, M, front, ref, k=0, d_acq=None):
         """The fold and the top-k of a two-objective sweep alone (gpx_ehvi_fold_dev) on this engine's stream: `d_mom` the device pointer of
         a (4, M) array mu1, s2_1, mu2, s2_2 (e.g. of two `sweep_update` calls), `d_acq` an optional device pointer of (M,) values.
         Returns dict(top_val, top_idx)."""
         front, ref = Engine._front_args(front, ref)
-        tv = np.empty(k)
-        ti = np.empty(k, dtype=np.int64)
-        self._check(self._lib.gpx_ehvi_fold_dev(self._h, _P(d_mom), int(M), _ptr(front) if len(front) else None, len(front), _ptr(ref), k,
-                                                _ptr(tv) if k else None, _ptr(ti) if k else None, _P(d_acq) if d_acq else None))
+        tv, ti, ptv, pti = _topk_out(k)
+        self._check(self._lib.gpx_ehvi_fold_dev(self._h, _P(d_mom), int(M), _ptr(front) if len(front) else None, len(front), _ptr(ref), k, ptv, pti,
+                                                _dptr(d_acq)))
         return dict(top_val=tv, top_idx=ti)
 
     def constrained_prune_report(self, vectors=True):
@@ -824,17 +822,10 @@ class Engine(object):
         objective's EI bound as the survivor pass read it, and idx, the survivors in compaction order (empty where it fell back)."""
         scal = np.full(11, np.nan)
         self._check(self._lib.gpx_constrained_prune_report(self._h, _ptr(scal), len(scal), None, None, 0))
-        names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'tau', 'gate', 'delta')
-        r = dict(zip(names, scal.tolist()))
-        for n in names[:8]:
-            r[n] = int(r[n])
-        r['path'] = Engine.PRUNE_PATHS[r['path']]
-        if vectors and r['path'] in ('pruned', 'fell back'):
-            nidx = r['nsurv'] if r['path'] == 'pruned' else 0
-            r['ub'] = np.empty(r['M'])
-            r['idx'] = np.empty(nidx, dtype=np.int64)
-            self._check(self._lib.gpx_constrained_prune_report(self._h, _ptr(scal), len(scal), _ptr(r['ub']), _ptr(r['idx']), nidx))
-        return r
+        r = _report_head(scal)
+        r.update(zip(('tau', 'gate', 'delta'), scal[8:].tolist()))
+        return _report_vectors(r, vectors, lambda ub, idx, nidx: self._check(
+            self._lib.gpx_constrained_prune_report(self._h, _ptr(scal), len(scal), ub, idx, nidx)))
 
     # -- Thompson --------------------------------------------------------------------------------
     def rff_gram(self, W, b):
@@ -872,11 +863,9 @@ class Engine(object):
         theta = _f64(theta).reshape(S, n)
         Xc = _f64(Xc).reshape(-1, d)
         M = len(Xc)
-        tv = np.empty((S, k))
-        ti = np.empty((S, k), dtype=np.int64)
+        tv, ti, ptv, pti = _topk_out(k, S)
         out = np.empty((S, M)) if want_all else None
-        self._check(self._lib.gpx_rff_sweep(self._h, _ptr(W), _ptr(b), _ptr(theta), S, n, d, bias, _ptr(Xc), M,
-                                            k, _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out)))
+        self._check(self._lib.gpx_rff_sweep(self._h, _ptr(W), _ptr(b), _ptr(theta), S, n, d, bias, _ptr(Xc), M, k, ptv, pti, _ptr(out)))
         return dict(top_val=tv, top_idx=ti, vals=out)
 
     def rff_eval_grad(self, W, b, theta, bias, Xc):
@@ -927,11 +916,10 @@ class Engine(object):
         v = _f64(v).reshape(S, -1)
         Xc = _f64(Xc).reshape(-1, d)
         M = len(Xc)
-        tv = np.empty((S, k))
-        ti = np.empty((S, k), dtype=np.int64)
+        tv, ti, ptv, pti = _topk_out(k, S)
         out = np.empty((S, M)) if want_all else None
-        self._check(self._lib.gpx_path_sweep(self._h, _ptr(W), _ptr(b), _ptr(theta), _ptr(v), v.shape[1], S, n, d, bias, _ptr(Xc), M,
-                                             k, _ptr(tv) if k else None, _ptr(ti) if k else None, _ptr(out)))
+        self._check(self._lib.gpx_path_sweep(self._h, _ptr(W), _ptr(b), _ptr(theta), _ptr(v), v.shape[1], S, n, d, bias, _ptr(Xc), M, k, ptv, pti,
+                                             _ptr(out)))
         return dict(top_val=tv, top_idx=ti, vals=out)
 
     def path_sweep_dev(self, W, b, theta, v, bias, dXc_ptr, M, k, d_vals=None):
@@ -940,11 +928,9 @@ class Engine(object):
         b = _f64(b).reshape(S, n)
         theta = _f64(theta).reshape(S, n)
         v = _f64(v).reshape(S, -1)
-        tv = np.empty((S, k))
-        ti = np.empty((S, k), dtype=np.int64)
-        self._check(self._lib.gpx_path_sweep_dev(self._h, _ptr(W), _ptr(b), _ptr(theta), _ptr(v), v.shape[1], S, n, d, bias,
-                                                 _P(dXc_ptr), M, k, _ptr(tv) if k else None, _ptr(ti) if k else None,
-                                                 _P(d_vals) if d_vals else None))
+        tv, ti, ptv, pti = _topk_out(k, S)
+        self._check(self._lib.gpx_path_sweep_dev(self._h, _ptr(W), _ptr(b), _ptr(theta), _ptr(v), v.shape[1], S, n, d, bias, _P(dXc_ptr), M, k, ptv,
+                                                 pti, _dptr(d_vals)))
         return tv, ti
 
     def path_eval_grad(self, W, b, theta, v, bias, Xc):
@@ -982,32 +968,28 @@ class Engine(object):
         weights without a positive one (None likewise)."""
         scal = np.full(22, np.nan)
         self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), None, None, 0, None, None, 0))
-        names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'S', 'delta', 'tau', 'gate_s2', 'thr_key', 'kept',
-                 'bound_kernel', 'guard', 'nR', 'nsurv2', 'E', 'gate_hint', 'bound_fact', 'bound_tpos')
-        r = dict(zip(names, scal.tolist()))
+        r = _report_head(scal)
+        r.update(zip(('S', 'delta', 'tau', 'gate_s2', 'thr_key', 'kept', 'bound_kernel', 'guard', 'nR', 'nsurv2', 'E', 'gate_hint', 'bound_fact',
+                      'bound_tpos'), scal[8:].tolist()))
         r['bound_fact'] = None if np.isnan(r['bound_fact']) else r['bound_fact'] == 1.0
         r['bound_tpos'] = None if np.isnan(r['bound_tpos']) else int(r['bound_tpos'])
         r['gate_hint'] = r['gate_hint'] == 1.0
         r['bound_kernel'] = None if np.isnan(r['bound_kernel']) else ('generic', 'mfma', 'mfma32')[int(r['bound_kernel'])]
-        for n in ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'kept', 'nR', 'nsurv2'):
+        for n in ('kept', 'nR', 'nsurv2'):
             r[n] = int(r[n])
-        r['path'] = self.PRUNE_PATHS[r['path']]
-        if vectors and r['path'] in ('pruned', 'fell back'):
-            M = r['M']
-            nidx = r['nsurv'] if r['path'] == 'pruned' else 0
-            r['ub'] = np.empty(M)
-            r['idx'] = np.empty(nidx, dtype=np.int64)
+
+        def fetch(ub, idx, nidx):
             kept = bool(r['kept'])
-            r['ub_kept'] = np.empty(M) if kept else None
+            r['ub_kept'] = np.empty(r['M']) if kept else None
             r['seed_idx'] = np.empty(r['G'], dtype=np.int64) if kept else None
-            self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), _ptr(r['ub']), _ptr(r['idx']), nidx,
-                                                   _ptr(r['ub_kept']), _ptr(r['seed_idx']), r['G'] if kept else 0))
+            self._check(self._lib.gpx_prune_report(self._h, _ptr(scal), len(scal), ub, idx, nidx, _ptr(r['ub_kept']), _ptr(r['seed_idx']),
+                                                   r['G'] if kept else 0))
             if r['nR'] > 0 and kept:
                 r['ub2'] = np.empty(nidx)
                 r['idx2'] = np.empty(r['nsurv2'], dtype=np.int64)
                 r['qR'] = np.empty(nidx)
                 self._check(self._lib.gpx_prune_rows(self._h, _ptr(r['qR']), _ptr(r['ub2']), _ptr(r['idx2']), r['nsurv2']))
-        return r
+        return _report_vectors(r, vectors, fetch)
 
     @staticmethod
     def ensemble_prune_report(engines, vectors=True):
@@ -1015,25 +997,16 @@ class Engine(object):
         dict(path, M, k, G, Gg, done, cap, nsurv, tau, gate, delta (n,), gate_hint: the gate was skipped on the carried decision); with `vectors`, where the bound pass ran, also ub (M,), the ensemble
         bound as the survivor pass read it, and idx, the survivors in compaction order (empty where it fell back).  bound_fact (n,): 1.0 where a
         member's dots came from the fp32 kernel's factorised walk, 0.0 from another kernel or form, NaN where the host chose the generic kernel."""
-        lead = engines[0]
-        handles = (_P * len(engines))(*[e._h for e in engines])
+        lead, handles = engines[0], _handles(engines)
         scal = np.full(11 + 2 * len(engines), np.nan)
         lead._check(lead._lib.gpx_ensemble_prune_report(handles, len(engines), _ptr(scal), len(scal), None, None, 0))
-        names = ('path', 'M', 'k', 'G', 'Gg', 'done', 'cap', 'nsurv', 'tau', 'gate')
-        r = dict(zip(names, scal[:10].tolist()))
-        for n in names[:8]:
-            r[n] = int(r[n])
-        r['path'] = Engine.PRUNE_PATHS[r['path']]
+        r = _report_head(scal)
+        r.update(zip(('tau', 'gate'), scal[8:10].tolist()))
         r['delta'] = scal[10:10 + len(engines)].copy()
         r['gate_hint'] = scal[10 + len(engines)] == 1.0
         r['bound_fact'] = scal[11 + len(engines):11 + 2 * len(engines)].copy()
-        if vectors and r['path'] in ('pruned', 'fell back'):
-            nidx = r['nsurv'] if r['path'] == 'pruned' else 0
-            r['ub'] = np.empty(r['M'])
-            r['idx'] = np.empty(nidx, dtype=np.int64)
-            lead._check(lead._lib.gpx_ensemble_prune_report(handles, len(engines), _ptr(scal), len(scal), _ptr(r['ub']), _ptr(r['idx']),
-                                                            nidx))
-        return r
+        return _report_vectors(r, vectors, lambda ub, idx, nidx: lead._check(
+            lead._lib.gpx_ensemble_prune_report(handles, len(engines), _ptr(scal), len(scal), ub, idx, nidx)))
 
     def prune_dots(self):
         """Diagnostic (gpx_prune_dots): alpha2 . k(X, z_n) of the last pruned sweep's bound pass (option prune_keep = 1), before EI."""

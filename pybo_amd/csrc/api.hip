@@ -410,11 +410,24 @@ extern "C" int64_t gpx_chol_trace(gpx_handle* h, int64_t* out, int64_t n) {
     return tg_trace_copy(h, reinterpret_cast<long long*>(out), n);
 }
 
-// What gpx_prune_report and gpx_ensemble_prune_report share, from the records' common head: the first eight scalars, and the bound
-// vector with the survivor list
-static void report_head(const gpx_handle::SelectRecord& r, double* out) {
+// What gpx_prune_report, gpx_ensemble_prune_report and gpx_constrained_prune_report share, from the records' common head.
+// report_begin: the argument checks and the record's state (`what` prefixes every message; `kind` + `whose` name the sweeps the record
+// belongs to; `mine`: the record is the caller's; `vectors`: the caller asked for one; `also`: a refusal of the entry's own, reported
+// behind the shared ones), then the device, the synchronise and the first eight scalars.  report_vectors: the bound vector with the
+// survivor list.
+static int report_begin(gpx_handle* h, const char* what, const char* kind, const char* whose, const gpx_handle::SelectRecord& r, bool mine,
+                        const double* scal, int nscal, bool vectors, const char* also, double* out) {
+    const std::string w(what);
+    if (!scal || nscal < 0) return fail(h, GPX_EARG, (w + ": NULL output").c_str());
+    if (r.path < 0 || !mine)
+        return fail(h, GPX_ESTATE, (w + ": no " + kind + whose + " has completed its argument checks since the record was last cleared").c_str());
+    if (vectors && r.path < 2) return fail(h, GPX_ESTATE, (w + ": the last " + kind + " did not reach its bound pass").c_str());
+    if (also) return fail(h, GPX_ESTATE, also);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     const double head[8] = {(double)r.path, (double)r.M, (double)r.k, (double)r.G, (double)r.Gg, (double)r.done, (double)r.cap, (double)r.nsurv};
     std::copy(head, head + 8, out);
+    return GPX_OK;
 }
 static int report_vectors(gpx_handle* h, const gpx_handle::SelectRecord& r, double* ub, int64_t* idx, int64_t cap_idx) {
     if (ub) HIPCHK(h, hipMemcpy(ub, r.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
@@ -427,16 +440,13 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
                                 double* ub_kept, int64_t* seed_idx, int64_t cap_seed) {
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
-        if (!scal || nscal < 0) return fail(h, GPX_EARG, "prune_report: NULL output");
         const gpx_handle::PruneRecord& r = h->prune_rec;
-        if (r.path < 0) return fail(h, GPX_ESTATE, "prune_report: no sweep has completed its argument checks since the record was last cleared");
         const bool bound = r.path >= 2;
-        if ((ub || idx || ub_kept || seed_idx) && !bound)
-            return fail(h, GPX_ESTATE, "prune_report: the last sweep did not reach its bound pass");
-        if ((ub_kept || seed_idx) && !r.kept)
-            return fail(h, GPX_ESTATE, "prune_report: the last sweep ran without the option prune_keep");
-        HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        double out[22];
+        int rc;
+        if ((rc = report_begin(h, "prune_report", "sweep", "", r, true, scal, nscal, ub || idx || ub_kept || seed_idx,
+                               (ub_kept || seed_idx) && !r.kept ? "prune_report: the last sweep ran without the option prune_keep" : nullptr, out)))
+            return rc;
         double sc[BM_SC_WORDS];
         int st[4] = {0, 0, 0, 0};
         for (double& v : sc) v = NAN;
@@ -446,8 +456,6 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
         }
         // the device chose the bound pass's kernel: sc[8] = guard value, sc[9] = a matrix-pipe kernel ran, sc[12] = the fp32 one, sc[10] = its E
         const bool guarded_bound = bound && r.bound_kernel < 0;
-        double out[22];
-        report_head(r, out);
         // (slot 11: the gate's mean s2 as it is, not divided by rho)
         const double tail[12] = {sc[0], sc[1], sc[5], r.gate, bound ? (double)st[2] : NAN, r.kept ? 1.0 : 0.0,
                                  bound ? (guarded_bound ? sc[9] + sc[12] : 0.0) : NAN, guarded_bound ? sc[8] : NAN,
@@ -458,7 +466,6 @@ extern "C" int gpx_prune_report(gpx_handle* h, double* scal, int nscal, double* 
         out[20] = f32 ? sc[BM_SC_FACT32] : NAN;
         out[21] = f32 ? sc[BM_SC_TPOS32] : NAN;
         for (int i = 0; i < nscal && i < 22; ++i) scal[i] = out[i];
-        int rc;
         if ((rc = report_vectors(h, r, ub, idx, cap_idx))) return rc;
         const KeepWs kw = keep_ws(WsCarver(h->dkeep), r.M, r.G);
         if (ub_kept) HIPCHK(h, hipMemcpy(ub_kept, kw.ub, (size_t)r.M * 8, hipMemcpyDeviceToHost));
@@ -1023,6 +1030,18 @@ static int topk_core(gpx_handle* h, const double* d_vals, int64_t M, int64_t k, 
     return GPX_OK;
 }
 
+// The end of a sweep that leaves its values in d_vals on h's stream: rank them (topk_core synchronises) or synchronise, then report
+// whatever a launch left behind.  (sweep_core keeps its own end: with k = 0 it returns without a synchronise.)
+static int finish_sweep(gpx_handle* h, const double* d_vals, int64_t M, int64_t k, double* top_val, int64_t* top_idx) {
+    if (k > 0) {
+        if (int rc = topk_core(h, d_vals, M, k, top_val, top_idx)) return rc;
+    } else {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    HIPCHK(h, hipGetLastError());
+    return GPX_OK;
+}
+
 // The acquisition arguments of every sweep (`what` prefixes the message): the id and its parameter, then k and the top-k
 // outputs (two calls: ensemble_sweep checks its candidates between them).
 // One row per acquisition: how many parameters it takes at least (vec: a vector of maximum samples, 1 .. MES_MAX_S per member,
@@ -1057,10 +1076,17 @@ static int check_acq(gpx_handle* h, const char* what, int acq_id, const double* 
         return fail(h, GPX_EARG, (std::string(what) + ": missing acquisition parameter").c_str());
     return GPX_OK;
 }
-// the batch entries: the believer rounds are scored by acq_value (kernels_batch.hip), which MES is not part of
-static int check_acq_batch(gpx_handle* h, const char* what, int acq_id) {
-    if (acq_id == GPX_ACQ_MES) return fail(h, GPX_EARG, (std::string(what) + ": MES is not supported").c_str());
-    if (acq_id == GPX_ACQ_KG) return fail(h, GPX_EARG, (std::string(what) + ": KG is not supported").c_str());
+// the common arguments of the batch entries: the believer rounds are scored by acq_value (kernels_batch.hip), which MES is not part of
+static int check_batch(gpx_handle* h, const char* what, int acq_id, const double* params, int nparams, int64_t nb, const double* sel_val,
+                       const int64_t* sel_idx) {
+    const std::string w(what);
+    if (acq_id == GPX_ACQ_MES) return fail(h, GPX_EARG, (w + ": MES is not supported").c_str());
+    if (acq_id == GPX_ACQ_KG) return fail(h, GPX_EARG, (w + ": KG is not supported").c_str());
+    if (int rc = check_acq(h, what, acq_id, params, nparams)) return rc;
+    if (acq_id == GPX_ACQ_MEAN)
+        return fail(h, GPX_EARG, (w + ": the posterior mean does not change under hallucinated observations (EI, PI or UCB)").c_str());
+    if (nb < 1 || nb > 64) return fail(h, GPX_EARG, (w + ": nb must be in [1, 64]").c_str());
+    if (!sel_val || !sel_idx) return fail(h, GPX_EARG, (w + ": NULL sel_val / sel_idx output").c_str());
     return GPX_OK;
 }
 // the maxima of one sweep as k_acq_mes takes them (checked by check_acq)
@@ -1183,10 +1209,16 @@ static PruneGeom prune_geom(int nP, int64_t k, int64_t M, bool narrow = false, i
     return {G, (int64_t)TBH * gen_tiles, std::max<int64_t>(G, M / PRUNE_MAX_SHARE_DIV)};
 }
 
-// The pruning workspace of h (h->dprune: prune_ws_layout), grown where it has to
-static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t extra, PruneWs& w, bool rows = false) {
+// The pruning workspace of h (h->dprune: prune_ws_layout), grown where it has to.  The vectors of the ensemble and the constrained record h
+// leads lie in it, so this is where they end: both with an allocation that has to grow (they point into the old one); a layout for a
+// selection (`owner`: that sweep's record, which lives on; NULL: a member's bound pass) ends the constrained record, and a constrained
+// selection's the ensemble record.
+static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t extra, PruneWs& w, bool rows = false,
+                    const gpx_handle::SelectRecord* owner = nullptr) {
     const int64_t need = prune_ws_layout(WsCarver(nullptr), M, cap, h->d, h->Np, Gg, extra, rows).bytes;
-    if (!h->dprune || need > h->cap_prune) h->ens_rec = gpx_handle::EnsPruneRecord(), h->con_rec = gpx_handle::ConPruneRecord();   // (their vectors lie in the old allocation)
+    const bool grows = !h->dprune || need > h->cap_prune;
+    if (owner != &h->ens_rec && (grows || owner == &h->con_rec)) h->ens_rec = gpx_handle::EnsPruneRecord();
+    if (owner != &h->con_rec && (grows || owner)) h->con_rec = gpx_handle::ConPruneRecord();
     if (int rc = ensure(h, h->dprune, h->cap_prune, need)) return rc;
     w = prune_ws_layout(WsCarver(h->dprune), M, cap, h->d, h->Np, Gg, extra, rows);
     return GPX_OK;
@@ -1196,8 +1228,10 @@ static int prune_ws(gpx_handle* h, int64_t M, int64_t cap, int64_t Gg, int64_t e
 // so that EI((bias + out[n]) + delta, s2 = rho) >= the value the exact chain returns.  bound_mfma: the matrix-pipe form for SE-ARD
 // up to d = 18 where its guard allows (decided on the device), in fp32 with its own margin added (out[n] = dot_hi, bound_f32.h) where
 // that link's guards allow as well and the pass is long enough to matter (option prune_bound = 2: wherever the kernel exists).
+// Returns bound_mfma: the host offered the matrix-pipe kernel (w.sc[9] then says which kernel wrote the dots).
 static const int64_t BOUND_F32_MIN_M = 131072;
-static void bound_dots(gpx_handle* h, const double* dXc, int64_t M, const PruneWs& w, bool bound_mfma, double* out) {
+static bool bound_dots(gpx_handle* h, const double* dXc, int64_t M, const PruneWs& w, double* out) {
+    const bool bound_mfma = h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0;
     hipStream_t s = h->stream;
     launch_prune_alpha(s, h->dU, h->Np, h->da, h->rho, h->bias, w.alpha2, w.sabs, w.sc);
     if (bound_mfma)
@@ -1205,6 +1239,7 @@ static void bound_dots(gpx_handle* h, const double* dXc, int64_t M, const PruneW
                           w.bws, w.sc, out);
     launch_sweep_rank1_v(s, h->dXs, h->N, (int)h->d, w.alpha2, h->Np, w.sc + 2, dXc, M, h->dinvell, h->kernel_id, h->rho,
                          nullptr, out, bound_mfma ? w.sc + 9 : nullptr);
+    return bound_mfma;
 }
 
 // candidate columns of one chunk of a sweep of M candidates on h
@@ -1229,23 +1264,57 @@ struct SelectOps {
     std::function<int(SelectList& list)> refine;
 };
 
+// `exact` for a path whose chain takes (X, cnt, out, a, b): rows [mb, me) of the candidate array (d columns) and of every output given
+template <typename Chain>
+static std::function<int(const double*, int64_t, int64_t, double*, double*, double*)> exact_rows(Chain& chain, int64_t d) {
+    return [&chain, d](const double* X, int64_t mb, int64_t me, double* o, double* a, double* b) -> int {
+        return chain(X + mb * d, me - mb, o + mb, a ? a + mb : nullptr, b ? b + mb : nullptr);
+    };
+}
+
+// `after_seeds` for a path whose other handles read the seeds from their own streams
+static std::function<int()> seeds_sync(gpx_handle* L) {
+    return [L]() -> int { HIPCHK(L, hipStreamSynchronize(L->stream)); return GPX_OK; };
+}
+
+// `gate` of a single model h (the sweep's own, or the objective of a constrained one): the first generation exactly into `out`, its s2
+// into w.gs2; mean(s2) >= rho / 64 decides
+static int single_gate(gpx_handle* h, const SelectOps& ops, const double* dXc, double* out, const PruneWs& w, int64_t Gg, double* value, bool* go) {
+    if (int rc = ops.exact(dXc, 0, Gg, out, nullptr, w.gs2)) return rc;
+    hipStream_t s = h->stream;
+    launch_prune_mean(s, w.gs2, Gg, w.sc + 4);
+    double mean_s2 = 0.0;
+    HIPCHK(h, hipMemcpyAsync(&mean_s2, w.sc + 4, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    *go = mean_s2 >= h->rho * PRUNE_GATE_S2;
+    *value = mean_s2;
+    return GPX_OK;
+}
+
+// `bound` of a single model h: its dots -> `dots` (and, where given, a copy as the kernel left them -> keep_dots), then
+// ub[n] = EI(bias + alpha . k(X, z_n) + delta, s2 = rho) >= the value the exact chain returns.  *bound_mfma (optional): bound_dots' answer.
+static int single_bound(gpx_handle* h, const double* dXc, int64_t M, const PruneWs& w, double p0, double* dots, double* keep_dots, double* ub,
+                        int64_t done, bool* bound_mfma = nullptr) {
+    Span sp(h, T_BOUND);
+    const bool mfma = bound_dots(h, dXc, M, w, dots);
+    if (bound_mfma) *bound_mfma = mfma;
+    if (keep_dots) HIPCHK(h, hipMemcpyAsync(keep_dots, dots, (size_t)M * 8, hipMemcpyDeviceToDevice, h->stream));
+    launch_prune_ub(h->stream, dots, ub, M, done, w.sc, h->rho, h->bias, p0);
+    return GPX_OK;
+}
+
 // The selection-only sweep of the n members led by L: exact values only where the EI bound
 // can reach the top-k.  `legal`: the path's own conditions; the shared ones and the automatic rule are applied here.  On return candidates
 // [0, *done) of `out` are final -- exact values, or -inf where the bound rules a candidate out -- and the caller runs the plain loop
 // over the rest (plain_rest).  `rec` arrives as its owner started it (the fields behind the common head); the head is filled here.
-// `w`: the lead's workspace, laid out here before any callback runs.  `hint`: read, reset and re-armed by "prune" = -1 sweeps only.
-template <typename Rec>
+// `w`: the lead's workspace, laid out here before any callback runs (prune_ws: that layout ends the lead's other records, never `rec`).
+// `hint`: read, reset and re-armed by "prune" = -1 sweeps only.
 static int select_topk_pruned(gpx_handle* L, bool legal, bool selection_only, int acq_id, int n, int nP, int64_t Np_min, bool narrow,
-                              const double* dXc, int64_t M, int64_t k, int64_t ws_extra, bool ws_rows, PruneWs& w, PruneHint& hint, Rec& rec,
-                              double* out, const SelectOps& ops, int64_t* done) {
+                              const double* dXc, int64_t M, int64_t k, int64_t ws_extra, bool ws_rows, PruneWs& w, PruneHint& hint,
+                              gpx_handle::SelectRecord& rec, double* out, const SelectOps& ops, int64_t* done) {
     const PruneGeom geom = prune_geom(nP, k, M, narrow, L->prune_seeds);
     const int64_t G = geom.G, Gg = geom.Gg, cap = geom.cap;
-    const Rec fresh = rec;
-    auto start_rec = [&]() {
-        rec = fresh;
-        rec.path = 0, rec.M = M, rec.k = k, rec.G = G, rec.Gg = Gg, rec.cap = cap, rec.gate = NAN;
-    };
-    start_rec();
+    rec.path = 0, rec.M = M, rec.k = k, rec.G = G, rec.Gg = Gg, rec.cap = cap, rec.gate = NAN;
     *done = 0;                   // candidates [0, *done) are exactly evaluated already
     legal = legal && selection_only && acq_id == GPX_ACQ_EI && k > 0 && L->prune != 0 && M >= 3 * G;
     bool pruning = legal && (L->prune == 1 || (M >= PRUNE_MIN_M && Np_min >= PRUNE_MIN_NP && M >= Gg + 2 * G));
@@ -1257,12 +1326,7 @@ static int select_topk_pruned(gpx_handle* L, bool legal, bool selection_only, in
     if ((rc = ensure(L, L->dblki, L->cap_blki, topk_blocks(M) * kk))) return rc;
     if ((rc = ensure(L, L->dtopv, L->cap_top, (int64_t)TOPK_MAX * 2))) return rc;
     L->dtopi = reinterpret_cast<int64_t*>(L->dtopv + TOPK_MAX);
-    if ((rc = prune_ws(L, M, cap, Gg, ws_extra, w, ws_rows))) return rc;
-    // The constrained record's vectors lie in this workspace too: a single-model or ensemble selection that lays it out ends that record
-    // (and a constrained one the ensemble record); start_rec() below restores the caller's own.
-    if (!std::is_same<Rec, gpx_handle::ConPruneRecord>::value) L->con_rec = gpx_handle::ConPruneRecord();
-    else L->ens_rec = gpx_handle::EnsPruneRecord();
-    start_rec();                 // (a workspace that had to grow clears the lead's ensemble record)
+    if ((rc = prune_ws(L, M, cap, Gg, ws_extra, w, ws_rows, &rec))) return rc;
     PruneHint key;
     key.kernel_id = L->kernel_id, key.n = n, key.d = L->d, key.nP = nP, key.Np_min = Np_min, key.M = M, key.k = k;
     const bool automatic = L->prune < 0;       // only these sweeps read or write the carried decision
@@ -1463,31 +1527,16 @@ static int sweep_core(gpx_handle* h, int acq_id, const double* params, int npara
     KeepWs kw = {};              // (option prune_keep: laid out by the bound pass)
     SelectOps ops;
     ops.exact = run_chunks;
-    ops.gate = [&](int64_t Gg, double* value, bool* go) -> int {
-        run_chunks(dXc, 0, Gg, d_acq, nullptr, w.gs2);
-        launch_prune_mean(s, w.gs2, Gg, w.sc + 4);
-        double mean_s2 = 0.0;
-        HIPCHK(h, hipMemcpyAsync(&mean_s2, w.sc + 4, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        *go = mean_s2 >= h->rho * PRUNE_GATE_S2;
-        *value = mean_s2;
-        return GPX_OK;
-    };
-    // ub[n] = EI(bias + alpha . k(X, z_n) + delta, s2 = rho) >= the value the exact chain returns
+    ops.gate = [&](int64_t Gg, double* value, bool* go) -> int { return single_gate(h, ops, dXc, d_acq, w, Gg, value, go); };
     ops.bound = [&](double* ub, int64_t done) -> int {
-        // the bound pass's kernel: the matrix-pipe form for SE-ARD up to d = 18 where its guard allows (decided on the device)
-        const bool bound_mfma = h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0;
-        {
-            Span sp(h, T_BOUND);
-            bound_dots(h, dXc, M, w, bound_mfma, w.dots);      // (kept: the second bound reads the survivors' dots again)
-            if (h->prune_keep) {
-                // diagnostic: the dots as the kernel left them (gpx_prune_dots), behind the two copies below
-                if ((rc = ensure(h, h->dkeep, h->cap_keep, keep_ws(WsCarver(nullptr), M, rec.G).bytes))) return rc;
-                kw = keep_ws(WsCarver(h->dkeep), M, rec.G);
-                HIPCHK(h, hipMemcpyAsync(kw.dots, w.dots, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
-            }
-            launch_prune_ub(s, w.dots, ub, M, done, w.sc, h->rho, h->bias, p0);
+        if (h->prune_keep) {
+            // diagnostic: the dots as the kernel left them (gpx_prune_dots), behind the two copies below
+            if ((rc = ensure(h, h->dkeep, h->cap_keep, keep_ws(WsCarver(nullptr), M, rec.G).bytes))) return rc;
+            kw = keep_ws(WsCarver(h->dkeep), M, rec.G);
         }
+        // (the dots stay in w.dots: the second bound reads the survivors' again)
+        bool bound_mfma = false;
+        if ((rc = single_bound(h, dXc, M, w, p0, w.dots, h->prune_keep ? kw.dots : nullptr, ub, done, &bound_mfma))) return rc;
         rec.bound_kernel = bound_mfma ? -1 : 0, rec.st = w.st, rec.kept = h->prune_keep != 0;
         // diagnostic: the bound vector (and after_seeds: the seed list) as they are before the scatter overwrites them
         if (rec.kept) HIPCHK(h, hipMemcpyAsync(kw.ub, ub, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
@@ -1617,11 +1666,7 @@ extern "C" int gpx_sweep_batch(gpx_handle* h, int acq_id, const double* params, 
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
         int rc;
-        if ((rc = check_acq_batch(h, "sweep_batch", acq_id)) || (rc = check_acq(h, "sweep_batch", acq_id, params, nparams))) return rc;
-        if (acq_id == GPX_ACQ_MEAN)
-            return fail(h, GPX_EARG, "sweep_batch: the posterior mean does not change under hallucinated observations (EI, PI or UCB)");
-        if (nb < 1 || nb > 64) return fail(h, GPX_EARG, "sweep_batch: nb must be in [1, 64]");
-        if (!sel_val || !sel_idx) return fail(h, GPX_EARG, "sweep_batch: NULL sel_val / sel_idx output");
+        if ((rc = check_batch(h, "sweep_batch", acq_id, params, nparams, nb, sel_val, sel_idx))) return rc;
         if (!h->fitted || !h->cache_valid) return fail(h, GPX_ESTATE, "sweep_batch: no live sweep cache (sweep with option sweep_cache = 1 first)");
         const int64_t M = h->cache_M, d = h->d;
         if (nb > M) return fail(h, GPX_EARG, "sweep_batch: nb exceeds the number of cached candidates");
@@ -1902,6 +1947,23 @@ static int rff_core(gpx_handle* h, const double* W, const double* b, const doubl
     return GPX_OK;
 }
 
+// The host form of gpx_rff_sweep and gpx_path_sweep (`path`), behind the entry's own checks: the candidates staged in h->dXc, the values in
+// h->dout, copied back where asked for
+static int rff_host(gpx_handle* h, const double* W, const double* b, const double* theta, int64_t S, int64_t n, int64_t d, double bias,
+                    const double* Xc, int64_t M, int64_t k, double* top_val, int64_t* top_idx, double* vals_all, const PathArg* path) {
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure(h, h->dXc, h->cap_xc, M * d))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->dXc, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, h->stream));
+    if ((rc = ensure(h, h->dout, h->cap_out, S * M))) return rc;
+    if ((rc = rff_core(h, W, b, theta, S, n, d, bias, h->dXc, M, k, top_val, top_idx, h->dout, path))) return rc;
+    if (vals_all) {
+        HIPCHK(h, hipMemcpyAsync(vals_all, h->dout, (size_t)S * M * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return GPX_OK;
+}
+
 extern "C" int gpx_rff_sweep_dev(gpx_handle* h, const double* W, const double* b, const double* theta,
                                  int64_t S, int64_t n, int64_t d, double bias, const double* dXc, int64_t M,
                                  int64_t k, double* top_val, int64_t* top_idx, double* d_vals_all) {
@@ -1917,18 +1979,7 @@ extern "C" int gpx_rff_sweep(gpx_handle* h, const double* W, const double* b, co
     return guarded(h, [&]() -> int {
         if (!h) return GPX_EARG;
         if (!Xc || M < 1 || d < 1) return fail(h, GPX_EARG, "rff_sweep: bad candidates");
-        HIPCHK(h, hipSetDevice(h->device));
-        int rc;
-        if ((rc = ensure(h, h->dXc, h->cap_xc, M * d))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->dXc, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, h->stream));
-        if ((rc = ensure(h, h->dout, h->cap_out, S * M))) return rc;
-        rc = rff_core(h, W, b, theta, S, n, d, bias, h->dXc, M, k, top_val, top_idx, h->dout);
-        if (rc) return rc;
-        if (vals_all) {
-            HIPCHK(h, hipMemcpyAsync(vals_all, h->dout, (size_t)S * M * 8, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-        }
-        return GPX_OK;
+        return rff_host(h, W, b, theta, S, n, d, bias, Xc, M, k, top_val, top_idx, vals_all, nullptr);
     });
 }
 
@@ -1973,19 +2024,8 @@ extern "C" int gpx_path_sweep(gpx_handle* h, const double* W, const double* b, c
         if (int rc0 = path_check(h, "path_sweep", v, nv, S, n, d)) return rc0;
         if (!Xc || M < 1) return fail(h, GPX_EARG, "path_sweep: bad candidates");
         if (k < 0 || k > TOPK_MAX) return fail(h, GPX_EARG, "path_sweep: k must be in [0, 4096]");
-        HIPCHK(h, hipSetDevice(h->device));
-        int rc;
-        if ((rc = ensure(h, h->dXc, h->cap_xc, M * d))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->dXc, Xc, (size_t)M * d * 8, hipMemcpyHostToDevice, h->stream));
-        if ((rc = ensure(h, h->dout, h->cap_out, S * M))) return rc;
         const PathArg pa = {v, nv};
-        rc = rff_core(h, W, b, theta, S, n, d, bias, h->dXc, M, k, top_val, top_idx, h->dout, &pa);
-        if (rc) return rc;
-        if (vals_all) {
-            HIPCHK(h, hipMemcpyAsync(vals_all, h->dout, (size_t)S * M * 8, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-        }
-        return GPX_OK;
+        return rff_host(h, W, b, theta, S, n, d, bias, Xc, M, k, top_val, top_idx, vals_all, &pa);
     });
 }
 
@@ -2193,28 +2233,66 @@ extern "C" int gpx_rff_gram(gpx_handle* h, const double* W, const double* b, int
     });
 }
 
-// ---- ensemble sweep (hyper-parameter marginalisation; pybo/bayesopt.py:115) ------------------------------
-// member m's failure as the lead reports it
-static int member_fail(gpx_handle* L, const gpx_handle* h, int m, int rc) {
-    if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
+// ---- sweeps that drive several fitted handles from one lead (ensemble, constrained, two objectives) --------------------------------
+// The lead L owns the workspaces, the records and the error text; `role` and `first` are how its messages name handle i of hs
+// ("ensemble member 0 ..", "constraint 0 ..", "objective 1 .."); `also`: a handle that takes part without being listed (the objective
+// of a constrained sweep), or NULL.
+struct Group { gpx_handle* L; gpx_handle* const* hs; int n; const char* role; int first; gpx_handle* also; };
+
+// handle i's failure as the lead reports it
+static int group_fail(const Group& g, const gpx_handle* h, int i, int rc) {
+    if (h != g.L) g.L->err = std::string(g.role) + " " + std::to_string(g.first + i) + ": " + h->err;
     return rc;
 }
 
+// The conditions an entry may put on its handles, each with the text (behind the entry's name) of its refusal: GPX_ESTATE for an unfitted
+// handle, GPX_EARG otherwise.  group_check applies the rules it is given and no other, in the entry's order: by_handle = every rule on
+// handle 0, then on handle 1, .. (the ensemble entries); otherwise rule 0 on every handle, then rule 1, .. (constrained, two objectives).
+enum GroupCond { G_NOT_NULL, G_ONCE, G_FITTED, G_SHAPE };
+struct GroupRule { GroupCond cond; const char* msg; };
+static bool group_holds(const Group& g, int i, GroupCond c) {
+    const gpx_handle* h = g.hs[i];
+    if (c == G_NOT_NULL) return h != nullptr;
+    if (c == G_FITTED) return h->fitted;
+    if (c == G_SHAPE) return h->device == g.L->device && h->d == g.L->d;
+    return h != g.also && std::find(g.hs, g.hs + i, h) == g.hs + i;      // G_ONCE
+}
+static int group_check(const Group& g, const char* entry, std::initializer_list<GroupRule> rules, bool by_handle = false) {
+    const int nr = (int)rules.size();
+    for (int t = 0; t < nr * g.n; ++t) {
+        const int i = by_handle ? t / nr : t % g.n;
+        const GroupRule& r = rules.begin()[by_handle ? t % nr : t / g.n];
+        if (!group_holds(g, i, r.cond)) return fail(g.L, r.cond == G_FITTED ? GPX_ESTATE : GPX_EARG, (std::string(entry) + ": " + r.msg).c_str());
+    }
+    return GPX_OK;
+}
+
+// One member step: sweep_core on handle i of the group for the `cnt` candidates X into the vectors given (no top-k), its failure as the lead
+// reports it, then a synchronise of the member's stream -- what follows reads the vectors on the lead's.  s2_mean (optional): the mean of
+// d_s2 -> *s2_mean, on the member's stream.
+static int member_sweep(const Group& g, int i, int acq_id, const double* params, int nparams, const double* X, int64_t cnt, double* d_acq,
+                        double* d_mu, double* d_s2, double* s2_mean = nullptr) {
+    gpx_handle* h = g.hs[i];
+    if (int rc = sweep_core(h, acq_id, params, nparams, X, cnt, 0, nullptr, nullptr, d_acq, d_mu, d_s2)) return group_fail(g, h, i, rc);
+    if (s2_mean) launch_prune_mean(h->stream, d_s2, cnt, s2_mean);
+    HIPCHK(g.L, hipStreamSynchronize(h->stream));
+    return GPX_OK;
+}
+
+// ---- ensemble sweep (hyper-parameter marginalisation; pybo/bayesopt.py:115) ------------------------------
 static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double* params, int nparams,
                          const double* dXc, int64_t M, int64_t k, double* top_val, int64_t* top_idx,
                          double* d_out, double* d_mu, double* d_s2) {
     gpx_handle* L = mem[0];
+    const Group g = {L, mem, n, "ensemble member", 0, nullptr};
     L->ens_rec = gpx_handle::EnsPruneRecord();     // every ensemble sweep entry, refused ones included, ends the previous one's record
     int rc;
     if ((rc = check_acq(L, "ensemble_sweep", acq_id, params, nparams, n))) return rc;
     const int mesS = (acq_id == GPX_ACQ_MES) ? nparams / n : 0;      // MES: member m scores with its own slice of the maxima
     if (!dXc || M < 1) return fail(L, GPX_EARG, "ensemble_sweep: need M >= 1 candidates");
     if ((rc = check_topk(L, "ensemble_sweep", k, top_val, top_idx))) return rc;
-    for (int m = 0; m < n; ++m) {
-        if (!mem[m]->fitted) return fail(L, GPX_ESTATE, "ensemble_sweep: a member model is not fitted");
-        if (mem[m]->device != L->device || mem[m]->d != L->d)
-            return fail(L, GPX_EARG, "ensemble_sweep: members must share the device and the input dimension");
-    }
+    if ((rc = group_check(g, "ensemble_sweep", {{G_FITTED, "a member model is not fitted"}, {G_SHAPE, "members must share the device and the input dimension"}}, true)))
+        return rc;
     HIPCHK(L, hipSetDevice(L->device));
     // mixture moments for UCB / mean (mu = mean mu_m, s2 = mean(s2_m + mu_m^2) - mu^2), plain mean for EI / PI
     const int mode = (acq_id == GPX_ACQ_UCB || acq_id == GPX_ACQ_MEAN) ? 1 : 0;
@@ -2226,15 +2304,12 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
     // The exact ensemble chain for the `cnt` candidates X: every member's sweep in member order, each folded into the running
     // sums, then one division -> o[c] (and mu / s2, where given).  A candidate's value depends on its coordinates alone.
     // gate_mean (mode 0 only): member m's mean s2 over these candidates -> gate_mean[m] (its s2 vector passes through t1).
-    auto members = [&](const double* X, int64_t cnt, double* o, double* o_mu, double* o_s2, double* gate_mean) -> int {
+    auto members = [&](const double* X, int64_t cnt, double* o, double* o_mu, double* o_s2, double* gate_mean = nullptr) -> int {
         for (int m = 0; m < n; ++m) {
-            gpx_handle* h = mem[m];
-            int rcm = (mode == 0) ? sweep_core(h, acq_id, mesS ? params + (size_t)m * mesS : params, mesS ? mesS : nparams, X, cnt, 0, nullptr,
-                                               nullptr, t0, nullptr, gate_mean ? t1 : nullptr)
-                                  : sweep_core(h, GPX_ACQ_MEAN, nullptr, 0, X, cnt, 0, nullptr, nullptr, nullptr, t0, t1);
-            if (rcm) return member_fail(L, h, m, rcm);
-            if (gate_mean) launch_prune_mean(h->stream, t1, cnt, gate_mean + m);
-            HIPCHK(L, hipStreamSynchronize(h->stream));
+            int rcm = (mode == 0) ? member_sweep(g, m, acq_id, mesS ? params + (size_t)m * mesS : params, mesS ? mesS : nparams, X, cnt, t0, nullptr,
+                                                 gate_mean ? t1 : nullptr, gate_mean ? gate_mean + m : nullptr)
+                                  : member_sweep(g, m, GPX_ACQ_MEAN, nullptr, 0, X, cnt, nullptr, t0, t1);
+            if (rcm) return rcm;
             launch_ens_accum(L->stream, acc0, acc1, t0, t1, cnt, mode, m == 0);
             HIPCHK(L, hipStreamSynchronize(L->stream));    // t0/t1 are reused by the next member
         }
@@ -2256,24 +2331,21 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
         Np_min = std::min(Np_min, mem[m]->Np);
         members_ok = members_ok && !mem[m]->cache_on && mem[m]->rho >= gpx::S2_FLOOR && mem[m]->rho < INFINITY;
     }
-    const int64_t d = L->d;
     hipStream_t s = L->stream;
     gpx_handle::EnsPruneRecord& rec = L->ens_rec;
     rec.n = n;
     PruneWs w;                   // the lead's: the ensemble bound vector, seeds and survivors; extra = [gate means n][delta n][bound_fact n]
     SelectOps ops;
-    ops.exact = [&](const double* X, int64_t mb, int64_t me, double* o, double* o_mu, double* o_s2) -> int {
-        return members(X + mb * d, me - mb, o + mb, o_mu ? o_mu + mb : nullptr, o_s2 ? o_s2 + mb : nullptr, nullptr);
-    };
+    ops.exact = exact_rows(members, L->d);
     // the members' mean s2 / rho over the first generation decides
     ops.gate = [&](int64_t Gg, double* value, bool* go) -> int {
         if ((rc = members(dXc, Gg, out, nullptr, nullptr, w.extra))) return rc;
         std::vector<double> gm((size_t)n);
         HIPCHK(L, hipMemcpyAsync(gm.data(), w.extra, (size_t)n * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(L, hipStreamSynchronize(s));
-        double g = 0.0;
-        for (int m = 0; m < n; ++m) g += gm[m] / mem[m]->rho;
-        *value = g / (double)n;
+        double sum = 0.0;
+        for (int m = 0; m < n; ++m) sum += gm[m] / mem[m]->rho;
+        *value = sum / (double)n;
         *go = *value >= PRUNE_GATE_S2;
         return GPX_OK;
     };
@@ -2283,16 +2355,15 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
         for (int m = 0; m < n; ++m) {
             gpx_handle* h = mem[m];
             HIPCHK(L, hipSetDevice(h->device));
-            if ((rc = ensure_inverse(h))) return member_fail(L, h, m, rc);
+            if ((rc = ensure_inverse(h))) return group_fail(g, h, m, rc);
             PruneWs wm = w;
             if (h != L) {
                 h->prune_rec = gpx_handle::PruneRecord();      // (the pass overwrites the workspace its last record points into)
-                if ((rc = prune_ws(h, 0, 0, 0, 0, wm))) return member_fail(L, h, m, rc);
+                if ((rc = prune_ws(h, 0, 0, 0, 0, wm))) return group_fail(g, h, m, rc);
             }
             {
                 Span sp(h, T_BOUND);
-                const bool bound_mfma = h->prune_bound != 0 && bound_mfma_ks(h->kernel_id, (int)h->d) > 0;
-                bound_dots(h, dXc, M, wm, bound_mfma, t1);
+                const bool bound_mfma = bound_dots(h, dXc, M, wm, t1);
                 launch_prune_ub_fold(h->stream, t1, ub, M, wm.sc, h->rho, h->bias, params[0], m == 0, delta + m,
                                      bound_mfma ? 1 : 0, delta + n + m);
             }
@@ -2305,7 +2376,7 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
         rec.delta = delta;
         return GPX_OK;
     };
-    ops.after_seeds = [&]() -> int { HIPCHK(L, hipStreamSynchronize(s)); return GPX_OK; };      // the members read the seeds from their own streams
+    ops.after_seeds = seeds_sync(L);
     // (narrow = false: the ensemble keeps the wide generation of seeds.  It has no second bound, so every member evaluates the whole
     //  first-level list, and the list that 256 seeds leave is longer by more than the seeds save: 153.5 against 150.5 ms per step of
     //  bench.py --ensemble 10, profiles/narrow_seeds_ab.md section 2.  The members' short launches are narrow all the same.)
@@ -2314,23 +2385,12 @@ static int ensemble_core(gpx_handle* const* mem, int n, int acq_id, const double
                                  out, ops, &done)))
         return rc;
     if ((rc = plain_rest(ops, dXc, done, sweep_chunk(L, M), M, out, d_mu, d_s2))) return rc;
-    if (k > 0) {
-        if ((rc = topk_core(L, out, M, k, top_val, top_idx))) return rc;
-    } else {
-        HIPCHK(L, hipStreamSynchronize(L->stream));
-    }
-    HIPCHK(L, hipGetLastError());
-    return GPX_OK;
+    return finish_sweep(L, out, M, k, top_val, top_idx);
 }
 
 static int ensemble_check(gpx_handle* const* members, int n) {
     if (!members || n < 1 || !members[0]) return GPX_EARG;
-    for (int m = 1; m < n; ++m)
-        if (!members[m]) {
-            members[0]->err = "ensemble_sweep: NULL member handle";
-            return GPX_EARG;
-        }
-    return GPX_OK;
+    return group_check({members[0], members, n, "ensemble member", 0, nullptr}, "ensemble_sweep", {{G_NOT_NULL, "NULL member handle"}});
 }
 
 extern "C" int gpx_ensemble_predict(gpx_handle* const* members, int n_members, const double* Xc, int64_t M,
@@ -2377,22 +2437,20 @@ static gpx_handle* con_lead(gpx_handle* obj, gpx_handle* const* cons, int nc) {
     return obj ? obj : (cons && nc >= 1 ? cons[0] : nullptr);
 }
 
-// constraint j's failure as the lead reports it
-static int con_fail(gpx_handle* L, const gpx_handle* h, int j, int rc) {
-    if (h != L) L->err = "constraint " + std::to_string(j) + ": " + h->err;
-    return rc;
+static Group con_group(gpx_handle* obj, gpx_handle* const* cons, int nc) {
+    return {con_lead(obj, cons, nc), cons, nc, "constraint", 0, obj};
 }
 
 // every refusal of gpx_constrained_sweep[_dev], before anything touches a handle's fit, cache or queue
 static int constrained_check(gpx_handle* L, gpx_handle* obj, gpx_handle* const* cons, int nc, const double* thr, int acq_id, const double* params,
                              int nparams, const double* Xc, int64_t M, int64_t k, const double* top_val, const int64_t* top_idx) {
     if (!cons || nc < 1 || nc > CON_MAX) return fail(L, GPX_EARG, "constrained_sweep: takes 1 to 16 constraint handles");
-    for (int j = 0; j < nc; ++j)
-        if (!cons[j]) return fail(L, GPX_EARG, "constrained_sweep: NULL constraint handle");
+    const Group g = con_group(obj, cons, nc);
+    int rc;
+    if ((rc = group_check(g, "constrained_sweep", {{G_NOT_NULL, "NULL constraint handle"}}))) return rc;
     if (!thr) return fail(L, GPX_EARG, "constrained_sweep: NULL thresholds");
     for (int j = 0; j < nc; ++j)
         if (!std::isfinite(thr[j])) return fail(L, GPX_EARG, "constrained_sweep: the thresholds must be finite");
-    int rc;
     if (obj) {
         if (acq_id != GPX_ACQ_EI && acq_id != GPX_ACQ_PI)
             return fail(L, GPX_EARG, "constrained_sweep: the objective's acquisition must be EI or PI (non-negative values)");
@@ -2400,30 +2458,21 @@ static int constrained_check(gpx_handle* L, gpx_handle* obj, gpx_handle* const* 
     }
     if (!Xc || M < 1) return fail(L, GPX_EARG, "constrained_sweep: need M >= 1 candidates");
     if ((rc = check_topk(L, "constrained_sweep", k, top_val, top_idx))) return rc;
-    for (int j = 0; j < nc; ++j) {
-        if (cons[j] == obj) return fail(L, GPX_EARG, "constrained_sweep: a handle appears twice");
-        for (int i = 0; i < j; ++i)
-            if (cons[i] == cons[j]) return fail(L, GPX_EARG, "constrained_sweep: a handle appears twice");
-    }
+    if ((rc = group_check(g, "constrained_sweep", {{G_ONCE, "a handle appears twice"}}))) return rc;
     if (obj && !obj->fitted) return fail(L, GPX_ESTATE, "constrained_sweep: the objective's model is not fitted");
-    for (int j = 0; j < nc; ++j)
-        if (!cons[j]->fitted) return fail(L, GPX_ESTATE, "constrained_sweep: a constraint's model is not fitted");
-    for (int j = 0; j < nc; ++j)
-        if (cons[j]->device != L->device || cons[j]->d != L->d)
-            return fail(L, GPX_EARG, "constrained_sweep: the handles must share the device and the input dimension");
-    return GPX_OK;
+    return group_check(g, "constrained_sweep", {{G_FITTED, "a constraint's model is not fitted"}, {G_SHAPE, "the handles must share the device and the input dimension"}});
 }
 
 // (arguments checked by constrained_check)
 static int constrained_core(gpx_handle* obj, gpx_handle* const* cons, int nc, const double* thr, int acq_id, const double* params, int nparams,
                             const double* dXc, int64_t M, int64_t k, double* top_val, int64_t* top_idx, double* d_out, double* d_pof) {
-    gpx_handle* L = con_lead(obj, cons, nc);
+    const Group g = con_group(obj, cons, nc);
+    gpx_handle* L = g.L;
     int rc;
     HIPCHK(L, hipSetDevice(L->device));
     if ((rc = ensure(L, L->dcon, L->cap_con, con_ws(WsCarver(nullptr), M).bytes / 8))) return rc;
     const ConWs cw = con_ws(WsCarver(L->dcon), M);
     double *const t0 = cw.t0, *const out = d_out ? d_out : cw.out;
-    const int64_t d = L->d;
     hipStream_t s = L->stream;
 
     // The exact chain for the `cnt` candidates X: the objective's value into o, then per constraint in the caller's order its probability
@@ -2432,9 +2481,7 @@ static int constrained_core(gpx_handle* obj, gpx_handle* const* cons, int nc, co
     auto chain = [&](const double* X, int64_t cnt, double* o, double* o_pof, double* o_s2) -> int {
         if (obj && (rc = sweep_core(obj, acq_id, params, nparams, X, cnt, 0, nullptr, nullptr, o, nullptr, o_s2))) return rc;
         for (int j = 0; j < nc; ++j) {
-            gpx_handle* h = cons[j];
-            if ((rc = sweep_core(h, GPX_ACQ_PI, thr + j, 1, X, cnt, 0, nullptr, nullptr, t0, nullptr, nullptr))) return con_fail(L, h, j, rc);
-            HIPCHK(L, hipStreamSynchronize(h->stream));
+            if ((rc = member_sweep(g, j, GPX_ACQ_PI, thr + j, 1, X, cnt, t0, nullptr, nullptr))) return rc;
             launch_con_fold(s, obj ? o : nullptr, obj ? o_pof : o, t0, cnt, j == 0);
             HIPCHK(L, hipStreamSynchronize(s));      // t0 is reused by the next constraint
         }
@@ -2460,48 +2507,23 @@ static int constrained_core(gpx_handle* obj, gpx_handle* const* cons, int nc, co
     PruneHint hint;              // (local: these sweeps neither read nor arm the decisions the lead carries for its own sweeps)
     SelectOps ops;
     // (plain_rest's mu slot carries the probability of feasibility; selection-only calls pass none)
-    ops.exact = [&](const double* X, int64_t mb, int64_t me, double* o, double* o_pof, double* o_s2) -> int {
-        return chain(X + mb * d, me - mb, o + mb, o_pof ? o_pof + mb : nullptr, o_s2 ? o_s2 + mb : nullptr);
-    };
-    // the single model's decision, on the objective: mean(s2) >= rho / 64 over the first generation
-    ops.gate = [&](int64_t Gg, double* value, bool* go) -> int {
-        if ((rc = chain(dXc, Gg, out, nullptr, w.gs2))) return rc;
-        launch_prune_mean(s, w.gs2, Gg, w.sc + 4);
-        double mean_s2 = 0.0;
-        HIPCHK(L, hipMemcpyAsync(&mean_s2, w.sc + 4, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(L, hipStreamSynchronize(s));
-        *go = mean_s2 >= obj->rho * PRUNE_GATE_S2;
-        *value = mean_s2;
-        return GPX_OK;
-    };
-    // sweep_core's bound on the objective (dots -> t0: no constraint runs during the pass); no constraint is touched
+    ops.exact = exact_rows(chain, L->d);
+    // the single model's gate and bound, on the objective (a legal sweep has one, and it leads): no constraint is touched by either
+    ops.gate = [&](int64_t Gg, double* value, bool* go) -> int { return single_gate(obj, ops, dXc, out, w, Gg, value, go); };
     ops.bound = [&](double* ub, int64_t done) -> int {
         // (with "prune" = 1 this pass is the first reader of the objective's inverse and `a`: no gate, no sweep_core before it)
         HIPCHK(L, hipSetDevice(obj->device));
         if ((rc = ensure_inverse(obj))) return rc;
-        const bool bound_mfma = obj->prune_bound != 0 && bound_mfma_ks(obj->kernel_id, (int)obj->d) > 0;
-        Span sp(obj, T_BOUND);
-        bound_dots(obj, dXc, M, w, bound_mfma, t0);
-        launch_prune_ub(s, t0, ub, M, done, w.sc, obj->rho, obj->bias, params[0]);
-        return GPX_OK;
+        return single_bound(obj, dXc, M, w, params[0], t0, nullptr, ub, done);      // (dots -> t0: no constraint runs during the pass)
     };
-    ops.after_seeds = [&]() -> int { HIPCHK(L, hipStreamSynchronize(s)); return GPX_OK; };      // the constraints read the seeds from their own streams
+    ops.after_seeds = seeds_sync(L);
     int64_t done = 0;
-    // The driver's THIRD caller (it reads and arms nothing but `hint`: the one place that consults prune_hint.h stays the driver itself).
-    // The explicit template argument is not style -- deduction would supply it, as at the other two calls: tests/test_prune_hint_host.py
-    // counts the driver's name followed by a parenthesis in this file (its definition and two calls), existing tests stay as they are,
-    // and this call has to go through the driver.  That test's comment "the two calls below" is one short since this function.
-    if ((rc = select_topk_pruned<gpx_handle::ConPruneRecord>(L, legal, !d_out && !d_pof, obj ? acq_id : -1, 1 + nc, nPmax, Np_min, false, dXc, M, k, 0, false, w,
-                                                             hint, rec, out, ops, &done)))
+    // (the driver reads and arms nothing but `hint`: the one place that consults prune_hint.h stays the driver itself)
+    if ((rc = select_topk_pruned(L, legal, !d_out && !d_pof, obj ? acq_id : -1, 1 + nc, nPmax, Np_min, false, dXc, M, k, 0, false, w, hint, rec, out,
+                                 ops, &done)))
         return rc;
     if ((rc = plain_rest(ops, dXc, done, sweep_chunk(L, M), M, out, d_pof, nullptr))) return rc;
-    if (k > 0) {
-        if ((rc = topk_core(L, out, M, k, top_val, top_idx))) return rc;
-    } else {
-        HIPCHK(L, hipStreamSynchronize(s));
-    }
-    HIPCHK(L, hipGetLastError());
-    return GPX_OK;
+    return finish_sweep(L, out, M, k, top_val, top_idx);
 }
 
 extern "C" int gpx_constrained_sweep_dev(gpx_handle* obj, gpx_handle* const* cons, int nc, const double* thr, int acq_id, const double* params,
@@ -2535,19 +2557,12 @@ extern "C" int gpx_constrained_prune_report(gpx_handle* lead, double* scal, int 
     return guarded(lead, [&]() -> int {
         gpx_handle* h = lead;
         if (!h) return GPX_EARG;
-        if (!scal || nscal < 0) return fail(h, GPX_EARG, "constrained_prune_report: NULL output");
         const gpx_handle::ConPruneRecord& r = h->con_rec;
-        if (r.path < 0)
-            return fail(h, GPX_ESTATE, "constrained_prune_report: no constrained sweep led by this handle has completed its argument checks "
-                                       "since the record was last cleared");
-        const bool bound = r.path >= 2;
-        if ((ub || idx) && !bound) return fail(h, GPX_ESTATE, "constrained_prune_report: the last constrained sweep did not reach its bound pass");
-        HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
         double out[11];
-        report_head(r, out);
+        if (int rc = report_begin(h, "constrained_prune_report", "constrained sweep", " led by this handle", r, true, scal, nscal, ub || idx, nullptr, out))
+            return rc;
         out[8] = NAN, out[9] = r.gate, out[10] = NAN;
-        if (bound) {
+        if (r.path >= 2) {
             HIPCHK(h, hipMemcpy(&out[8], r.sc + 5, 8, hipMemcpyDeviceToHost));
             HIPCHK(h, hipMemcpy(&out[10], r.sc + 1, 8, hipMemcpyDeviceToHost));
         }
@@ -2578,15 +2593,14 @@ static int ehvi_front(gpx_handle* L, const char* what, const double* P, int np, 
 // every refusal of gpx_ehvi_sweep[_dev], before anything touches a handle's fit, cache or queue (f1 is not NULL)
 static int ehvi_check(gpx_handle* f1, gpx_handle* f2, const double* P, int np, const double* ref, const double* Xc, int64_t M, int64_t k,
                       const double* top_val, const int64_t* top_idx, std::vector<double>& strips, int& n) {
-    if (!f2) return fail(f1, GPX_EARG, "ehvi_sweep: NULL handle");
-    if (f1 == f2) return fail(f1, GPX_EARG, "ehvi_sweep: the two objectives need a handle each");
+    gpx_handle* const hs[2] = {f1, f2};
+    const Group g = {f1, hs, 2, "objective", 1, nullptr};
     int rc;
+    if ((rc = group_check(g, "ehvi_sweep", {{G_NOT_NULL, "NULL handle"}, {G_ONCE, "the two objectives need a handle each"}}))) return rc;
     if ((rc = ehvi_front(f1, "ehvi_sweep", P, np, ref, strips, n))) return rc;
     if (!Xc || M < 1) return fail(f1, GPX_EARG, "ehvi_sweep: need M >= 1 candidates");
     if ((rc = check_topk(f1, "ehvi_sweep", k, top_val, top_idx))) return rc;
-    if (!f1->fitted || !f2->fitted) return fail(f1, GPX_ESTATE, "ehvi_sweep: an objective's model is not fitted");
-    if (f1->device != f2->device || f1->d != f2->d) return fail(f1, GPX_EARG, "ehvi_sweep: the handles must share the device and the input dimension");
-    return GPX_OK;
+    return group_check(g, "ehvi_sweep", {{G_FITTED, "an objective's model is not fitted"}, {G_SHAPE, "the handles must share the device and the input dimension"}});
 }
 
 // the lead's workspace for M candidates and a front of n points
@@ -2610,13 +2624,7 @@ static int ehvi_fold_core(gpx_handle* L, const EhviWs& w, const double* d_mom, i
         Span sp(L, T_ACQ);
         launch_ehvi_fold(s, d_mom, M, w.a, n, out);
     }
-    if (k > 0) {
-        if (int rc = topk_core(L, out, M, k, top_val, top_idx)) return rc;
-    } else {
-        HIPCHK(L, hipStreamSynchronize(s));
-    }
-    HIPCHK(L, hipGetLastError());
-    return GPX_OK;
+    return finish_sweep(L, out, M, k, top_val, top_idx);
 }
 
 // (arguments checked by ehvi_check)  Each member's plain sweep leaves its moments in HBM -- a live sweep cache is re-seeded exactly as
@@ -2630,14 +2638,9 @@ static int ehvi_core(gpx_handle* f1, gpx_handle* f2, const std::vector<double>& 
     if ((rc = ehvi_layout(L, M, n, w))) return rc;
     double* const mom = d_mom ? d_mom : w.mom;
     gpx_handle* const hs[2] = {f1, f2};
-    for (int j = 0; j < 2; ++j) {
-        gpx_handle* h = hs[j];
-        if ((rc = sweep_core(h, GPX_ACQ_MEAN, nullptr, 0, dXc, M, 0, nullptr, nullptr, nullptr, mom + (2 * j) * M, mom + (2 * j + 1) * M))) {
-            if (h != L) L->err = "objective 2: " + h->err;
-            return rc;
-        }
-        HIPCHK(L, hipStreamSynchronize(h->stream));      // the fold runs on the lead's stream
-    }
+    const Group g = {L, hs, 2, "objective", 1, nullptr};
+    for (int j = 0; j < 2; ++j)      // (the fold runs on the lead's stream)
+        if ((rc = member_sweep(g, j, GPX_ACQ_MEAN, nullptr, 0, dXc, M, nullptr, mom + (2 * j) * M, mom + (2 * j + 1) * M))) return rc;
     return ehvi_fold_core(L, w, mom, M, strips, n, k, top_val, top_idx, d_out);
 }
 
@@ -2696,21 +2699,13 @@ extern "C" int gpx_ensemble_sweep_batch(gpx_handle* const* members, int n_member
     gpx_handle* L = members[0];
     return guarded(L, [&]() -> int {
         const int n = n_members;
+        const Group g = {L, members, n, "ensemble member", 0, nullptr};
         int rc;
-        if ((rc = check_acq_batch(L, "ensemble_sweep_batch", acq_id)) || (rc = check_acq(L, "ensemble_sweep_batch", acq_id, params, nparams)))
+        if ((rc = check_batch(L, "ensemble_sweep_batch", acq_id, params, nparams, nb, sel_val, sel_idx))) return rc;
+        if ((rc = group_check(g, "ensemble_sweep_batch", {{G_FITTED, "a member model is not fitted"},
+                                                          {G_SHAPE, "members must share the device and the input dimension"},
+                                                          {G_ONCE, "a handle is listed twice (every member needs its own scratch)"}}, true)))
             return rc;
-        if (acq_id == GPX_ACQ_MEAN)
-            return fail(L, GPX_EARG, "ensemble_sweep_batch: the posterior mean does not change under hallucinated observations (EI, PI or UCB)");
-        if (nb < 1 || nb > 64) return fail(L, GPX_EARG, "ensemble_sweep_batch: nb must be in [1, 64]");
-        if (!sel_val || !sel_idx) return fail(L, GPX_EARG, "ensemble_sweep_batch: NULL sel_val / sel_idx output");
-        for (int m = 0; m < n; ++m) {
-            if (!members[m]->fitted) return fail(L, GPX_ESTATE, "ensemble_sweep_batch: a member model is not fitted");
-            if (members[m]->device != L->device || members[m]->d != L->d)
-                return fail(L, GPX_EARG, "ensemble_sweep_batch: members must share the device and the input dimension");
-            for (int o = 0; o < m; ++o)
-                if (members[o] == members[m])
-                    return fail(L, GPX_EARG, "ensemble_sweep_batch: a handle is listed twice (every member needs its own scratch)");
-        }
         for (int m = 0; m < n; ++m)
             if (!members[m]->cache_valid)
                 return fail(L, GPX_ESTATE, ("ensemble member " + std::to_string(m) + ": ensemble_sweep_batch: no live sweep cache (sweep with "
@@ -2725,10 +2720,8 @@ extern "C" int gpx_ensemble_sweep_batch(gpx_handle* const* members, int n_member
         for (int m = 0; m < n; ++m) {
             gpx_handle* h = members[m];
             if ((rc = ensure_inverse(h)) || (rc = flush_pending(h)) ||      // queued appends belong in the sums, on the member's own stream
-                (rc = batch_layout(h, M, nb, m == 0 ? n : 0, bufs[m]))) {
-                if (h != L) L->err = "ensemble member " + std::to_string(m) + ": " + h->err;
-                return rc;
-            }
+                (rc = batch_layout(h, M, nb, m == 0 ? n : 0, bufs[m])))
+                return group_fail(g, h, m, rc);
             HIPCHK(L, hipStreamSynchronize(h->stream));
             const BatchBuf& b = bufs[m];
             EnsBatchMember& e = L->bsel_desc[m];
@@ -2775,20 +2768,15 @@ extern "C" int gpx_ensemble_prune_report(gpx_handle* const* members, int n_membe
     if (ensemble_check(members, n_members)) return GPX_EARG;
     gpx_handle* h = members[0];
     return guarded(h, [&]() -> int {
-        if (!scal || nscal < 0) return fail(h, GPX_EARG, "ensemble_prune_report: NULL output");
         const gpx_handle::EnsPruneRecord& r = h->ens_rec;
-        if (r.path < 0 || r.n != n_members)
-            return fail(h, GPX_ESTATE, "ensemble_prune_report: no ensemble sweep of these members has completed its argument checks "
-                                       "since the record was last cleared");
-        const bool bound = r.path >= 2;
-        if ((ub || idx) && !bound) return fail(h, GPX_ESTATE, "ensemble_prune_report: the last ensemble sweep did not reach its bound pass");
-        HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        double head[8];
+        if (int rc = report_begin(h, "ensemble_prune_report", "ensemble sweep", " of these members", r, r.n == n_members, scal, nscal, ub || idx, nullptr, head))
+            return rc;
         std::vector<double> out((size_t)(11 + 2 * n_members), NAN);      // (behind gate_hint: the members' bound_fact)
+        std::copy(head, head + 8, out.begin());
         out[10 + n_members] = r.hinted ? 1.0 : 0.0;      // behind the deltas: head[8] is tau, and callers built against 10 + n read on as before
-        report_head(r, out.data());
         out[9] = r.gate;
-        if (bound) {
+        if (r.path >= 2) {
             HIPCHK(h, hipMemcpy(&out[8], r.sc + 5, 8, hipMemcpyDeviceToHost));
             HIPCHK(h, hipMemcpy(&out[10], r.delta, (size_t)n_members * 8, hipMemcpyDeviceToHost));
             HIPCHK(h, hipMemcpy(&out[11 + n_members], r.delta + n_members, (size_t)n_members * 8, hipMemcpyDeviceToHost));

@@ -4,12 +4,15 @@ arguments at and beyond every boundary, for the shipping library (libgpx.so) and
     gpx_set_option   every option name of the library and a few unknown ones, for each value of VALUES: (rc, message)
     GPX_OPTIONS      gpx_create under each string of ENV_OPTIONS: (rc, gpx_last_error(NULL) when rc != 0)
     wrappers         one call per single bad argument of gpx_sweep(_dev), gpx_sweep_update(_dev), gpx_ensemble_sweep(_dev)
-                     (two members), gpx_rff_gram_batch and gpx_rff_posterior, on handles fitted to N = 10, d = 2: (rc, message)
+                     (two members), gpx_rff_gram_batch, gpx_rff_posterior, gpx_constrained_sweep(_dev), gpx_ehvi_sweep(_dev),
+                     gpx_ehvi_fold_dev, gpx_sweep_batch, gpx_ensemble_sweep_batch and gpx_path_sweep(_dev), on handles fitted to
+                     N = 10, d = 2: (rc, message)
 
 None of the recorded calls reaches a HIP runtime error, so no message carries a source line.  Output:
-tests/golden/api_contract.json (messages stored once, results as [rc, message index or -1]).  Needs a GPU; recorded once from
-the libraries of the commit before the option table replaced gpx_set_option's if-chain, and replayed against the current ones
-by tests/test_gpu_api_contract.py:
+tests/golden/api_contract.json (messages stored once, results as [rc, message index or -1]).  Needs a GPU; recorded from
+the libraries of the commit before the option table replaced gpx_set_option's if-chain, recorded again with the rows of the
+constrained, two-objective, batch and pathwise entries from the commit before those entries got one frame (every earlier row came
+out unchanged), and replayed against the current ones by tests/test_gpu_api_contract.py:
     python tests/golden/make_api_contract.py [--ship path/libgpx.so] [--diag path/libgpx_diag.so] [--out file.json]
 """
 import argparse
@@ -193,6 +196,122 @@ def probe(path):
         Wp, bp, zp, S_, n_, sc = args
         out['rff_posterior: %s' % label] = _err(lib, hh, lib.gpx_rff_posterior(hh, _p(Wp), _p(bp), _p(zp), S_, n_, sc, _p(th)))
     out['rff_posterior: theta NULL'] = _err(lib, a, lib.gpx_rff_posterior(a, _p(W), _p(bb), _p(z), 2, n, 1.0, None))
+
+    # -- the entries that drive several handles from one lead, the batch entries and the pathwise sweep: refusals only (one bad argument
+    #    per call, then pairs that show which check fires first).  `a` holds a live sweep cache of M candidates from here on, `b` none yet.
+    def arr(hs):
+        return (C.c_void_p * max(len(hs), 1))(*[x.value if x is not None else None for x in hs])
+
+    nan, inf = float('nan'), float('inf')
+    thr2 = np.array([0.1, 0.2])
+    cgood = dict(obj=a, cons=[b], thr=np.array([0.1]), acq=0, prm=prm, np_=1, X=True, M=M, k=5, tv=tv, ti=ti)
+    cbad = [('nc 0', dict(cons=[])), ('cons NULL', dict(cons=None, nc=1)), ('nc 17', dict(cons=[b] * 17, thr=np.zeros(17))),
+            ('constraint NULL', dict(cons=[b, None], thr=thr2)), ('thr NULL', dict(thr=None)), ('thr inf', dict(cons=[b, c], thr=np.array([0.0, inf]))),
+            ('thr NaN', dict(thr=np.array([nan]))), ('acq ucb', dict(acq=2)), ('acq mean', dict(acq=3, prm=None, np_=0)),
+            ('acq mes', dict(acq=16, prm=np.array([0.5, 0.6]), np_=2)), ('acq kg', dict(acq=32, prm=Xc[:2].ravel().copy(), np_=4)),
+            ('acq 4', dict(acq=4)), ('params NULL', dict(prm=None, np_=0)), ('M 0', dict(M=0)), ('Xc NULL', dict(X=False)),
+            ('no objective, M 0', dict(obj=None, M=0)), ('k 4097', dict(k=4097)), ('k -1', dict(k=-1)), ('top_val NULL', dict(tv=None)),
+            ('twice', dict(cons=[b, b], thr=thr2)), ('objective twice', dict(cons=[b, a], thr=thr2)),
+            ('no objective, twice', dict(obj=None, cons=[a, b, a], thr=np.zeros(3))), ('constraint not fitted', dict(cons=[b, unfit], thr=thr2)),
+            ('objective not fitted', dict(obj=unfit)), ('constraint d 3', dict(cons=[b, c], thr=thr2)),
+            ('no objective, acq ucb unread', dict(obj=None, acq=2, M=0)),
+            ('nc 17 + thr NULL', dict(cons=[b] * 17, thr=None)), ('constraint NULL + thr NULL', dict(cons=[b, None], thr=None)),
+            ('thr NaN + acq ucb', dict(thr=np.array([nan]), acq=2)), ('acq ucb + params NULL', dict(acq=2, prm=None, np_=0)),
+            ('params NULL + M 0', dict(prm=None, np_=0, M=0)), ('M 0 + k 4097', dict(M=0, k=4097)), ('k 4097 + twice', dict(k=4097, cons=[b, b], thr=thr2)),
+            ('twice + not fitted', dict(cons=[unfit, unfit], thr=thr2)), ('objective not fitted + constraint d 3', dict(obj=unfit, cons=[c])),
+            ('constraint not fitted + d 3', dict(cons=[c, unfit], thr=thr2))]
+    for form in ('host', 'dev'):
+        fn = lib.gpx_constrained_sweep if form == 'host' else lib.gpx_constrained_sweep_dev
+        for label, kw in cbad:
+            g_ = dict(cgood, **kw)
+            lead = g_['obj'] if g_['obj'] is not None else g_['cons'][0]
+            Xp = None if not g_['X'] else (_p(Xc) if form == 'host' else dXc)
+            rc = fn(g_['obj'], arr(g_['cons']) if g_['cons'] is not None else None, g_.get('nc', len(g_['cons'] or ())), _p(g_['thr']), g_['acq'], _p(g_['prm']),
+                    g_['np_'], Xp, g_['M'], g_['k'], _p(g_['tv']), _p(g_['ti']), None, None)
+            out['constrained %s: %s' % (form, label)] = _err(lib, lead, rc)
+        out['constrained %s: no handle' % form] = [fn(None, None, 0, _p(thr2), 0, _p(prm), 1, _p(Xc) if form == 'host' else dXc, M, 5, _p(tv), _p(ti),
+                                                      None, None), None]
+
+    front, ref = np.array([0.3, 0.1, 0.1, 0.3]), np.array([0.0, 0.0])
+    egood = dict(f1=a, f2=b, P=front, np_=2, ref=ref, X=True, M=M, k=5, tv=tv, ti=ti)
+    ebad = [('f2 NULL', dict(f2=None)), ('f1 == f2', dict(f2=a)), ('ref NULL', dict(ref=None)), ('ref NaN', dict(ref=np.array([0.0, nan]))),
+            ('np -1', dict(np_=-1)), ('np 4097', dict(np_=4097)), ('P NULL', dict(P=None)), ('P inf', dict(P=np.array([0.3, 0.1, inf, 0.3]))),
+            ('M 0', dict(M=0)), ('Xc NULL', dict(X=False)), ('k 4097', dict(k=4097)), ('top_idx NULL', dict(ti=None)),
+            ('f2 not fitted', dict(f2=unfit)), ('f2 d 3', dict(f2=c)),
+            ('f1 == f2 + ref NaN', dict(f2=a, ref=np.array([nan, 0.0]))), ('ref NaN + np -1', dict(ref=np.array([nan, 0.0]), np_=-1)),
+            ('P NULL + M 0', dict(P=None, M=0)), ('M 0 + k 4097', dict(M=0, k=4097)), ('k 4097 + f2 not fitted', dict(k=4097, f2=unfit)),
+            ('f2 not fitted + Xc NULL', dict(f2=unfit, X=False)), ('f1 not fitted, f2 d 3', dict(f1=unfit, f2=c))]
+    for label, kw in ebad:
+        g_ = dict(egood, **kw)
+        f2 = g_['f2']
+        out['ehvi host: %s' % label] = _err(lib, g_['f1'], lib.gpx_ehvi_sweep(g_['f1'], f2, _p(g_['P']), g_['np_'], _p(g_['ref']), _p(Xc) if g_['X'] else None,
+                                                                               g_['M'], g_['k'], _p(g_['tv']), _p(g_['ti']), None))
+        out['ehvi dev: %s' % label] = _err(lib, g_['f1'], lib.gpx_ehvi_sweep_dev(g_['f1'], f2, _p(g_['P']), g_['np_'], _p(g_['ref']), dXc if g_['X'] else None,
+                                                                                  g_['M'], g_['k'], _p(g_['tv']), _p(g_['ti']), None, None))
+        if not any(key in kw for key in ('f1', 'f2')):      # the fold alone: the lead, the moments (here: any device pointer, never read) and the front
+            out['ehvi fold: %s' % label] = _err(lib, a, lib.gpx_ehvi_fold_dev(a, dXc if g_['X'] else None, g_['M'], _p(g_['P']), g_['np_'], _p(g_['ref']),
+                                                                              g_['k'], _p(g_['tv']), _p(g_['ti']), None))
+    out['ehvi host: f1 NULL'] = [lib.gpx_ehvi_sweep(None, b, _p(front), 2, _p(ref), _p(Xc), M, 5, _p(tv), _p(ti), None), None]
+    out['ehvi fold: lead NULL'] = [lib.gpx_ehvi_fold_dev(None, dXc, M, _p(front), 2, _p(ref), 5, _p(tv), _p(ti), None), None]
+
+    sv, si, ss = np.zeros(64), np.zeros(64, dtype=np.int64), np.zeros(2 * 64)
+    bgood = dict(mem=[a, b], acq=0, prm=prm, np_=1, nb=2, sv=sv, si=si)
+    bbad = [('MES', dict(acq=16)), ('KG', dict(acq=32)), ('MEAN', dict(acq=3)), ('acq 4', dict(acq=4)), ('params NULL', dict(prm=None, np_=0)),
+            ('nb 0', dict(nb=0)), ('nb 65', dict(nb=65)), ('sel_val NULL', dict(sv=None)), ('sel_idx NULL', dict(si=None)),
+            ('MES + nb 0', dict(acq=16, nb=0)), ('MEAN + params NULL', dict(acq=3, prm=None, np_=0)), ('MEAN + nb 65', dict(acq=3, nb=65)),
+            ('nb 65 + sel_val NULL', dict(nb=65, sv=None))]
+
+    def batch(hh, g_):
+        return lib.gpx_sweep_batch(hh, g_['acq'], _p(g_['prm']), g_['np_'], g_['nb'], _p(g_['sv']), _p(g_['si']), None, None)
+
+    def ens_batch(g_, n=None):
+        return lib.gpx_ensemble_sweep_batch(arr(g_['mem']) if g_['mem'] is not None else None, len(g_['mem'] or ()) if n is None else n, g_['acq'],
+                                            _p(g_['prm']), g_['np_'], g_['nb'], _p(g_['sv']), _p(g_['si']), _p(ss))
+
+    for label, kw in bbad:
+        out['sweep_batch: %s' % label] = _err(lib, a, batch(a, dict(bgood, **kw)))
+        out['ensemble_sweep_batch: %s' % label] = _err(lib, a, ens_batch(dict(bgood, **kw)))
+    out['sweep_batch: no cache'] = _err(lib, b, batch(b, bgood))
+    out['sweep_batch: no cache + sel_val NULL'] = _err(lib, b, batch(b, dict(bgood, sv=None)))
+    out['sweep_batch: not fitted'] = _err(lib, unfit, batch(unfit, bgood))
+    out['sweep_batch: handle NULL'] = [batch(None, bgood), None]
+    out['ensemble_sweep_batch: no cache'] = _err(lib, a, ens_batch(bgood))
+    out['ensemble_sweep_batch: no cache on the lead'] = _err(lib, b, ens_batch(dict(bgood, mem=[b, a])))
+    out['ensemble_sweep_batch: twice'] = _err(lib, a, ens_batch(dict(bgood, mem=[a, a])))
+    out['ensemble_sweep_batch: twice + no cache'] = _err(lib, b, ens_batch(dict(bgood, mem=[b, b])))
+    out['ensemble_sweep_batch: n_members 65'] = _err(lib, a, ens_batch(dict(bgood, mem=[a] * 65)))
+    out['ensemble_sweep_batch: n_members 65 + MES'] = _err(lib, a, ens_batch(dict(bgood, mem=[a] * 65, acq=16)))
+    out['ensemble_sweep_batch: n_members 0'] = _err(lib, a, ens_batch(bgood, n=0))
+    out['ensemble_sweep_batch: member NULL'] = _err(lib, a, ens_batch(dict(bgood, mem=[a, None])))
+    out['ensemble_sweep_batch: members NULL'] = [ens_batch(dict(bgood, mem=None), n=2), None]
+    out['ensemble_sweep_batch: member not fitted'] = _err(lib, a, ens_batch(dict(bgood, mem=[a, unfit])))
+    out['ensemble_sweep_batch: member d 3'] = _err(lib, a, ens_batch(dict(bgood, mem=[a, c])))
+    out['ensemble_sweep_batch: member not fitted + twice'] = _err(lib, a, ens_batch(dict(bgood, mem=[a, unfit, unfit])))
+    out['ensemble_sweep_batch: sel_val NULL + member d 3'] = _err(lib, a, ens_batch(dict(bgood, mem=[a, c], sv=None)))
+    assert lib.gpx_set_option(b, b'sweep_cache', 1) == 0          # b: a live cache of another size
+    assert lib.gpx_sweep(b, 0, _p(prm), 1, _p(Xc), M // 2, 5, _p(tv), _p(ti), None, None, None) == 0
+    out['sweep_batch: nb 33 > M 32'] = _err(lib, b, batch(b, dict(bgood, nb=33)))
+    out['ensemble_sweep_batch: caches differ in size'] = _err(lib, a, ens_batch(bgood))
+    out['ensemble_sweep_batch: caches differ in size + nb 64'] = _err(lib, a, ens_batch(dict(bgood, nb=64)))
+
+    nv = 10
+    vv = rng.randn(2 * nv)
+    pgood = dict(h=a, v=vv, nv=nv, S=2, n=n, d=d, X=True, M=M, k=5)
+    pbad = [('not fitted', dict(h=unfit)), ('v NULL', dict(v=None)), ('d 3', dict(d=3)), ('nv 0', dict(nv=0)), ('nv N + 1', dict(nv=11)),
+            ('S 0', dict(S=0)), ('n 4097', dict(n=4097)), ('n 0', dict(n=0)), ('k 4097', dict(k=4097)), ('k -1', dict(k=-1)), ('Xc NULL', dict(X=False)),
+            ('M 0', dict(M=0)), ('not fitted + v NULL', dict(h=unfit, v=None)), ('v NULL + d 3', dict(v=None, d=3)), ('d 3 + nv 0', dict(d=3, nv=0)),
+            ('nv 0 + S 0', dict(nv=0, S=0)), ('S 0 + n 4097', dict(S=0, n=4097)), ('n 4097 + Xc NULL', dict(n=4097, X=False)),
+            ('Xc NULL + k 4097', dict(X=False, k=4097)), ('M 0 + k 4097', dict(M=0, k=4097))]
+    tvp, tip = np.zeros(2 * 8), np.zeros(2 * 8, dtype=np.int64)
+    for form in ('host', 'dev'):
+        fn = lib.gpx_path_sweep if form == 'host' else lib.gpx_path_sweep_dev
+        for label, kw in pbad:
+            g_ = dict(pgood, **kw)
+            Xp = None if not g_['X'] else (_p(Xc) if form == 'host' else dXc)
+            rc = fn(g_['h'], _p(W), _p(bb), _p(z), _p(g_['v']), g_['nv'], g_['S'], g_['n'], g_['d'], 0.0, Xp, g_['M'], g_['k'], _p(tvp), _p(tip), None)
+            out['path_sweep %s: %s' % (form, label)] = _err(lib, g_['h'], rc)
+        out['path_sweep %s: W NULL' % form] = _err(lib, a, fn(a, None, _p(bb), _p(z), _p(vv), nv, 2, n, d, 0.0, _p(Xc) if form == 'host' else dXc, M, 5,
+                                                           _p(tvp), _p(tip), None))
 
     lib.gpx_grid_destroy(grid)
     for hh in (unfit, a, b, c):

@@ -1,5 +1,6 @@
-"""Bit-exact digests of the INTERMEDIATE state of selection-only sweeps (DESIGN.md sections 2.1 and 2.2), recorded from the commit
-BEFORE the single model's and the ensemble's selection steps moved into one driver: the bit-for-bit tests compare the pruned top-k
+"""Bit-exact digests of the INTERMEDIATE state of selection-only sweeps (DESIGN.md sections 2.1 to 2.3), recorded from the commit
+BEFORE the single model's and the ensemble's selection steps moved into one driver, and again -- every earlier entry unchanged, the
+constrained cases added -- from the commit before the multi-model sweeps got one frame: the bit-for-bit tests compare the pruned top-k
 with the plain loop's, which a refactor that evaluates another set of candidates, or moves `done`, would still pass.
 
 Per sweep: every scalar of the device's report as repr (path, M, k, G, Gg, done, cap, nsurv, tau, the gate's value, the hint flag,
@@ -20,7 +21,15 @@ the second bound ran) qR, ub2, idx2, and the counters sweep_trmm_launches / swee
     illegal calls on an armed handle    UCB and a call that asks for every value, each followed by the next automatic sweep: hinted
                                         still, so the illegal call neither read nor dropped the hint (single model and ensemble)
 
-The classes named above are asserted when recording, from the device's own report (CLASSES), so an input that drifted fails loudly.
+    constrained (tests/con_cases.py)    prune = 1 on the objective: se_j2 at k = 10 and 200 (host form, each followed by the call that
+                                        asks for every value and probability of feasibility: plain), m5_j3 at k = 200 (device form,
+                                        1517 survivors), se_j1 with PI (not selection-legal: plain), se_j2 without an objective (plain);
+                                        prune = -1: se_j2_n9 at M = 33001 twice (gated and pruned, both times)
+    one lead, several entries           a forced constrained sweep, a plain ensemble sweep led by the same handle (the constrained
+                                        report reads as before), a forced ensemble EI selection (it ends the constrained record)
+
+The classes named above are asserted when recording, from the device's own report (CLASSES, CON_PATHS), so an input that drifted fails
+loudly.
 
 Output: tests/golden/select_digests.json.  Needs a GPU.  Record it from the PARENT commit's diagnostics library, never from the one
 under test; tests/test_gpu_select_digests.py replays the cases:
@@ -186,6 +195,106 @@ def _ens_auto():
     return out
 
 
+def _con_engines(p):
+    """[objective, constraints ..] of a problem of tests/con_cases.py, freshly fitted (tests/test_gpu_constrained.py: _fit_engines)."""
+    from pybo_amd._lib import Engine
+    engines = []
+    for i, (sn2, rho, ell, bias) in enumerate(p['hypers']):
+        e = Engine(0)
+        e.fit(p['X'], p['y'] if i == 0 else p['C'][:, i - 1], p['kernel'], ell, rho, sn2, bias)
+        engines.append(e)
+    return engines
+
+
+def _con_sweep(p, engines, acq, Z, k, obj=True, want_all=False):
+    """One constrained sweep of engines[0] (obj) under engines[1:]: the lead's report, the top-k, with want_all every value and
+    probability of feasibility, and the counters of the objective and of every constraint."""
+    from pybo_amd._lib import Engine
+    for e in engines:
+        e.timers(reset=True)
+    r = Engine.constrained_sweep(engines[0] if obj else None, engines[1:], p['thr'], acq, p['target'], Z, k=k, want_all=want_all,
+                                 want_pof=want_all)
+    lead = engines[0] if obj else engines[1]
+    return _record(lead.constrained_prune_report(vectors=True), (r['top_val'], r['top_idx']), engines, [('acq', r['acq']), ('pof', r['pof'])])
+
+
+def _con_forced(name, k, dev=False, acq='ei', obj=True):
+    """prune = 1 on the objective of the case `name` of tests/con_cases.py; then the call that asks for every value (host form: plain)."""
+    import con_cases
+    from test_gpu_ens_prune import _dev_cand
+    p = con_cases.problem(name)
+    engines = _con_engines(p)
+    engines[0].set_option('prune', 1)
+    out = {'sweep 1': _con_sweep(p, engines, acq, _dev_cand(p['Z']) if dev else p['Z'], k, obj=obj)}
+    if not dev:
+        out['want_all'] = _con_sweep(p, engines, acq, p['Z'], k, obj=obj, want_all=True)
+    for e in engines:
+        e.close()
+    return out
+
+
+def _con_auto():
+    """prune = -1 (a fresh handle's default) on se_j2_n9 at M = 33001 (Np = 1152 >= PRUNE_MIN_NP, M >= PRUNE_MIN_M and Gg + 2 G =
+    13056 + 8192): two sweeps in a row.  A constrained sweep carries no decision, so both run the gate (done = Gg = 13056); it passes
+    (mean s2 = 0.2365 against rho / 64) and both prune, with no survivor beyond the seeds."""
+    import con_cases
+    p = con_cases.problem('se_j2_n9', m=33001)
+    engines = _con_engines(p)
+    out = {'sweep %d' % (i + 1): _con_sweep(p, engines, 'ei', p['Z'], 10) for i in range(2)}
+    for e in engines:
+        e.close()
+    return out
+
+
+def _con_interleaved():
+    """Which entry ends which of the lead's records: a plain ensemble sweep led by the objective leaves its constrained report as it
+    was (the step's report IS the constrained one, read again); a forced ensemble EI selection lays the workspace out anew and ends it."""
+    import con_cases
+    from pybo_amd._lib import Engine, GpxError
+    p = con_cases.problem('se_j2')
+    engines = _con_engines(p)
+    obj, pair = engines[0], engines[:2]
+    obj.set_option('prune', 1)
+    out = {'constrained': _con_sweep(p, engines, 'ei', p['Z'], 10)}
+    for e in engines:
+        e.timers(reset=True)
+    r = Engine.ensemble_sweep(pair, 'ucb', 2.0, p['Z'], k=10, want_all=False)
+    out['after ensemble ucb'] = _record(obj.constrained_prune_report(vectors=True), (r['top_val'], r['top_idx']), engines)
+    r = Engine.ensemble_sweep(pair, 'ei', p['target'], p['Z'], k=10, want_all=False)
+    out['ensemble ei'] = _record(Engine.ensemble_prune_report(pair, vectors=True), (r['top_val'], r['top_idx']), engines)
+    try:
+        obj.constrained_prune_report()
+        code = 0
+    except GpxError as err:
+        code = err.code
+    out['ensemble ei']['constrained report'] = repr(code)
+    for e in engines:
+        e.close()
+    return out
+
+
+# constrained case -> step -> the path the lead's report must show when recording (a constrained report has no gate_hint)
+CON_PATHS = {
+    'constrained forced se_j2 k=10': {'sweep 1': 'pruned', 'want_all': 'plain'},
+    'constrained forced se_j2 k=200': {'sweep 1': 'pruned', 'want_all': 'plain'},
+    'constrained forced m5_j3 k=200 dev': {'sweep 1': 'pruned'},
+    'constrained pi se_j1 k=10': {'sweep 1': 'plain', 'want_all': 'plain'},
+    'constrained no objective se_j2 k=10': {'sweep 1': 'plain', 'want_all': 'plain'},
+    'constrained auto se_j2_n9': {'sweep 1': 'pruned', 'sweep 2': 'pruned'},
+    'constrained interleaved': {'constrained': 'pruned', 'after ensemble ucb': 'pruned', 'ensemble ei': 'pruned'},
+}
+
+
+def con_cases_list():
+    out = [('constrained forced se_j2 k=%d' % k, lambda k=k: _con_forced('se_j2', k)) for k in (10, 200)]
+    out.append(('constrained forced m5_j3 k=200 dev', lambda: _con_forced('m5_j3', 200, dev=True)))
+    out.append(('constrained pi se_j1 k=10', lambda: _con_forced('se_j1', 10, acq='pi')))
+    out.append(('constrained no objective se_j2 k=10', lambda: _con_forced('se_j2', 10, obj=False)))
+    out.append(('constrained auto se_j2_n9', _con_auto))
+    out.append(('constrained interleaved', _con_interleaved))
+    return out
+
+
 def cases():
     """[(name, thunk)]: every thunk returns {step: {output: repr or digest}}."""
     out = []
@@ -210,7 +319,7 @@ def cases():
     out.append(('ensemble forced m5_n3_d5 k=200', lambda: _ens_forced('m5_n3_d5', 200, False)))
     out.append(('ensemble forced se_n3_app k=10 dev', lambda: _ens_forced('se_n3_app', 10, True)))
     out.append(('ensemble auto', _ens_auto))
-    return out
+    return out + con_cases_list()
 
 
 def main():
@@ -229,6 +338,12 @@ def main():
             first = {s: {k: v for k, v in first[s].items() if second[s].get(k) == v} for s in first}
         for step, (path, hinted) in CLASSES.get(name, {}).items():
             assert (first[step]['path'], first[step]['gate_hint']) == (repr(path), repr(hinted)), (name, step, first[step])
+        for step, path in CON_PATHS.get(name, {}).items():
+            assert first[step]['path'] == repr(path), (name, step, first[step])
+        if name == 'constrained interleaved':      # the second reading of the constrained report is the first; the forced ensemble sweep ends it
+            a, b = first['constrained'], first['after ensemble ucb']
+            assert all(b[k] == a[k] for k in a if not k.startswith(('top_', 'sweep_trmm_'))), (a, b)
+            assert first['ensemble ei']['constrained report'] == repr(-5), first['ensemble ei']
         if name.startswith(('single forced', 'ensemble forced')):
             assert first['sweep 1']['path'] == repr('pruned'), (name, first['sweep 1'])
         if name in SURVIVORS:

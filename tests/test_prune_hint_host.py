@@ -53,9 +53,12 @@ def test_the_library_includes_the_header_the_check_includes():
     driver = api[api.index('static int select_topk_pruned('):api.index('static int plain_rest(')]
     for call in ('prune_hint_matches(', 'prune_hint_after('):
         assert api.count(call) == 1 and driver.count(call) == 1, call
-    assert api.count('select_topk_pruned(') == 3                                      # its definition and the two calls below
+    assert api.count('select_topk_pruned(') == 4                                      # its definition and the three calls below
     for body, hint in ((api[api.index('static int sweep_core('):api.index('extern "C" int gpx_sweep_dev(')], 'h->prune_hint'),
                        (api[api.index('static int ensemble_core('):api.index('static int ensemble_check(')], 'L->ens_hint')):
         assert body.count('select_topk_pruned(') == 1 and body.count(hint) == 1        # each hands its own hint object to the driver
+    # the constrained sweep hands it a local one: it neither reads nor arms the decisions the lead carries for its own sweeps
+    body = api[api.index('static int constrained_core('):api.index('extern "C" int gpx_constrained_sweep_dev(')]
+    assert body.count('select_topk_pruned(') == 1 and 'PruneHint hint;' in body and 'h->prune_hint' not in body and 'L->ens_hint' not in body
     assert '#include "../../pybo_amd/csrc/prune_hint.h"' in open(SRC).read()
     assert 'prune_hint.h' in open(os.path.join(csrc, 'build.sh')).read()              # a dependency of the incremental build
