@@ -262,9 +262,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_rff_mfma5(const double* __r
     stash(Bt0);
     __syncthreads();
     const double* as = At + w * 32 + fr;
-    double rmask[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rmask[r] = (((lane >> 2) & 3) == r) ? 1.0 : 0.0;
     for (int tile = 0; tile < S; ++tile) {
         const double* Bt = Bt0 + ((DB && (tile & 1)) ? bstride : 0);
         const double* bs = Bt + fr;
@@ -340,26 +337,35 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_rff_mfma5(const double* __r
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) rowsum[i][r] = fma(tj[j], cos_cw(acc[i][j][r]), rowsum[i][r]);
+        // The remainder columns: a 4x4x4 result belongs to candidate row fk + 4 (fr >> 2), column fr & 3 of its sub-tile -- the four
+        // lanes of quad fr >> 2 hold that row's remainder terms.  They are summed over the sub-tiles in the lane and over the quad, and
+        // added to the row's sum over the 16-column groups AFTER that sum's own reduction, by the quad's first lane: every row is added
+        // in the same order.  (Added into rowsum[.][fr >> 2] before the reduction, they sat in a different quad of the tree for every
+        // r, and a candidate's last bits depended on its row in the tile.)
+        double rem[2] = {0.0, 0.0};
 #pragma unroll
-        for (int q = 0; q < NSUB; ++q)
+        for (int i = 0; i < 2; ++i) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const double v = tjr[q] * cos_cw(accr[i][q]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) rowsum[i][r] = fma(rmask[r], v, rowsum[i][r]);
+            for (int q = 0; q < NSUB; ++q) rem[i] = fma(tjr[q], cos_cw(accr[i][q]), rem[i]);
+            if (NSUB > 0) {
+                rem[i] += dpp_f64<0xB1>(rem[i]);       // quad_perm [1, 0, 3, 2]
+                rem[i] += dpp_f64<0x4E>(rem[i]);       // quad_perm [2, 3, 0, 1]
             }
+        }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                // the 16 lanes of a DPP row share the candidate row: quad butterflies, then the mirrors (no LDS round trips)
+                // the 16 lanes of a DPP row share the candidate row: quad butterflies, then the mirrors (no LDS round trips); all 16 end
+                // with the same sum
                 double v = rowsum[i][r];
                 v += dpp_f64<0xB1>(v);       // quad_perm [1, 0, 3, 2]
                 v += dpp_f64<0x4E>(v);       // quad_perm [2, 3, 0, 1]
                 v += dpp_f64<0x141>(v);      // row_half_mirror: quad 0 <-> 1, 2 <-> 3
                 v += dpp_f64<0x140>(v);      // row_mirror: half 0 <-> 1
+                if (NSUB > 0) v += rem[i];   // (the value of row fk + 4 r in the lanes of quad r alone)
                 const int64_t gm = m0 + w * 32 + i * 16 + fk + 4 * r;
-                if (fr == 0 && gm < M) vals[(int64_t)tile * M + gm] = bias + v;
+                if (fr == (NSUB > 0 ? 4 * r : 0) && gm < M) vals[(int64_t)tile * M + gm] = bias + v;
             }
         __syncthreads();   // the next tile's image is complete
     }

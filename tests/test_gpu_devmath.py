@@ -201,8 +201,8 @@ def test_cosines_meet_their_bounds():
     e = _engine()
     e.fit(np.ones((1, 1)), np.array([1.0]), 'se', [1.0], 1.0, 0.1, 0.0)
     one = np.ones((1, 1, 1))
-    # (a NaN candidate goes alone: in the sweep's 4x4 MFMA tail it shares registers with candidates 4 rows away, and its
-    #  masked-out NaN still reaches them through the masking multiply -- a defect of its own, not of cos_cw)
+    # (a NaN candidate goes alone, as it did while the sweep's 4x4 MFMA tail let a NaN reach the candidates 4 rows away through a
+    #  masking multiply; the tail adds a row's remainder terms without one now, tests/test_gpu_instantiations.py)
     fin = np.isfinite(z)
     v = np.full(len(z), np.nan)
     v[fin] = e.rff_sweep(one, np.zeros((1, 1)), np.ones((1, 1)), 0.0, z[fin, None])['vals'][0]

@@ -22,6 +22,7 @@ Held here, at the shapes of tests/test_gpu_prune_bound_mfma.py with the kernel f
 import numpy as np
 import pytest
 
+import inst_cases as ic
 from test_gpu_prune import _dev
 from test_gpu_prune_bound import _engine, _expected_sizes, _problem, check_sweep
 from test_gpu_prune_bound_mfma import DS, MS, NS, _eps_k
@@ -90,6 +91,13 @@ def test_bound_invariants_and_margin_with_the_fp32_kernel(N, d, M):
     assert r['path'] in ('pruned', 'fell back') and r['bound_kernel'] == 'mfma32', (label, r['bound_kernel'])
     _margin(e, w, w['Xc'], r, e.prune_dots(), label)
     e.close()
+
+
+@pytest.mark.parametrize('N,d', [(N, d) for N in ic.BOUND_NS for d in ic.BOUND_DS])
+def test_bound_invariants_and_margin_at_the_template_cases_the_shapes_above_do_not_reach(N, d):
+    """k_bound_mfma32<KS, NC, false> at d = 3, 4 (1, NC), 5, 6 (2, -), 11, 12 (3, NC), 13, 14 (4, -), 17, 18 (5, -): the same body
+    (tests/inst_cases.py, tests/test_instantiation_cases_cpu.py: with DS these reach every instantiation)."""
+    test_bound_invariants_and_margin_with_the_fp32_kernel(N, d, 3 * G + 1)
 
 
 def test_a_candidate_on_an_observation_a_nan_one_and_a_far_one():

@@ -21,6 +21,7 @@ check_sweep asserts the pruned top-k array_equal to the plain one in every case.
 import numpy as np
 import pytest
 
+import inst_cases as ic
 from oracle import gp_ref
 from test_gpu_prune_bound import _engine, _problem, check_sweep
 
@@ -86,6 +87,13 @@ def test_bound_invariants_with_either_kernel_and_with_the_guard(N, d, M):
     assert r0['path'] in ('pruned', 'fell back') and r1['path'] in ('pruned', 'fell back')
     _agree(r0, r1, w, label)
     e.close()
+
+
+@pytest.mark.parametrize('N,d', [(N, d) for N in ic.BOUND_NS for d in ic.BOUND_DS])
+def test_bound_invariants_at_the_template_cases_the_shapes_above_do_not_reach(N, d):
+    """k_bound_mfma<KS, NC> at d = 3, 4 (1, NC), 5, 6 (2, -), 11, 12 (3, NC), 13, 14 (4, -), 17, 18 (5, -): the same body (tests/inst_cases.py,
+    tests/test_instantiation_cases_cpu.py: with DS these reach every instantiation)."""
+    test_bound_invariants_with_either_kernel_and_with_the_guard(N, d, 3 * G + 1)
 
 
 def test_a_candidate_on_an_observation_a_nan_one_and_a_far_one():
