@@ -6,9 +6,7 @@
 # The two libraries link the same objects but one: diag_flag.cpp, compiled twice (diag_flag.o, and diag_flag_diag.o with
 # -DGPX_DIAGNOSTICS), decides whether gpx_set_option accepts the diagnostic knobs of gpx_diag.h.  The test-suite drives
 # libgpx_diag.so (tests/conftest.py: GPX_DIAGNOSTICS=1); everything else loads libgpx.so.
-# A/B builds (never shipped): EXTRA="-DGPX_TG_REGLOOPS" compiles the factorisation's workers with the register-staged k-loops of rounds
-# 2-5 instead of the LDS-DMA ones; EXTRA="-DGPX_PF16_COUNTED_WAIT" lets the diagonal role publish a step with its next tile's stores in flight
-# (round 5's hand-counted s_waitcnt; 2-5 % faster up to N = 4096, see ADVICE round 5 for why it is off); EXTRA="-DGPX_BOUND32_NOFACT" makes
+# A/B builds (never shipped): EXTRA="-DGPX_PF16_COUNTED_WAIT" lets the diagonal role publish a step with its next tile's stores in flight (round 5's hand-counted s_waitcnt; 2-5 % faster up to N = 4096, see ADVICE round 5 for why it is off); EXTRA="-DGPX_BOUND32_NOFACT" makes
 # the option bound_fact default to 0: the fp32 bound kernel with its sign tiles alone (profiles/bound_f32_ops_ab.md, build A).
 set -e
 cd "$(dirname "$0")"

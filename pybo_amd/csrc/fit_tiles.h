@@ -504,7 +504,7 @@ __device__ __forceinline__ void panel_solve16_body(const double* __restrict__ U,
 }
 
 
-// DB: `smem` holds two k-step images and the workgroup has its compute unit to itself (gemm_tile_128_d)
+// DB: `smem` holds two k-step images and the workgroup has its compute unit to itself (gemm_tile_128_l2)
 template <bool AG = false, int PRIO = 1, bool DB = false>
 __device__ __forceinline__ void syrk_tile(const double* __restrict__ R, double* __restrict__ S, int64_t Np, int kb0,
                                           int kb1, int I, int J, double* smem) {
@@ -513,14 +513,9 @@ __device__ __forceinline__ void syrk_tile(const double* __restrict__ R, double* 
     d4 acc[4][4];
     double* tile = S + i0 * Np + j0;
     tile128_load<AG>(acc, tile, Np);
-#ifdef GPX_TG_REGLOOPS       // A/B builds only: the register-staged k-loops of rounds 2-5
-    if constexpr (DB) gemm_tile_128_d<PRIO, true, AG ? 16 : 0>(acc, R + i0, Np, R + j0, Np, kb0 * NB, kb1 * NB, smem);
-    else gemm_tile_128_g<PRIO, true>(acc, R + i0, Np, R + j0, Np, kb0 * NB, kb1 * NB, smem);
-#else
     // operands by LDS-DMA (round 6): no staging registers, no ds_write phase; A is negated by the MFMA itself -- same bits
-    if constexpr (DB) gemm_tile_128_ld<PRIO, true, AG ? 16 : 0>(acc, R + i0, Np, R + j0, Np, kb0 * NB, kb1 * NB, smem);
+    if constexpr (DB) gemm_tile_128_l2<PRIO, 2, false, false, true, AG ? 16 : 0, false, 4, 4>(acc, R + i0, Np, R + j0, Np, kb0 * NB, kb1 * NB, smem);
     else gemm_tile_128_l<32, (PRIO > 2 ? 2 : PRIO), 2, false, false, true>(acc, R + i0, Np, R + j0, Np, kb0 * NB, kb1 * NB, smem);
-#endif
     tile128_store<AG>(acc, tile, Np);
 }
 

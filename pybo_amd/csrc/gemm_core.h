@@ -18,13 +18,13 @@
 //   operands by LDS-DMA (round 6; buffer_load_dwordx4 ... lds, no staging registers):
 //     gemm_tile_128_l   k-step 32 (or 16) through ONE LDS image: the sweep (two workgroups per CU), the triangular inverse, the
 //                       factorisation's workers at two workgroups per CU; optional skip of a triangular last k-block (TRI)
-//     gemm_tile_128_ld  two images, the next step's loads behind the first four MFMA groups: a workgroup alone on its CU
-//     gemm_tile_128_l2  gemm_tile_128_l<32> on two images (skip, order, narrow tiles and all): the sweep's short launches, one workgroup per CU
-//     gemm_tile_128_w   every WAVE keeps its own operand halves: no barrier at all (a witness of the sweep: it moves twice the bytes)
+//     gemm_tile_128_l2  gemm_tile_128_l<32> on two images (skip, order, narrow tiles and all), the next step's loads behind the first MFMA
+//                       groups: a workgroup alone on its CU -- the sweep's short launches, the factorisation's workers at one per CU
+//                       (both are drivers of gemm_dma_operands + gemm_l_groups: they state only their own barriers and waits)
+//     gemm_tile_128_w  every WAVE keeps its own operand halves: no barrier at all (a witness of the sweep: it moves twice the bytes)
 //   operands through registers (rounds 1-5; kept as independently scheduled witnesses and for the Gram / RFF products):
 //     gemm_tile_128_s   k-step 32, buffer loads, banded priority, second fragment set (round 5's sweep)
 //     gemm_tile_128_g   k-step 32, flat loads (round 2);  gemm_tile_128_b  k-step 16 through a 2-deep ring (round 1)
-//     gemm_tile_128_d   two images, LDS writes behind the MFMA groups (round 5's lone workgroup)
 // fp64 MFMA is 64 cycles/instruction/SIMD: a 32-row k-step is 8192 matrix cycles per wave.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -324,120 +324,6 @@ __device__ __forceinline__ void gemm_tile_128_s(d4 (&acc)[4][4], const double* _
     }
 }
 
-// The k-loop for a workgroup that has its compute unit to ITSELF (round 5: the task-graph factorisation's workers up to 72
-// blocks -- one workgroup per CU, LDS 2 x 72 KB).  A lone workgroup on the single-buffer loops above runs at 0.68 of the matrix
-// peak (scripts/sweep_phase: mode 256): barrier - LDS write - barrier stands exposed in every k-step and nobody fills it.
-// Here the k-step of 32 goes through TWO LDS buffers: while the MFMAs of step t read buffer t & 1, the registers holding tile
-// t + 1 are written to the other buffer two 16-byte pieces per MFMA group, and each register is refilled at once with its piece
-// of tile t + 2 -- every global load has a whole step to arrive, every LDS write hides behind 16 MFMAs, ONE barrier per step.
-// Same arithmetic in the same order as the other loops: bit-identical results.  smem: 2 x GEMM_LDS_F64 doubles.
-// AUX: cache policy of the operand loads (16 = sc1: past this CU's L1 -- operands another workgroup of the SAME launch has just
-// stored write-through need no acquire fence then; every element is loaded once per workgroup, the L1 had nothing to give)
-template <int PRIO = 1, bool NEGA = false, int AUX = 0>
-__device__ __forceinline__ void gemm_tile_128_d(d4 (&acc)[4][4], const double* __restrict__ A, int64_t lda,
-                                                const double* __restrict__ B, int64_t ldb, int k_lo, int k_hi,
-                                                double* smem) {
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int w = t >> 6;
-    const int wm = w >> 1, wn = w & 1;
-    const int lrow = w;
-    const int lcol = lane * 2;
-    d2 ra[8], rb[8];
-    const int nk = (k_hi - k_lo) / BK32;
-    if (nk <= 0) return;
-    const char* Abase = reinterpret_cast<const char*>(A + (int64_t)k_lo * lda);
-    const char* Bbase = reinterpret_cast<const char*>(B + (int64_t)k_lo * ldb);
-    const int voA = (int)(((int64_t)lrow * lda + lcol) * 8), voB = (int)(((int64_t)lrow * ldb + lcol) * 8);
-    const int soA = (int)(4 * lda * 8), soB = (int)(4 * ldb * 8);
-    const int fr = lane & 15, fk = lane >> 4;
-    // tile 0 -> buffer 0, tile 1 -> registers
-    {
-        __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Abase, 0, -1, 0x00020000);
-        __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bbase, 0, -1, 0x00020000);
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            ra[p] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rA, voA, p * soA, AUX));
-            rb[p] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rB, voB, p * soB, AUX));
-        }
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            *reinterpret_cast<d2*>(smem + (lrow + 4 * p) * LDT + lcol) = NEGA ? -ra[p] : ra[p];
-            *reinterpret_cast<d2*>(smem + BK32 * LDT + (lrow + 4 * p) * LDT + lcol) = rb[p];
-        }
-        Abase += (int64_t)BK32 * lda * 8;
-        Bbase += (int64_t)BK32 * ldb * 8;
-        if (nk > 1) {
-            __amdgpu_buffer_rsrc_t rA1 = __builtin_amdgcn_make_buffer_rsrc((void*)Abase, 0, -1, 0x00020000);
-            __amdgpu_buffer_rsrc_t rB1 = __builtin_amdgcn_make_buffer_rsrc((void*)Bbase, 0, -1, 0x00020000);
-#pragma unroll
-            for (int p = 0; p < 8; ++p) {
-                ra[p] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rA1, voA, p * soA, AUX));
-                rb[p] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rB1, voB, p * soB, AUX));
-            }
-            Abase += (int64_t)BK32 * lda * 8;
-            Bbase += (int64_t)BK32 * ldb * 8;
-        }
-    }
-    __syncthreads();
-    if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
-    // one k-step; W1: tile kt + 1 exists (its registers go to the other buffer), W2: tile kt + 2 exists (registers refilled).
-    // Compile-time flags: with run-time tests around the writes and loads every MFMA group became a basic block of its own
-    // and nothing overlapped (0.65 instead of 0.73 of peak alone on a CU).
-    auto step = [&](int kt, auto w1_, auto w2_) {
-        constexpr bool W1 = decltype(w1_)::value, W2 = decltype(w2_)::value;
-        double* cur = smem + (kt & 1) * GEMM_LDS_F64;
-        double* nxt = smem + ((kt + 1) & 1) * GEMM_LDS_F64;
-        const double* as = cur + wm * 64 + fr;
-        const double* bs = cur + BK32 * LDT + wn * 64 + fr;
-        __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Abase, 0, -1, 0x00020000);
-        __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bbase, 0, -1, 0x00020000);
-        double a[2][4], b[2][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            a[0][i] = as[fk * LDT + i * 16];
-            b[0][i] = bs[fk * LDT + i * 16];
-        }
-#pragma unroll
-        for (int kk = 0; kk < BK32 / 4; ++kk) {
-            if (kk + 1 < BK32 / 4) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    a[(kk + 1) & 1][i] = as[((kk + 1) * 4 + fk) * LDT + i * 16];
-                    b[(kk + 1) & 1][i] = bs[((kk + 1) * 4 + fk) * LDT + i * 16];
-                }
-            }
-            __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);      // the LDS reads of group kk + 1,
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk & 1][i], b[kk & 1][j], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);     // the 16 MFMAs of group kk,
-            if (W1) {                                               // piece kk of tile kt + 1 into the other buffer ...
-                *reinterpret_cast<d2*>(nxt + (lrow + 4 * kk) * LDT + lcol) = NEGA ? -ra[kk] : ra[kk];
-                *reinterpret_cast<d2*>(nxt + BK32 * LDT + (lrow + 4 * kk) * LDT + lcol) = rb[kk];
-                __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
-            }
-            if (W2) {                                               // ... and its registers refilled with tile kt + 2
-                ra[kk] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rA, voA, kk * soA, AUX));
-                rb[kk] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rB, voB, kk * soB, AUX));
-                __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-            }
-        }
-        if (W2) {
-            Abase += (int64_t)BK32 * lda * 8;
-            Bbase += (int64_t)BK32 * ldb * 8;
-        }
-        __syncthreads();               // buffer kt & 1 has been read by everyone, the other one is complete
-    };
-    int kt = 0;
-    for (; kt + 2 < nk; ++kt) step(kt, std::true_type{}, std::true_type{});
-    if (kt + 1 < nk) { step(kt, std::true_type{}, std::false_type{}); ++kt; }
-    step(kt, std::false_type{}, std::false_type{});
-    if (PRIO) __builtin_amdgcn_s_setprio(PRIO - 1);
-}
-
 // The sweep's k-loop for THREE workgroups per compute unit (round 6).  What the round-5 stamps left standing: the matrix
 // pipe of a SIMD serves one wave's matrix phase at a time, and a lone streaming wave leaves ~3 % of the pipe's issue slots
 // empty (its own LDS reads, waits and priority changes); the partner cannot fill them because it is staging or parked
@@ -454,12 +340,80 @@ typedef __attribute__((address_space(3))) void* gemm_lds_ptr;
 template <int BKL>
 constexpr int gemm_l_lds_f64() { return 2 * BKL * LDT; }
 
+// What the LDS-DMA loops share (gemm_tile_128_l, gemm_tile_128_l2), part 1: where a wave's operand rows come from.  The base of
+// the step to fetch lives in SGPRs and moves by SALU, the row of load p is an SGPR offset, the lane's position one constant VGPR
+// offset per operand (no bounds: num_records = 2^32 - 1; the base moves with the step, so the offsets stay below BKL rows).
+// AUX: cache policy of the loads (16 = sc1: past this CU's L1 -- operands another workgroup of the SAME launch has just stored
+// write-through need no acquire fence then; every element is loaded once per workgroup, the L1 had nothing to give).
+// REV: the steps run from [k_hi - BKL, k_hi) downwards.
+template <int BKL, int AUX, bool REV>
+struct gemm_dma_operands {
+    const char *Abase, *Bbase;         // the step that issue() fetches
+    const int64_t stepA, stepB;
+    const int voA, voB, soA, soB;      // four rows on: the SGPR offset of load p is p * so
+    const int w;
+    __device__ __forceinline__ gemm_dma_operands(const double* A, int64_t lda, const double* B, int64_t ldb, int k_lo, int k_hi,
+                                                 int w_, int lane)
+        : Abase(reinterpret_cast<const char*>(A + (int64_t)(REV ? k_hi - BKL : k_lo) * lda)),
+          Bbase(reinterpret_cast<const char*>(B + (int64_t)(REV ? k_hi - BKL : k_lo) * ldb)),
+          stepA((REV ? -1 : 1) * (int64_t)BKL * lda * 8), stepB((REV ? -1 : 1) * (int64_t)BKL * ldb * 8),
+          voA((int)(((int64_t)w_ * lda + 2 * lane) * 8)), voB((int)(((int64_t)w_ * ldb + 2 * lane) * 8)),
+          soA((int)(4 * lda * 8)), soB((int)(4 * ldb * 8)), w(w_) {}
+    // rows w + 4 p, p = p0 .. p1 - 1, of the step at Abase / Bbase into the image [A | B][BKL][LDT] at img
+    __device__ __forceinline__ void issue(double* img, int p0, int p1) const {
+        double* As = img;
+        double* Bs = img + BKL * LDT;
+        __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Abase, 0, -1, 0x00020000);
+        __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bbase, 0, -1, 0x00020000);
+#pragma unroll
+        for (int p = p0; p < p1; ++p) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (gemm_lds_ptr)(As + (w + 4 * p) * LDT), 16, voA, p * soA, 0, AUX);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (gemm_lds_ptr)(Bs + (w + 4 * p) * LDT), 16, voB, p * soB, 0, AUX);
+        }
+    }
+    __device__ __forceinline__ void bump() {
+        Abase += stepA;
+        Bbase += stepB;
+    }
+};
+
+// Part 2: the matrix phase of one k-step: G groups of (4 - I0) x NJ MFMAs out of the image whose fragments of this lane start at
+// as / bs, the fragments of group kk + 1 requested ahead of the MFMAs of group kk (NSET = 2; NSET = 1: behind them).  I0: row
+// blocks i < I0 are skipped (TRI); IST: row-block stride of a wave's A fragments.  after(kk) runs behind the MFMAs of group kk:
+// what a loop hangs between the groups (the next step's loads, a priority change).
+template <int G, int NSET, int I0, int IST, bool NEGA, int NJ, class Hook>
+__device__ __forceinline__ void gemm_l_groups(d4 (&acc)[4][NJ], const double* as, const double* bs, Hook after) {
+    double a[NSET][4], b[NSET][NJ];
+    auto frag = [&](int set, int g) {
+#pragma unroll
+        for (int i = I0; i < 4; ++i) a[set][i] = as[g * 4 * LDT + i * IST];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) b[set][j] = bs[g * 4 * LDT + j * 16];
+    };
+    frag(0, 0);
+#pragma unroll
+    for (int kk = 0; kk < G; ++kk) {
+        if (NSET == 2 && kk + 1 < G) {
+            frag((kk + 1) & 1, kk + 1);
+            __builtin_amdgcn_sched_group_barrier(0x100, 4 + NJ - I0, 0); // the LDS reads of group kk + 1 first,
+        }
+#pragma unroll
+        for (int i = I0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk % NSET][i], b[kk % NSET][j], acc[i][j], 0, 0, NEGA ? 1 : 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, NJ * (4 - I0), 0);   // then the MFMAs of group kk,
+        after(kk);                                                       // then what the loop puts behind them
+        if (NSET == 1 && kk + 1 < G) frag(0, kk + 1);
+    }
+}
+
 // TRI (needs ILV): A's last 128 k-rows [k_hi - 128, k_hi) are a lower-triangular block (A(m, k) = 0 for k > m, m and k
 //      counted inside the block).  In its j-th 32-row quarter the row blocks 2 i + wm < 2 j hold only zeros for BOTH waves
 //      when i < j: their MFMAs are skipped (an exact no-op: the skipped products are +0).  The interleaved rows are what
 //      makes the skip worth it: both wave rows lose the same share (1.5 of the block's 4 quarters).
 // NEGA: acc += -(A) B through the MFMA's own negation of its A operand (neg:[1,0,0]): the same bits as negating A on its way
-//      into LDS (the register-staged loops), which a DMA cannot do.  AUX: cache policy of the operand loads (see gemm_tile_128_d).
+//      into LDS (the register-staged loops), which a DMA cannot do.  AUX: cache policy of the operand loads (gemm_dma_operands).
 // REV: the 32-row k-steps in DESCENDING order (see gemm_tile_128_g).
 // NJ (deduced from acc): the 16-column groups a wave owns.  NJ = 4 is the 128 x 128 tile.  NJ = 2, 1: a NARROW tile of 128 rows x
 //      32 NJ columns that starts at column bcol (a multiple of 32 NJ) of the 128-column B image: wave (wm, wn) keeps its rows and
@@ -477,30 +431,17 @@ __device__ __forceinline__ void gemm_tile_128_l(d4 (&acc)[4][NJ], const double* 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = w >> 1, wn = w & 1;
-    double* As = smem;                 // [BKL][LDT]
-    double* Bs = smem + BKL * LDT;     // [BKL][LDT]
     const int nk = (k_hi - k_lo) / BKL;
     if (nk <= 0) return;
-    const char* Abase = reinterpret_cast<const char*>(A + (int64_t)(REV ? k_hi - BKL : k_lo) * lda);
-    const char* Bbase = reinterpret_cast<const char*>(B + (int64_t)(REV ? k_hi - BKL : k_lo) * ldb);
-    const int64_t stepA = (REV ? -1 : 1) * (int64_t)BKL * lda * 8, stepB = (REV ? -1 : 1) * (int64_t)BKL * ldb * 8;
-    const int voA = (int)(((int64_t)w * lda + 2 * lane) * 8), voB = (int)(((int64_t)w * ldb + 2 * lane) * 8);
-    const int soA = (int)(4 * lda * 8), soB = (int)(4 * ldb * 8);      // four rows on: the SGPR offset of load p is p * so
+    gemm_dma_operands<BKL, AUX, REV> src(A, lda, B, ldb, k_lo, k_hi, w, lane);
     auto issue = [&]() {
-        __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Abase, 0, -1, 0x00020000);
-        __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bbase, 0, -1, 0x00020000);
-#pragma unroll
-        for (int p = 0; p < BKL / 4; ++p) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (gemm_lds_ptr)(As + (w + 4 * p) * LDT), 16, voA, p * soA, 0, AUX);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (gemm_lds_ptr)(Bs + (w + 4 * p) * LDT), 16, voB, p * soB, 0, AUX);
-        }
-        Abase += stepA;
-        Bbase += stepB;
+        src.issue(smem, 0, G);
+        src.bump();
     };
     const int fr = lane & 15, fk = lane >> 4;
     constexpr int IST = ILV ? 32 : 16;                                  // row-block stride of a wave's A fragments
-    const double* as = As + (ILV ? wm * 16 : wm * 64) + fr + fk * LDT;
-    const double* bs = Bs + bcol + wn * (16 * NJ) + fr + fk * LDT;
+    const double* as = smem + (ILV ? wm * 16 : wm * 64) + fr + fk * LDT;
+    const double* bs = smem + BKL * LDT + bcol + wn * (16 * NJ) + fr + fk * LDT;
     // one k-step; I0: row blocks i < I0 are skipped (TRI); more: there is a next step whose loads go out at the end
     auto step = [&](auto i0c, bool more) {
         constexpr int I0 = decltype(i0c)::value;
@@ -508,29 +449,9 @@ __device__ __forceinline__ void gemm_tile_128_l(d4 (&acc)[4][NJ], const double* 
         __builtin_amdgcn_s_barrier();                  // every wave's rows of this step are in LDS
         asm volatile("" ::: "memory");
         if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
-        double a[NSET][4], b[NSET][NJ];
-        auto frag = [&](int set, int g) {
-#pragma unroll
-            for (int i = I0; i < 4; ++i) a[set][i] = as[g * 4 * LDT + i * IST];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) b[set][j] = bs[g * 4 * LDT + j * 16];
-        };
-        frag(0, 0);
-#pragma unroll
-        for (int kk = 0; kk < G; ++kk) {
-            if (PRIO && kk == G / 2) __builtin_amdgcn_s_setprio(PRIO + 1);
-            if (NSET == 2 && kk + 1 < G) {
-                frag((kk + 1) & 1, kk + 1);
-                __builtin_amdgcn_sched_group_barrier(0x100, 4 + NJ - I0, 0); // the LDS reads of group kk + 1 first,
-            }
-#pragma unroll
-            for (int i = I0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk % NSET][i], b[kk % NSET][j], acc[i][j], 0, 0, NEGA ? 1 : 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, NJ * (4 - I0), 0);   // then the MFMAs of group kk
-            if (NSET == 1 && kk + 1 < G) frag(0, kk + 1);
-        }
+        gemm_l_groups<G, NSET, I0, IST, NEGA>(acc, as, bs, [&](int kk) {
+            if (PRIO && kk + 1 == G / 2) __builtin_amdgcn_s_setprio(PRIO + 1);     // the second half of the step's groups
+        });
         if (PRIO) __builtin_amdgcn_s_setprio(0);
         // (lgkmcnt: the compiler may sink a step's last MFMAs below the barrier and leave their fragment reads in flight above
         //  it; no LDS read of this wave may still be pending when another wave's DMA starts to overwrite the buffer)
@@ -559,108 +480,13 @@ __device__ __forceinline__ void gemm_tile_128_l(d4 (&acc)[4][NJ], const double* 
     }
 }
 
-// The register-free loop for a workgroup that has its compute unit to ITSELF (two k-step images of LDS, 2 x 73,728 B): while
-// step t is multiplied out of image t & 1, the DMA of step t + 1 fills the other image -- issued four instructions at a time
-// behind the step's first four MFMA groups -- and ONE barrier ends the step: behind it every wave has finished reading image
-// t & 1 AND every wave's rows of step t + 1 have landed (each wave waits for its own loads first).  Against gemm_tile_128_d
-// (registers, LDS writes behind the MFMA groups): no staging registers, no ds_write.  Same arithmetic, same order, same bits.
-template <int PRIO = 1, bool NEGA = false, int AUX = 0>
-__device__ __forceinline__ void gemm_tile_128_ld(d4 (&acc)[4][4], const double* __restrict__ A, int64_t lda,
-                                                 const double* __restrict__ B, int64_t ldb, int k_lo, int k_hi,
-                                                 double* smem) {
-    constexpr int G = BK32 / 4;
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = w >> 1, wn = w & 1;
-    const int nk = (k_hi - k_lo) / BK32;
-    if (nk <= 0) return;
-    const char* Abase = reinterpret_cast<const char*>(A + (int64_t)k_lo * lda);
-    const char* Bbase = reinterpret_cast<const char*>(B + (int64_t)k_lo * ldb);
-    const int voA = (int)(((int64_t)w * lda + 2 * lane) * 8), voB = (int)(((int64_t)w * ldb + 2 * lane) * 8);
-    const int soA = (int)(4 * lda * 8), soB = (int)(4 * ldb * 8);
-    // rows w + 4 p, p = P0 .. P1 - 1, of the step at Abase / Bbase into image img
-    auto issue = [&](int img, auto p0c, auto p1c) {
-        constexpr int P0 = decltype(p0c)::value, P1 = decltype(p1c)::value;
-        double* As = smem + img * GEMM_LDS_F64;
-        double* Bs = As + BK32 * LDT;
-        __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Abase, 0, -1, 0x00020000);
-        __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bbase, 0, -1, 0x00020000);
-#pragma unroll
-        for (int p = P0; p < P1; ++p) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (gemm_lds_ptr)(As + (w + 4 * p) * LDT), 16, voA, p * soA, 0, AUX);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (gemm_lds_ptr)(Bs + (w + 4 * p) * LDT), 16, voB, p * soB, 0, AUX);
-        }
-    };
-    auto bump = [&]() {
-        Abase += (int64_t)BK32 * lda * 8;
-        Bbase += (int64_t)BK32 * ldb * 8;
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I8 = std::integral_constant<int, 8>;
-    const int fr = lane & 15, fk = lane >> 4;
-    const int aoff = wm * 64 + fr + fk * LDT, boff = BK32 * LDT + wn * 64 + fr + fk * LDT;
-    issue(0, I0{}, I8{});
-    bump();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
-    // One step.  FILL: the loads of the NEXT step go out behind this step's first four MFMA groups, four at a time, into the
-    // image the previous step was read from (the barrier that ended it freed it); they have the step's other four groups
-    // (4096 matrix clocks) to land.
-    auto step = [&](int kt, auto fillc) {
-        constexpr bool FILL = decltype(fillc)::value;
-        const double* as = smem + (kt & 1) * GEMM_LDS_F64 + aoff;
-        const double* bs = smem + (kt & 1) * GEMM_LDS_F64 + boff;
-        const int img = (kt + 1) & 1;
-        asm volatile("" ::: "memory");
-        double a[2][4], b[2][4];
-        auto frag = [&](int set, int g) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[set][i] = as[g * 4 * LDT + i * 16];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[set][j] = bs[g * 4 * LDT + j * 16];
-        };
-        frag(0, 0);
-#pragma unroll
-        for (int kk = 0; kk < G; ++kk) {
-            if (kk + 1 < G) {
-                frag((kk + 1) & 1, kk + 1);
-                __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk & 1][i], b[kk & 1][j], acc[i][j], 0, 0, NEGA ? 1 : 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
-            if (FILL && kk < 4) {
-                if (kk == 0) issue(img, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
-                if (kk == 1) issue(img, std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
-                if (kk == 2) issue(img, std::integral_constant<int, 4>{}, std::integral_constant<int, 6>{});
-                if (kk == 3) issue(img, std::integral_constant<int, 6>{}, std::integral_constant<int, 8>{});
-                __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);
-            }
-        }
-        asm volatile("" ::: "memory");
-        if (FILL) {
-            bump();
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's rows of the next step; its LDS reads of this one
-            __builtin_amdgcn_s_barrier();                               // image kt & 1 is read, the other image is complete
-        }
-    };
-    int kt = 0;
-    for (; kt + 1 < nk; ++kt) step(kt, std::true_type{});
-    step(kt, std::false_type{});
-    if (PRIO) __builtin_amdgcn_s_setprio(PRIO - 1);
-    __builtin_amdgcn_s_barrier();                                       // the caller may reuse LDS
-}
-
-// The SWEEP's loop for a workgroup that has its compute unit to itself: gemm_tile_128_l<32> with the two images and the one barrier
-// per step of gemm_tile_128_ld.  A short exact launch (at most one working workgroup per compute unit) has no partner workgroup to
-// cover the load-to-barrier latency the single-image loop leaves standing in every step; here the DMA of step t + 1 fills image
+// gemm_tile_128_l<32> for a workgroup that has its compute unit to ITSELF, on two k-step images of LDS and with ONE barrier per
+// step: the sweep's short exact launches (at most one working workgroup per compute unit) and, plain (no ILV, TRI or REV; NEGA,
+// FG = 4), the task-graph factorisation's workers up to 112 block rows.  A lone workgroup has no partner to cover the
+// load-to-barrier latency the single-image loop leaves standing in every step; here the DMA of step t + 1 fills image
 // (t + 1) & 1 while step t is multiplied out of image t & 1.  The loads go out behind the step's first FG MFMA groups, 16 / FG
-// instructions at a time: FG = 4 as in gemm_tile_128_ld, but all 16 behind the first group of the narrowest tile, whose step is
-// so short that its loads must leave at once to have the rest of it to land (256 columns at N = 8192, 32 wide: 0.414 ms against
+// instructions at a time, and have the step's other groups to land (FG = 4: 4096 matrix clocks of the wide tile): FG = 4, but all
+// 16 behind the first group of the narrowest tile, whose step is so short that its loads must leave at once to have the rest of it to land (256 columns at N = 8192, 32 wide: 0.414 ms against
 // 0.444 / 0.428 with FG = 2 / 4; 64 wide: 0.531 with FG = 4 against 0.578 with 2 -- profiles/exact_launch_images_ab.md).  The
 // barrier that ends step t: every wave has finished reading image t & 1 (lgkmcnt) and its own rows of step t + 1 have landed (vmcnt).
 // ILV, TRI (the sequence I0 = 0, .., 0, 1, 2, 3; 3, 2, 1, 0, .. under REV), NEGA, AUX, REV, NJ and bcol as in gemm_tile_128_l: per
@@ -680,33 +506,13 @@ __device__ __forceinline__ void gemm_tile_128_l2(d4 (&acc)[4][NJ], const double*
     const int wm = w >> 1, wn = w & 1;
     const int nk = (k_hi - k_lo) / BK32;
     if (nk <= 0) return;
-    const char* Abase = reinterpret_cast<const char*>(A + (int64_t)(REV ? k_hi - BK32 : k_lo) * lda);
-    const char* Bbase = reinterpret_cast<const char*>(B + (int64_t)(REV ? k_hi - BK32 : k_lo) * ldb);
-    const int64_t stepA = (REV ? -1 : 1) * (int64_t)BK32 * lda * 8, stepB = (REV ? -1 : 1) * (int64_t)BK32 * ldb * 8;
-    const int voA = (int)(((int64_t)w * lda + 2 * lane) * 8), voB = (int)(((int64_t)w * ldb + 2 * lane) * 8);
-    const int soA = (int)(4 * lda * 8), soB = (int)(4 * ldb * 8);      // four rows on: the SGPR offset of load p is p * so
-    // rows w + 4 p, p = p0 .. p1 - 1, of the step at Abase / Bbase into image img
-    auto issue = [&](int img, int p0, int p1) {
-        double* As = smem + img * IMG;
-        double* Bs = As + BK32 * LDT;
-        __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Abase, 0, -1, 0x00020000);
-        __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bbase, 0, -1, 0x00020000);
-#pragma unroll
-        for (int p = p0; p < p1; ++p) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (gemm_lds_ptr)(As + (w + 4 * p) * LDT), 16, voA, p * soA, 0, AUX);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (gemm_lds_ptr)(Bs + (w + 4 * p) * LDT), 16, voB, p * soB, 0, AUX);
-        }
-    };
-    auto bump = [&]() {
-        Abase += stepA;
-        Bbase += stepB;
-    };
+    gemm_dma_operands<BK32, AUX, REV> src(A, lda, B, ldb, k_lo, k_hi, w, lane);
     const int fr = lane & 15, fk = lane >> 4;
     constexpr int IST = ILV ? 32 : 16;                                  // row-block stride of a wave's A fragments
     const int aoff = (ILV ? wm * 16 : wm * 64) + fr + fk * LDT;
     const int boff = BK32 * LDT + bcol + wn * (16 * NJ) + fr + fk * LDT;
-    issue(0, 0, G);
-    bump();
+    src.issue(smem, 0, G);
+    src.bump();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                                       // every wave's rows of the first step are in image 0
     if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
@@ -717,37 +523,17 @@ __device__ __forceinline__ void gemm_tile_128_l2(d4 (&acc)[4][NJ], const double*
         constexpr bool FILL = decltype(fillc)::value;
         const double* as = smem + (kt & 1) * IMG + aoff;
         const double* bs = smem + (kt & 1) * IMG + boff;
-        const int img = (kt + 1) & 1;
+        double* nxt = smem + ((kt + 1) & 1) * IMG;
         asm volatile("" ::: "memory");
-        double a[NSET][4], b[NSET][NJ];
-        auto frag = [&](int set, int g) {
-#pragma unroll
-            for (int i = I0; i < 4; ++i) a[set][i] = as[g * 4 * LDT + i * IST];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) b[set][j] = bs[g * 4 * LDT + j * 16];
-        };
-        frag(0, 0);
-#pragma unroll
-        for (int kk = 0; kk < G; ++kk) {
-            if (NSET == 2 && kk + 1 < G) {
-                frag((kk + 1) & 1, kk + 1);
-                __builtin_amdgcn_sched_group_barrier(0x100, 4 + NJ - I0, 0); // the LDS reads of group kk + 1 first,
-            }
-#pragma unroll
-            for (int i = I0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk % NSET][i], b[kk % NSET][j], acc[i][j], 0, 0, NEGA ? 1 : 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, NJ * (4 - I0), 0);   // then the MFMAs of group kk,
-            if (FILL && kk < FG) {                                           // then its piece of the next step's loads
-                issue(img, kk * (G / FG), (kk + 1) * (G / FG));
+        gemm_l_groups<G, NSET, I0, IST, NEGA>(acc, as, bs, [&](int kk) {
+            if (FILL && kk < FG) {                                           // group kk's piece of the next step's loads
+                src.issue(nxt, kk * (G / FG), (kk + 1) * (G / FG));
                 __builtin_amdgcn_sched_group_barrier(0x020, 2 * (G / FG), 0);
             }
-            if (NSET == 1 && kk + 1 < G) frag(0, kk + 1);
-        }
+        });
         asm volatile("" ::: "memory");
         if (FILL) {
-            bump();
+            src.bump();
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's rows of the next step; its LDS reads of this one
             __builtin_amdgcn_s_barrier();                               // image kt & 1 is read, the other image is complete
         }

@@ -172,8 +172,8 @@ __device__ __forceinline__ int tg_take(const TgArgs& a, TgTask& out, int lane, T
 
 // The workgroup's LDS (dynamic: the size is the launch's): 8 doubles of control words -- the task in hand (2), role / flags
 // (2), the held ticket (20 bytes) -- then the tile engine's buffer: ONE k-step image (72 KB; two workgroups per CU; the
-// diagonal kernel's panels fit inside) or TWO (144 KB: a workgroup alone on its CU runs the double-buffered k-loop,
-// gemm_tile_128_d).  File scope, so that the role bodies below can be separate (non-inlined) functions with their own register
+// diagonal kernel's panels fit inside) or TWO (144 KB: a workgroup alone on its CU runs the two-image k-loop,
+// gemm_tile_128_l2).  File scope, so that the role bodies below can be separate (non-inlined) functions with their own register
 // allocation and still address it with ds_* instructions: inlined into one kernel body the roles spilled 319 VGPRs.
 constexpr int TG_CTL_F64 = 32;        // control words: [0..1] the task in hand, [2..3] codes, [4..6] the held ticket, [8..15] the dispatcher's trace sums, [16..31] the argument block
 extern __shared__ __attribute__((aligned(16))) double tg_smem[];

@@ -2,8 +2,8 @@
 // INTO this binary: what is timed is the library's code).  Synthetic operands; every variant must give the same checksum.
 // Usage: sweep_ab.bin N cols reps tile_order[:super_m] [tile_order[:super_m] ...]        (build: scripts/probe/build.sh, -DGPX_SWEEP_PROBES)
 //   tile_order < 32: the library's schedules (include/gpx.h).  Probe-only codes: 19 + 32 c -- c = 1 .. 5 cache policy of the DMA loads
-//   (sc0, nt, sc1, sc0 sc1, sc0 nt), 6 every tile upwards, 7 one launch per generation of 512 workgroups; 1000 / 1001 / 1002: ONE
-//   workgroup per CU on gemm_tile_128_d / _ld / _w<2> (the factorisation's worker loops); 2000 / 2001: the wave-private loop with /
+//   (sc0, nt, sc1, sc0 sc1, sc0 nt), 6 every tile upwards, 7 one launch per generation of 512 workgroups; 1001 / 1002: ONE
+//   workgroup per CU on the factorisation's worker loop (gemm_tile_128_l2, plain) / gemm_tile_128_w<2>; 2000 / 2001: the wave-private loop with /
 //   without the diagonal-block skip, every tile upwards.  bash scripts/probe/pmc_fetch.sh adds the L2 -> fabric read bytes.
 //   Suffixes of a variant, in this order: "/S" the launch's short_map (sweep_map.h: 0 never, 1 the short form of map 3, 2 its strided form;
 //   default -1, by size as the library); "wW" the width of the default schedule's tiles, W = 128 (default), 64 or 32 candidates (narrow tiles:
@@ -39,7 +39,8 @@ __global__ void k_tri(double* U, int64_t Np) {
 }
 
 // ONE workgroup per compute unit (two k-step images of LDS): the loops of the task-graph factorisation's workers on the sweep's
-// tiles.  WHICH 0: gemm_tile_128_d (registers), 1: gemm_tile_128_ld (DMA).  Selected by tile_order 1000 + WHICH.
+// tiles.  WHICH 1: gemm_tile_128_l2 as syrk_tile calls it (shared images), 2: gemm_tile_128_w<2> (wave-private images).  Selected by
+// tile_order 1000 + WHICH.
 template <int WHICH>
 __global__ __launch_bounds__(GEMM_THREADS, 1) void k_lone(const double* __restrict__ U, int64_t Np, const double* __restrict__ Ks,
                                                           int NT, const double* __restrict__ avec, double* __restrict__ Qp,
@@ -54,8 +55,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void k_lone(const double* __restri
         const int64_t m0 = (int64_t)mt * TB, n0 = (int64_t)nt * TB;
         d4 acc[4][4];
         acc_zero(acc);
-        if (WHICH == 0) gemm_tile_128_d<1>(acc, U + m0, Np, Ks + (int64_t)nt * Np * TB, TB, 0, (mt + 1) * TB, dsm);
-        else if (WHICH == 1) gemm_tile_128_ld<1>(acc, U + m0, Np, Ks + (int64_t)nt * Np * TB, TB, 0, (mt + 1) * TB, dsm);
+        if (WHICH == 1) gemm_tile_128_l2<1, 2, false, false, false, 0, false, 4, 4>(acc, U + m0, Np, Ks + (int64_t)nt * Np * TB, TB, 0, (mt + 1) * TB, dsm);
         else gemm_tile_128_w<2, 1>(acc, U + m0, Np, Ks + (int64_t)nt * Np * TB, TB, 0, (mt + 1) * TB, dsm);
         sweep_epilogue<false>(acc, avec, m0, Qp + (int64_t)mt * ldp + n0, Pp + (int64_t)mt * ldp + n0, dsm);
     }
@@ -120,6 +120,7 @@ int main(int argc, char** argv) {
         if (const char* c = strchr(argv[v], 'i')) images = atoi(c + 1);
         if (const char* c = strchr(argv[v], 'f')) fg = atoi(c + 1);
         if (images != 1 && images != 2) { fprintf(stderr, "images must be 1 or 2\n"); return 1; }
+        if (to >= 1000 && to != 1001 && to != 1002 && to != 2000 && to != 2001) { fprintf(stderr, "no probe variant %d\n", to); return 1; }
         if ((to >= 1000 || (to & 3) != 3) && nR != nP) { fprintf(stderr, "row-prefix mode: the library's schedules on map 3 only\n"); return 1; }
         g_sweep_probe_fg = fg;
         const bool cold = argv[v][strlen(argv[v]) - 1] == 'c';
@@ -139,9 +140,7 @@ int main(int argc, char** argv) {
             } else if (to >= 1000) {
                 const size_t lb = (size_t)2 * GEMM_LDS_F64 * 8;
                 const unsigned nblk = sweep_grid<32>(3, sm, (int)(cols / TB), nP);
-                if (to == 1000) { CK(hipFuncSetAttribute((const void*)k_lone<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-                    hipLaunchKernelGGL(k_lone<0>, dim3(nblk), dim3(GEMM_THREADS), lb, 0, U, Np, Ks, (int)(cols / TB), a, Qp, Pp, cols, sm); }
-                else if (to == 1001) { CK(hipFuncSetAttribute((const void*)k_lone<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
+                if (to == 1001) { CK(hipFuncSetAttribute((const void*)k_lone<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
                     hipLaunchKernelGGL(k_lone<1>, dim3(nblk), dim3(GEMM_THREADS), lb, 0, U, Np, Ks, (int)(cols / TB), a, Qp, Pp, cols, sm); }
                 else { CK(hipFuncSetAttribute((const void*)k_lone<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
                     hipLaunchKernelGGL(k_lone<2>, dim3(nblk), dim3(GEMM_THREADS), lb, 0, U, Np, Ks, (int)(cols / TB), a, Qp, Pp, cols, sm); }

@@ -5,7 +5,9 @@ bit where it was, and the tolerance tests would not notice an equally accurate b
     inverse   get_matrix('L'), get_matrix('T'), get_vectors() for N = 300 (3 block rows), 1000, 2500 (20, not a power of two),
               5000 (40: a short trailing group), 8192 (64: levels below 32 on 64-tiles, level 32 on 128-tiles), each with
               trtri_left 0 and 1 and, from 8 block rows on, with the leading part riding behind the factorisation
-              (trtri_ahead 1; the number of times it did is part of the record); refine_inverse once at N = 2500
+              (trtri_ahead 1; the number of times it did is part of the record); refine_inverse once at N = 2500; N = 1000 with
+              chol_tg_db 0 and 1 (the default, -1, means the two-image workers at every size here: nothing else runs their
+              one-image k-loop)
     sweep     acq, mu, s2 of M = 4096 uniform candidates and the top-10 pairs for N = 1000 (nothing walks downwards) and
               N = 4224 (33 block rows: the downward rule is live), one k-loop schedule per kernel template and -1 (by size)
     rff       the sweep of one set of four posterior draws (n = 100 features: k_rff_mfma5)
@@ -98,6 +100,8 @@ def cases():
         if N >= AHEAD_MIN_N:
             out.append(('inverse N=%d ahead' % N, lambda N=N: _inverse(N, trtri_ahead=1)))
     out.append(('inverse N=2500 refined', lambda: _inverse(2500, refine_inverse=1)))
+    for db in (0, 1):                      # the factorisation's workers forced onto the one-image / the two-image k-loop
+        out.append(('inverse N=1000 db%d' % db, lambda db=db: _inverse(1000, trtri_ahead=0, chol_tg_db=db)))
     for N in SWEEP_N:
         out.append(('sweep N=%d' % N, lambda N=N: _sweep(N)))
     out.append(('rff sweep', _rff))

@@ -1,7 +1,8 @@
 """The kernels give the bits they gave before they were folded together: tests/golden/kernel_digests.json holds, per case of
 tests/golden/make_kernel_digests.py, the SHA-256 of every output (the factor, its inverse and the solve vectors for five sizes
 under both association orders of the inverse, with and without its leading part riding behind the factorisation, once
-refined; the sweep's values, moments and top-k under every k-loop schedule; one RFF sweep) as the library of the recorded
+refined, and at N = 1000 with the factorisation's workers forced onto their one-image and their two-image k-loop (chol_tg_db
+0 / 1: the default takes the two-image one at every size here); the sweep's values, moments and top-k under every k-loop schedule; one RFF sweep) as the library of the recorded
 commit produced them.  The same cases run on the current library and must reproduce every digest."""
 import json
 import os
