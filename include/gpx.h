@@ -1,9 +1,6 @@
-/*
- * gpx.h -- C-ABI of libgpx.so: the MI355X (gfx950) GP-posterior + acquisition engine.
- *
+/* gpx.h -- C-ABI of libgpx.so: the MI355X (gfx950) GP-posterior + acquisition engine.
  * The reference (mwhoffman/pybo) has NO native boundary: its GP arithmetic is a set of Python method calls on a duck-typed `model` object (the un-vendored
  * `reggie` package).  Each entry point below therefore cites the *call site in pybo* whose work it performs; pybo_amd/ binds these by ctypes.
- *
  * Conventions
  *   - every function returns an int status: 0 = GPX_OK, negative = error class; gpx_last_error(h) returns a NUL-terminated description (handle-local; NULL
  *     handle -> thread-local string of the last failed gpx_create).
@@ -11,9 +8,9 @@
  *   - `_dev` variants take DEVICE pointers (e.g. torch.Tensor.data_ptr()) valid on the handle's device; they enqueue on the handle's stream and are synchronous
  *     on return only where an output lands in a host buffer (top-k, status).
  *   - a handle is not re-entrant; distinct handles may be driven from distinct threads.
- *   - a handle owns up to four HIP streams (its own or the caller's + three side streams created on first need); a process
- *     that keeps several handles alive should export GPU_MAX_HW_QUEUES=8 BEFORE its first HIP call, or work meant to overlap
- *     inside a handle may share a hardware queue and serialise (+2.3 ms per warm iteration at N = 8192).  Results never depend on it.
+ *   - a handle owns up to four HIP streams (its own or the caller's + three side streams created on first need); a process that keeps several handles alive
+ *     should export GPU_MAX_HW_QUEUES=8 BEFORE its first HIP call, or work meant to overlap inside a handle may share a hardware queue and serialise
+ *     (+2.3 ms per warm iteration at N = 8192).  Results never depend on it.
  *   - no C++ exception crosses this boundary.
  */
 #ifndef GPX_H
@@ -24,8 +21,7 @@ extern "C" {
 #endif
 typedef struct gpx_handle gpx_handle;
 enum gpx_status {
-    GPX_OK = 0,
-    GPX_EARG = -1,    /* bad argument */
+    GPX_OK = 0, GPX_EARG = -1, /* bad argument */
     GPX_ENOTPD = -2,  /* K + sn2*I not positive definite; see gpx_fail_pivot */
     GPX_EHIP = -3,    /* HIP runtime error */
     GPX_EOOM = -4,    /* device allocation failed */
@@ -39,8 +35,7 @@ enum gpx_kernel {
     GPX_KERN_MATERN32 = 2, /* rho * (1 + sqrt3 r) exp(-sqrt3 r) */
     GPX_KERN_MATERN12 = 3  /* rho * exp(-r) */
 };
-/* acquisition functions evaluated by the sweep */
-enum gpx_acq {
+enum gpx_acq {        /* acquisition functions evaluated by the sweep */
     GPX_ACQ_EI = 0,   /* model.get_improvement(target, X)  [pybo/policies/simple.py:25]  params = {target} */
     GPX_ACQ_PI = 1,   /* model.get_tail(target, X)         [pybo/policies/simple.py:39]  params = {target} */
     GPX_ACQ_UCB = 2,  /* mu + sqrt(beta*s2)                [pybo/policies/simple.py:62-73] params = {beta} */
@@ -167,6 +162,11 @@ int gpx_sweep_update_dev(gpx_handle *h, int acq_id, const double *params, int np
  * EI / PI / UCB (GPX_ACQ_MEAN: GPX_EARG).  1 <= nb <= min(64, M).  sel_val, sel_idx (nb) required; sel_s2 (nb) and s2all (M: the variances
  * that scored the LAST pick) optional, all host.  Model, cache, queued corrections and a pending announcement are untouched. GPX_ESTATE without a cache. */
 int gpx_sweep_batch(gpx_handle *h, int acq_id, const double *params, int nparams, int64_t nb, double *sel_val, int64_t *sel_idx, double *sel_s2, double *s2all);
+/* The same with the pending outcomes INTEGRATED OUT over S joint fantasies (Snoek et al. 2012).  EI / PI only (else GPX_EARG): value = mean_s acq(mu +
+ * sum_{l<j} v_l eps[s][l], s2, t_s), eps (S, ld_eps >= max(nb - 1, 1)) finite standard normals, 1 <= S <= 64.  incumbent 0: t_s = params[0]; 1: t_s <- max(t_s,
+ * fantasy s's mean at each pick after its observation).  Rounds < npend < nb: forced to the distinct rows pend_idx.  S = 1, eps = 0: gpx_sweep_batch's bits. */
+int gpx_sweep_batch_fantasy(gpx_handle *h, int acq_id, const double *params, int nparams, int64_t nb, const double *eps, int64_t S, int64_t ld_eps,
+                            int incumbent, const int64_t *pend_idx, int64_t npend, double *sel_val, int64_t *sel_idx, double *sel_s2, double *s2all);
 /* Knowledge gradient (GPX_ACQ_KG) and its gradient at M <= 4096 points, host buffers: A (m, d) the support set as for the sweep, f (M,), g (M, d) -- the
  * `f(x, grad=True)` of the L-BFGS refinement.  f agrees with the sweep's value to rounding.  One host synchronisation; fit, sweep cache and queue untouched. */
 int gpx_kg_grad(gpx_handle *h, const double *A, int64_t m, const double *Xc, int64_t M, double *f, double *g);
@@ -290,7 +290,7 @@ int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, 
  * task-graph factorisation gave up and re-ran on the stream schedule [16] the shader clock in MHz the sweep_trmm launches sustained (their workgroups'
  * s_memtime over s_memrealtime ticks) [17] the same for the Thompson sweep kernel [18] inversions whose leading part ran behind the factorisation
  * ("trtri_ahead": for those [2] holds only what was left after the factor was done) [19] bound pass of selection-only sweeps [20] batch selection
- * (gpx_[ensemble_]sweep_batch) [21] joint posterior (gpx_predict_cov / gpx_sample_joint: all between their copies).  Synchronises; returns slots written. */
+ * (gpx_[ensemble_]sweep_batch*) [21] joint posterior (gpx_predict_cov / gpx_sample_joint: all between their copies).  Synchronises; returns slots written. */
 int gpx_timers(gpx_handle *h, double *out, int n, int reset);
 int gpx_diagnostics(void);     /* 1 when the library was built with -DGPX_DIAGNOSTICS (the diagnostic options above are accepted), else 0 */
 int gpx_sync(gpx_handle *h);

@@ -82,6 +82,7 @@ SYMBOLS = {
     'gpx_sweep_update': (C.c_int, [_P, C.c_int, _P, C.c_int, _i64, _P, _P, _P, _P, _P]),
     'gpx_sweep_update_dev': (C.c_int, [_P, C.c_int, _P, C.c_int, _i64, _P, _P, _P, _P, _P]),
     'gpx_sweep_batch': (C.c_int, [_P, C.c_int, _P, C.c_int, _i64, _P, _P, _P, _P]),
+    'gpx_sweep_batch_fantasy': (C.c_int, [_P, C.c_int, _P, C.c_int, _i64, _P, _i64, _i64, C.c_int, _P, _i64, _P, _P, _P, _P]),
     'gpx_sweep_cache_size': (_i64, [_P]),
     'gpx_kg_grad': (C.c_int, [_P, _P, _i64, _P, _i64, _P, _P]),
     'gpx_rff_sweep': (C.c_int, [_P, _P, _P, _P, _i64, _i64, _i64, _dbl, _P, _i64, _i64, _P, _P, _P]),
@@ -718,6 +719,26 @@ class Engine(object):
             out['s2_all'] = np.empty(self.sweep_cache_size())
         self._check(self._lib.gpx_sweep_batch(self._h, aid, _ptr(params), nparams, int(nb), _ptr(out['sel_val']), _ptr(out['sel_idx']),
                                               _ptr(out['sel_s2']), _ptr(out.get('s2_all'))))
+        return out
+
+    def sweep_batch_fantasy(self, kind, param, nb, eps, incumbent=1, pending=None, want_s2_all=False):
+        """nb greedy picks on the live sweep cache with the pending outcomes integrated out over the S = len(eps) joint fantasies
+        (gpx_sweep_batch_fantasy): `eps` (S, >= nb - 1) standard normals, row s the innovations of fantasy s in pick order;
+        `incumbent` 1: every fantasy's EI / PI target follows its own fantasised observations, 0: it stays at `param`; `pending`:
+        cache rows already being evaluated, which the leading rounds are forced to.  Returns dict(sel_val, sel_idx, sel_s2[, s2_all])."""
+        aid = acq_id(kind)
+        params, nparams = _acq_params(param)
+        eps = _f64(eps)
+        if eps.ndim != 2:
+            raise ValueError('eps must be a (S, >= nb - 1) array')
+        pend = None if pending is None else np.ascontiguousarray(pending, dtype=np.int64).reshape(-1)
+        n = max(int(nb), 0)
+        out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty(n))
+        if want_s2_all:
+            out['s2_all'] = np.empty(self.sweep_cache_size())
+        self._check(self._lib.gpx_sweep_batch_fantasy(self._h, aid, _ptr(params), nparams, int(nb), _ptr(eps), eps.shape[0], eps.shape[1],
+                                                      int(incumbent), _ptr(pend), 0 if pend is None else len(pend), _ptr(out['sel_val']),
+                                                      _ptr(out['sel_idx']), _ptr(out['sel_s2']), _ptr(out.get('s2_all'))))
         return out
 
     def sweep_dev(self, acq, param, dXc_ptr, M, k, d_acq=None, d_mu=None, d_s2=None):

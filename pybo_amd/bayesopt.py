@@ -340,11 +340,11 @@ def _bo_step(model, trace, objective, bounds, policy, solver, recommender):
     return x, y, xbest
 
 
-def _bo_batch_step(model, trace, objective, bounds, policy, recommender, nb, xgrid, rng):
+def _bo_batch_step(model, trace, objective, bounds, policy, recommender, nb, xgrid, rng, fantasies=0):
     """One batch iteration: propose nb grid points (pybo_amd/batch.py), evaluate them in order, absorb them in ONE add_data,
     recommend once.  `xbest` is appended once per evaluated point, so the trace keeps counting evaluations."""
     from .batch import _propose
-    Xq, _, _ = _propose(model, bounds, trace.x, nb, policy, xgrid, 10000, rng)
+    Xq, _, _ = _propose(model, bounds, trace.x, nb, policy, xgrid, 10000, rng, fantasies)
     Yq = [objective(x) for x in Xq]
     model.add_data(Xq, Yq)
     xbest = recommender(model, bounds, trace.x)     # (trace.x does not contain the batch yet, as in _bo_step)
@@ -357,7 +357,7 @@ def _bo_batch_step(model, trace, objective, bounds, policy, recommender, nb, xgr
 
 def solve_bayesopt(objective, bounds, model=None, niter=100, policy='ei', solver='lbfgs',
                    recommender='latent', ninit=None, verbose=False, log=None, rng=None, spmd=None, nbatch=1,
-                   batch_grid=None):
+                   batch_grid=None, batch_fantasies=0):
     """
     Maximise `objective` over the box `bounds` ((d,2) array-like) by Bayesian optimisation.
 
@@ -379,7 +379,9 @@ def solve_bayesopt(objective, bounds, model=None, niter=100, policy='ei', solver
     earlier ones at their posterior mean; Thompson: independent draws), evaluates the objective on them in order, absorbs them
     in one `model.add_data(Xq, Yq)` and recommends once.  `niter` still counts evaluations and a checkpoint still resumes.
     The points are candidates of `batch_grid` ((M, d) array or DeviceGrid; default: a fresh `init_uniform(bounds, 10000, rng)`
-    per iteration) -- the `solver` plays no part.  Not together with `spmd`.
+    per iteration) -- the `solver` plays no part.  Not together with `spmd`.  `batch_fantasies=S > 0`: the batches integrate over
+    their own pending outcomes with S joint fantasies instead of believing the means (`propose_batch(..., fantasies=S)`: EI / PI on
+    a single model).
     """
     nbatch = int(nbatch)
     if nbatch < 1:
@@ -395,13 +397,13 @@ def solve_bayesopt(objective, bounds, model=None, niter=100, policy='ei', solver
         _SPMD.update(on=True, group=group)
     try:
         return _solve_bayesopt(objective, bounds, model, niter, policy, solver, recommender, ninit, verbose, log, rng,
-                               spmd if on else None, nbatch, batch_grid)
+                               spmd if on else None, nbatch, batch_grid, int(batch_fantasies))
     finally:
         _SPMD.update(saved)
 
 
 def _solve_bayesopt(objective, bounds, model, niter, policy, solver, recommender, ninit, verbose, log, rng, spmd, nbatch=1,
-                    batch_grid=None):
+                    batch_grid=None, batch_fantasies=0):
     rng = rstate(rng)
     bounds = np.array(bounds, dtype=float, ndmin=2)
     policy = get_component(policy, policies, rng)
@@ -429,7 +431,7 @@ def _solve_bayesopt(objective, bounds, model, niter, policy, solver, recommender
     while nbatch > 1 and len(trace.xbest) < niter:
         i = len(trace.xbest)
         Xq, Yq, xbest = _bo_batch_step(model, trace, objective, bounds, policy, recommender, min(nbatch, niter - i), batch_grid,
-                                       rng)
+                                       rng, batch_fantasies)
         safe_dump(model, trace, filename=log)
         if verbose:
             for k, (x, y) in enumerate(zip(Xq, Yq)):

@@ -1,6 +1,6 @@
 // acq_core.h -- the per-candidate arithmetic every acquisition kernel shares, each piece defined ONCE: the sums and moments of a
 // candidate, the variance floor, the ensemble's fold and finish, the constraint fold, the total order of the top-k and of the batch picks, the batch
-// fold and a pick's four scalars.  The library promises bit-for-bit agreement between many of its paths (a cache seeded by any
+// fold, a pick's four scalars and the fantasised picks' mean step, average and incumbent.  The library promises bit-for-bit agreement between many of its paths (a cache seeded by any
 // acquisition, pruned against exhaustive sweeps, ensemble against its members, batch against single picks); those promises hold
 // because the paths call the functions below, not because their statements were kept in step.
 // Plain C++ (no HIP type, no thread index): the kernels and the host-only program tests/c/acq_core_check.cpp include this one
@@ -149,6 +149,39 @@ GPX_ACQ_FN void pick_scalars(double s2, double sn2, double* scal) {
     scal[1] = 1.0 / dd;
     scal[2] = 0.0;
     scal[3] = d2;
+}
+
+// ---- fantasised batch picks ---------------------------------------------------------------------------------------------------
+// Pending observations integrated out over S joint fantasies (gpx_sweep_batch_fantasy): row l of V turns the standard-normal
+// innovation eps[s][l] of pick l into a shift of every candidate's mean.  One step of a fantasy's mean, the product rounded before
+// it is added; the walk starts at bias + p (moments_of_sums' mu) and takes the rows in pick order.  A zero eps leaves mu's bits.
+GPX_ACQ_FN double fant_mean_step(double m, double v, double e) {
+    GPX_NO_CONTRACT;
+    const double prod = v * e;
+    return m + prod;
+}
+
+// the fantasy average of S values: ens_fold's mode 0 in fantasy order (`first` starts the sum at the term), then ens_mean's one
+// division (S = 1: the value's own bits)
+GPX_ACQ_FN void fant_fold(bool first, double val, double& acc) {
+    double unused = 0.0;
+    ens_fold(0, first, val, 0.0, acc, unused);
+}
+
+GPX_ACQ_FN double fant_average(double acc, int S) { return ens_mean(acc, (double)S); }
+
+// A fantasy's incumbent after pick j at row r: its posterior mean at the pick right after its own fantasised observation there,
+//     u = (bias + p_r) + sum_{i<j} V[i][r] eps[i] + (s2 / d) eps[j]          t <- max(t, u)
+// mu = bias + p_r; cross[i * cs] = V[i][r] (cs = 1: the gathered cross terms, cs = M: the rows of V at column r); eps: the fantasy's
+// innovations with stride es; s2, d: the pick's conditioned variance and pick_scalars' d.  A NaN u leaves t.
+GPX_ACQ_FN double fant_incumbent(double t, double mu, int j, const double* cross, int64_t cs, const double* eps, int64_t es, double s2,
+                                 double d) {
+    GPX_NO_CONTRACT;
+    double u = mu;
+    for (int i = 0; i < j; ++i) u = fant_mean_step(u, cross[(int64_t)i * cs], eps[(int64_t)i * es]);
+    const double gain = s2 / d;
+    u = fant_mean_step(u, gain, eps[(int64_t)j * es]);
+    return fmax(t, u);
 }
 
 }  // namespace gpx

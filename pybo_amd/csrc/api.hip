@@ -253,7 +253,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // 680: GPX_ACQ_KG = 32 (knowledge gradient over a support set: gpx_sweep*; params = the support coordinates) and gpx_kg_grad.
 // 690: gpx_constrained_sweep[_dev] (EI / PI times the probability of feasibility of up to 16 constraint models), gpx_constrained_prune_report.
 // 700: gpx_ehvi_sweep[_dev], gpx_ehvi_fold_dev (expected hypervolume improvement of two objectives over a Pareto front).
-extern "C" int gpx_version(void) { return 700; }
+// 710: gpx_sweep_batch_fantasy (batch picks with the pending outcomes integrated out over joint fantasies; time in timers slot 20).
+extern "C" int gpx_version(void) { return 710; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -362,7 +363,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dcon, h->dehvi, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw, h->dpath};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dcon, h->dehvi, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw, h->dfant, h->dpath};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -1688,6 +1689,83 @@ extern "C" int gpx_sweep_batch(gpx_handle* h, int acq_id, const double* params, 
                 launch_batch_pick(s, j, M, (int)d, b.partv, b.parti, h->dcZ, h->dinvell, b.qp, b.V, h->rho, h->sn2, b.x, b.xs,
                                   b.scal, b.cross, b.sel_val, b.sel_idx, b.sel_s2, b.taken);
                 if (j == (int)nb - 1) break;
+                batch_condition(h, s, b, b.x, h->dcZ, M, j);
+            }
+            HIPCHK(h, hipGetLastError());
+        }
+        HIPCHK(h, hipMemcpyAsync(sel_val, b.sel_val, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(sel_idx, b.sel_idx, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        if (sel_s2) HIPCHK(h, hipMemcpyAsync(sel_s2, b.sel_s2, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        if (s2_all) HIPCHK(h, hipMemcpyAsync(s2_all, b.s2, (size_t)M * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        return GPX_OK;
+    });
+}
+
+// gpx_sweep_batch with the pending outcomes integrated out over S joint fantasies (kernels_batch.hip: k_fant_score, k_fant_pick).  The
+// launch chain, the conditioning and the believer's scratch (h->dbsel) are gpx_sweep_batch's; the innovations (re-packed pick-major,
+// zero-padded to the kernel's chunk), the incumbents and the forced rows go up once into h->dfant (fant_ws) before the first round.
+extern "C" int gpx_sweep_batch_fantasy(gpx_handle* h, int acq_id, const double* params, int nparams, int64_t nb, const double* eps,
+                                       int64_t S, int64_t ld_eps, int incumbent, const int64_t* pend_idx, int64_t npend,
+                                       double* sel_val, int64_t* sel_idx, double* sel_s2, double* s2_all) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        int rc;
+        const char* const what = "sweep_batch_fantasy";
+        if ((rc = check_batch(h, what, acq_id, params, nparams, nb, sel_val, sel_idx))) return rc;
+        if (acq_id != GPX_ACQ_EI && acq_id != GPX_ACQ_PI)
+            return fail(h, GPX_EARG, "sweep_batch_fantasy: EI or PI (UCB is linear in the mean: its fantasy average is gpx_sweep_batch's value)");
+        if (S < 1 || S > FANT_MAX_S) return fail(h, GPX_EARG, "sweep_batch_fantasy: S must be in [1, 64]");
+        if (incumbent != 0 && incumbent != 1) return fail(h, GPX_EARG, "sweep_batch_fantasy: incumbent must be 0 or 1");
+        if (!eps || ld_eps < std::max<int64_t>(nb - 1, 1)) return fail(h, GPX_EARG, "sweep_batch_fantasy: eps is (S, ld_eps >= max(nb - 1, 1))");
+        if (npend < 0 || npend >= nb || (npend > 0 && !pend_idx)) return fail(h, GPX_EARG, "sweep_batch_fantasy: npend must be in [0, nb)");
+        if (!h->fitted || !h->cache_valid) return fail(h, GPX_ESTATE, "sweep_batch_fantasy: no live sweep cache (sweep with option sweep_cache = 1 first)");
+        const int64_t M = h->cache_M, d = h->d;
+        if (nb > M) return fail(h, GPX_EARG, "sweep_batch_fantasy: nb exceeds the number of cached candidates");
+        for (int64_t i = 0; i < npend; ++i) {
+            bool ok = pend_idx[i] >= 0 && pend_idx[i] < M;
+            for (int64_t k = 0; ok && k < i; ++k) ok = pend_idx[k] != pend_idx[i];
+            if (!ok) return fail(h, GPX_EARG, "sweep_batch_fantasy: pend_idx must hold distinct rows of the cache");
+        }
+        const FantWs lay = fant_ws(WsCarver(nullptr), nb, S);
+        const int64_t Sp = lay.Sp, words = lay.bytes / 8;
+        h->fant_host.assign((size_t)lay.bytes, 0);
+        {
+            const FantWs hw = fant_ws(WsCarver(h->fant_host.data()), nb, S);
+            for (int64_t s = 0; s < S; ++s)
+                for (int64_t l = 0; l + 1 < nb; ++l) {
+                    const double e = eps[s * ld_eps + l];
+                    if (!std::isfinite(e)) return fail(h, GPX_EARG, "sweep_batch_fantasy: eps must be finite");
+                    hw.eps[l * Sp + s] = e;
+                }
+            for (int64_t s = 0; s < Sp; ++s) hw.t[s] = params[0];
+            for (int64_t i = 0; i < npend; ++i) hw.pend[i] = pend_idx[i];
+        }
+        HIPCHK(h, hipSetDevice(h->device));
+        if ((rc = ensure_inverse(h))) return rc;
+        if ((rc = flush_pending(h))) return rc;                  // queued appends belong in the sums the picks are scored with
+        BatchBuf b;
+        if ((rc = batch_layout(h, M, nb, 0, b))) return rc;
+        if ((rc = ensure(h, h->dfant, h->cap_fant, words))) return rc;
+        const FantWs f = fant_ws(WsCarver(h->dfant), nb, S);
+        hipStream_t s = h->stream;
+        {
+            Span sp(h, T_COPY);
+            HIPCHK(h, hipMemcpyAsync(f.eps, h->fant_host.data(), (size_t)lay.bytes, hipMemcpyHostToDevice, s));
+        }
+        {
+            Span sp(h, T_BATCH);
+            HIPCHK(h, hipMemsetAsync(b.taken, 0, (size_t)b.ntaken * 8, s));
+            HIPCHK(h, hipMemsetAsync(b.flag, 0, sizeof(int), s));
+            for (int j = 0; j < (int)nb; ++j) {
+                const bool last = j == (int)nb - 1;
+                double* s2_out = (s2_all && last) ? b.s2 : nullptr;    // the variances that score the LAST pick
+                launch_fant_score(s, j - 1, M, h->dcq, h->dcp, b.qp, b.V, b.cross, b.scal, b.taken, h->rho, h->bias, acq_id, f.eps, f.t,
+                                  (int)S, (int)Sp, f.pend, (int)npend, s2_out, b.partv, b.parti);
+                launch_fant_pick(s, j, M, (int)d, b.partv, b.parti, h->dcZ, h->dinvell, b.qp, h->dcp, b.V, h->rho, h->sn2, h->bias, f.eps,
+                                 f.t, (int)S, (int)Sp, (incumbent && !last) ? 1 : 0, b.x, b.xs, b.scal, b.cross, b.sel_val, b.sel_idx,
+                                 b.sel_s2, b.taken);
+                if (last) break;
                 batch_condition(h, s, b, b.x, h->dcZ, M, j);
             }
             HIPCHK(h, hipGetLastError());

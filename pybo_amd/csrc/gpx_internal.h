@@ -242,6 +242,9 @@ struct gpx_handle {
     double* dbsel = nullptr;
     int64_t cap_bsel = 0;
     std::vector<gpx::EnsBatchMember> bsel_desc;   // host source of the lead's descriptor table (gpx_ensemble_sweep_batch): outlives its copy
+    double* dfant = nullptr;                      // gpx_sweep_batch_fantasy: innovations, incumbents, forced rows (fant_ws)
+    int64_t cap_fant = 0;
+    std::vector<unsigned char> fant_host;         // host source of that upload: outlives its copy
 
     // joint posterior (gpx_predict_cov / gpx_sample_joint): scratch of its own (joint_ws); the cross-Gram of the points goes
     // through dKs like a sweep's
@@ -434,6 +437,17 @@ void launch_batch_pick(hipStream_t s, int j, int64_t M, int d, const double* par
                        const double* invell, const double* qp, const double* V, double rho, double sn2, double* x,
                        double* xs, double* scal, double* cross, double* sel_val, int64_t* sel_idx, double* sel_s2,
                        unsigned char* taken);
+// the fantasised forms (gpx_sweep_batch_fantasy; EI / PI only): the value is the mean over S fantasies of the acquisition at the mean
+// shifted by the rows of V times eps (pick-major, pitch Sp) against the incumbents tinc; pend[0 .. npend): the forced rows of the leading
+// rounds; update: move the incumbents after pick j (reads row j of eps)
+void launch_fant_score(hipStream_t s, int j, int64_t M, const double* cq, const double* cp, double* qp, double* V,
+                       const double* cross, const double* scal, const unsigned char* taken, double rho, double bias, int acq_id,
+                       const double* eps, const double* tinc, int S, int Sp, const int64_t* pend, int npend, double* s2_out,
+                       double* partv, int64_t* parti);
+void launch_fant_pick(hipStream_t s, int j, int64_t M, int d, const double* partv, const int64_t* parti, const double* Z,
+                      const double* invell, const double* qp, const double* cp, const double* V, double rho, double sn2,
+                      double bias, const double* eps, double* tinc, int S, int Sp, int update, double* x, double* xs, double* scal,
+                      double* cross, double* sel_val, int64_t* sel_idx, double* sel_s2, unsigned char* taken);
 // the ensemble forms (gpx_ensemble_sweep_batch): ONE scoring pass over the candidates with all n members inside it (each member's
 // fold as above, its value or moments summed in member order, one division), the pick that leaves every member's next round on the
 // device (sel_s2: (n, nb) member-major), and the bitwise compare of two candidate sets (*flag <- 1 where a 64-bit word differs)

@@ -178,6 +178,17 @@ inline BatchBuf batch_ws(WsCarver c, int64_t xpad, int64_t ld, int64_t M, int64_
     return b;
 }
 
+// Fantasised batch proposals (h->dfant; the per-candidate state is the believer's BatchBuf, so nothing here grows with M): the
+// innovations eps[l][s] pick-major over max(nb - 1, 1) rows of pitch Sp = S rounded up to the scoring kernel's chunk of FANT_CHUNK
+// fantasies (padding: zeros), so that a round's rows are one contiguous copy into LDS and a chunk one aligned run; the incumbents
+// t[Sp]; the forced rows of the leading rounds.
+constexpr int FANT_CHUNK = 16, FANT_MAX_S = 64;
+struct FantWs { double *eps, *t; int64_t* pend; int64_t Sp, bytes; };
+inline FantWs fant_ws(WsCarver c, int64_t nb, int64_t S) {
+    const int64_t Sp = (S + FANT_CHUNK - 1) / FANT_CHUNK * FANT_CHUNK, rows = nb > 1 ? nb - 1 : 1;
+    return {c.take<double>(rows * Sp, "eps"), c.take<double>(Sp, "t"), c.take<int64_t>(64, "pend_idx"), Sp, c.bytes()};
+}
+
 // predict with gradients (h->dgrad): GB points, per point k*, its gradient panel, V, w over Np rows, `per` = 2 + 2 d outputs, and the
 // register-blocked matvec's nseg segment partials
 struct GradWs { double *X, *ks, *g, *V, *w, *out, *part; int64_t bytes; };

@@ -608,11 +608,19 @@ class GP(object):
                 eng.set_option('sweep_cache', 0)      # other sweeps of this engine must not overwrite the cache
         return eng
 
-    def acq_batch(self, kind, param, xgrid, nb):
+    def acq_batch(self, kind, param, xgrid, nb, eps=None, incumbent=1, pending=None):
         """nb grid points to evaluate in parallel: greedy EI / PI / UCB picks, each conditioned on the earlier ones at their
         posterior mean (gpx_sweep_batch).  Returns dict(sel_val, sel_idx, sel_s2).  The cache is handled by `_cache_grid`; the
-        picks then cost one O(N M) pass each and leave model and cache as they were."""
-        return self._cache_grid(kind, param, xgrid).sweep_batch(kind, param, int(nb))
+        picks then cost one O(N M) pass each and leave model and cache as they were.
+        `eps` (S, >= nb - 1) standard normals: the pending outcomes are integrated out over S joint fantasies instead (EI / PI;
+        gpx_sweep_batch_fantasy), `incumbent` 1 / 0: every fantasy's target follows its own observations / stays at `param`,
+        `pending`: grid rows already being evaluated, which the leading picks are forced to."""
+        eng = self._cache_grid(kind, param, xgrid)
+        if eps is None:
+            if pending is not None:
+                raise ValueError('pending points need fantasies (eps)')
+            return eng.sweep_batch(kind, param, int(nb))
+        return eng.sweep_batch_fantasy(kind, param, int(nb), eps, incumbent=incumbent, pending=pending)
 
     def topk_engine(self):
         """The device handle whose HBM holds the (value, index) pairs of the last `acq_topk`."""

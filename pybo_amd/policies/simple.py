@@ -14,7 +14,7 @@ New: when the model is the device-backed `pybo_amd.models.GP`, the returned inde
 `index.topk(xgrid, k)` -- the whole-grid evaluation + top-k done on the GPU in one call -- which
 `pybo_amd.solvers.solve_lbfgs` uses instead of `argsort(f(xgrid))` (pybo/solvers/lbfgs.py:50-51).
 Any other model (e.g. a test stub) gets plain closures, exactly as in the reference.  Every EI / PI / UCB index also
-carries `index.acq = (kind, param)` and, for models with `acq_batch`, `index.batch(xgrid, nb)` (pybo_amd/batch.py).
+carries `index.acq = (kind, param)` and, for models with `acq_batch`, `index.batch(xgrid, nb, **kw)` (pybo_amd/batch.py).
 `MES` (max-value entropy search), `KG` (knowledge gradient over a support set), `CEI` (constrained expected improvement on a
 `models.Constrained`) and `EHVI` (expected hypervolume improvement on a `models.MultiObjective`) are this build's own: the reference
 has none of them.
@@ -28,7 +28,7 @@ def _attach_topk(index, model, kind, param):
     index.acq = (kind, param)              # the frozen target / beta: what a batch proposal scores every round with
     batch = getattr(model, 'acq_batch', None)
     if batch is not None:                  # device models: nb greedy picks on the swept grid (pybo_amd.propose_batch)
-        index.batch = lambda xgrid, nb: batch(kind, param, xgrid, nb)
+        index.batch = lambda xgrid, nb, **kw: batch(kind, param, xgrid, nb, **kw)
     fast = getattr(model, 'acq_topk', None)
     if fast is not None:
         index.topk = lambda xgrid, k: fast(kind, param, xgrid, k)
