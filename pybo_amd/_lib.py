@@ -708,15 +708,20 @@ class Engine(object):
     def sweep_cache_size(self):
         return int(self._lib.gpx_sweep_cache_size(self._h))
 
+    def _batch_out(self, nb, want_s2_all):
+        """The result of a single-model batch entry, for the library to fill: dict(sel_val, sel_idx, sel_s2[, s2_all])."""
+        n = max(int(nb), 0)
+        out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty(n))
+        if want_s2_all:
+            out['s2_all'] = np.empty(self.sweep_cache_size())
+        return out
+
     def sweep_batch(self, kind, param, nb, want_s2_all=False):
         """nb greedy picks on the live sweep cache (gpx_sweep_batch), each conditioned on the earlier ones at their posterior
         mean.  Returns dict(sel_val, sel_idx, sel_s2[, s2_all]); model, cache and a pending announcement are untouched."""
         aid = acq_id(kind)
         params, nparams = _acq_params(param)
-        n = max(int(nb), 0)
-        out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty(n))
-        if want_s2_all:
-            out['s2_all'] = np.empty(self.sweep_cache_size())
+        out = self._batch_out(nb, want_s2_all)
         self._check(self._lib.gpx_sweep_batch(self._h, aid, _ptr(params), nparams, int(nb), _ptr(out['sel_val']), _ptr(out['sel_idx']),
                                               _ptr(out['sel_s2']), _ptr(out.get('s2_all'))))
         return out
@@ -732,10 +737,7 @@ class Engine(object):
         if eps.ndim != 2:
             raise ValueError('eps must be a (S, >= nb - 1) array')
         pend = None if pending is None else np.ascontiguousarray(pending, dtype=np.int64).reshape(-1)
-        n = max(int(nb), 0)
-        out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty(n))
-        if want_s2_all:
-            out['s2_all'] = np.empty(self.sweep_cache_size())
+        out = self._batch_out(nb, want_s2_all)
         self._check(self._lib.gpx_sweep_batch_fantasy(self._h, aid, _ptr(params), nparams, int(nb), _ptr(eps), eps.shape[0], eps.shape[1],
                                                       int(incumbent), _ptr(pend), 0 if pend is None else len(pend), _ptr(out['sel_val']),
                                                       _ptr(out['sel_idx']), _ptr(out['sel_s2']), _ptr(out.get('s2_all'))))

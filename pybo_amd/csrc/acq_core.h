@@ -1,5 +1,5 @@
 // acq_core.h -- the per-candidate arithmetic every acquisition kernel shares, each piece defined ONCE: the sums and moments of a
-// candidate, the variance floor, the ensemble's fold and finish, the constraint fold, the total order of the top-k and of the batch picks, the batch
+// candidate, the variance floor, the ensemble's fold and finish, the constraint fold, the total order of the top-k and of the batch picks, a batch member's state and its
 // fold, a pick's four scalars and the fantasised picks' mean step, average and incumbent.  The library promises bit-for-bit agreement between many of its paths (a cache seeded by any
 // acquisition, pruned against exhaustive sweeps, ensemble against its members, batch against single picks); those promises hold
 // because the paths call the functions below, not because their statements were kept in step.
@@ -139,6 +139,49 @@ GPX_ACQ_FN double batch_fold(int j, int64_t M, int64_t n, double* __restrict__ V
     V[(int64_t)j * M + n] = v;
     const double vv = v * v;
     return qprev + vv;
+}
+
+// One member's batch state as every kernel of kernels_batch.hip sees it (gpx_sweep_batch and gpx_sweep_batch_fantasy: the one model,
+// by value; gpx_ensemble_sweep_batch: a table of n in device memory): the member's cached sums, its model constants, and where its
+// recurrence lies in its own handle's dbsel (batch_ws).  What a batch shares -- the candidates, the raw x, taken, the partials, the
+// picks -- belongs to the lead and travels beside it.
+struct BatchMember {
+    const double *cq, *cp, *invell;
+    double *qp, *V, *cross, *scal, *xs;
+    double rho, bias, sn2;
+};
+
+// what the fantasised form adds (fant_ws): the innovations pick-major with pitch Sp, the S incumbents, the forced rows of the leading rounds
+struct FantArg {
+    const double* eps;
+    double* t;
+    const int64_t* pend;
+    int S, Sp, npend;
+};
+
+// Member e's q' of candidate n in the round after pick j (j < 0: round 0, q' <- q of the cache), stored and returned, from its streamed
+// words qprev (q, else q') and vraw (row j of V as the rank-1 pass left it; unread in round 0)
+// (a member's pointers are taken apart into __restrict__ parameters here: a struct's fields cannot promise that they do not alias,
+// and without the promise the scoring kernels hold two to twenty-six more VGPRs and lose a wave per SIMD)
+GPX_ACQ_FN double batch_q(int j, int64_t M, int64_t n, double* __restrict__ V, const double* __restrict__ cross, const double* __restrict__ scal,
+                          double* __restrict__ qp, double qprev, double vraw) {
+    const double q = (j < 0) ? qprev : batch_fold(j, M, n, V, cross, scal[1], vraw, qprev);
+    qp[n] = q;
+    return q;
+}
+
+// the single-model forms' candidate: its words loaded here, its moments, the optional store of the variance
+GPX_ACQ_FN CandMoments batch_cand(int j, int64_t M, int64_t n, const double* __restrict__ cq, const double* __restrict__ cp, double* __restrict__ qp,
+                                  double* __restrict__ V, const double* __restrict__ cross, const double* __restrict__ scal, double rho,
+                                  double bias, double* __restrict__ s2_out) {
+    const double q = (j < 0) ? batch_q(j, M, n, V, cross, scal, qp, cq[n], 0.0)      // (one branch on j, not a select per word)
+                             : batch_q(j, M, n, V, cross, scal, qp, qp[n], V[(int64_t)j * M + n]);
+    const CandMoments c = moments_of_sums(q, cp[n], rho, bias);
+    if (s2_out) s2_out[n] = c.s2;
+    return c;
+}
+GPX_ACQ_FN CandMoments batch_cand(int j, int64_t M, int64_t n, const BatchMember& e, double* s2_out) {
+    return batch_cand(j, M, n, e.cq, e.cp, e.qp, e.V, e.cross, e.scal, e.rho, e.bias, s2_out);
 }
 
 // a pick's four scalars from its conditioned variance: [0] d  [1] 1/d  [2] 0 (the `a` slot of launch_pend_store: no value exists)  [3] d^2

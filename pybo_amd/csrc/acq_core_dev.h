@@ -1,5 +1,6 @@
 // acq_core_dev.h -- the device-only part of acq_core.h: what needs a workgroup.  One copy each of the arg-max reduction of the
-// top-k and the batch picks, the front of the two pick kernels, and the frame of the one-thread-per-candidate acquisition kernels.
+// top-k and the batch picks, the parts of a batch pick kernel (merge_pick, pick_member, pick_gather), the frame of the batch scoring
+// kernels (batch_score_frame) and the frame of the one-thread-per-candidate acquisition kernels (acq_frame).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,6 +48,49 @@ __device__ __forceinline__ int64_t merge_pick(int j, int nblk, const double* __r
         if (!none) taken[row] = 1;
     }
     return row;
+}
+
+// Member e's part of pick j at candidate `row`, by thread t of the nt (>= j) that share it: its floored variance there (returned to every
+// thread) into sel_s2[j] and pick_scalars' four words, the cross terms V[l][row] for l < j, and xs = z_row / ell.
+__device__ __forceinline__ double pick_member(const BatchMember& e, int j, int64_t M, int d, const double* __restrict__ Z, int64_t row,
+                                              double* __restrict__ sel_s2, int t, int nt) {
+    const double s2 = s2_floored(e.rho, e.qp[row]);
+    if (t == 0) {
+        sel_s2[j] = s2;
+        pick_scalars(s2, e.sn2, e.scal);
+    }
+    if (t < j) e.cross[t] = e.V[(int64_t)t * M + row];
+    for (int k = t; k < d; k += nt) e.xs[k] = Z[row * d + k] * e.invell[k];
+    return s2;
+}
+
+// the raw x = z_row, by the whole workgroup
+__device__ __forceinline__ void pick_gather(const double* __restrict__ Z, int64_t row, int d, double* __restrict__ x) {
+    for (int k = threadIdx.x; k < d; k += 256) x[k] = Z[row * d + k];
+}
+
+// The frame of a batch scoring kernel (256 threads per workgroup, any grid): every candidate, live or not, goes through fold(n) (its
+// fold and its stores); the live ones -- not taken yet and, in a round forced to one row (forced >= 0), that row -- then through
+// value(n, what fold returned), and their arg-max under the total order is the workgroup's partial.
+template <class Fold, class Value>
+__device__ __forceinline__ void batch_score_frame(int64_t M, const unsigned char* __restrict__ taken, int64_t forced, const Fold& fold,
+                                                  const Value& value, double* __restrict__ partv, int64_t* __restrict__ parti) {
+    __shared__ double sv[4];
+    __shared__ int64_t si[4];
+    double bv = NEG_INF;
+    int64_t bi = IDX_NONE;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < M; n += stride) {
+        const auto c = fold(n);
+        if (taken[n] || (forced >= 0 && n != forced)) continue;
+        const double val = nan_last(value(n, c));
+        if (better(val, n, bv, bi)) { bv = val; bi = n; }
+    }
+    block_argmax(bv, bi, sv, si);
+    if (threadIdx.x == 0) {
+        partv[blockIdx.x] = bv;
+        parti[blockIdx.x] = bi;
+    }
 }
 
 // The frame of an acquisition kernel with one thread per candidate of the chunk at m0 (256 per workgroup): the candidate's sums and

@@ -1640,145 +1640,6 @@ extern "C" int gpx_sweep_update(gpx_handle* h, int acq_id, const double* params,
     });
 }
 
-// Batch proposals: nb greedy picks on the live cache, each conditioned on the earlier ones at their posterior mean (kernels_batch.hip).
-// Per extra pick: launch_append_prepare (k(X, x), r = T k, w = U r -- its scalars and flag land in this call's own words and are
-// not read: d comes from the CONDITIONED variance), the weight row [w, -1], one rank-1 pass over the cached candidates, one fold +
-// scoring pass.  Everything is enqueued on the handle's stream with ONE synchronisation at the end; the picked index never
-// leaves the device, so no launch depends on it.  Scratch: h->dbsel (batch_ws), shared by gpx_sweep_batch and, per member, by
-// gpx_ensemble_sweep_batch (n_lead > 0: the lead of that many members).
-static int batch_layout(gpx_handle* h, int64_t M, int64_t nb, int64_t n_lead, BatchBuf& b) {
-    const int64_t xpad = (h->cap_d + 63) / 64 * 64, ld = h->cap_np + NB;      // N + 1 <= ld whatever the padding holds
-    const int64_t ndesc = (n_lead * (int64_t)sizeof(EnsBatchMember) + 7) / 8;
-    if (int rc = ensure(h, h->dbsel, h->cap_bsel, batch_ws(WsCarver(nullptr), xpad, ld, M, nb, n_lead, ndesc).bytes / 8)) return rc;
-    b = batch_ws(WsCarver(h->dbsel), xpad, ld, M, nb, n_lead, ndesc);
-    return GPX_OK;
-}
-
-// one extra pick's conditioning of member h on the point x (raw) / xs (scaled by h's 1/ell), enqueued on s: row j of V
-static void batch_condition(gpx_handle* h, hipStream_t s, const BatchBuf& b, const double* x, const double* Z, int64_t M, int j) {
-    launch_append_prepare(h, s, x, b.ks, b.g, b.r, b.tu, 0.0, b.scal_prep, b.flag);
-    launch_pend_store(s, b.tu, h->N, b.ld, b.scal, b.row, b.pscal);
-    launch_sweep_rank1_v(s, h->dXs, h->N + 1, (int)h->d, b.row, b.ld, b.pscal, Z, M, h->dinvell, h->kernel_id, h->rho, b.xs,
-                         b.V + (int64_t)j * M);
-}
-
-extern "C" int gpx_sweep_batch(gpx_handle* h, int acq_id, const double* params, int nparams, int64_t nb, double* sel_val,
-                               int64_t* sel_idx, double* sel_s2, double* s2_all) {
-    return guarded(h, [&]() -> int {
-        if (!h) return GPX_EARG;
-        int rc;
-        if ((rc = check_batch(h, "sweep_batch", acq_id, params, nparams, nb, sel_val, sel_idx))) return rc;
-        if (!h->fitted || !h->cache_valid) return fail(h, GPX_ESTATE, "sweep_batch: no live sweep cache (sweep with option sweep_cache = 1 first)");
-        const int64_t M = h->cache_M, d = h->d;
-        if (nb > M) return fail(h, GPX_EARG, "sweep_batch: nb exceeds the number of cached candidates");
-        HIPCHK(h, hipSetDevice(h->device));
-        if ((rc = ensure_inverse(h))) return rc;
-        if ((rc = flush_pending(h))) return rc;                  // queued appends belong in the sums the picks are scored with
-        BatchBuf b;
-        if ((rc = batch_layout(h, M, nb, 0, b))) return rc;
-        const double p0 = params[0];
-        hipStream_t s = h->stream;
-        {
-            Span sp(h, T_BATCH);
-            HIPCHK(h, hipMemsetAsync(b.taken, 0, (size_t)b.ntaken * 8, s));
-            HIPCHK(h, hipMemsetAsync(b.flag, 0, sizeof(int), s));
-            for (int j = 0; j < (int)nb; ++j) {
-                double* s2_out = (s2_all && j == (int)nb - 1) ? b.s2 : nullptr;    // the variances that score the LAST pick
-                launch_batch_score(s, j - 1, M, h->dcq, h->dcp, b.qp, b.V, b.cross, b.scal, b.taken, h->rho, h->bias, acq_id, p0,
-                                   s2_out, b.partv, b.parti);
-                launch_batch_pick(s, j, M, (int)d, b.partv, b.parti, h->dcZ, h->dinvell, b.qp, b.V, h->rho, h->sn2, b.x, b.xs,
-                                  b.scal, b.cross, b.sel_val, b.sel_idx, b.sel_s2, b.taken);
-                if (j == (int)nb - 1) break;
-                batch_condition(h, s, b, b.x, h->dcZ, M, j);
-            }
-            HIPCHK(h, hipGetLastError());
-        }
-        HIPCHK(h, hipMemcpyAsync(sel_val, b.sel_val, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(sel_idx, b.sel_idx, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        if (sel_s2) HIPCHK(h, hipMemcpyAsync(sel_s2, b.sel_s2, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        if (s2_all) HIPCHK(h, hipMemcpyAsync(s2_all, b.s2, (size_t)M * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        return GPX_OK;
-    });
-}
-
-// gpx_sweep_batch with the pending outcomes integrated out over S joint fantasies (kernels_batch.hip: k_fant_score, k_fant_pick).  The
-// launch chain, the conditioning and the believer's scratch (h->dbsel) are gpx_sweep_batch's; the innovations (re-packed pick-major,
-// zero-padded to the kernel's chunk), the incumbents and the forced rows go up once into h->dfant (fant_ws) before the first round.
-extern "C" int gpx_sweep_batch_fantasy(gpx_handle* h, int acq_id, const double* params, int nparams, int64_t nb, const double* eps,
-                                       int64_t S, int64_t ld_eps, int incumbent, const int64_t* pend_idx, int64_t npend,
-                                       double* sel_val, int64_t* sel_idx, double* sel_s2, double* s2_all) {
-    return guarded(h, [&]() -> int {
-        if (!h) return GPX_EARG;
-        int rc;
-        const char* const what = "sweep_batch_fantasy";
-        if ((rc = check_batch(h, what, acq_id, params, nparams, nb, sel_val, sel_idx))) return rc;
-        if (acq_id != GPX_ACQ_EI && acq_id != GPX_ACQ_PI)
-            return fail(h, GPX_EARG, "sweep_batch_fantasy: EI or PI (UCB is linear in the mean: its fantasy average is gpx_sweep_batch's value)");
-        if (S < 1 || S > FANT_MAX_S) return fail(h, GPX_EARG, "sweep_batch_fantasy: S must be in [1, 64]");
-        if (incumbent != 0 && incumbent != 1) return fail(h, GPX_EARG, "sweep_batch_fantasy: incumbent must be 0 or 1");
-        if (!eps || ld_eps < std::max<int64_t>(nb - 1, 1)) return fail(h, GPX_EARG, "sweep_batch_fantasy: eps is (S, ld_eps >= max(nb - 1, 1))");
-        if (npend < 0 || npend >= nb || (npend > 0 && !pend_idx)) return fail(h, GPX_EARG, "sweep_batch_fantasy: npend must be in [0, nb)");
-        if (!h->fitted || !h->cache_valid) return fail(h, GPX_ESTATE, "sweep_batch_fantasy: no live sweep cache (sweep with option sweep_cache = 1 first)");
-        const int64_t M = h->cache_M, d = h->d;
-        if (nb > M) return fail(h, GPX_EARG, "sweep_batch_fantasy: nb exceeds the number of cached candidates");
-        for (int64_t i = 0; i < npend; ++i) {
-            bool ok = pend_idx[i] >= 0 && pend_idx[i] < M;
-            for (int64_t k = 0; ok && k < i; ++k) ok = pend_idx[k] != pend_idx[i];
-            if (!ok) return fail(h, GPX_EARG, "sweep_batch_fantasy: pend_idx must hold distinct rows of the cache");
-        }
-        const FantWs lay = fant_ws(WsCarver(nullptr), nb, S);
-        const int64_t Sp = lay.Sp, words = lay.bytes / 8;
-        h->fant_host.assign((size_t)lay.bytes, 0);
-        {
-            const FantWs hw = fant_ws(WsCarver(h->fant_host.data()), nb, S);
-            for (int64_t s = 0; s < S; ++s)
-                for (int64_t l = 0; l + 1 < nb; ++l) {
-                    const double e = eps[s * ld_eps + l];
-                    if (!std::isfinite(e)) return fail(h, GPX_EARG, "sweep_batch_fantasy: eps must be finite");
-                    hw.eps[l * Sp + s] = e;
-                }
-            for (int64_t s = 0; s < Sp; ++s) hw.t[s] = params[0];
-            for (int64_t i = 0; i < npend; ++i) hw.pend[i] = pend_idx[i];
-        }
-        HIPCHK(h, hipSetDevice(h->device));
-        if ((rc = ensure_inverse(h))) return rc;
-        if ((rc = flush_pending(h))) return rc;                  // queued appends belong in the sums the picks are scored with
-        BatchBuf b;
-        if ((rc = batch_layout(h, M, nb, 0, b))) return rc;
-        if ((rc = ensure(h, h->dfant, h->cap_fant, words))) return rc;
-        const FantWs f = fant_ws(WsCarver(h->dfant), nb, S);
-        hipStream_t s = h->stream;
-        {
-            Span sp(h, T_COPY);
-            HIPCHK(h, hipMemcpyAsync(f.eps, h->fant_host.data(), (size_t)lay.bytes, hipMemcpyHostToDevice, s));
-        }
-        {
-            Span sp(h, T_BATCH);
-            HIPCHK(h, hipMemsetAsync(b.taken, 0, (size_t)b.ntaken * 8, s));
-            HIPCHK(h, hipMemsetAsync(b.flag, 0, sizeof(int), s));
-            for (int j = 0; j < (int)nb; ++j) {
-                const bool last = j == (int)nb - 1;
-                double* s2_out = (s2_all && last) ? b.s2 : nullptr;    // the variances that score the LAST pick
-                launch_fant_score(s, j - 1, M, h->dcq, h->dcp, b.qp, b.V, b.cross, b.scal, b.taken, h->rho, h->bias, acq_id, f.eps, f.t,
-                                  (int)S, (int)Sp, f.pend, (int)npend, s2_out, b.partv, b.parti);
-                launch_fant_pick(s, j, M, (int)d, b.partv, b.parti, h->dcZ, h->dinvell, b.qp, h->dcp, b.V, h->rho, h->sn2, h->bias, f.eps,
-                                 f.t, (int)S, (int)Sp, (incumbent && !last) ? 1 : 0, b.x, b.xs, b.scal, b.cross, b.sel_val, b.sel_idx,
-                                 b.sel_s2, b.taken);
-                if (last) break;
-                batch_condition(h, s, b, b.x, h->dcZ, M, j);
-            }
-            HIPCHK(h, hipGetLastError());
-        }
-        HIPCHK(h, hipMemcpyAsync(sel_val, b.sel_val, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(sel_idx, b.sel_idx, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        if (sel_s2) HIPCHK(h, hipMemcpyAsync(sel_s2, b.sel_s2, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        if (s2_all) HIPCHK(h, hipMemcpyAsync(s2_all, b.s2, (size_t)M * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        return GPX_OK;
-    });
-}
-
 extern "C" int64_t gpx_sweep_cache_size(const gpx_handle* h) { return (h && h->cache_valid) ? h->cache_M : 0; }
 
 extern "C" int gpx_predict(gpx_handle* h, const double* Xc, int64_t M, double* mu, double* s2, double* dmu,
@@ -2763,10 +2624,178 @@ extern "C" int gpx_ehvi_fold_dev(gpx_handle* lead, const double* d_mom, int64_t 
     });
 }
 
-// Batch proposals on the ensemble: the members frozen, every round scored with ensemble_core's rule, every member conditioned on the
-// pick at its own posterior mean (gpx_sweep_batch's recurrence per member, in that member's dbsel).  The lead's dbsel also holds what
-// the members share: taken, the argmax partials, sel_val / sel_idx, the raw x, and behind its V [sel_s2 n nb][descriptors n].
-// The members' streams are drained on entry; from there on everything runs on the lead's stream with ONE synchronisation.
+// ---- batch proposals (kernels_batch.hip) --------------------------------------------------------------------------------------------------
+// nb greedy picks on the live cache, each conditioned on the earlier ones: at their posterior mean (gpx_sweep_batch), with the pending
+// outcomes integrated out over S fantasies (gpx_sweep_batch_fantasy), or by every member of a frozen ensemble at its own posterior mean
+// (gpx_ensemble_sweep_batch).  ONE driver: batch_check, batch_prepare, batch_rounds; an entry keeps its own arguments and what only it needs.
+// Per extra pick and member: launch_append_prepare (k(X, x), r = T k, w = U r -- its scalars and flag land in this call's own words and are
+// not read: d comes from the CONDITIONED variance), the weight row [w, -1], one rank-1 pass over the cached candidates, then one fold +
+// scoring pass for all.  Everything is enqueued on the lead's stream with ONE synchronisation at the end; the picked index never
+// leaves the device, so no launch depends on it.  Scratch: every member's h->dbsel (batch_ws); the lead's (n_lead > 0: that many members)
+// also holds what they share: taken, the argmax partials, sel_val / sel_idx, the raw x, and behind its V [sel_s2 n nb][descriptors n].
+static int batch_layout(gpx_handle* h, int64_t M, int64_t nb, int64_t n_lead, BatchBuf& b) {
+    const int64_t xpad = (h->cap_d + 63) / 64 * 64, ld = h->cap_np + NB;      // N + 1 <= ld whatever the padding holds
+    const int64_t ndesc = (n_lead * (int64_t)sizeof(BatchMember) + 7) / 8;
+    if (int rc = ensure(h, h->dbsel, h->cap_bsel, batch_ws(WsCarver(nullptr), xpad, ld, M, nb, n_lead, ndesc).bytes / 8)) return rc;
+    b = batch_ws(WsCarver(h->dbsel), xpad, ld, M, nb, n_lead, ndesc);
+    return GPX_OK;
+}
+
+// one extra pick's conditioning of member h on the point x (raw) / xs (scaled by h's 1/ell), enqueued on s: row j of V
+static void batch_condition(gpx_handle* h, hipStream_t s, const BatchBuf& b, const double* x, const double* Z, int64_t M, int j) {
+    launch_append_prepare(h, s, x, b.ks, b.g, b.r, b.tu, 0.0, b.scal_prep, b.flag);
+    launch_pend_store(s, b.tu, h->N, b.ld, b.scal, b.row, b.pscal);
+    launch_sweep_rank1_v(s, h->dXs, h->N + 1, (int)h->d, b.row, b.ld, b.pscal, Z, M, h->dinvell, h->kernel_id, h->rho, b.xs,
+                         b.V + (int64_t)j * M);
+}
+
+// member h as the kernels see it: its cached sums and constants, its recurrence in b
+static BatchMember batch_member(const gpx_handle* h, const BatchBuf& b) {
+    return {h->dcq, h->dcp, h->dinvell, b.qp, b.V, b.cross, b.scal, b.xs, h->rho, h->bias, h->sn2};
+}
+
+// one call: the entry's name, its members (g.role: set when refusals name the member), and from batch_check / batch_prepare on M and the scratch
+struct BatchCall {
+    const char* what;
+    Group g;
+    int64_t nb, M;
+    std::vector<BatchBuf> bufs;
+};
+
+// every member holds a live cache, all of one size M >= nb
+static int batch_check(BatchCall& c) {
+    gpx_handle* L = c.g.L;
+    const std::string w(c.what);
+    for (int m = 0; m < c.g.n; ++m)
+        if (!c.g.hs[m]->fitted || !c.g.hs[m]->cache_valid)
+            return fail(L, GPX_ESTATE, ((c.g.role ? std::string(c.g.role) + " " + std::to_string(m) + ": " : std::string()) + w +
+                                        ": no live sweep cache (sweep with option sweep_cache = 1 first)").c_str());
+    c.M = L->cache_M;
+    for (int m = 1; m < c.g.n; ++m)
+        if (c.g.hs[m]->cache_M != c.M) return fail(L, GPX_EARG, (w + ": the members' caches differ in size").c_str());
+    if (c.nb > c.M) return fail(L, GPX_EARG, (w + ": nb exceeds the number of cached candidates").c_str());
+    return GPX_OK;
+}
+
+// per member, on its own stream: the inverse, the queued appends (they belong in the sums the picks are scored with), its scratch
+static int batch_prepare(BatchCall& c) {
+    HIPCHK(c.g.L, hipSetDevice(c.g.L->device));
+    c.bufs.assign((size_t)c.g.n, BatchBuf());
+    for (int m = 0; m < c.g.n; ++m) {
+        gpx_handle* h = c.g.hs[m];
+        int rc;
+        if ((rc = ensure_inverse(h)) || (rc = flush_pending(h)) || (rc = batch_layout(h, c.M, c.nb, (m == 0 && c.g.role) ? c.g.n : 0, c.bufs[m])))
+            return group_fail(c.g, h, m, rc);
+    }
+    return GPX_OK;
+}
+
+// The rounds, on the lead's stream, and the results.  score(j, s2_out) enqueues the scoring pass that folds row j of V (j < 0: round 0;
+// s2_out: the variances that score the LAST pick, when asked for), pick(j, last) the pick; unless it was the last, every member is then
+// conditioned on the lead's x.  sel_s2: n_s2 words from d_sel_s2; same: the lead's same-grid word (the ensemble).  The one synchronisation.
+template <class Score, class Pick>
+static int batch_rounds(const BatchCall& c, const Score& score, const Pick& pick, double* sel_val, int64_t* sel_idx, double* sel_s2,
+                        const double* d_sel_s2, int64_t n_s2, double* s2_all, int* same = nullptr) {
+    gpx_handle* L = c.g.L;
+    const BatchBuf& lb = c.bufs[0];
+    hipStream_t s = L->stream;
+    {
+        Span sp(L, T_BATCH);
+        HIPCHK(L, hipMemsetAsync(lb.taken, 0, (size_t)lb.ntaken * 8, s));
+        for (const BatchBuf& b : c.bufs) HIPCHK(L, hipMemsetAsync(b.flag, 0, sizeof(int), s));
+        for (int j = 0; j < (int)c.nb; ++j) {
+            const bool last = j == (int)c.nb - 1;
+            score(j - 1, (s2_all && last) ? lb.s2 : nullptr);
+            pick(j, last);
+            if (last) break;
+            for (int m = 0; m < c.g.n; ++m) batch_condition(c.g.hs[m], s, c.bufs[m], lb.x, L->dcZ, c.M, j);
+        }
+        HIPCHK(L, hipGetLastError());
+    }
+    HIPCHK(L, hipMemcpyAsync(sel_val, lb.sel_val, (size_t)c.nb * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(L, hipMemcpyAsync(sel_idx, lb.sel_idx, (size_t)c.nb * 8, hipMemcpyDeviceToHost, s));
+    if (sel_s2) HIPCHK(L, hipMemcpyAsync(sel_s2, d_sel_s2, (size_t)n_s2 * 8, hipMemcpyDeviceToHost, s));
+    if (s2_all) HIPCHK(L, hipMemcpyAsync(s2_all, lb.s2, (size_t)c.M * 8, hipMemcpyDeviceToHost, s));
+    if (same) HIPCHK(L, hipMemcpyAsync(same, lb.same, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(L, hipStreamSynchronize(s));
+    return GPX_OK;
+}
+
+// the rounds of the single-model forms.  f: the fantasised form's arguments on the device (moving: every fantasy's incumbent follows its
+// own observations), NULL: the believer's
+static int single_rounds(const BatchCall& c, int acq_id, double p0, const FantArg* f, bool moving, double* sel_val, int64_t* sel_idx,
+                         double* sel_s2, double* s2_all) {
+    gpx_handle* h = c.g.L;
+    const BatchBuf& b = c.bufs[0];
+    const BatchMember e = batch_member(h, b);
+    hipStream_t s = h->stream;
+    return batch_rounds(c, [&](int j, double* s2_out) { launch_batch_score(s, j, c.M, e, b, acq_id, p0, f, s2_out); },
+                        [&](int j, bool last) { launch_batch_pick(s, j, c.M, (int)h->d, h->dcZ, e, b, f, moving && !last); },
+                        sel_val, sel_idx, sel_s2, b.sel_s2, c.nb, s2_all);
+}
+
+extern "C" int gpx_sweep_batch(gpx_handle* h, int acq_id, const double* params, int nparams, int64_t nb, double* sel_val,
+                               int64_t* sel_idx, double* sel_s2, double* s2_all) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        int rc;
+        BatchCall c = {"sweep_batch", {h, &h, 1, nullptr, 0, nullptr}, nb, 0, {}};
+        if ((rc = check_batch(h, c.what, acq_id, params, nparams, nb, sel_val, sel_idx)) || (rc = batch_check(c)) || (rc = batch_prepare(c)))
+            return rc;
+        return single_rounds(c, acq_id, params[0], nullptr, false, sel_val, sel_idx, sel_s2, s2_all);
+    });
+}
+
+// gpx_sweep_batch with the pending outcomes integrated out over S joint fantasies (kernels_batch.hip: k_fant_score, k_fant_pick).  The
+// innovations (re-packed pick-major, zero-padded to the kernel's chunk), the incumbents and the forced rows go up once into h->dfant
+// (fant_ws) before the first round.
+extern "C" int gpx_sweep_batch_fantasy(gpx_handle* h, int acq_id, const double* params, int nparams, int64_t nb, const double* eps,
+                                       int64_t S, int64_t ld_eps, int incumbent, const int64_t* pend_idx, int64_t npend,
+                                       double* sel_val, int64_t* sel_idx, double* sel_s2, double* s2_all) {
+    return guarded(h, [&]() -> int {
+        if (!h) return GPX_EARG;
+        int rc;
+        BatchCall c = {"sweep_batch_fantasy", {h, &h, 1, nullptr, 0, nullptr}, nb, 0, {}};
+        if ((rc = check_batch(h, c.what, acq_id, params, nparams, nb, sel_val, sel_idx))) return rc;
+        if (acq_id != GPX_ACQ_EI && acq_id != GPX_ACQ_PI)
+            return fail(h, GPX_EARG, "sweep_batch_fantasy: EI or PI (UCB is linear in the mean: its fantasy average is gpx_sweep_batch's value)");
+        if (S < 1 || S > FANT_MAX_S) return fail(h, GPX_EARG, "sweep_batch_fantasy: S must be in [1, 64]");
+        if (incumbent != 0 && incumbent != 1) return fail(h, GPX_EARG, "sweep_batch_fantasy: incumbent must be 0 or 1");
+        if (!eps || ld_eps < std::max<int64_t>(nb - 1, 1)) return fail(h, GPX_EARG, "sweep_batch_fantasy: eps is (S, ld_eps >= max(nb - 1, 1))");
+        if (npend < 0 || npend >= nb || (npend > 0 && !pend_idx)) return fail(h, GPX_EARG, "sweep_batch_fantasy: npend must be in [0, nb)");
+        if ((rc = batch_check(c))) return rc;
+        for (int64_t i = 0; i < npend; ++i) {
+            bool ok = pend_idx[i] >= 0 && pend_idx[i] < c.M;
+            for (int64_t k = 0; ok && k < i; ++k) ok = pend_idx[k] != pend_idx[i];
+            if (!ok) return fail(h, GPX_EARG, "sweep_batch_fantasy: pend_idx must hold distinct rows of the cache");
+        }
+        const FantWs lay = fant_ws(WsCarver(nullptr), nb, S);
+        const int64_t Sp = lay.Sp;
+        h->fant_host.assign((size_t)lay.bytes, 0);
+        {
+            const FantWs hw = fant_ws(WsCarver(h->fant_host.data()), nb, S);
+            for (int64_t s = 0; s < S; ++s)
+                for (int64_t l = 0; l + 1 < nb; ++l) {
+                    const double e = eps[s * ld_eps + l];
+                    if (!std::isfinite(e)) return fail(h, GPX_EARG, "sweep_batch_fantasy: eps must be finite");
+                    hw.eps[l * Sp + s] = e;
+                }
+            for (int64_t s = 0; s < Sp; ++s) hw.t[s] = params[0];
+            for (int64_t i = 0; i < npend; ++i) hw.pend[i] = pend_idx[i];
+        }
+        if ((rc = batch_prepare(c)) || (rc = ensure(h, h->dfant, h->cap_fant, lay.bytes / 8))) return rc;
+        const FantWs w = fant_ws(WsCarver(h->dfant), nb, S);
+        {
+            Span sp(h, T_COPY);
+            HIPCHK(h, hipMemcpyAsync(w.eps, h->fant_host.data(), (size_t)lay.bytes, hipMemcpyHostToDevice, h->stream));
+        }
+        const FantArg f = {w.eps, w.t, w.pend, (int)S, (int)Sp, (int)npend};
+        return single_rounds(c, acq_id, params[0], &f, incumbent != 0, sel_val, sel_idx, sel_s2, s2_all);
+    });
+}
+
+// The ensemble: the members frozen, every round scored with ensemble_core's rule.  The members' streams are drained on entry; from there
+// on everything runs on the lead's stream.
 extern "C" int gpx_ensemble_sweep_batch(gpx_handle* const* members, int n_members, int acq_id, const double* params,
                                         int nparams, int64_t nb, double* sel_val, int64_t* sel_idx, double* sel_s2) {
     if (members && members[0] && (n_members < 1 || n_members > 64)) {
@@ -2777,65 +2806,35 @@ extern "C" int gpx_ensemble_sweep_batch(gpx_handle* const* members, int n_member
     gpx_handle* L = members[0];
     return guarded(L, [&]() -> int {
         const int n = n_members;
-        const Group g = {L, members, n, "ensemble member", 0, nullptr};
+        BatchCall c = {"ensemble_sweep_batch", {L, members, n, "ensemble member", 0, nullptr}, nb, 0, {}};
         int rc;
-        if ((rc = check_batch(L, "ensemble_sweep_batch", acq_id, params, nparams, nb, sel_val, sel_idx))) return rc;
-        if ((rc = group_check(g, "ensemble_sweep_batch", {{G_FITTED, "a member model is not fitted"},
-                                                          {G_SHAPE, "members must share the device and the input dimension"},
-                                                          {G_ONCE, "a handle is listed twice (every member needs its own scratch)"}}, true)))
+        if ((rc = check_batch(L, c.what, acq_id, params, nparams, nb, sel_val, sel_idx))) return rc;
+        if ((rc = group_check(c.g, c.what, {{G_FITTED, "a member model is not fitted"},
+                                            {G_SHAPE, "members must share the device and the input dimension"},
+                                            {G_ONCE, "a handle is listed twice (every member needs its own scratch)"}}, true)))
             return rc;
-        for (int m = 0; m < n; ++m)
-            if (!members[m]->cache_valid)
-                return fail(L, GPX_ESTATE, ("ensemble member " + std::to_string(m) + ": ensemble_sweep_batch: no live sweep cache (sweep with "
-                                            "option sweep_cache = 1 first)").c_str());
-        const int64_t M = L->cache_M, d = L->d;
-        for (int m = 1; m < n; ++m)
-            if (members[m]->cache_M != M) return fail(L, GPX_EARG, "ensemble_sweep_batch: the members' caches differ in size");
-        if (nb > M) return fail(L, GPX_EARG, "ensemble_sweep_batch: nb exceeds the number of cached candidates");
-        HIPCHK(L, hipSetDevice(L->device));
-        std::vector<BatchBuf> bufs((size_t)n);
-        L->bsel_desc.assign((size_t)n, EnsBatchMember());
+        if ((rc = batch_check(c)) || (rc = batch_prepare(c))) return rc;
+        const int64_t M = c.M, d = L->d;
+        L->bsel_desc.resize((size_t)n);
         for (int m = 0; m < n; ++m) {
-            gpx_handle* h = members[m];
-            if ((rc = ensure_inverse(h)) || (rc = flush_pending(h)) ||      // queued appends belong in the sums, on the member's own stream
-                (rc = batch_layout(h, M, nb, m == 0 ? n : 0, bufs[m])))
-                return group_fail(g, h, m, rc);
-            HIPCHK(L, hipStreamSynchronize(h->stream));
-            const BatchBuf& b = bufs[m];
-            EnsBatchMember& e = L->bsel_desc[m];
-            e.cq = h->dcq, e.cp = h->dcp, e.invell = h->dinvell;
-            e.qp = b.qp, e.V = b.V, e.cross = b.cross, e.scal = b.scal, e.xs = b.xs;
-            e.rho = h->rho, e.bias = h->bias, e.sn2 = h->sn2;
+            HIPCHK(L, hipStreamSynchronize(members[m]->stream));
+            L->bsel_desc[m] = batch_member(members[m], c.bufs[m]);
         }
-        const BatchBuf& lb = bufs[0];
-        double* dsel_s2 = lb.ens_s2;
-        EnsBatchMember* ddesc = reinterpret_cast<EnsBatchMember*>(lb.desc);
+        const BatchBuf& lb = c.bufs[0];
+        BatchMember* ddesc = reinterpret_cast<BatchMember*>(lb.desc);
         const double p0 = params[0];
         hipStream_t s = L->stream;
         int differ = 0;
         {
             Span sp(L, T_BATCH);
-            HIPCHK(L, hipMemcpyAsync(ddesc, L->bsel_desc.data(), (size_t)n * sizeof(EnsBatchMember), hipMemcpyHostToDevice, s));
-            HIPCHK(L, hipMemsetAsync(lb.taken, 0, (size_t)lb.ntaken * 8, s));
+            HIPCHK(L, hipMemcpyAsync(ddesc, L->bsel_desc.data(), (size_t)n * sizeof(BatchMember), hipMemcpyHostToDevice, s));
             HIPCHK(L, hipMemsetAsync(lb.same, 0, sizeof(int), s));
-            for (int m = 0; m < n; ++m) {
-                HIPCHK(L, hipMemsetAsync(bufs[m].flag, 0, sizeof(int), s));
-                if (m > 0) launch_ens_same_grid(s, L->dcZ, members[m]->dcZ, M * d, lb.same);
-            }
-            for (int j = 0; j < (int)nb; ++j) {
-                launch_ens_batch_score(s, j - 1, n, M, ddesc, lb.taken, acq_id, p0, lb.partv, lb.parti);
-                launch_ens_batch_pick(s, j, n, nb, M, (int)d, lb.partv, lb.parti, L->dcZ, ddesc, lb.x, lb.sel_val, lb.sel_idx,
-                                      dsel_s2, lb.taken);
-                if (j == (int)nb - 1) break;
-                for (int m = 0; m < n; ++m) batch_condition(members[m], s, bufs[m], lb.x, L->dcZ, M, j);
-            }
-            HIPCHK(L, hipGetLastError());
+            for (int m = 1; m < n; ++m) launch_ens_same_grid(s, L->dcZ, members[m]->dcZ, M * d, lb.same);
         }
-        HIPCHK(L, hipMemcpyAsync(sel_val, lb.sel_val, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(L, hipMemcpyAsync(sel_idx, lb.sel_idx, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-        if (sel_s2) HIPCHK(L, hipMemcpyAsync(sel_s2, dsel_s2, (size_t)n * nb * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(L, hipMemcpyAsync(&differ, lb.same, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(L, hipStreamSynchronize(s));
+        if ((rc = batch_rounds(c, [&](int j, double*) { launch_ens_batch_score(s, j, n, M, ddesc, lb, acq_id, p0); },
+                               [&](int j, bool) { launch_ens_batch_pick(s, j, n, nb, M, (int)d, L->dcZ, ddesc, lb); },
+                               sel_val, sel_idx, sel_s2, lb.ens_s2, n * nb, nullptr, &differ)))
+            return rc;
         if (differ) return fail(L, GPX_EARG, "ensemble_sweep_batch: the members' caches hold different candidates");
         return GPX_OK;
     });

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/gpx.h"
+#include "acq_core.h"
 #include "prune_hint.h"
 #include "sweep_map.h"
 #include "ws_layout.h"
@@ -23,14 +24,6 @@ enum Timer {
 };
 
 struct EventPair { hipEvent_t a, b; int slot; };
-
-// one member of an ensemble batch (gpx_ensemble_sweep_batch) as the kernels of kernels_batch.hip see it: the member's cached sums,
-// its model constants, and where its batch state lies in its own handle's dbsel (batch_ws)
-struct EnsBatchMember {
-    const double *cq, *cp, *invell;
-    double *qp, *V, *cross, *scal, *xs;
-    double rho, bias, sn2;
-};
 
 }  // namespace gpx
 
@@ -241,7 +234,7 @@ struct gpx_handle {
     // batch proposals (gpx_sweep_batch): scratch of its own (batch_ws) -- nothing the append / announcement paths own
     double* dbsel = nullptr;
     int64_t cap_bsel = 0;
-    std::vector<gpx::EnsBatchMember> bsel_desc;   // host source of the lead's descriptor table (gpx_ensemble_sweep_batch): outlives its copy
+    std::vector<gpx::BatchMember> bsel_desc;      // host source of the lead's descriptor table (gpx_ensemble_sweep_batch): outlives its copy
     double* dfant = nullptr;                      // gpx_sweep_batch_fantasy: innovations, incumbents, forced rows (fant_ws)
     int64_t cap_fant = 0;
     std::vector<unsigned char> fant_host;         // host source of that upload: outlives its copy
@@ -428,34 +421,20 @@ int rff_grad_host(gpx_handle* h, const double* W, const double* b, const double*
                   double bias, const double* Xc, int64_t M, double* f, double* g);
 
 // launchers (kernels_batch.hip): one scoring pass (j < 0: round 0; else fold row j of V first) with per-block argmax partials
-// (batch_blocks(M) of them), and the one-workgroup pick that merges them and leaves everything round j + 1 needs on the device
+// (batch_blocks(M) of them), and the one-workgroup pick that merges them and leaves everything round j + 1 needs on the device.
+// e: the model's batch state; b: the scratch that holds what a batch shares (taken, partials, picks, x); f: the fantasised form
+// (EI / PI; update: move the incumbents after pick j, which reads row j of eps), NULL: the believer's
 int batch_blocks(int64_t M);
-void launch_batch_score(hipStream_t s, int j, int64_t M, const double* cq, const double* cp, double* qp, double* V,
-                        const double* cross, const double* scal, const unsigned char* taken, double rho, double bias,
-                        int acq_id, double p0, double* s2_out, double* partv, int64_t* parti);
-void launch_batch_pick(hipStream_t s, int j, int64_t M, int d, const double* partv, const int64_t* parti, const double* Z,
-                       const double* invell, const double* qp, const double* V, double rho, double sn2, double* x,
-                       double* xs, double* scal, double* cross, double* sel_val, int64_t* sel_idx, double* sel_s2,
-                       unsigned char* taken);
-// the fantasised forms (gpx_sweep_batch_fantasy; EI / PI only): the value is the mean over S fantasies of the acquisition at the mean
-// shifted by the rows of V times eps (pick-major, pitch Sp) against the incumbents tinc; pend[0 .. npend): the forced rows of the leading
-// rounds; update: move the incumbents after pick j (reads row j of eps)
-void launch_fant_score(hipStream_t s, int j, int64_t M, const double* cq, const double* cp, double* qp, double* V,
-                       const double* cross, const double* scal, const unsigned char* taken, double rho, double bias, int acq_id,
-                       const double* eps, const double* tinc, int S, int Sp, const int64_t* pend, int npend, double* s2_out,
-                       double* partv, int64_t* parti);
-void launch_fant_pick(hipStream_t s, int j, int64_t M, int d, const double* partv, const int64_t* parti, const double* Z,
-                      const double* invell, const double* qp, const double* cp, const double* V, double rho, double sn2,
-                      double bias, const double* eps, double* tinc, int S, int Sp, int update, double* x, double* xs, double* scal,
-                      double* cross, double* sel_val, int64_t* sel_idx, double* sel_s2, unsigned char* taken);
-// the ensemble forms (gpx_ensemble_sweep_batch): ONE scoring pass over the candidates with all n members inside it (each member's
-// fold as above, its value or moments summed in member order, one division), the pick that leaves every member's next round on the
-// device (sel_s2: (n, nb) member-major), and the bitwise compare of two candidate sets (*flag <- 1 where a 64-bit word differs)
-void launch_ens_batch_score(hipStream_t s, int j, int n, int64_t M, const EnsBatchMember* mem, const unsigned char* taken,
-                            int acq_id, double p0, double* partv, int64_t* parti);
-void launch_ens_batch_pick(hipStream_t s, int j, int n, int64_t nb, int64_t M, int d, const double* partv, const int64_t* parti,
-                           const double* Z, const EnsBatchMember* mem, double* x, double* sel_val, int64_t* sel_idx,
-                           double* sel_s2, unsigned char* taken);
+void launch_batch_score(hipStream_t s, int j, int64_t M, const BatchMember& e, const BatchBuf& b, int acq_id, double p0, const FantArg* f,
+                        double* s2_out);
+void launch_batch_pick(hipStream_t s, int j, int64_t M, int d, const double* Z, const BatchMember& e, const BatchBuf& b, const FantArg* f,
+                       bool update);
+// the ensemble forms: ONE scoring pass with all n members of the device table `mem` inside it (each member's fold, its value or moments
+// summed in member order, one division), the pick that leaves every member's next round on the device (b.ens_s2: (n, nb) member-major),
+// and the bitwise compare of two candidate sets (*flag <- 1 where a 64-bit word differs)
+void launch_ens_batch_score(hipStream_t s, int j, int n, int64_t M, const BatchMember* mem, const BatchBuf& b, int acq_id, double p0);
+void launch_ens_batch_pick(hipStream_t s, int j, int n, int64_t nb, int64_t M, int d, const double* Z, const BatchMember* mem,
+                           const BatchBuf& b);
 void launch_ens_same_grid(hipStream_t s, const double* Za, const double* Zb, int64_t words, int* flag);
 
 // launchers (kernels_cov.hip): the joint posterior at cols = Mp padded points -- V = T Ks stored panel-major [cols / 128][Np][128],

@@ -7,8 +7,11 @@ do not pin:
     seeded caches   a sweep with sweep_cache = 1 by each of ei, mes, kg, two appends, then sweep_update for ei and mes (the cache
                     form of the moments: no row blocks left to add)
     batch           sweep_batch, nb = 4, for ei, pi, ucb with s2_all
+    fantasy         sweep_batch_fantasy, nb = 4, for ei and pi over S = 1 (one ragged chunk), 5, 16 (one full chunk) and 17 (two chunks,
+                    one live lane in the second) fantasies, eps = RandomState(23).randn(S, 3), each with incumbent 0 and 1 and with
+                    s2_all; one case with two pending rows and one with nb = 1 (no conditioning, eps unread)
     ensemble        three members (N = 300, 300, 100; their own ell, rho, bias): ensemble_sweep for ei, pi, mean, ucb (mean and ucb
-                    with the mixture moments), mes with S = 2 per member; ensemble_batch, nb = 4, for ei and ucb
+                    with the mixture moments), mes with S = 2 per member; ensemble_batch, nb = 4, for ei, pi and ucb
     predict         with gradients at one point (the one-pass form) and at five (the two-pass form), and both forms forced
 
 d = 5; N = 300 (three row blocks) and N = 100 (one); M = 4099 uniform candidates under chunk = 1024 (five chunks, the last with
@@ -19,6 +22,9 @@ Output: tests/golden/acq_digests.json, per case the SHA-256 of the raw bytes of 
 PARENT commit's diagnostics library, never from the one under test; tests/test_gpu_acq_digests.py replays the cases:
     GPX_LIB_PATH=<parent>/pybo_amd/csrc/libgpx_diag.so python tests/golden/make_acq_digests.py --commit <hash> [--out file.json]
 Every case runs twice and the recorder fails if the two runs differ anywhere: no output is left out.
+Cases added after the first recording (the fantasy rows and the ensemble batch for pi, from the commit before the batch kernels
+got one frame) go in with --add: every case runs, the rows the file already holds must come out as recorded and stay, and the
+new ones are listed under "added" by the commit that produced them.
 """
 import argparse
 import hashlib
@@ -125,7 +131,25 @@ def _batch(N, kind, param):
     e.set_option('sweep_cache', 0)
     r = e.sweep_batch(kind, param, NB, want_s2_all=True)
     e.close()
-    return _digest(r, ('sel_val', 'sel_idx', 'sel_s2', 's2_all'))
+    return _digest(r, BATCH_KEYS)
+
+
+BATCH_KEYS = ('sel_val', 'sel_idx', 'sel_s2', 's2_all')
+PENDING = (7, 2048)
+
+
+def _fantasy(N, kind, S, incumbents, nb=NB, pending=None):
+    e = _engine(N)
+    e.set_option('sweep_cache', 1)
+    _tied(lambda Z: e.sweep('ei', _target(N), Z, k=TOPK, want_all=False))
+    e.set_option('sweep_cache', 0)
+    eps = np.random.RandomState(23).randn(S, 3)
+    out = {}
+    for inc in incumbents:
+        r = e.sweep_batch_fantasy(kind, _target(N), nb, eps, incumbent=inc, pending=pending, want_s2_all=True)
+        out.update({'incumbent %d %s' % (inc, k): v for k, v in _digest(r, BATCH_KEYS).items()})
+    e.close()
+    return out
 
 
 def _members():
@@ -179,12 +203,17 @@ def cases():
             out.append(('cache seeded by %s N=%d' % (acq, N), lambda N=N, acq=acq, param=param: _seeded(N, acq, param)))
         for kind, param in (('ei', t), ('pi', t), ('ucb', 2.0)):
             out.append(('batch %s N=%d' % (kind, N), lambda N=N, kind=kind, param=param: _batch(N, kind, param)))
+        for kind in ('ei', 'pi'):
+            for S in (1, 5, 16, 17):
+                out.append(('fantasy %s S=%d N=%d' % (kind, S, N), lambda N=N, kind=kind, S=S: _fantasy(N, kind, S, (0, 1))))
+    out.append(('fantasy ei S=5 N=300 pending', lambda: _fantasy(300, 'ei', 5, (1,), pending=PENDING)))
+    out.append(('fantasy ei S=5 N=300 nb=1', lambda: _fantasy(300, 'ei', 5, (1,), nb=1)))
     t = _target(300)
     for acq, param, moments in (('ei', t, False), ('pi', t, False), ('mean', None, True), ('ucb', 2.0, True)):
         out.append(('ensemble %s' % acq, lambda acq=acq, param=param, moments=moments: _ens_sweep(acq, param, moments)))
     ys = np.array([_maxima(N, 2, 0.1 * i) for i, (N, _, _, _) in enumerate(MEMBERS)])
     out.append(('ensemble mes S=2', lambda: _ens_sweep('mes', ys, False)))
-    for kind, param in (('ei', t), ('ucb', 2.0)):
+    for kind, param in (('ei', t), ('pi', t), ('ucb', 2.0)):
         out.append(('ensemble batch %s' % kind, lambda kind=kind, param=param: _ens_batch(kind, param)))
     for npts, form in ((1, 0), (5, 0), (5, 1), (5, 2)):
         out.append(('predict grad %d points form %d' % (npts, form), lambda npts=npts, form=form: _predict(npts, form)))
@@ -195,16 +224,28 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--commit', required=True, help='hash of the commit the loaded library was built from')
     ap.add_argument('--out', default=OUT)
+    ap.add_argument('--add', action='store_true', help='keep the rows of --out (they must replay) and add the cases it lacks')
     args = ap.parse_args()
     from pybo_amd import _lib
     doc = dict(commit=args.commit, library=os.path.basename(_lib.LIB_PATH), cases={})
+    old = {}
+    if args.add:
+        with open(args.out) as f:
+            doc = json.load(f)
+        old = dict(doc['cases'])
+        assert doc['library'] == os.path.basename(_lib.LIB_PATH), doc['library']
     for name, run in cases():
         first, second = run(), run()
         unstable = sorted(k for k in first if first[k] != second.get(k))
         if unstable or sorted(first) != sorted(second):
             sys.exit('NOT reproducible in %s: %s -- a finding about the recording library; nothing was written' % (name, unstable))
+        if name in old and first != old[name]:
+            sys.exit('%s does not replay the recorded row: nothing was written' % name)
         doc['cases'][name] = first
         print(name, 'ok', sorted(first), flush=True)
+    new = sorted(set(doc['cases']) - set(old))
+    if args.add and new:
+        doc.setdefault('added', {})[args.commit] = new
     with open(args.out, 'w') as f:
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write('\n')

@@ -5,14 +5,15 @@ arguments at and beyond every boundary, for the shipping library (libgpx.so) and
     GPX_OPTIONS      gpx_create under each string of ENV_OPTIONS: (rc, gpx_last_error(NULL) when rc != 0)
     wrappers         one call per single bad argument of gpx_sweep(_dev), gpx_sweep_update(_dev), gpx_ensemble_sweep(_dev)
                      (two members), gpx_rff_gram_batch, gpx_rff_posterior, gpx_constrained_sweep(_dev), gpx_ehvi_sweep(_dev),
-                     gpx_ehvi_fold_dev, gpx_sweep_batch, gpx_ensemble_sweep_batch and gpx_path_sweep(_dev), on handles fitted to
+                     gpx_ehvi_fold_dev, gpx_sweep_batch, gpx_sweep_batch_fantasy, gpx_ensemble_sweep_batch and gpx_path_sweep(_dev), on handles fitted to
                      N = 10, d = 2: (rc, message)
 
 None of the recorded calls reaches a HIP runtime error, so no message carries a source line.  Output:
 tests/golden/api_contract.json (messages stored once, results as [rc, message index or -1]).  Needs a GPU; recorded from
 the libraries of the commit before the option table replaced gpx_set_option's if-chain, recorded again with the rows of the
 constrained, two-objective, batch and pathwise entries from the commit before those entries got one frame (every earlier row came
-out unchanged), and replayed against the current ones by tests/test_gpu_api_contract.py:
+out unchanged), once more with the rows of gpx_sweep_batch_fantasy from the commit before the batch entries got one driver (again
+every earlier row unchanged), and replayed against the current ones by tests/test_gpu_api_contract.py:
     python tests/golden/make_api_contract.py [--ship path/libgpx.so] [--diag path/libgpx_diag.so] [--out file.json]
 """
 import argparse
@@ -275,6 +276,27 @@ def probe(path):
     out['sweep_batch: no cache + sel_val NULL'] = _err(lib, b, batch(b, dict(bgood, sv=None)))
     out['sweep_batch: not fitted'] = _err(lib, unfit, batch(unfit, bgood))
     out['sweep_batch: handle NULL'] = [batch(None, bgood), None]
+    # gpx_sweep_batch_fantasy on `a` (M = 64 cached candidates): S = 4 fantasies, nb = 3 picks, eps wide enough for every probe
+    feps = np.random.RandomState(11).randn(65, 32)
+    feps_nan = feps.copy()
+    feps_nan[1, 1] = nan
+    fgood = dict(bgood, h=a, nb=3, eps=feps, S=4, ld=32, inc=1, pend=None, npend=0)
+    fbad = [('not fitted', dict(h=unfit)), ('no cache', dict(h=b)), ('nb 0', dict(nb=0)), ('nb 65', dict(nb=65)), ('sel_val NULL', dict(sv=None)),
+            ('UCB', dict(acq=2)), ('MES', dict(acq=16)), ('S 0', dict(S=0)), ('S 65', dict(S=65)), ('incumbent 2', dict(inc=2)),
+            ('eps NULL', dict(eps=None)), ('ld_eps 1 < nb - 1', dict(ld=1)), ('npend = nb', dict(pend=[0, 1, 2], npend=3)),
+            ('pend_idx NULL, npend 1', dict(npend=1)), ('pending row twice', dict(pend=[5, 5], npend=2)),
+            ('pending row 64 = M', dict(pend=[64], npend=1)), ('eps NaN', dict(eps=feps_nan)),
+            ('no cache + sel_val NULL', dict(h=b, sv=None)), ('no cache + UCB', dict(h=b, acq=2)), ('S 65 + eps NULL', dict(S=65, eps=None))]
+
+    def fantasy(g_):
+        pend = None if g_['pend'] is None else np.array(g_['pend'], dtype=np.int64)
+        return lib.gpx_sweep_batch_fantasy(g_['h'], g_['acq'], _p(g_['prm']), g_['np_'], g_['nb'], _p(g_['eps']), g_['S'], g_['ld'], g_['inc'],
+                                           _p(pend), g_['npend'], _p(g_['sv']), _p(g_['si']), None, None)
+
+    for label, kw in fbad:
+        g_ = dict(fgood, **kw)
+        out['sweep_batch_fantasy: %s' % label] = _err(lib, g_['h'], fantasy(g_))
+    out['sweep_batch_fantasy: handle NULL'] = [fantasy(dict(fgood, h=None)), None]
     out['ensemble_sweep_batch: no cache'] = _err(lib, a, ens_batch(bgood))
     out['ensemble_sweep_batch: no cache on the lead'] = _err(lib, b, ens_batch(dict(bgood, mem=[b, a])))
     out['ensemble_sweep_batch: twice'] = _err(lib, a, ens_batch(dict(bgood, mem=[a, a])))
@@ -291,6 +313,7 @@ def probe(path):
     assert lib.gpx_set_option(b, b'sweep_cache', 1) == 0          # b: a live cache of another size
     assert lib.gpx_sweep(b, 0, _p(prm), 1, _p(Xc), M // 2, 5, _p(tv), _p(ti), None, None, None) == 0
     out['sweep_batch: nb 33 > M 32'] = _err(lib, b, batch(b, dict(bgood, nb=33)))
+    out['sweep_batch_fantasy: nb 33 > M 32'] = _err(lib, b, fantasy(dict(fgood, h=b, nb=33)))
     out['ensemble_sweep_batch: caches differ in size'] = _err(lib, a, ens_batch(bgood))
     out['ensemble_sweep_batch: caches differ in size + nb 64'] = _err(lib, a, ens_batch(dict(bgood, nb=64)))
 

@@ -114,6 +114,23 @@ def test_the_kernels_use_the_header_the_check_includes():
     everything = '\n'.join(open(os.path.join(CSRC, n)).read() for n in sorted(os.listdir(CSRC)) if n.endswith(('.hip', '.h', '.cpp')))
     for fn in ('fant_mean_step', 'fant_fold', 'fant_average', 'fant_incumbent'):
         assert len(re.findall(r'^(?:GPX_ACQ_FN|__device__ __forceinline__)[^\n(]*\b%s\(' % fn, everything, flags=re.M)) == 1, fn
-    # the device scores with the believer's own fold and moments: one recurrence, two values
-    for fn in ('batch_fold', 'moments_of_sums', 'merge_pick', 'pick_scalars'):
-        assert len(re.findall(r'\b%s\(' % fn, src)) >= 2, fn
+    # the device scores with the believer's own fold and moments: one recurrence, two values.  Both scoring kernels are the frame around
+    # batch_cand (the fold and the moments, stated once in acq_core.h), both pick kernels are single_pick (the merge, the member's part
+    # with its scalars, the gather), and no kernel of the file restates any of it
+    def body(name):
+        m = re.search(r'void %s\(.*?\n}\n' % re.escape(name), src, flags=re.S)
+        assert m, name
+        return m.group(0)
+    for kernel in ('k_batch_score', 'k_fant_score'):
+        assert 'batch_score_frame(' in body(kernel) and 'batch_cand(j, M, n, e, s2_out)' in body(kernel), kernel
+    for kernel in ('k_batch_pick', 'k_fant_pick'):
+        assert 'single_pick(' in body(kernel), kernel
+    for fn in ('merge_pick', 'pick_member', 'pick_gather'):
+        assert '%s(' % fn in body('single_pick'), fn
+    core = open(os.path.join(CSRC, 'acq_core.h')).read()
+    dev = open(os.path.join(CSRC, 'acq_core_dev.h')).read()
+    cand = re.search(r'CandMoments batch_cand\(int j, int64_t M, int64_t n, const double\* __restrict__ cq.*?\n}\n', core, flags=re.S).group(0)
+    assert 'batch_q(' in cand and 'moments_of_sums(' in cand
+    assert 'batch_fold(' in re.search(r'double batch_q\(.*?\n}\n', core, flags=re.S).group(0)
+    assert 'pick_scalars(' in re.search(r'double pick_member\(.*?\n}\n', dev, flags=re.S).group(0)
+    assert not re.search(r'\b(batch_fold|s2_floored|block_argmax|better|nan_last)\(', src)
