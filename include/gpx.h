@@ -23,8 +23,7 @@ typedef struct gpx_handle gpx_handle;
 enum gpx_status {
     GPX_OK = 0, GPX_EARG = -1, /* bad argument */
     GPX_ENOTPD = -2,  /* K + sn2*I not positive definite; see gpx_fail_pivot */
-    GPX_EHIP = -3,    /* HIP runtime error */
-    GPX_EOOM = -4,    /* device allocation failed */
+    GPX_EHIP = -3,    /* HIP runtime error */                  GPX_EOOM = -4, /* device allocation failed */
     GPX_ESTATE = -5,  /* call order error (e.g. sweep before fit) */
     GPX_ERCCL = -6    /* RCCL could not be loaded, or a collective failed; see gpx_comm_last_error */
 };
@@ -77,9 +76,8 @@ int gpx_version(void);
  *                    schedule (~250 launches over four streams) [1].  "chol_tg_db" -1 / 0 / 1: one workgroup per CU with two k-step images of LDS up to
  *                    "chol_tg_db_max" (112) blocks / never / always [-1]; "chol_tg_fuse" 1: a column's solve and the final chunk of the tile below it are one
  *                    task [1]; "chol_tg_tmo_ms": bound of every spin -- on expiry the fit re-runs on the stream schedule and says so on stderr [2000]
- *   "chol_w", "chol_rl", "chol_merge", "chol_fuse", "chol_graph"   the stream schedule: outer panel width in blocks (2..8, 0 = by
- *                    size), right- / left-looking in-panel updates [1], far updates of two panels in one pass [1], diagonal block
- *                    factored inside the panel solve [0], replay from a captured hipGraph [0]
+ *   "chol_w", "chol_rl", "chol_merge", "chol_fuse", "chol_graph"   the stream schedule: outer panel width in blocks (2..8, 0 = by size), right- / left-looking
+ *                    in-panel updates [1], far updates of two panels in one pass [1], diagonal block factored in the panel solve [0], replay from hipGraph [0]
  * Diagnostic knobs ("chol_tg_chunks", "chol_tg_nap", "chol_tg_grid", "chol_tg_isolate", "chol_tg_trace", "grad_rb_cs", "x_rff", "x_bg*", "x_skip" -- the last
  * one leaves parts of the factorisation OUT) exist only in a library built with -DGPX_DIAGNOSTICS (pybo_amd/csrc/libgpx_diag.so; pybo_amd/csrc/gpx_diag.h); the
  * shipping library answers them with GPX_EARG. Environment: GPX_OPTIONS="name=value,name=value" applies options to every handle at creation (A/B runs through a
@@ -128,8 +126,7 @@ int gpx_var_at_obs(gpx_handle *h, double *s2_host);
 /* rows (a multiple of 128) the factor buffers are allocated for: 4 matrices of capacity^2 doubles stay on the device until gpx_destroy (size pools by it) */
 int64_t gpx_capacity(const gpx_handle *h);
 /* ---- posterior moments = model.predict(X, grad) [pybo/policies/simple.py:64] ------------- */
-/* Xc (M,d) -> mu (M,), s2 (M,) latent variance; dmu, ds2 (M,d) optional (NULL to skip).  With gradients a single point
- * (M = 1) is answered in the one-pass form, batches in the two-pass form: option "grad_form" above. */
+/* Xc (M,d) -> mu, s2 (M,) latent variance; dmu, ds2 (M,d) optional (NULL).  With gradients M = 1 takes the one-pass form, batches the two-pass: "grad_form". */
 int gpx_predict(gpx_handle *h, const double *Xc, int64_t M, double *mu, double *s2, double *dmu, double *ds2);
 /* The mean alone, mu (M,) and optionally dmu (M,d) (NULL to skip): mu = bias + k(x, X).alpha reads neither the factor nor its inverse -- what the latent
  * recommender maximises, model.predict(X, True)[0::2] [pybo/recommenders.py:17-24], without the two triangular passes per point the variance costs. */
@@ -148,12 +145,11 @@ int gpx_sweep(gpx_handle *h, int acq_id, const double *params, int nparams, cons
               double *top_val, int64_t *top_idx, double *acq_all, double *mu, double *s2);
 int gpx_sweep_dev(gpx_handle *h, int acq_id, const double *params, int nparams, const double *dXc, int64_t M, int64_t k,
                   double *top_val, int64_t *top_idx, double *d_acq_all, double *d_mu, double *d_s2);
-/* ---- warm BO step: the NEXT iteration's `index(xgrid)` over the SAME grid with the SAME hyper-parameters
- *      [pybo/bayesopt.py:262-269 with a fixed `xgrid=` in pybo/solvers/lbfgs.py:42-50].  The reference pays a full refit and a full
- *      solve again; with option "sweep_cache" = 1 a full gpx_sweep* keeps the candidates and their reduced sums q = colsum(V^2),
- *      p = V^T a in HBM (8 (d + 2) M bytes), every gpx_append adds the one new row of V to them (N*M covariance evaluations; up to 8
- *      appended points share one pass), and gpx_sweep_update re-scores the whole grid in O(M) (the target / beta may change from call
- *      to call) + top-k.  Outputs as in gpx_sweep*.  GPX_ESTATE without a valid cache (never swept, or refitted since). */
+/* ---- warm BO step: the NEXT iteration's `index(xgrid)` over the SAME grid with the SAME hyper-parameters [pybo/bayesopt.py:262-269 with a fixed `xgrid=` in
+ *      pybo/solvers/lbfgs.py:42-50].  The reference pays a full refit and a full solve again; with option "sweep_cache" = 1 a full gpx_sweep* keeps the
+ *      candidates and their reduced sums q = colsum(V^2), p = V^T a in HBM (8 (d + 2) M bytes), every gpx_append adds the one new row of V to them (N*M
+ *      covariance evaluations; up to 8 appended points share one pass), and gpx_sweep_update re-scores the whole grid in O(M) (the target / beta may change
+ *      from call to call) + top-k.  Outputs as in gpx_sweep*.  GPX_ESTATE without a valid cache (never swept, or refitted since). */
 int gpx_sweep_update(gpx_handle *h, int acq_id, const double *params, int nparams, int64_t k, double *top_val,
                      int64_t *top_idx, double *acq_all, double *mu, double *s2);
 int gpx_sweep_update_dev(gpx_handle *h, int acq_id, const double *params, int nparams, int64_t k,
@@ -237,6 +233,10 @@ int gpx_constrained_sweep(gpx_handle *obj, gpx_handle *const *cons, int nc, cons
                           const double *Xc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *acq_all, double *pof_all);
 int gpx_constrained_sweep_dev(gpx_handle *obj, gpx_handle *const *cons, int nc, const double *thr, int acq_id, const double *params, int nparams,
                               const double *dXc, int64_t M, int64_t k, double *top_val, int64_t *top_idx, double *d_acq_all, double *d_pof_all);
+/* gpx_ensemble_sweep_batch's rules (live caches of the same candidates, 1 <= nb <= min(64, M), handles untouched) on this index: nb greedy picks, target and
+ * thr frozen, the objective and every constraint conditioned on a pick at ITS OWN posterior mean.  Arguments as above; sel_s2 (members, nb) optional. */
+int gpx_constrained_sweep_batch(gpx_handle *obj, gpx_handle *const *cons, int nc, const double *thr, int acq_id, const double *params, int nparams,
+                                int64_t nb, double *sel_val, int64_t *sel_idx, double *sel_s2);
 /* ---- two objectives, maximised: expected hypervolume improvement (Emmerich et al. 2011; Yang et al. 2019) of independent posteriors over the front of the raw
  *      points P (np, 2), 0 <= np <= 4096, above the reference point ref (2); P, ref finite, on the HOST in every variant.  Points not strictly above ref,
  *      weakly dominated ones and duplicates are dropped; at most 1024 may remain (else GPX_EARG); np = 0: an empty front.  With the n survivors by f1
@@ -290,7 +290,7 @@ int gpx_topk_allgather(gpx_comm *c, int64_t n, int64_t index_offset, int64_t k, 
  * task-graph factorisation gave up and re-ran on the stream schedule [16] the shader clock in MHz the sweep_trmm launches sustained (their workgroups'
  * s_memtime over s_memrealtime ticks) [17] the same for the Thompson sweep kernel [18] inversions whose leading part ran behind the factorisation
  * ("trtri_ahead": for those [2] holds only what was left after the factor was done) [19] bound pass of selection-only sweeps [20] batch selection
- * (gpx_[ensemble_]sweep_batch*) [21] joint posterior (gpx_predict_cov / gpx_sample_joint: all between their copies).  Synchronises; returns slots written. */
+ * (gpx_*sweep_batch*) [21] joint posterior (gpx_predict_cov / gpx_sample_joint: all between their copies).  Synchronises; returns slots written. */
 int gpx_timers(gpx_handle *h, double *out, int n, int reset);
 int gpx_diagnostics(void);     /* 1 when the library was built with -DGPX_DIAGNOSTICS (the diagnostic options above are accepted), else 0 */
 int gpx_sync(gpx_handle *h);

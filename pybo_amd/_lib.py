@@ -101,6 +101,7 @@ SYMBOLS = {
     'gpx_ensemble_predict': (C.c_int, [_P, C.c_int, _P, _i64, _P, _P, _P, _P]),
     'gpx_constrained_sweep': (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P]),
     'gpx_constrained_sweep_dev': (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _i64, _i64, _P, _P, _P, _P]),
+    'gpx_constrained_sweep_batch': (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _i64, _P, _P, _P]),
     'gpx_ehvi_sweep': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _i64, _i64, _P, _P, _P]),
     'gpx_ehvi_sweep_dev': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _i64, _i64, _P, _P, _P, _P]),
     'gpx_ehvi_fold_dev': (C.c_int, [_P, _P, _i64, _P, C.c_int, _P, _i64, _P, _P, _P]),
@@ -808,6 +809,26 @@ class Engine(object):
         lead._check(fn(obj._h if obj is not None else None, _handles(cons), len(cons), _ptr(thr), aid, _ptr(params), nparams, X, M, k, ptv, pti,
                        *outs))
         return dict(top_val=tv, top_idx=ti, **o)
+
+    @staticmethod
+    def constrained_batch(obj, cons, thr, acq, param, nb):
+        """nb greedy picks of the constrained index on the members' live sweep caches (gpx_constrained_sweep_batch): EI / PI of the engine
+        `obj` times every constraint engine's probability of exceeding `thr[j]`, target and thresholds frozen, every member conditioned
+        on a pick at its own posterior mean; obj = None: the probability of feasibility alone (acq / param unread).  Returns
+        dict(sel_val (nb,), sel_idx (nb,), sel_s2 (n, nb)), n = the members, the objective first; they are left as they were."""
+        cons = list(cons)
+        lead = obj if obj is not None else cons[0]
+        thr = _f64(thr).reshape(-1)
+        if len(thr) != len(cons):
+            raise ValueError('one threshold per constraint')
+        aid = acq_id(acq) if obj is not None else 0
+        params, nparams = _acq_params(param)
+        n = max(int(nb), 0)
+        out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty((len(cons) + (obj is not None), n)))
+        lead._check(lead._lib.gpx_constrained_sweep_batch(obj._h if obj is not None else None, _handles(cons), len(cons), _ptr(thr), aid,
+                                                          _ptr(params), nparams, int(nb), _ptr(out['sel_val']), _ptr(out['sel_idx']),
+                                                          _ptr(out['sel_s2'])))
+        return out
 
     @staticmethod
     def _front_args(front, ref):

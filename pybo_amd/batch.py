@@ -18,6 +18,13 @@ Three paths, chosen by what the policy's index carries:
     score the grid, pick, `copy()` the model once and `add_data(x, predict(x)[0])` per round.  On an `MCMC` that `add_data`
     advances the chain: the hyper-parameters are RE-SAMPLED on the hallucinated observation every round, unlike the device path;
   * neither (Thompson, or any sampled policy): nb independent policy calls, each one's best grid point; duplicates are allowed.
+`policy='cei'` on a constrained model (`pybo_amd.models.Constrained`): its index carries `.acq = ('cei', target)` and never `.batch`, so
+the dispatch is on the kind and the MODEL is asked.  One with `acq_batch` and device members on one device takes the device path
+(gpx_constrained_sweep_batch: target and thresholds frozen, the objective AND every constraint conditioned on a pick at its own posterior
+mean, one call for the whole batch); any other (oracle members, stubs) takes the generic host path, `_score` reading `get_constrained` and
+the believer step observing EVERY member at its own posterior mean, a (1, 1 + J) row to `add_data`.  `fantasies > 0` or `pending` on a
+constrained model raise a ValueError before any index is built (not built; nor are MCMC / ShardedGP members, off-grid refinement of the
+picks, pruned seeding of the caches, or batches for EHVI, MES and KG).
 `policy='mes'` is refused: its index carries `.acq = ('mes', ystar)` but no `.batch`, and `_score` below raises the ValueError for any kind
 but EI, PI and UCB -- scoring the believer rounds with max-value entropy search is not built (the sampled maxima would have to follow them).
 `policy='kg'` is refused the same way: `.acq = ('kg', support)`, no `.batch` (the support set's means would have to follow the rounds).
@@ -57,7 +64,16 @@ def _score(model, kind, param, Z):
     if kind == 'ucb':
         mu, s2 = model.predict(Z)
         return mu + np.sqrt(param * s2)
-    raise ValueError('batch proposals need an EI, PI or UCB index, not %r' % (kind,))
+    if kind == 'cei':                                 # a constrained model: EI times feasibility (param None: feasibility alone)
+        return model.get_constrained(param, Z)
+    raise ValueError('batch proposals need an EI, PI or UCB index (or CEI on a constrained model), not %r' % (kind,))
+
+
+def _believe(work, kind, x):
+    """What the believer observes at x: the posterior mean; on a constrained model EVERY member's own, a (1, 1 + J) row."""
+    if kind == 'cei':
+        return np.array([[float(m.predict(x)[0][0]) for m in [work.objective] + list(work.constraints)]])
+    return work.predict(x)[0]
 
 
 def _host_batch(model, kind, param, Z, nb):
@@ -71,7 +87,7 @@ def _host_batch(model, kind, param, Z, nb):
         vals.append(float(v[i]) if not np.isnan(v[i]) else -np.inf)
         if j + 1 < nb:
             x = Z[i:i + 1]
-            work.add_data(x, work.predict(x)[0])          # the believer: observe the posterior mean
+            work.add_data(x, _believe(work, kind, x))     # the believer: observe the posterior mean
     return np.array(vals), np.array(idx, dtype=np.int64)
 
 
@@ -150,6 +166,8 @@ def _propose(model, bounds, X, nb, policy, xgrid, ngrid, rng, fantasies=0, incum
         xgrid = inits.init_uniform(bounds, ngrid, rng)
     if nb > len(xgrid):
         raise ValueError('nb exceeds the number of grid points')
+    if hasattr(model, 'get_constrained') and (fantasies or pending is not None):
+        raise ValueError('fantasies and pending points are not supported on constrained models (models.Constrained): believer picks only')
     if fantasies:
         _fantasy_model(model, nb, fantasies)
     index = policy(model, bounds, X)
@@ -179,6 +197,9 @@ def _propose(model, bounds, X, nb, policy, xgrid, ngrid, rng, fantasies=0, incum
                 vals.append(float(v[i]))
                 idx.append(i)
         vals, idx = np.array(vals), np.array(idx, dtype=np.int64)
+    elif acq[0] == 'cei' and getattr(model, 'acq_batch', None) is not None and getattr(model, '_device_members', lambda: False)():
+        out = model.acq_batch('cei', acq[1], xgrid, nb)      # (the CEI index carries no `.batch`: the model is asked)
+        vals, idx = np.asarray(out['sel_val']), np.asarray(out['sel_idx'], dtype=np.int64)
     elif getattr(index, 'batch', None) is not None:
         out = index.batch(xgrid, nb)
         vals, idx = np.asarray(out['sel_val']), np.asarray(out['sel_idx'], dtype=np.int64)

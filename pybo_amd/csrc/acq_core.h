@@ -1,5 +1,5 @@
 // acq_core.h -- the per-candidate arithmetic every acquisition kernel shares, each piece defined ONCE: the sums and moments of a
-// candidate, the variance floor, the ensemble's fold and finish, the constraint fold, the total order of the top-k and of the batch picks, a batch member's state and its
+// candidate, the variance floor, the ensemble's fold and finish, the constraint fold and chain, the total order of the top-k and of the batch picks, a batch member's state and its
 // fold, a pick's four scalars and the fantasised picks' mean step, average and incumbent.  The library promises bit-for-bit agreement between many of its paths (a cache seeded by any
 // acquisition, pruned against exhaustive sweeps, ensemble against its members, batch against single picks); those promises hold
 // because the paths call the functions below, not because their statements were kept in step.
@@ -113,6 +113,23 @@ GPX_ACQ_FN double con_fold(double v, double p) {
     GPX_NO_CONTRACT;
     return v * (p > 1.0 ? 1.0 : p);
 }
+
+// The chain of a constrained index one member at a time (gpx_constrained_sweep_batch: the members in the caller's order, the objective
+// first where there is one): t is the member's own term -- the objective's EI / PI, a constraint's probability of feasibility -- and v the
+// chain so far, unread by the first member.  The objective starts the chain at its value; without one the first constraint starts it
+// at con_fold(1, P_1), exactly as k_con_fold starts pof_all.
+GPX_ACQ_FN double con_chain(bool first, bool objective, double v, double t) {
+    GPX_NO_CONTRACT;
+    if (objective) return t;
+    return con_fold(first ? 1.0 : v, t);
+}
+
+// what the constrained batch's scoring kernel takes by value: the thresholds in constraint order, the objective's target and acquisition
+struct ConBatchArg {
+    double thr[16];
+    double target;
+    int acq_id, has_obj;      // has_obj 1: member 0 is the objective, constraint j is member 1 + j; 0: constraint j is member j
+};
 
 // ---- the order --------------------------------------------------------------------------------------------------------------------
 // value descending, ties -> lower index, NaN below everything: a strict total order on (nan_last(value), index)

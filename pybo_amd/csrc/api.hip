@@ -254,7 +254,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // 690: gpx_constrained_sweep[_dev] (EI / PI times the probability of feasibility of up to 16 constraint models), gpx_constrained_prune_report.
 // 700: gpx_ehvi_sweep[_dev], gpx_ehvi_fold_dev (expected hypervolume improvement of two objectives over a Pareto front).
 // 710: gpx_sweep_batch_fantasy (batch picks with the pending outcomes integrated out over joint fantasies; time in timers slot 20).
-extern "C" int gpx_version(void) { return 710; }
+// 720: gpx_constrained_sweep_batch (greedy batch picks of the constrained index over the members' live caches; time in timers slot 20).
+extern "C" int gpx_version(void) { return 720; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -2178,9 +2179,14 @@ extern "C" int gpx_rff_gram(gpx_handle* h, const double* W, const double* b, int
 // of a constrained sweep), or NULL.
 struct Group { gpx_handle* L; gpx_handle* const* hs; int n; const char* role; int first; gpx_handle* also; };
 
+// how messages name handle i (first = -1: the constrained batch lists its objective in front of constraint 0)
+static std::string group_name(const Group& g, int i) {
+    return g.first + i < 0 ? std::string("objective") : std::string(g.role) + " " + std::to_string(g.first + i);
+}
+
 // handle i's failure as the lead reports it
 static int group_fail(const Group& g, const gpx_handle* h, int i, int rc) {
-    if (h != g.L) g.L->err = std::string(g.role) + " " + std::to_string(g.first + i) + ": " + h->err;
+    if (h != g.L) g.L->err = group_name(g, i) + ": " + h->err;
     return rc;
 }
 
@@ -2380,26 +2386,40 @@ static Group con_group(gpx_handle* obj, gpx_handle* const* cons, int nc) {
     return {con_lead(obj, cons, nc), cons, nc, "constraint", 0, obj};
 }
 
+// The refusals every constrained entry shares (`what`: its name), in two parts with the entry's own arguments checked between them:
+// the constraints, thresholds and the objective's acquisition ..
+static int constrained_check_args(gpx_handle* L, const char* what, gpx_handle* obj, gpx_handle* const* cons, int nc, const double* thr, int acq_id,
+                                  const double* params, int nparams) {
+    const std::string w(what);
+    if (!cons || nc < 1 || nc > CON_MAX) return fail(L, GPX_EARG, (w + ": takes 1 to 16 constraint handles").c_str());
+    int rc;
+    if ((rc = group_check(con_group(obj, cons, nc), what, {{G_NOT_NULL, "NULL constraint handle"}}))) return rc;
+    if (!thr) return fail(L, GPX_EARG, (w + ": NULL thresholds").c_str());
+    for (int j = 0; j < nc; ++j)
+        if (!std::isfinite(thr[j])) return fail(L, GPX_EARG, (w + ": the thresholds must be finite").c_str());
+    if (obj) {
+        if (acq_id != GPX_ACQ_EI && acq_id != GPX_ACQ_PI)
+            return fail(L, GPX_EARG, (w + ": the objective's acquisition must be EI or PI (non-negative values)").c_str());
+        if ((rc = check_acq(L, what, acq_id, params, nparams))) return rc;
+    }
+    return GPX_OK;
+}
+// .. and the handles: each once, fitted, on one device with one input dimension
+static int constrained_check_handles(gpx_handle* L, const char* what, gpx_handle* obj, gpx_handle* const* cons, int nc) {
+    const Group g = con_group(obj, cons, nc);
+    if (int rc = group_check(g, what, {{G_ONCE, "a handle appears twice"}})) return rc;
+    if (obj && !obj->fitted) return fail(L, GPX_ESTATE, (std::string(what) + ": the objective's model is not fitted").c_str());
+    return group_check(g, what, {{G_FITTED, "a constraint's model is not fitted"}, {G_SHAPE, "the handles must share the device and the input dimension"}});
+}
+
 // every refusal of gpx_constrained_sweep[_dev], before anything touches a handle's fit, cache or queue
 static int constrained_check(gpx_handle* L, gpx_handle* obj, gpx_handle* const* cons, int nc, const double* thr, int acq_id, const double* params,
                              int nparams, const double* Xc, int64_t M, int64_t k, const double* top_val, const int64_t* top_idx) {
-    if (!cons || nc < 1 || nc > CON_MAX) return fail(L, GPX_EARG, "constrained_sweep: takes 1 to 16 constraint handles");
-    const Group g = con_group(obj, cons, nc);
     int rc;
-    if ((rc = group_check(g, "constrained_sweep", {{G_NOT_NULL, "NULL constraint handle"}}))) return rc;
-    if (!thr) return fail(L, GPX_EARG, "constrained_sweep: NULL thresholds");
-    for (int j = 0; j < nc; ++j)
-        if (!std::isfinite(thr[j])) return fail(L, GPX_EARG, "constrained_sweep: the thresholds must be finite");
-    if (obj) {
-        if (acq_id != GPX_ACQ_EI && acq_id != GPX_ACQ_PI)
-            return fail(L, GPX_EARG, "constrained_sweep: the objective's acquisition must be EI or PI (non-negative values)");
-        if ((rc = check_acq(L, "constrained_sweep", acq_id, params, nparams))) return rc;
-    }
+    if ((rc = constrained_check_args(L, "constrained_sweep", obj, cons, nc, thr, acq_id, params, nparams))) return rc;
     if (!Xc || M < 1) return fail(L, GPX_EARG, "constrained_sweep: need M >= 1 candidates");
     if ((rc = check_topk(L, "constrained_sweep", k, top_val, top_idx))) return rc;
-    if ((rc = group_check(g, "constrained_sweep", {{G_ONCE, "a handle appears twice"}}))) return rc;
-    if (obj && !obj->fitted) return fail(L, GPX_ESTATE, "constrained_sweep: the objective's model is not fitted");
-    return group_check(g, "constrained_sweep", {{G_FITTED, "a constraint's model is not fitted"}, {G_SHAPE, "the handles must share the device and the input dimension"}});
+    return constrained_check_handles(L, "constrained_sweep", obj, cons, nc);
 }
 
 // (arguments checked by constrained_check)
@@ -2627,7 +2647,8 @@ extern "C" int gpx_ehvi_fold_dev(gpx_handle* lead, const double* d_mom, int64_t 
 // ---- batch proposals (kernels_batch.hip) --------------------------------------------------------------------------------------------------
 // nb greedy picks on the live cache, each conditioned on the earlier ones: at their posterior mean (gpx_sweep_batch), with the pending
 // outcomes integrated out over S fantasies (gpx_sweep_batch_fantasy), or by every member of a frozen ensemble at its own posterior mean
-// (gpx_ensemble_sweep_batch).  ONE driver: batch_check, batch_prepare, batch_rounds; an entry keeps its own arguments and what only it needs.
+// (gpx_ensemble_sweep_batch), or by the objective and every constraint of a constrained index at theirs (gpx_constrained_sweep_batch).
+// ONE driver: batch_check, batch_prepare, batch_rounds; an entry keeps its own arguments and what only it needs.
 // Per extra pick and member: launch_append_prepare (k(X, x), r = T k, w = U r -- its scalars and flag land in this call's own words and are
 // not read: d comes from the CONDITIONED variance), the weight row [w, -1], one rank-1 pass over the cached candidates, then one fold +
 // scoring pass for all.  Everything is enqueued on the lead's stream with ONE synchronisation at the end; the picked index never
@@ -2668,7 +2689,7 @@ static int batch_check(BatchCall& c) {
     const std::string w(c.what);
     for (int m = 0; m < c.g.n; ++m)
         if (!c.g.hs[m]->fitted || !c.g.hs[m]->cache_valid)
-            return fail(L, GPX_ESTATE, ((c.g.role ? std::string(c.g.role) + " " + std::to_string(m) + ": " : std::string()) + w +
+            return fail(L, GPX_ESTATE, ((c.g.role ? group_name(c.g, m) + ": " : std::string()) + w +
                                         ": no live sweep cache (sweep with option sweep_cache = 1 first)").c_str());
     c.M = L->cache_M;
     for (int m = 1; m < c.g.n; ++m)
@@ -2732,6 +2753,38 @@ static int single_rounds(const BatchCall& c, int acq_id, double p0, const FantAr
     return batch_rounds(c, [&](int j, double* s2_out) { launch_batch_score(s, j, c.M, e, b, acq_id, p0, f, s2_out); },
                         [&](int j, bool last) { launch_batch_pick(s, j, c.M, (int)h->d, h->dcZ, e, b, f, moving && !last); },
                         sel_val, sel_idx, sel_s2, b.sel_s2, c.nb, s2_all);
+}
+
+// The rounds of the forms whose kernels read a table of the members in device memory (the ensemble, the constrained index).  The members'
+// streams are drained; from there on everything runs on the lead's: the table goes up, every member's candidates are compared with the
+// lead's (k_ens_same_grid), score(s, j, table, lead's scratch) enqueues a round's scoring pass, the pick is k_ens_batch_pick.
+// sel_s2: (n, nb) member-major.
+template <class Score>
+static int table_rounds(const BatchCall& c, const Score& score, double* sel_val, int64_t* sel_idx, double* sel_s2) {
+    gpx_handle* L = c.g.L;
+    const int n = c.g.n;
+    const int64_t M = c.M, d = L->d, nb = c.nb;
+    L->bsel_desc.resize((size_t)n);
+    for (int m = 0; m < n; ++m) {
+        HIPCHK(L, hipStreamSynchronize(c.g.hs[m]->stream));
+        L->bsel_desc[m] = batch_member(c.g.hs[m], c.bufs[m]);
+    }
+    const BatchBuf& lb = c.bufs[0];
+    BatchMember* ddesc = reinterpret_cast<BatchMember*>(lb.desc);
+    hipStream_t s = L->stream;
+    int differ = 0;
+    {
+        Span sp(L, T_BATCH);
+        HIPCHK(L, hipMemcpyAsync(ddesc, L->bsel_desc.data(), (size_t)n * sizeof(BatchMember), hipMemcpyHostToDevice, s));
+        HIPCHK(L, hipMemsetAsync(lb.same, 0, sizeof(int), s));
+        for (int m = 1; m < n; ++m) launch_ens_same_grid(s, L->dcZ, c.g.hs[m]->dcZ, M * d, lb.same);
+    }
+    if (int rc = batch_rounds(c, [&](int j, double*) { score(s, j, ddesc, lb); },
+                              [&](int j, bool) { launch_ens_batch_pick(s, j, n, nb, M, (int)d, L->dcZ, ddesc, lb); },
+                              sel_val, sel_idx, sel_s2, lb.ens_s2, n * nb, nullptr, &differ))
+        return rc;
+    if (differ) return fail(L, GPX_EARG, (std::string(c.what) + ": the members' caches hold different candidates").c_str());
+    return GPX_OK;
 }
 
 extern "C" int gpx_sweep_batch(gpx_handle* h, int acq_id, const double* params, int nparams, int64_t nb, double* sel_val,
@@ -2814,29 +2867,43 @@ extern "C" int gpx_ensemble_sweep_batch(gpx_handle* const* members, int n_member
                                             {G_ONCE, "a handle is listed twice (every member needs its own scratch)"}}, true)))
             return rc;
         if ((rc = batch_check(c)) || (rc = batch_prepare(c))) return rc;
-        const int64_t M = c.M, d = L->d;
-        L->bsel_desc.resize((size_t)n);
-        for (int m = 0; m < n; ++m) {
-            HIPCHK(L, hipStreamSynchronize(members[m]->stream));
-            L->bsel_desc[m] = batch_member(members[m], c.bufs[m]);
-        }
-        const BatchBuf& lb = c.bufs[0];
-        BatchMember* ddesc = reinterpret_cast<BatchMember*>(lb.desc);
         const double p0 = params[0];
-        hipStream_t s = L->stream;
-        int differ = 0;
-        {
-            Span sp(L, T_BATCH);
-            HIPCHK(L, hipMemcpyAsync(ddesc, L->bsel_desc.data(), (size_t)n * sizeof(BatchMember), hipMemcpyHostToDevice, s));
-            HIPCHK(L, hipMemsetAsync(lb.same, 0, sizeof(int), s));
-            for (int m = 1; m < n; ++m) launch_ens_same_grid(s, L->dcZ, members[m]->dcZ, M * d, lb.same);
-        }
-        if ((rc = batch_rounds(c, [&](int j, double*) { launch_ens_batch_score(s, j, n, M, ddesc, lb, acq_id, p0); },
-                               [&](int j, bool) { launch_ens_batch_pick(s, j, n, nb, M, (int)d, L->dcZ, ddesc, lb); },
-                               sel_val, sel_idx, sel_s2, lb.ens_s2, n * nb, nullptr, &differ)))
+        return table_rounds(c, [&](hipStream_t s, int j, const BatchMember* mem, const BatchBuf& lb) {
+            launch_ens_batch_score(s, j, n, c.M, mem, lb, acq_id, p0);
+        }, sel_val, sel_idx, sel_s2);
+    });
+}
+
+// The constrained index in batches: the members are the objective (where there is one) and the constraints in the
+// caller's order, target and thresholds frozen, every member conditioned on a pick at its own posterior mean.  The refusals are those of
+// gpx_constrained_sweep and gpx_ensemble_sweep_batch, the rounds the ensemble's with k_con_batch_score as the scoring pass.
+static_assert(sizeof(ConBatchArg::thr) == CON_MAX * sizeof(double), "ConBatchArg holds CON_MAX thresholds");
+extern "C" int gpx_constrained_sweep_batch(gpx_handle* obj, gpx_handle* const* cons, int nc, const double* thr, int acq_id, const double* params,
+                                           int nparams, int64_t nb, double* sel_val, int64_t* sel_idx, double* sel_s2) {
+    gpx_handle* L = con_lead(obj, cons, nc);
+    if (!L) return GPX_EARG;
+    return guarded(L, [&]() -> int {
+        const char* what = "constrained_sweep_batch";
+        int rc;
+        if ((rc = constrained_check_args(L, what, obj, cons, nc, thr, acq_id, params, nparams))) return rc;
+        // (without an objective acq_id and params are not read: the batch's own arguments are checked beside a constraint's PI)
+        if ((rc = obj ? check_batch(L, what, acq_id, params, nparams, nb, sel_val, sel_idx) : check_batch(L, what, GPX_ACQ_PI, thr, 1, nb, sel_val, sel_idx)))
             return rc;
-        if (differ) return fail(L, GPX_EARG, "ensemble_sweep_batch: the members' caches hold different candidates");
-        return GPX_OK;
+        if ((rc = constrained_check_handles(L, what, obj, cons, nc))) return rc;
+        std::vector<gpx_handle*> hs;
+        if (obj) hs.push_back(obj);
+        hs.insert(hs.end(), cons, cons + nc);
+        const int n = (int)hs.size();
+        BatchCall c = {what, {L, hs.data(), n, "constraint", obj ? -1 : 0, nullptr}, nb, 0, {}};
+        if ((rc = batch_check(c)) || (rc = batch_prepare(c))) return rc;
+        ConBatchArg a = {};
+        std::copy(thr, thr + nc, a.thr);
+        a.target = obj ? params[0] : 0.0;
+        a.acq_id = obj ? acq_id : GPX_ACQ_PI;
+        a.has_obj = obj ? 1 : 0;
+        return table_rounds(c, [&](hipStream_t s, int j, const BatchMember* mem, const BatchBuf& lb) {
+            launch_con_batch_score(s, j, n, c.M, mem, lb, a);
+        }, sel_val, sel_idx, sel_s2);
     });
 }
 

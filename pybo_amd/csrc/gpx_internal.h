@@ -436,6 +436,9 @@ void launch_ens_batch_score(hipStream_t s, int j, int n, int64_t M, const BatchM
 void launch_ens_batch_pick(hipStream_t s, int j, int n, int64_t nb, int64_t M, int d, const double* Z, const BatchMember* mem,
                            const BatchBuf& b);
 void launch_ens_same_grid(hipStream_t s, const double* Za, const double* Zb, int64_t words, int* flag);
+// the constrained form's scoring pass over the same table (the objective first where a.has_obj): con_chain of the members' terms; its pick is
+// launch_ens_batch_pick
+void launch_con_batch_score(hipStream_t s, int j, int n, int64_t M, const BatchMember* mem, const BatchBuf& b, const ConBatchArg& a);
 
 // launchers (kernels_cov.hip): the joint posterior at cols = Mp padded points -- V = T Ks stored panel-major [cols / 128][Np][128],
 // mu = bias + V^T a (Pp: Np / 128 x cols partial sums), C = Kss - V^T V (Mp, Mp) symmetric bit for bit, B = C + add I with identity

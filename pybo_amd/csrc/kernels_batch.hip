@@ -9,14 +9,15 @@
 // The first two terms over d are one pass of the cache correction's rank-1 kernel (k_sweep_rankq<1> with `vout`, weight row
 // [w, -1, 0..], xlast = x scaled) -- launched by the driver in api.hip between a round's two kernels.
 //
-// Three forms, ONE frame.  A member's state is a BatchMember (acq_core.h); a scoring kernel is batch_score_frame (acq_core_dev.h: the
+// Four forms, ONE frame. A member's state is a BatchMember (acq_core.h); a scoring kernel is batch_score_frame (acq_core_dev.h: the
 // walk over the candidates, who is live, the order, the block arg-max, the partial) around the one thing in which the forms differ, the
 // value of a candidate; a pick kernel is merge_pick (the partials merged, the pick recorded), pick_member per member (its variance at
 // the pick, 1/d, the cross terms v_l[i_j], x / ell) and pick_gather (the raw x), all in device scratch: the host never sees an index.
 //   believer   gpx_sweep_batch           k_batch_score      acq_value at the member's moments                 k_batch_pick
 //   fantasies  gpx_sweep_batch_fantasy   k_fant_score<ACQ>  the mean of acq_value over S fantasised means     k_fant_pick (+ incumbents)
 //   ensemble   gpx_ensemble_sweep_batch  k_ens_batch_score  the members' values or moments folded in order    k_ens_batch_pick
-// The single-model kernels take their member by value, the ensemble's read a table of n in device memory: every member is conditioned
+//   constrained gpx_constrained_sweep_batch k_con_batch_score  the objective's value times every constraint's PI  k_ens_batch_pick
+// The single-model kernels take their member by value, the ensemble's and the constrained form's read a table of n in device memory: every member is conditioned
 // on the pick at ITS OWN posterior mean and keeps its own w, d, cross terms, 1/ell, V and q'.  k_ens_same_grid: the members' caches hold
 // the same candidates, bit for bit (one flag word, read at the call's only sync).
 // The argmax runs over a total order and every candidate's arithmetic is its own thread's: results do not depend on the grid.
@@ -115,6 +116,36 @@ __global__ __launch_bounds__(256) void k_ens_batch_score(int j, int nmem, int64_
     batch_score_frame(M, taken, -1, fold, [&](int64_t, const Sums& a) { return ens_value(mode, a.acc0, a.acc1, nd, p0); }, partv, parti);
 }
 
+// The constrained index over the same table (the objective first where a.has_obj, then the constraints in the caller's order): every
+// member's own recurrence and moments as above, its term -- acq_value of the objective at the target, PI of a constraint at its
+// threshold -- taken into the chain by con_chain.  The same load schedule, the same n (j + 4) 8 M bytes per round.
+__global__ __launch_bounds__(256) void k_con_batch_score(int j, int nmem, int64_t M, const BatchMember* __restrict__ mem,
+                                                         const unsigned char* __restrict__ taken, ConBatchArg a,
+                                                         double* __restrict__ partv, int64_t* __restrict__ parti) {
+    const auto fold = [&](int64_t n) {
+        double v = 0.0;
+        double qn = (j < 0) ? mem[0].cq[n] : mem[0].qp[n];
+        double pn = mem[0].cp[n];
+        double vn = (j < 0) ? 0.0 : mem[0].V[(int64_t)j * M + n];
+        for (int m = 0; m < nmem; ++m) {
+            const BatchMember& e = mem[m];
+            const double qprev = qn, p = pn, vraw = vn;
+            if (m + 1 < nmem) {
+                const BatchMember& f = mem[m + 1];
+                qn = (j < 0) ? f.cq[n] : f.qp[n];
+                pn = f.cp[n];
+                if (j >= 0) vn = f.V[(int64_t)j * M + n];
+            }
+            const CandMoments c = moments_of_sums(batch_q(j, M, n, e.V, e.cross, e.scal, e.qp, qprev, vraw), p, e.rho, e.bias);
+            const bool objective = m < a.has_obj;
+            v = con_chain(m == 0, objective, v,
+                          acq_value(objective ? a.acq_id : GPX_ACQ_PI, c.mu, c.s2, objective ? a.target : a.thr[m - a.has_obj]));
+        }
+        return v;
+    };
+    batch_score_frame(M, taken, -1, fold, [&](int64_t, double v) { return v; }, partv, parti);
+}
+
 // The single-model pick (one workgroup).  f.S > 0: one thread per fantasy then moves its incumbent, t_s <- max(t_s, posterior mean at
 // the pick after the fantasy's own observation there); eps[j][s] is read, so the driver passes no fantasies after the last pick.
 __device__ __forceinline__ void single_pick(int j, int nblk, const double* __restrict__ partv, const int64_t* __restrict__ parti, int64_t M,
@@ -202,6 +233,10 @@ void launch_batch_pick(hipStream_t s, int j, int64_t M, int d, const double* Z, 
 void launch_ens_batch_score(hipStream_t s, int j, int n, int64_t M, const BatchMember* mem, const BatchBuf& b, int acq_id, double p0) {
     hipLaunchKernelGGL(k_ens_batch_score, dim3((unsigned)batch_blocks(M)), dim3(256), 0, s, j, n, M, mem, b.taken, acq_id, p0, b.partv,
                        b.parti);
+}
+
+void launch_con_batch_score(hipStream_t s, int j, int n, int64_t M, const BatchMember* mem, const BatchBuf& b, const ConBatchArg& a) {
+    hipLaunchKernelGGL(k_con_batch_score, dim3((unsigned)batch_blocks(M)), dim3(256), 0, s, j, n, M, mem, b.taken, a, b.partv, b.parti);
 }
 
 void launch_ens_batch_pick(hipStream_t s, int j, int n, int64_t nb, int64_t M, int d, const double* Z, const BatchMember* mem,

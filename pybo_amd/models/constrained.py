@@ -7,7 +7,8 @@ noisy evaluations (Gardner et al. 2014; Gelbart et al. 2014).  The reference has
 
 The factors are independent GPs, each with its own hyper-parameters.  With device members (`pybo_amd.models.GP` on one device) the
 whole-grid product and its top-k are one call into the library (gpx_constrained_sweep_dev: `acq_topk`), and moments and gradients of
-all 1 + J members at a few points are one call too (gpx_ensemble_predict: `get_constrained`); with any other members (a test oracle,
+all 1 + J members at a few points are one call too (gpx_ensemble_predict: `get_constrained`), and so are nb greedy batch picks over the
+members' warm sweep caches (gpx_constrained_sweep_batch: `acq_batch`, for `pybo_amd.propose_batch`); with any other members (a test oracle,
 a stub) the same arithmetic runs through their `get_improvement` / `get_tail`.  Host logic only: no GP arithmetic lives here.
 """
 import numpy as np
@@ -152,6 +153,26 @@ class Constrained(object):
                                             want_all=False)
         self._lead = lead
         return out['top_val'], out['top_idx']
+
+    def acq_batch(self, kind, target, xgrid, nb):
+        """nb grid points to evaluate in parallel, on the device (gpx_constrained_sweep_batch): greedy picks of the constrained index
+        with target and thresholds frozen and EVERY member -- the objective and each constraint -- conditioned on a pick at its own
+        posterior mean (target = None: the probability of feasibility alone, the objective takes no part).  Every member's sweep cache
+        is brought onto `xgrid` first (`GP._cache_grid`: a `DeviceGrid` that member's state has swept before is re-used, anything else
+        is swept once with the cache on).  Returns dict(sel_val (nb,), sel_idx (nb,), sel_s2 (n, nb)), the objective first.
+        Not built: fantasised or pending picks, MCMC / ShardedGP members, off-grid refinement of the picks, pruned seeding of the caches."""
+        if kind != 'cei':
+            raise ValueError("Constrained.acq_batch takes 'cei', not %r" % (kind,))
+        if not self._device_members():
+            raise TypeError('Constrained.acq_batch needs device GP members on one device')
+        members = self.constraints if target is None else self._members
+        if not isinstance(xgrid, DeviceGrid) or int(xgrid.device) != int(members[0].device):
+            xgrid = np.array(xgrid, ndmin=2, dtype=float)        # one host copy for all members
+        params = ([] if target is None else [float(target)]) + [float(t) for t in self.thresholds]
+        kinds = ([] if target is None else ['ei']) + ['pi'] * len(self.constraints)
+        engines = [m._cache_grid(k, p, xgrid) for m, k, p in zip(members, kinds, params)]
+        obj = None if target is None else engines[0]
+        return _lib.Engine.constrained_batch(obj, engines[len(engines) - len(self.constraints):], self.thresholds, 'ei', target, int(nb))
 
     def topk_engine(self):
         """The device handle whose HBM holds the (value, index) pairs of the last `acq_topk`: the lead of that sweep."""

@@ -177,7 +177,10 @@ def CEI(model, _, X, xi=0.0, pmin=0.5):
     """Constrained expected improvement (Gardner et al. 2014; Gelbart et al. 2014) on a `models.Constrained`: EI of the objective
     times the probability that every constraint holds.  The target is the highest objective posterior mean among the observed X
     whose `feasibility` is at least `pmin`, plus xi; while no observation qualifies the index is the probability of feasibility
-    alone (target None).  The index carries `.acq = ('cei', target)` and, for models with `acq_topk`, `.topk`; never `.batch`."""
+    alone (target None).  The index carries `.acq = ('cei', target)` and, for models with `acq_topk`, `.topk`; never `.batch`:
+    batch proposals (`pybo_amd.propose_batch(..., policy='cei')`, `solve_bayesopt(nbatch=)`) read `.acq` and ask the MODEL -- a
+    `models.Constrained` over device members makes its greedy picks in one device call (`acq_batch`: gpx_constrained_sweep_batch),
+    any other takes the generic host path, every member believing its own posterior mean at a pick."""
     model = model.copy()
     lacking = [n for n in ('feasibility', 'get_constrained') if getattr(model, n, None) is None]
     if lacking:
