@@ -21,17 +21,14 @@ extern "C" {
 #endif
 typedef struct gpx_handle gpx_handle;
 enum gpx_status {
-    GPX_OK = 0, GPX_EARG = -1, /* bad argument */
-    GPX_ENOTPD = -2,  /* K + sn2*I not positive definite; see gpx_fail_pivot */
-    GPX_EHIP = -3,    /* HIP runtime error */                  GPX_EOOM = -4, /* device allocation failed */
-    GPX_ESTATE = -5,  /* call order error (e.g. sweep before fit) */
+    GPX_OK = 0, GPX_EARG = -1, /* bad argument */      GPX_ENOTPD = -2,  /* K + sn2*I not positive definite; see gpx_fail_pivot */
+    GPX_EHIP = -3, /* HIP runtime error */   GPX_EOOM = -4, /* device allocation failed */   GPX_ESTATE = -5, /* call order error (e.g. sweep before fit) */
     GPX_ERCCL = -6    /* RCCL could not be loaded, or a collective failed; see gpx_comm_last_error */
 };
 /* covariance functions; parametrisation (sn2, rho, ell[d], bias) = the arguments of reggie.make_gp(sn2, rho, ell, bias) [pybo/bayesopt.py:98-105] */
 enum gpx_kernel {
     GPX_KERN_SE_ARD = 0,   /* rho * exp(-r2/2),                      r2 = sum_k ((x_k-z_k)/ell_k)^2 */
-    GPX_KERN_MATERN52 = 1, /* rho * (1 + sqrt5 r + 5 r2/3) exp(-sqrt5 r) */
-    GPX_KERN_MATERN32 = 2, /* rho * (1 + sqrt3 r) exp(-sqrt3 r) */
+    GPX_KERN_MATERN52 = 1, /* rho * (1 + sqrt5 r + 5 r2/3) exp(-sqrt5 r) */      GPX_KERN_MATERN32 = 2, /* rho * (1 + sqrt3 r) exp(-sqrt3 r) */
     GPX_KERN_MATERN12 = 3  /* rho * exp(-r) */
 };
 enum gpx_acq {        /* acquisition functions evaluated by the sweep */
@@ -49,8 +46,7 @@ enum gpx_acq {        /* acquisition functions evaluated by the sweep */
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* `stream` is a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) or NULL for a library-owned stream. */
 int gpx_create(int device, void *stream, gpx_handle **out);
-int gpx_destroy(gpx_handle *h);
-const char *gpx_last_error(const gpx_handle *h);
+int gpx_destroy(gpx_handle *h);      const char *gpx_last_error(const gpx_handle *h);
 int gpx_version(void);
 /* Options (int64 values), defaults in brackets: schedules that give BIT-IDENTICAL results unless an option says otherwise.  Measurements: DESIGN.md section 4.
  *   "chunk"          candidate columns per sweep chunk, a multiple of 128 [by size: 65536; 131072 up to N = 4096]
@@ -251,6 +247,11 @@ int gpx_ehvi_sweep_dev(gpx_handle *f1, gpx_handle *f2, const double *P, int np, 
                        double *top_val, int64_t *top_idx, double *d_acq_all, double *d_mom);
 int gpx_ehvi_fold_dev(gpx_handle *lead, const double *d_mom, int64_t M, const double *P, int np, const double *ref, int64_t k,
                       double *top_val, int64_t *top_idx, double *d_acq_all);
+/* gpx_ensemble_sweep_batch's rules on this index: nb greedy picks, f1, f2 and ref frozen, each conditioned on a pick at ITS OWN posterior mean, and the pick's
+ * believed outcome (mu_1, mu_2) taken into the front before the next round (on the device; n + nb - 1 <= 1024, else GPX_EARG).  Optional, on the host:
+ * sel_s2 (2, nb), sel_y (nb, 2) the believed outcomes, sel_nfront (nb) the size of the front that scored pick j. */
+int gpx_ehvi_sweep_batch(gpx_handle *f1, gpx_handle *f2, const double *P, int np, const double *ref, int64_t nb,
+                         double *sel_val, int64_t *sel_idx, double *sel_s2, double *sel_y, int64_t *sel_nfront);
 /* ---- candidate grid generated and kept in HBM = the solver's grid xgrid = init_uniform(bounds, ngrid, rng) [pybo/solvers/lbfgs.py:45;
  *      pybo/inits/methods.py:24-38] or a Sobol' grid [pybo/inits/methods.py:62-77] without the host array and its PCIe upload; pass gpx_grid_data() to
  *      the *_dev sweeps.
@@ -258,8 +259,7 @@ int gpx_ehvi_fold_dev(gpx_handle *lead, const double *d_mom, int64_t M, const do
  *      53-bit uniforms of output c; x = lo + u*(hi-lo); rows first .. first+M-1 of that array are generated (a shard holds the numbers the whole grid holds).
  * GPX_GRID_SOBOL: unscrambled Sobol' points first .. first+M-1 in Gray-code order (the order of scipy.stats.qmc.Sobol), from caller-supplied direction
  *      numbers sv (d, bits) uint32, 1 <= bits <= 32.  bounds (d,2) row-major [lo, hi].  Errors of the grid calls are read with gpx_last_error(NULL). */
-typedef struct gpx_grid gpx_grid;
-enum { GPX_GRID_UNIFORM = 0, GPX_GRID_SOBOL = 1 };
+typedef struct gpx_grid gpx_grid;      enum { GPX_GRID_UNIFORM = 0, GPX_GRID_SOBOL = 1 };
 int gpx_grid_create(int device, int kind, const double *bounds, int64_t M, int64_t d, uint64_t seed,
                     int64_t first, const uint32_t *sv, int bits, gpx_grid **out);
 const double *gpx_grid_data(const gpx_grid *g);     /* device pointer, (M,d) row-major */

@@ -105,6 +105,7 @@ SYMBOLS = {
     'gpx_ehvi_sweep': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _i64, _i64, _P, _P, _P]),
     'gpx_ehvi_sweep_dev': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _i64, _i64, _P, _P, _P, _P]),
     'gpx_ehvi_fold_dev': (C.c_int, [_P, _P, _i64, _P, C.c_int, _P, _i64, _P, _P, _P]),
+    'gpx_ehvi_sweep_batch': (C.c_int, [_P, _P, _P, C.c_int, _P, _i64, _P, _P, _P, _P, _P]),
     'gpx_grid_create': (C.c_int, [C.c_int, C.c_int, _P, _i64, _i64, C.c_uint64, _i64, _P, C.c_int, C.POINTER(_P)]),
     'gpx_grid_data': (_P, [_P]),
     'gpx_grid_rows': (C.c_int, [_P, _P, _i64, _P]),
@@ -849,6 +850,21 @@ class Engine(object):
         args = (f1._h, f2._h, _ptr(front) if len(front) else None, len(front), _ptr(ref), X, M, k, ptv, pti)
         f1._check(f1._lib.gpx_ehvi_sweep_dev(*args, _dptr(d_acq), _dptr(d_mom)) if dev else f1._lib.gpx_ehvi_sweep(*args, _ptr(o['acq'])))
         return dict(top_val=tv, top_idx=ti, **o)
+
+    @staticmethod
+    def ehvi_batch(f1, f2, front, ref, nb):
+        """nb greedy picks of the two-objective index on the engines' live sweep caches (gpx_ehvi_sweep_batch): both members and `ref`
+        frozen, each member conditioned on a pick at its own posterior mean, and the pick's believed outcome (mu_1, mu_2) taken into the
+        front -- on the device -- before the next round.  `front` (np, 2), `ref` (2): host arrays.  Returns dict(sel_val (nb,), sel_idx
+        (nb,), sel_s2 (2, nb), sel_y (nb, 2) the believed outcomes, sel_nfront (nb,) the size of the front that scored each pick); the
+        engines are left as they were, f1 (the lead) raises the errors."""
+        front, ref = Engine._front_args(front, ref)
+        n = max(int(nb), 0)
+        out = dict(sel_val=np.empty(n), sel_idx=np.empty(n, dtype=np.int64), sel_s2=np.empty((2, n)), sel_y=np.empty((n, 2)),
+                   sel_nfront=np.empty(n, dtype=np.int64))
+        f1._check(f1._lib.gpx_ehvi_sweep_batch(f1._h, f2._h, _ptr(front) if len(front) else None, len(front), _ptr(ref), int(nb),
+                                               *[_ptr(out[k]) for k in ('sel_val', 'sel_idx', 'sel_s2', 'sel_y', 'sel_nfront')]))
+        return out
 
     def ehvi_fold(self, d_mom, M, front, ref, k=0, d_acq=None):
         """The fold and the top-k of a two-objective sweep alone (gpx_ehvi_fold_dev) on this engine's stream: `d_mom` the device pointer of

@@ -24,7 +24,12 @@ the dispatch is on the kind and the MODEL is asked.  One with `acq_batch` and de
 mean, one call for the whole batch); any other (oracle members, stubs) takes the generic host path, `_score` reading `get_constrained` and
 the believer step observing EVERY member at its own posterior mean, a (1, 1 + J) row to `add_data`.  `fantasies > 0` or `pending` on a
 constrained model raise a ValueError before any index is built (not built; nor are MCMC / ShardedGP members, off-grid refinement of the
-picks, pruned seeding of the caches, or batches for EHVI, MES and KG).
+picks, pruned seeding of the caches, or batches for MES and KG).
+`policy='ehvi'` on a two-objective model (`pybo_amd.models.MultiObjective`) goes the same way: `.acq = ('ehvi', (front, ref))`, never
+`.batch`.  Both members and `ref` are frozen and each member is conditioned on a pick at its own posterior mean; new here, THE FRONT FOLLOWS
+THE PICKS: a believer leaves every pick's mean on or above the old front, so the pick's believed outcome `(mu_1(x), mu_2(x))` joins the front
+before the next round (what it dominates leaves).  Device members: one call (gpx_ehvi_sweep_batch; the front is updated on the device);
+others: the host path, `_score` reading `get_ehvi` over the grown front, a (1, 2) row to `add_data`.  `fantasies` / `pending`: ValueError.
 `policy='mes'` is refused: its index carries `.acq = ('mes', ystar)` but no `.batch`, and `_score` below raises the ValueError for any kind
 but EI, PI and UCB -- scoring the believer rounds with max-value entropy search is not built (the sampled maxima would have to follow them).
 `policy='kg'` is refused the same way: `.acq = ('kg', support)`, no `.batch` (the support set's means would have to follow the rounds).
@@ -66,13 +71,18 @@ def _score(model, kind, param, Z):
         return mu + np.sqrt(param * s2)
     if kind == 'cei':                                 # a constrained model: EI times feasibility (param None: feasibility alone)
         return model.get_constrained(param, Z)
-    raise ValueError('batch proposals need an EI, PI or UCB index (or CEI on a constrained model), not %r' % (kind,))
+    if kind == 'ehvi' and getattr(model, 'get_ehvi', None) is not None:      # two objectives: param = (front, ref), the front AS IT STANDS
+        return model.get_ehvi(param[0], param[1], Z)
+    raise ValueError('batch proposals need an EI, PI or UCB index (or CEI on a constrained, EHVI on a two-objective model), not %r' % (kind,))
 
 
 def _believe(work, kind, x):
-    """What the believer observes at x: the posterior mean; on a constrained model EVERY member's own, a (1, 1 + J) row."""
+    """What the believer observes at x: the posterior mean; on a constrained model EVERY member's own, a (1, 1 + J) row; on a
+    two-objective model the (1, 2) row of both members' means."""
     if kind == 'cei':
         return np.array([[float(m.predict(x)[0][0]) for m in [work.objective] + list(work.constraints)]])
+    if kind == 'ehvi':
+        return np.array([[float(m.predict(x)[0][0]) for m in work.objectives]])
     return work.predict(x)[0]
 
 
@@ -87,7 +97,10 @@ def _host_batch(model, kind, param, Z, nb):
         vals.append(float(v[i]) if not np.isnan(v[i]) else -np.inf)
         if j + 1 < nb:
             x = Z[i:i + 1]
-            work.add_data(x, _believe(work, kind, x))     # the believer: observe the posterior mean
+            y = _believe(work, kind, x)
+            work.add_data(x, y)                           # the believer: observe the posterior mean
+            if kind == 'ehvi':                            # .. and the front follows the picks: the believed outcome joins it
+                param = (np.vstack([np.asarray(param[0], dtype=float).reshape(-1, 2), y]), param[1])
     return np.array(vals), np.array(idx, dtype=np.int64)
 
 
@@ -168,6 +181,8 @@ def _propose(model, bounds, X, nb, policy, xgrid, ngrid, rng, fantasies=0, incum
         raise ValueError('nb exceeds the number of grid points')
     if hasattr(model, 'get_constrained') and (fantasies or pending is not None):
         raise ValueError('fantasies and pending points are not supported on constrained models (models.Constrained): believer picks only')
+    if hasattr(model, 'get_ehvi') and (fantasies or pending is not None):
+        raise ValueError('fantasies and pending points are not supported on two-objective models (models.MultiObjective): believer picks only')
     if fantasies:
         _fantasy_model(model, nb, fantasies)
     index = policy(model, bounds, X)
@@ -199,6 +214,9 @@ def _propose(model, bounds, X, nb, policy, xgrid, ngrid, rng, fantasies=0, incum
         vals, idx = np.array(vals), np.array(idx, dtype=np.int64)
     elif acq[0] == 'cei' and getattr(model, 'acq_batch', None) is not None and getattr(model, '_device_members', lambda: False)():
         out = model.acq_batch('cei', acq[1], xgrid, nb)      # (the CEI index carries no `.batch`: the model is asked)
+        vals, idx = np.asarray(out['sel_val']), np.asarray(out['sel_idx'], dtype=np.int64)
+    elif acq[0] == 'ehvi' and getattr(model, 'acq_batch', None) is not None and getattr(model, '_device_members', lambda: False)():
+        out = model.acq_batch('ehvi', acq[1], xgrid, nb)     # (nor does the EHVI index: the model is asked)
         vals, idx = np.asarray(out['sel_val']), np.asarray(out['sel_idx'], dtype=np.int64)
     elif getattr(index, 'batch', None) is not None:
         out = index.batch(xgrid, nb)

@@ -255,7 +255,8 @@ static std::string apply_env_options(gpx_handle* h) {
 // 700: gpx_ehvi_sweep[_dev], gpx_ehvi_fold_dev (expected hypervolume improvement of two objectives over a Pareto front).
 // 710: gpx_sweep_batch_fantasy (batch picks with the pending outcomes integrated out over joint fantasies; time in timers slot 20).
 // 720: gpx_constrained_sweep_batch (greedy batch picks of the constrained index over the members' live caches; time in timers slot 20).
-extern "C" int gpx_version(void) { return 720; }
+// 730: gpx_ehvi_sweep_batch (greedy batch picks of the two-objective index; the front follows the picks on the device; timers slot 20).
+extern "C" int gpx_version(void) { return 730; }
 
 extern "C" const char* gpx_last_error(const gpx_handle* h) {
     return h ? h->err.c_str() : g_create_err.c_str();
@@ -364,7 +365,7 @@ extern "C" int gpx_destroy(gpx_handle* h) {
     for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
     void* ptrs[] = {h->dXs, h->dXraw, h->dy, h->dS, h->dR, h->dT, h->dU, h->da, h->dalpha, h->dsmall, h->dKs, h->dQp, h->dXc, h->dout, h->dblkv, h->dblki,
-                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dcon, h->dehvi, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw, h->dfant, h->dpath};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
+                    h->dtopv, h->drff, h->drffs, h->dgrad, h->dens, h->dcon, h->dehvi, h->dehvib, h->dprune, h->dkeep, h->dcZ, h->dcq, h->dbatch, h->dhyper, h->dpend, h->drefine, h->dspec, h->dbsel, h->djoint, h->dkg, h->dkgw, h->dfant, h->dpath};  // dPp, dtopi, dcp alias dQp, dtopv, dcq
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->hpin) hipHostFree(h->hpin);
@@ -2713,10 +2714,12 @@ static int batch_prepare(BatchCall& c) {
 
 // The rounds, on the lead's stream, and the results.  score(j, s2_out) enqueues the scoring pass that folds row j of V (j < 0: round 0;
 // s2_out: the variances that score the LAST pick, when asked for), pick(j, last) the pick; unless it was the last, every member is then
-// conditioned on the lead's x.  sel_s2: n_s2 words from d_sel_s2; same: the lead's same-grid word (the ensemble).  The one synchronisation.
+// conditioned on the lead's x.  sel_s2: n_s2 words from d_sel_s2; same: the lead's same-grid word (the ensemble); more: what else a form
+// brings home (dst NULL: skipped).  The one synchronisation.
+struct BatchCopy { void* dst; const void* src; size_t bytes; };
 template <class Score, class Pick>
 static int batch_rounds(const BatchCall& c, const Score& score, const Pick& pick, double* sel_val, int64_t* sel_idx, double* sel_s2,
-                        const double* d_sel_s2, int64_t n_s2, double* s2_all, int* same = nullptr) {
+                        const double* d_sel_s2, int64_t n_s2, double* s2_all, int* same = nullptr, std::initializer_list<BatchCopy> more = {}) {
     gpx_handle* L = c.g.L;
     const BatchBuf& lb = c.bufs[0];
     hipStream_t s = L->stream;
@@ -2738,6 +2741,8 @@ static int batch_rounds(const BatchCall& c, const Score& score, const Pick& pick
     if (sel_s2) HIPCHK(L, hipMemcpyAsync(sel_s2, d_sel_s2, (size_t)n_s2 * 8, hipMemcpyDeviceToHost, s));
     if (s2_all) HIPCHK(L, hipMemcpyAsync(s2_all, lb.s2, (size_t)c.M * 8, hipMemcpyDeviceToHost, s));
     if (same) HIPCHK(L, hipMemcpyAsync(same, lb.same, sizeof(int), hipMemcpyDeviceToHost, s));
+    for (const BatchCopy& m : more)
+        if (m.dst) HIPCHK(L, hipMemcpyAsync(m.dst, m.src, m.bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(L, hipStreamSynchronize(s));
     return GPX_OK;
 }
@@ -2755,15 +2760,16 @@ static int single_rounds(const BatchCall& c, int acq_id, double p0, const FantAr
                         sel_val, sel_idx, sel_s2, b.sel_s2, c.nb, s2_all);
 }
 
-// The rounds of the forms whose kernels read a table of the members in device memory (the ensemble, the constrained index).  The members'
-// streams are drained; from there on everything runs on the lead's: the table goes up, every member's candidates are compared with the
-// lead's (k_ens_same_grid), score(s, j, table, lead's scratch) enqueues a round's scoring pass, the pick is k_ens_batch_pick.
-// sel_s2: (n, nb) member-major.
-template <class Score>
-static int table_rounds(const BatchCall& c, const Score& score, double* sel_val, int64_t* sel_idx, double* sel_s2) {
+// The rounds of the forms whose kernels read a table of the members in device memory (the ensemble, the constrained index, two objectives).
+// The members' streams are drained; from there on everything runs on the lead's: the table goes up, every member's candidates are compared
+// with the lead's (k_ens_same_grid), score(s, j, table, lead's scratch) enqueues a round's scoring pass, pick(s, j, last, table, lead's
+// scratch) its pick.  sel_s2: (n, nb) member-major; more: batch_rounds'.
+template <class Score, class Pick>
+static int table_rounds(const BatchCall& c, const Score& score, const Pick& pick, double* sel_val, int64_t* sel_idx, double* sel_s2,
+                        std::initializer_list<BatchCopy> more = {}) {
     gpx_handle* L = c.g.L;
     const int n = c.g.n;
-    const int64_t M = c.M, d = L->d, nb = c.nb;
+    const int64_t M = c.M, d = L->d;
     L->bsel_desc.resize((size_t)n);
     for (int m = 0; m < n; ++m) {
         HIPCHK(L, hipStreamSynchronize(c.g.hs[m]->stream));
@@ -2779,12 +2785,18 @@ static int table_rounds(const BatchCall& c, const Score& score, double* sel_val,
         HIPCHK(L, hipMemsetAsync(lb.same, 0, sizeof(int), s));
         for (int m = 1; m < n; ++m) launch_ens_same_grid(s, L->dcZ, c.g.hs[m]->dcZ, M * d, lb.same);
     }
-    if (int rc = batch_rounds(c, [&](int j, double*) { score(s, j, ddesc, lb); },
-                              [&](int j, bool) { launch_ens_batch_pick(s, j, n, nb, M, (int)d, L->dcZ, ddesc, lb); },
-                              sel_val, sel_idx, sel_s2, lb.ens_s2, n * nb, nullptr, &differ))
+    if (int rc = batch_rounds(c, [&](int j, double*) { score(s, j, ddesc, lb); }, [&](int j, bool last) { pick(s, j, last, ddesc, lb); },
+                              sel_val, sel_idx, sel_s2, lb.ens_s2, n * c.nb, nullptr, &differ, more))
         return rc;
     if (differ) return fail(L, GPX_EARG, (std::string(c.what) + ": the members' caches hold different candidates").c_str());
     return GPX_OK;
+}
+// .. with the pick the ensemble and the constrained index share (k_ens_batch_pick)
+template <class Score>
+static int table_rounds(const BatchCall& c, const Score& score, double* sel_val, int64_t* sel_idx, double* sel_s2) {
+    return table_rounds(c, score, [&](hipStream_t s, int j, bool, const BatchMember* mem, const BatchBuf& lb) {
+        launch_ens_batch_pick(s, j, c.g.n, c.nb, c.M, (int)c.g.L->d, c.g.L->dcZ, mem, lb);
+    }, sel_val, sel_idx, sel_s2, {});
 }
 
 extern "C" int gpx_sweep_batch(gpx_handle* h, int acq_id, const double* params, int nparams, int64_t nb, double* sel_val,
@@ -2904,6 +2916,50 @@ extern "C" int gpx_constrained_sweep_batch(gpx_handle* obj, gpx_handle* const* c
         return table_rounds(c, [&](hipStream_t s, int j, const BatchMember* mem, const BatchBuf& lb) {
             launch_con_batch_score(s, j, n, c.M, mem, lb, a);
         }, sel_val, sel_idx, sel_s2);
+    });
+}
+
+// Two objectives in batches: both members and the reference point frozen, every round scored by EHVI over the front
+// AS IT STANDS, and -- what no other form needs -- the front follows the picks: a pick's believed outcome (the members' own posterior means
+// there) is taken into the strips on the device by the pick kernel (ehvi_insert), so the strips go up once, at their capacity, into the
+// lead's h->dehvib (ehvi_batch_ws) and the size of the front is a device word the scoring pass reads.  A front of n points may grow to
+// n + nb - 1 before the last round: beyond EHVI_MAX_FRONT the call is refused.  The refusals are those of gpx_ehvi_sweep and
+// gpx_ensemble_sweep_batch, the rounds table_rounds' with this form's two kernels.
+extern "C" int gpx_ehvi_sweep_batch(gpx_handle* f1, gpx_handle* f2, const double* P, int np, const double* ref, int64_t nb, double* sel_val,
+                                    int64_t* sel_idx, double* sel_s2, double* sel_y, int64_t* sel_nfront) {
+    if (!f1) return GPX_EARG;
+    return guarded(f1, [&]() -> int {
+        const char* what = "ehvi_sweep_batch";
+        gpx_handle* L = f1;
+        gpx_handle* const hs[2] = {f1, f2};
+        BatchCall c = {what, {L, hs, 2, "objective", 1, nullptr}, nb, 0, {}};
+        std::vector<double> strips;
+        int n = 0, rc;
+        if ((rc = group_check(c.g, what, {{G_NOT_NULL, "NULL handle"}, {G_ONCE, "the two objectives need a handle each"}}))) return rc;
+        if ((rc = ehvi_front(L, what, P, np, ref, strips, n))) return rc;
+        if ((rc = check_batch(L, what, GPX_ACQ_EI, ref, 1, nb, sel_val, sel_idx))) return rc;      // (nb and the outputs: every EI here is over a strip's edge)
+        if (n + nb - 1 > EHVI_MAX_FRONT)
+            return fail(L, GPX_EARG, (std::string(what) + ": the front may grow by a point per pick: n + nb - 1 must not exceed 1024").c_str());
+        if ((rc = group_check(c.g, what, {{G_FITTED, "an objective's model is not fitted"}, {G_SHAPE, "the handles must share the device and the input dimension"}})))
+            return rc;
+        if ((rc = batch_check(c)) || (rc = batch_prepare(c))) return rc;
+        if ((rc = ensure(L, L->dehvib, L->cap_ehvib, ehvi_batch_ws(WsCarver(nullptr), EHVI_STRIP_LD).bytes / 8))) return rc;
+        const EhviBatchWs w = ehvi_batch_ws(WsCarver(L->dehvib), EHVI_STRIP_LD);
+        // ehvi_front's strips (a then b, n + 2 each) at the device's pitch; the words behind them are never read before they are written
+        std::vector<double> up((size_t)2 * EHVI_STRIP_LD, 0.0);
+        std::copy(strips.begin(), strips.begin() + n + 2, up.begin());
+        std::copy(strips.begin() + n + 2, strips.end(), up.begin() + EHVI_STRIP_LD);
+        {
+            Span sp(L, T_COPY);
+            // (pageable host memory: each copy has read it before it returns; a and b are adjacent in the walk)
+            HIPCHK(L, hipMemcpyAsync(w.a, up.data(), up.size() * 8, hipMemcpyHostToDevice, L->stream));
+            HIPCHK(L, hipMemcpyAsync(w.n, &n, sizeof(int), hipMemcpyHostToDevice, L->stream));
+        }
+        return table_rounds(c, [&](hipStream_t s, int j, const BatchMember* mem, const BatchBuf& lb) { launch_ehvi_batch_score(s, j, c.M, mem, lb, w); },
+                            [&](hipStream_t s, int j, bool last, const BatchMember* mem, const BatchBuf& lb) {
+                                launch_ehvi_batch_pick(s, j, nb, c.M, (int)L->d, L->dcZ, mem, lb, w, last);
+                            }, sel_val, sel_idx, sel_s2,
+                            {{sel_y, w.y, (size_t)nb * 16}, {sel_nfront, w.nfront, (size_t)nb * 8}});
     });
 }
 

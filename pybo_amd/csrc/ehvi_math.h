@@ -3,8 +3,9 @@
 //     HVI(y) = sum_i [min(y1, a_{i+1}) - a_i]_+ [y2 - b_i]_+        EHVI = sum_i w_i EI_2(b_i),  w_i = max(EI_1(a_i) - EI_1(a_{i+1}), 0)
 // with EI_j(t) the expected improvement of objective j over t and EI_1(+inf) := 0.
 // (a) Plain C++ as acq_core.h (no HIP type; tests/c/ehvi_check.cpp includes this file): ehvi_strips, the filter and sort that turns raw
-//     points into strips, run on the host by api.hip; ehvi_fold_term, one strip's clamp, product and add, each rounded (GPX_NO_CONTRACT).
-// (b) Device only: ehvi_value, the per-candidate loop of k_ehvi_fold.  Every EI is gpx_math.h's acq_value -- the bits of
+//     points into strips, run on the host by api.hip; ehvi_insert, one more point taken into the strips in place (the batch picks' front
+//     follows them on the device); ehvi_fold_term, one strip's clamp, product and add, each rounded (GPX_NO_CONTRACT).
+// (b) Device only: ehvi_value, the per-candidate loop of k_ehvi_fold and k_ehvi_batch_score.  Every EI is gpx_math.h's acq_value -- the bits of
 //     gpx_sweep(GPX_ACQ_EI) -- so the kernel file includes gpx_math.h first and defines GPX_EHVI_DEVICE.
 #ifndef GPX_EHVI_MATH_H
 #define GPX_EHVI_MATH_H
@@ -55,7 +56,41 @@ GPX_ACQ_FN double ehvi_fold_term(double acc, double e_prev, double e_next, doubl
     return acc + t;
 }
 
-#if defined(GPX_EHVI_DEVICE)      // (set by kernels_ehvi.hip after it has included gpx_math.h)
+// One more point y = (y1, y2) taken into the strips a[0 .. n + 1], b[0 .. n] in place, by ehvi_strips' own filtering rule: starting from
+// ehvi_strips(P, r) and inserting y_0 .. y_{j-1} in order leaves the arrays of ehvi_strips(P + {y_0 .. y_{j-1}}, r), bit for bit (every
+// output is a copy of an input double).  A y not strictly above r, or weakly dominated by (or equal to) a front point, changes nothing;
+// otherwise the front points it weakly dominates -- one run [lo, end) of the order by f1 -- go and it takes their place.  Returns the
+// new n <= n + 1: a must hold n + 3 and b n + 2 doubles.  No allocation, no container: the batch pick kernel runs the same text
+// (kernels_batch.hip, one thread).  Point i = 1 .. n is (a[i], b[i - 1]): a ascending, b descending, a[n + 1] = +inf ends every search.
+GPX_ACQ_FN int ehvi_insert(double* a, double* b, int n, double y1, double y2) {
+    if (!(y1 > a[0] && y2 > b[n])) return n;
+    int l = 1, h = n + 1;      // end: the first point with f1 > y1
+    while (l < h) {
+        const int mid = (l + h) / 2;
+        if (a[mid] > y1) h = mid; else l = mid + 1;
+    }
+    const int end = l;
+    const int at = (end > 1 && a[end - 1] == y1) ? end - 1 : end;      // the first point with f1 >= y1: of those, the one highest in f2
+    if (at <= n && b[at - 1] >= y2) return n;
+    l = 1, h = end;            // lo: the first point left of `end` with f2 <= y2
+    while (l < h) {
+        const int mid = (l + h) / 2;
+        if (b[mid - 1] <= y2) h = mid; else l = mid + 1;
+    }
+    const int lo = l, shift = lo + 1 - end;      // the points from `end` on, a's +inf and b's r2 move by shift <= 1
+    if (shift > 0) {
+        for (int i = n + 1; i >= end; --i) a[i + 1] = a[i];
+        for (int i = n; i >= end - 1; --i) b[i + 1] = b[i];
+    } else if (shift < 0) {
+        for (int i = end; i <= n + 1; ++i) a[i + shift] = a[i];
+        for (int i = end - 1; i <= n; ++i) b[i + shift] = b[i];
+    }
+    a[lo] = y1;
+    b[lo - 1] = y2;
+    return n + shift;
+}
+
+#if defined(GPX_EHVI_DEVICE)      // (set by kernels_ehvi.hip and kernels_batch.hip after they have included gpx_math.h)
 // EHVI of one candidate from its four moments and the strips a[0 .. n + 1], b[0 .. n]: the accumulator starts at +0.0, the strips are
 // added in order i = 0 .. n, every EI_1(a_i) is computed once and carried to the next strip.  a[n + 1] is never read (EI_1(+inf) := 0).
 __device__ __forceinline__ double ehvi_value(double mu1, double s2_1, double mu2, double s2_2, const double* a, const double* b, int n) {

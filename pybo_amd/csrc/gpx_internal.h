@@ -151,6 +151,8 @@ struct gpx_handle {
     int64_t cap_con = 0;
     double* dehvi = nullptr;  // two-objective sweep: the members' four moment vectors, the values, the front's strips (ehvi_ws)
     int64_t cap_ehvi = 0;
+    double* dehvib = nullptr; // two-objective batch picks: the lead's strips at capacity, believed outcomes, front sizes (ehvi_batch_ws)
+    int64_t cap_ehvib = 0;
     int prune = -1;          // option: selection-only sweeps skip candidates whose EI bound cannot reach the top-k (-1 by size and gate, 0 never, 1 wherever legal)
     char* dprune = nullptr;   // their workspace (one allocation: prune_ws_layout)
     int64_t cap_prune = 0;    // ... in bytes
@@ -439,6 +441,11 @@ void launch_ens_same_grid(hipStream_t s, const double* Za, const double* Zb, int
 // the constrained form's scoring pass over the same table (the objective first where a.has_obj): con_chain of the members' terms; its pick is
 // launch_ens_batch_pick
 void launch_con_batch_score(hipStream_t s, int j, int n, int64_t M, const BatchMember* mem, const BatchBuf& b, const ConBatchArg& a);
+// the two-objective form over a table of the two members: EHVI over the strips w.a / w.b of the w.n[0] points the device holds, and the
+// pick that records the believed outcome (the members' means at the pick) and, unless it was the last, takes it into the strips
+void launch_ehvi_batch_score(hipStream_t s, int j, int64_t M, const BatchMember* mem, const BatchBuf& b, const EhviBatchWs& w);
+void launch_ehvi_batch_pick(hipStream_t s, int j, int64_t nb, int64_t M, int d, const double* Z, const BatchMember* mem, const BatchBuf& b,
+                            const EhviBatchWs& w, bool last);
 
 // launchers (kernels_cov.hip): the joint posterior at cols = Mp padded points -- V = T Ks stored panel-major [cols / 128][Np][128],
 // mu = bias + V^T a (Pp: Np / 128 x cols partial sums), C = Kss - V^T V (Mp, Mp) symmetric bit for bit, B = C + add I with identity

@@ -9,7 +9,7 @@
 // The first two terms over d are one pass of the cache correction's rank-1 kernel (k_sweep_rankq<1> with `vout`, weight row
 // [w, -1, 0..], xlast = x scaled) -- launched by the driver in api.hip between a round's two kernels.
 //
-// Four forms, ONE frame. A member's state is a BatchMember (acq_core.h); a scoring kernel is batch_score_frame (acq_core_dev.h: the
+// Five forms, ONE frame. A member's state is a BatchMember (acq_core.h); a scoring kernel is batch_score_frame (acq_core_dev.h: the
 // walk over the candidates, who is live, the order, the block arg-max, the partial) around the one thing in which the forms differ, the
 // value of a candidate; a pick kernel is merge_pick (the partials merged, the pick recorded), pick_member per member (its variance at
 // the pick, 1/d, the cross terms v_l[i_j], x / ell) and pick_gather (the raw x), all in device scratch: the host never sees an index.
@@ -17,6 +17,7 @@
 //   fantasies  gpx_sweep_batch_fantasy   k_fant_score<ACQ>  the mean of acq_value over S fantasised means     k_fant_pick (+ incumbents)
 //   ensemble   gpx_ensemble_sweep_batch  k_ens_batch_score  the members' values or moments folded in order    k_ens_batch_pick
 //   constrained gpx_constrained_sweep_batch k_con_batch_score  the objective's value times every constraint's PI  k_ens_batch_pick
+//   two objectives gpx_ehvi_sweep_batch   k_ehvi_batch_score EHVI of the two members' moments over the front's strips  k_ehvi_batch_pick (+ the front)
 // The single-model kernels take their member by value, the ensemble's and the constrained form's read a table of n in device memory: every member is conditioned
 // on the pick at ITS OWN posterior mean and keeps its own w, d, cross terms, 1/ell, V and q'.  k_ens_same_grid: the members' caches hold
 // the same candidates, bit for bit (one flag word, read at the call's only sync).
@@ -29,6 +30,8 @@
 #include "acq_core_dev.h"
 #include "gpx_internal.h"
 #include "gpx_math.h"
+#define GPX_EHVI_DEVICE
+#include "ehvi_math.h"
 
 namespace gpx {
 
@@ -116,6 +119,35 @@ __global__ __launch_bounds__(256) void k_ens_batch_score(int j, int nmem, int64_
     batch_score_frame(M, taken, -1, fold, [&](int64_t, const Sums& a) { return ens_value(mode, a.acc0, a.acc1, nd, p0); }, partv, parti);
 }
 
+// Two objectives (a table of two members): each member's own recurrence and moments on the load schedule above -- objective 2's three
+// streaming loads are issued before objective 1's arithmetic --, then ehvi_value over the strips of the front AS THE DEVICE HOLDS IT:
+// *n_word points (the pick kernel moves it), a then b of pitch EHVI_STRIP_LD, staged once per workgroup into LDS as in k_ehvi_fold; in
+// the loop every lane reads the same word, which the LDS broadcasts.  Compute-bound from a few strips on: 2 (n + 1) + 1 EI per candidate.
+__global__ __launch_bounds__(256) void k_ehvi_batch_score(int j, int64_t M, const BatchMember* __restrict__ mem,
+                                                          const unsigned char* __restrict__ taken, const double* __restrict__ strips,
+                                                          const int* __restrict__ n_word, double* __restrict__ partv,
+                                                          int64_t* __restrict__ parti) {
+    __shared__ double sa[EHVI_STRIP_LD], sb[EHVI_STRIP_LD];
+    const int nf = min(max(*n_word, 0), EHVI_MAX_FRONT);      // (the driver's capacity rule keeps it there; never index past the arrays)
+    for (int i = threadIdx.x; i < nf + 2; i += 256) {
+        sa[i] = strips[i];
+        sb[i] = strips[EHVI_STRIP_LD + i];
+    }
+    __syncthreads();
+    struct Mom { double mu1, s2_1, mu2, s2_2; };
+    const auto fold = [&](int64_t n) {
+        const BatchMember& e = mem[0];
+        const BatchMember& f = mem[1];
+        const double q1 = (j < 0) ? e.cq[n] : e.qp[n], p1 = e.cp[n], v1 = (j < 0) ? 0.0 : e.V[(int64_t)j * M + n];
+        const double q2 = (j < 0) ? f.cq[n] : f.qp[n], p2 = f.cp[n], v2 = (j < 0) ? 0.0 : f.V[(int64_t)j * M + n];
+        const CandMoments c1 = moments_of_sums(batch_q(j, M, n, e.V, e.cross, e.scal, e.qp, q1, v1), p1, e.rho, e.bias);
+        const CandMoments c2 = moments_of_sums(batch_q(j, M, n, f.V, f.cross, f.scal, f.qp, q2, v2), p2, f.rho, f.bias);
+        return Mom{c1.mu, c1.s2, c2.mu, c2.s2};
+    };
+    batch_score_frame(M, taken, -1, fold, [&](int64_t, const Mom& c) { return ehvi_value(c.mu1, c.s2_1, c.mu2, c.s2_2, sa, sb, nf); },
+                      partv, parti);
+}
+
 // The constrained index over the same table (the objective first where a.has_obj, then the constraints in the caller's order): every
 // member's own recurrence and moments as above, its term -- acq_value of the objective at the target, PI of a constraint at its
 // threshold -- taken into the chain by con_chain.  The same load schedule, the same n (j + 4) 8 M bytes per round.
@@ -189,6 +221,30 @@ __global__ __launch_bounds__(256) void k_ens_batch_pick(int j, int nblk, const d
     pick_gather(Z, row, d, x);
 }
 
+// k_ens_batch_pick for the two objectives, and the front follows the pick: one thread records the size of the front that scored pick j and
+// the believed outcome y_j -- each member's own posterior mean bias + p[row], which the believer does not move -- and, unless it was the
+// last pick, takes y_j into the strips by ehvi_insert (the host's text; at most n + 2 words move, in place).  The next scoring pass reads
+// the strips and *w.n: neither the index nor the front's size reaches the host before the call's final copy.
+__global__ __launch_bounds__(256) void k_ehvi_batch_pick(int j, int nblk, const double* __restrict__ partv,
+                                                         const int64_t* __restrict__ parti, int64_t M, int d,
+                                                         const double* __restrict__ Z, int64_t nb, const BatchMember* __restrict__ mem,
+                                                         double* __restrict__ x, double* __restrict__ sel_val,
+                                                         int64_t* __restrict__ sel_idx, double* __restrict__ sel_s2,
+                                                         unsigned char* __restrict__ taken, EhviBatchWs w, int last) {
+    const int64_t row = merge_pick(j, nblk, partv, parti, M, sel_val, sel_idx, taken);
+    for (int m = threadIdx.x >> 6; m < 2; m += 4) pick_member(mem[m], j, M, d, Z, row, sel_s2 + (int64_t)m * nb, threadIdx.x & 63, 64);
+    pick_gather(Z, row, d, x);
+    if (threadIdx.x == 0) {
+        const int n = *w.n;
+        const double y1 = moments_of_sums(mem[0].qp[row], mem[0].cp[row], mem[0].rho, mem[0].bias).mu;
+        const double y2 = moments_of_sums(mem[1].qp[row], mem[1].cp[row], mem[1].rho, mem[1].bias).mu;
+        w.nfront[j] = n;
+        w.y[2 * j] = y1;
+        w.y[2 * j + 1] = y2;
+        if (!last && n >= 0 && n < EHVI_MAX_FRONT) *w.n = ehvi_insert(w.a, w.b, n, y1, y2);      // (n < the cap: the driver's capacity rule)
+    }
+}
+
 __global__ __launch_bounds__(256) void k_ens_same_grid(const unsigned long long* __restrict__ a,
                                                        const unsigned long long* __restrict__ b, int64_t words,
                                                        int* __restrict__ flag) {
@@ -237,6 +293,16 @@ void launch_ens_batch_score(hipStream_t s, int j, int n, int64_t M, const BatchM
 
 void launch_con_batch_score(hipStream_t s, int j, int n, int64_t M, const BatchMember* mem, const BatchBuf& b, const ConBatchArg& a) {
     hipLaunchKernelGGL(k_con_batch_score, dim3((unsigned)batch_blocks(M)), dim3(256), 0, s, j, n, M, mem, b.taken, a, b.partv, b.parti);
+}
+
+void launch_ehvi_batch_score(hipStream_t s, int j, int64_t M, const BatchMember* mem, const BatchBuf& b, const EhviBatchWs& w) {
+    hipLaunchKernelGGL(k_ehvi_batch_score, dim3((unsigned)batch_blocks(M)), dim3(256), 0, s, j, M, mem, b.taken, w.a, w.n, b.partv, b.parti);
+}
+
+void launch_ehvi_batch_pick(hipStream_t s, int j, int64_t nb, int64_t M, int d, const double* Z, const BatchMember* mem, const BatchBuf& b,
+                            const EhviBatchWs& w, bool last) {
+    hipLaunchKernelGGL(k_ehvi_batch_pick, dim3(1), dim3(256), 0, s, j, batch_blocks(M), b.partv, b.parti, M, d, Z, nb, mem, b.x, b.sel_val,
+                       b.sel_idx, b.ens_s2, b.taken, w, last ? 1 : 0);
 }
 
 void launch_ens_batch_pick(hipStream_t s, int j, int n, int64_t nb, int64_t M, int d, const double* Z, const BatchMember* mem,

@@ -77,6 +77,17 @@ inline EhviWs ehvi_ws(WsCarver c, int64_t M, int64_t n) {
     return {mom, c.take<double>(M, "out"), c.take<double>(n + 2, "a"), c.take<double>(n + 2, "b"), c.bytes()};
 }
 
+// What the two-objective batch (gpx_ehvi_sweep_batch) adds to the lead's scratch (h->dehvib; nothing here grows with M): the strips at
+// their capacity -- a then b, ld = EHVI_STRIP_LD doubles each, so that a front may grow in place and one upload fills both --, the picks'
+// believed outcomes (64, 2), the size of the front that scored each pick, and the current size n, the word the scoring kernel reads
+struct EhviBatchWs { double *a, *b, *y; int64_t* nfront; int* n; int64_t bytes; };
+inline EhviBatchWs ehvi_batch_ws(WsCarver c, int64_t ld) {
+    EhviBatchWs w = {c.take<double>(ld, "a"), c.take<double>(ld, "b"), c.take<double>(128, "sel_y"), c.take<int64_t>(64, "sel_nfront"),
+                     c.take<int>(1, "n"), 0};
+    c.skip<int>(1), w.bytes = c.bytes();
+    return w;
+}
+
 // The matrix-pipe bound kernels' operands (kernels_sweep.hip: launch_bound_mfma), every one on a 32-byte boundary: the augmented rows
 // in KS k-steps, the weights, the norms where they go through the accumulator (nc; KS <= 4 there), the centre at its fixed place, then
 // the fp32 copies over Np + B32_ZROWS rows (W': the factorised walk's scaled weights).  Sized with KS = BM_KS_MAX, nc = false.

@@ -4,7 +4,8 @@ Two competing objectives behind ONE object with the model protocol, for black bo
 for which the expected hypervolume improvement over a Pareto front is exact and closed-form (pybo_amd/pareto.py; Emmerich et al. 2011,
 Yang et al. 2019).  With device members (`pybo_amd.models.GP` on one device) the whole-grid index and its top-k are one call into the
 library (gpx_ehvi_sweep[_dev]: `acq_topk`) and the moments and gradients of both members at a few points are one call too
-(gpx_ensemble_predict: `get_ehvi`); any other members (a test oracle, a stub) go through their `predict`.  Host logic only.
+(gpx_ensemble_predict: `get_ehvi`), and so are nb greedy batch picks over the members' warm sweep caches (gpx_ehvi_sweep_batch:
+`acq_batch`, for `pybo_amd.propose_batch`); any other members (a test oracle, a stub) go through their `predict`.  Host logic only.
 """
 import numpy as np
 
@@ -98,6 +99,23 @@ class MultiObjective(object):
         out = _lib.Engine.ehvi_sweep(f1, f2, front, ref, xgrid, k=int(k), want_all=False)
         self._lead = f1
         return out['top_val'], out['top_idx']
+
+    def acq_batch(self, kind, param, xgrid, nb):
+        """nb grid points to evaluate in parallel, on the device (gpx_ehvi_sweep_batch): greedy picks of EHVI with both members and the
+        reference point frozen, each member conditioned on a pick at its own posterior mean and the pick's believed outcome -- the two
+        means there -- taken into the front before the next round.  kind 'ehvi', param = (front, ref).  Each member's sweep cache is brought
+        onto `xgrid` first (`GP._cache_grid`: a `DeviceGrid` that member's state has swept before is re-used, anything else is swept once
+        with the cache on).  Returns dict(sel_val (nb,), sel_idx (nb,), sel_s2 (2, nb), sel_y (nb, 2), sel_nfront (nb,)).
+        Not built: fantasised or pending picks, MCMC / ShardedGP members, off-grid refinement, pruned seeding, a moving reference point."""
+        if kind != 'ehvi':
+            raise ValueError("MultiObjective.acq_batch takes 'ehvi', not %r" % (kind,))
+        if not self._device_members():
+            raise TypeError('MultiObjective.acq_batch needs device GP members on one device')
+        front, ref = param
+        if not isinstance(xgrid, DeviceGrid) or int(xgrid.device) != int(self.objectives[0].device):
+            xgrid = np.array(xgrid, ndmin=2, dtype=float)        # one host copy for both members
+        f1, f2 = [m._cache_grid('ei', float(ref[j]), xgrid) for j, m in enumerate(self.objectives)]
+        return _lib.Engine.ehvi_batch(f1, f2, front, ref, int(nb))
 
     def topk_engine(self):
         """The device handle whose HBM holds the (value, index) pairs of the last `acq_topk`: the first objective's."""
